@@ -10,10 +10,14 @@ real-shaped SVD UNet (random-init, fp16) for 14 frames x 576x1024 (latents 72x12
 clips / wall time (max over ranks).  With N > 1 the frames of the ONE clip are sharded over the ranks
 (lkgd_amd/dist.py: CFG-parallel x frame slices, RCCL) - strong scaling.
 
-Prints ONE JSON line on rank 0, with
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the K steps and prints the line (``ms_per_step`` = the
+wall time of one timed step).  ``--full`` adds what the headline figure does not need:
   roofline     - the dominant kernel (the MFMA GEMM / implicit-conv kernel): algorithmic TFLOP/s measured live with
                  HIP events around every launch inside the timed region, against the dense fp16 MFMA peak;
-  cpu_baseline - the fp32 CPU oracle (oracle/, "port") timed on this box's host cores on a bounded sample.
+  end_to_end   - the untimed CLIP / VAE stages either side of the loop;
+  cpu_baseline - the fp32 CPU oracle (oracle/, "port") timed on this box's host cores.
+``--dump-outputs DIR`` writes what the last timed step returned as DIR/<name>.npy (float32; seeded inputs and weights, so two
+builds run with the same arguments compare output for output).
 """
 from __future__ import annotations
 
@@ -64,7 +68,31 @@ def parse():
                          "DDIM; NOT the headline workload, single GPU); a 'step' is one clip of --inference-steps DiT steps")
     ap.add_argument("--controlnet", action="store_true",
                     help="also run the ControlNet-SVD encoder every step (SURVEY.md 8f rank 1; not the headline workload)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the roofline (HIP events inside the timed region), the untimed CLIP / VAE stages and the CPU "
+                         "baseline; --no-kernel-events / --no-vae / --no-cpu-baseline switch parts of it off")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the latents the last timed step returned as DIR/<name>.npy (float32)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
+
+
+DUMP_BUDGET_BYTES = 60 << 20     # --dump-outputs writes at most this much (plus .npy headers)
+
+
+def dump_outputs(dirname, arrays):
+    """``arrays``: name -> tensor, as a caller of the timed path receives them.  Written as float32; an array larger than its share
+    of DUMP_BUDGET_BYTES is written as an evenly strided sample of its flattened elements (the same elements on every run)."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    share = DUMP_BUDGET_BYTES // (4 * len(arrays))
+    for name, t in arrays.items():
+        a = t.detach().float().cpu().numpy()
+        if a.size > share:
+            a = a.reshape(-1)[::-(-a.size // share)]
+        np.save(os.path.join(dirname, name + ".npy"), a)
 
 
 def synthetic_inputs(dev, frames, h, w):
@@ -357,6 +385,8 @@ def bench_cogvideox(args):
         tt = torch.tensor([dt], device=dev, dtype=torch.float64)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"latents": out})
     L = cfg.max_text_seq_length + f * (cfg.sample_height // 2) * (cfg.sample_width // 2)
     D = cfg.num_attention_heads * 64
     tflop = 2 * cfg.num_layers * (2.0 * L * D * D * 12 + 4.0 * L * L * D) / 1e12        # CFG batch 2: projections + FF, attention
@@ -474,9 +504,9 @@ def main():
 
     for _ in range(args.warmup):
         one_clip()
-    # per-launch HIP events of the GEMM family are recorded on every EVENT_CLIP_STRIDE-th timed clip (the first one
+    # --full: per-launch HIP events of the GEMM family are recorded on every EVENT_CLIP_STRIDE-th timed clip (the first one
     # included): an event pair per launch is ~15 000 extra queue packets per clip, which the other clips are spared
-    events = [] if not args.no_kernel_events else None
+    events = [] if args.full and not args.no_kernel_events else None
     clips_sampled = 0
     barrier()
     torch.cuda.reset_peak_memory_stats(dev)
@@ -494,6 +524,8 @@ def main():
         tt = torch.tensor([dt], device=dev, dtype=torch.float64)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"latents": out})
     finite = bool(torch.isfinite(out.float()).all().item())
     # working set of the timed region: live tensors at the peak (weights, packed weights, the forward's
     # activations, bench inputs), what the caching allocator holds for them, and the recorded forward's private pool alone
@@ -534,11 +566,11 @@ def main():
                         "" if not distributed else f", {sampled} of {args.inference_steps} Euler steps each")}
 
     e2e = None
-    if rank == 0 and world == 1 and not args.tiny and not args.no_vae:
+    if args.full and rank == 0 and world == 1 and not args.tiny and not args.no_vae:
         e2e = vae_stages(dev, args, out, dt / args.steps / nclips)
     if rank == 0:
         cpu = None
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             cpu = cpu_baseline(args)
         fps = args.steps * nclips * args.frames / dt
         line = {

@@ -1,7 +1,9 @@
 """Pins the CPU oracle against fixtures produced by the reference's own code (tests/golden/make_goldens.py)."""
 import json
+import math
 import os
 
+import numpy as np
 import pytest
 import torch
 from safetensors.torch import load_file
@@ -32,14 +34,31 @@ def test_scheduler_tables_and_steps(kat, idx):
     s = EulerDiscreteOracle(SchedulerConfig(**kat["config"]))
     s.set_timesteps(case["n"])
     assert torch.equal(s.sigmas, torch.tensor(case["sigmas"]))
-    assert torch.equal(s.timesteps, torch.tensor(case["timesteps"]))
+    # timesteps = 0.25 * log(sigma), the reference's float32 expression: bit for bit as this host evaluates it, and within one ulp
+    # of the table (float32 log rounds differently on different CPUs; the table's host rounded these correctly)
+    kat_t = torch.tensor(case["timesteps"])
+    assert torch.equal(s.timesteps, torch.stack([0.25 * x.log() for x in s.sigmas[:-1]]))
+    assert torch.all((s.timesteps == kat_t) | (torch.nextafter(kat_t, s.timesteps) == s.timesteps))
     assert float(s.init_noise_sigma) == case["init_noise_sigma"]
     x = torch.tensor(case["x0"]).reshape(1, 2, 4, 3, 3)
-    for t, st in zip(s.timesteps, case["steps"]):
+    for i, (t, st) in enumerate(zip(s.timesteps, case["steps"])):
         v = torch.tensor(st["v"]).reshape(x.shape)
-        assert torch.equal(s.scale_model_input(x, t).flatten(), torch.tensor(st["scaled"]))
-        x = s.step(v, t, x)
-        assert torch.equal(x.flatten(), torch.tensor(st["prev"]))
+        scaled, prev = torch.tensor(st["scaled"]), torch.tensor(st["prev"])
+        got_scaled = s.scale_model_input(x, t).flatten()
+        got_prev = s.step(v, t, x).flatten()
+        if _sqrt_rounds_correctly(s.sigmas[i]):
+            assert torch.equal(got_scaled, scaled) and torch.equal(got_prev, prev)
+        else:       # a one-ulp scale moves the step's outputs by up to 4 eps * max|output| (v-prediction cancels)
+            for got, ref in ((got_scaled, scaled), (got_prev, prev)):
+                assert (got - ref).abs().max() <= 8 * torch.finfo(torch.float32).eps * ref.abs().max()
+        x = prev.reshape(x.shape)        # the table's sample: the same as chaining wherever the steps are bit-exact
+
+
+def _sqrt_rounds_correctly(sigma):
+    """whether this host evaluates the step's scale (sigma ** 2 + 1) ** 0.5 - the reference's float32 expression - as the correctly
+    rounded square root, as the host that made the tables did; some hosts' float32 sqrt / log of a 0-d tensor are one ulp off"""
+    q = np.float32(np.float32(float(sigma)) * np.float32(float(sigma)) + np.float32(1))
+    return ((sigma ** 2 + 1) ** 0.5).item() == float(np.float32(math.sqrt(float(q))))
 
 
 def test_scheduler_stochastic_step(golden_dir):

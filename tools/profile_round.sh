@@ -6,9 +6,9 @@ out=$PWD/gpurun_out/prof_$tag
 mkdir -p $out
 cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
-rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace -o bench -- python3 $R/bench.py --steps 1 --warmup 1 --no-cpu-baseline > $out/bench_under_rocprof.json 2> $out/trace.log
-rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $out/fetch -o f -- python3 $R/bench.py --steps 1 --warmup 0 --inference-steps 2 --no-cpu-baseline --no-kernel-events > /dev/null 2> $out/fetch.log
-rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $out/write -o w -- python3 $R/bench.py --steps 1 --warmup 0 --inference-steps 2 --no-cpu-baseline --no-kernel-events > /dev/null 2> $out/write.log
+rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace -o bench -- python3 $R/bench.py --full --steps 1 --warmup 1 --no-cpu-baseline > $out/bench_under_rocprof.json 2> $out/trace.log
+rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $out/fetch -o f -- python3 $R/bench.py --full --steps 1 --warmup 0 --inference-steps 2 --no-cpu-baseline --no-kernel-events > /dev/null 2> $out/fetch.log
+rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $out/write -o w -- python3 $R/bench.py --full --steps 1 --warmup 0 --inference-steps 2 --no-cpu-baseline --no-kernel-events > /dev/null 2> $out/write.log
 cd $R
 F=$(find $out/fetch -name "*counter_collection.csv" | head -1); W=$(find $out/write -name "*counter_collection.csv" | head -1)
 python3 tools/pmc_summary.py $F $W $out/pmc_traffic.json > $out/pmc_hbm_traffic.txt

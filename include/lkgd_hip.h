@@ -289,6 +289,15 @@ int lkgd_prepare_unet_input(const void* latents, int32_t latents_is_f32, const v
 int lkgd_cfg_euler_step(const void* noise_tokens, void* latents, int32_t latents_is_f32, const float* guidance,
                         int32_t B, int32_t F, int32_t H, int32_t W, int32_t cfg, float sigma, float sigma_next,
                         int32_t prediction_type /*0 eps, 1 v*/, lkgd_stream_t stream);
+/* lkgd_cfg_fusion_euler_step: the direct-fusion step of pipeline_stable_video_diffusion_trans_controlnet.py:637-667.  B even,
+ *   P = B/2 pairs: clip b (forward) and clip b+P (backward).  Per clip, per-frame CFG and x0 exactly as lkgd_cfg_euler_step forms
+ *   them; then xb[b,f] = x0[b,f]*weight[f] + x0[b+P,F-1-f]*(1-weight[f]) in fp32, and the Euler update x + (x - x0')/sigma *
+ *   (sigma_next - sigma) with x0' = xb[b,f] for latents[b,f] AND for latents[b+P,F-1-f].  weight: device fp32 [F] (the
+ *   reference's torch.linspace(1, 0, F)); guidance: device fp32 [F], may be NULL when cfg == 1.  One launch, no allocation,
+ *   no host sync; in place on fp16 or fp32 latents. */
+int lkgd_cfg_fusion_euler_step(const void* noise_tokens, void* latents, int32_t latents_is_f32, const float* guidance,
+                               const float* weight, int32_t B, int32_t F, int32_t H, int32_t W, int32_t cfg, float sigma,
+                               float sigma_next, int32_t prediction_type /*0 eps, 1 v*/, lkgd_stream_t stream);
 /* Frame-sharded ranks: rows of this rank's [fl, HW, C] fp16 slice regrouped by destination pixel shard (pack != 0: the send
  * buffer of the all-to-all that re-shards the temporal attention by pixels - row (f, p) goes to fl*p0[r] + f*px[r] + (p - p0[r]),
  * r = the shard owning pixel p, px[0..k-1] = pixels per shard, k <= 16, sum = HW) or back (pack == 0: dst is the [fl, HW, C]

@@ -67,6 +67,75 @@ __global__ __launch_bounds__(256) void cfg_euler_kernel(const half_t* __restrict
   }
 }
 
+// ---- direct-fusion Euler step of the trans-ControlNet pipeline (pipeline_stable_video_diffusion_trans_controlnet.py
+// :637-667): per-frame CFG and x0 of every clip as cfg_euler_kernel forms them, then the forward clip b and the
+// frame-reversed backward clip b+P are blended through their x0 with weight[f] = linspace(1, 0, F)[f] (fp32), and both
+// clips take the Euler step from the blend (clip b+P at frame F-1-f from xb[b, f]).  One thread owns element (b, f, ., p)
+// and its mirror (b+P, F-1-f, ., p): it reads both latents before it writes either, so the in-place update is race-free.
+__device__ __forceinline__ half4_t cfg_combine(const half_t* __restrict__ noise, long long i, long long total, int cfg,
+                                               const float* __restrict__ guidance, int f) {
+  half4_t u = *(const half4_t*)(noise + i * 4);
+  if (cfg != 2) return u;
+  half4_t c = *(const half4_t*)(noise + (i + total) * 4);
+  const half_t g = (half_t)guidance[f];
+  half4_t n;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    half_t d = (half_t)((float)c[e] - (float)u[e]);
+    half_t gd = (half_t)((float)g * (float)d);
+    n[e] = (half_t)((float)u[e] + (float)gd);
+  }
+  return n;
+}
+
+template <typename LT>
+__global__ __launch_bounds__(256) void cfg_fusion_euler_kernel(const half_t* __restrict__ noise,
+                                                               LT* __restrict__ latents,
+                                                               const float* __restrict__ guidance,
+                                                               const float* __restrict__ weight, int B, int F, int HW,
+                                                               int cfg, float sigma, float sigma_next, int vpred) {
+  const int P = B / 2;
+  const long long total = (long long)B * F * HW;         // token rows of one CFG half
+  const long long pairs = (long long)P * F * HW;         // threads: one per (b < P, f, p)
+  const float c_out = -sigma / sqrtf(sigma * sigma + 1.0f);
+  const float c_skip = sigma * sigma + 1.0f;
+  const float dt = sigma_next - sigma;
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < pairs; i += (long long)gridDim.x * 256) {
+    const int p = (int)(i % HW);
+    const long long bf = i / HW;
+    const int f = (int)(bf % F);
+    const int b = (int)(bf / F);
+    const int fm = F - 1 - f;
+    const long long im = ((long long)(b + P) * F + fm) * HW + p;     // token row of the mirror element
+    const half4_t na = cfg_combine(noise, i, total, cfg, guidance, f);
+    const half4_t nm = cfg_combine(noise, im, total, cfg, guidance, fm);
+    const float w = weight[f];
+    const float wc = 1.0f - w;
+    const long long la = ((long long)b * F + f) * 4 * HW + p;
+    const long long lm = ((long long)(b + P) * F + fm) * 4 * HW + p;
+    float xa[4], xm[4];
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      xa[c] = (float)latents[la + (long long)c * HW];
+      xm[c] = (float)latents[lm + (long long)c * HW];
+    }
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      float x0a, x0m;
+      if (vpred) {
+        x0a = (float)(half_t)((float)na[c] * c_out) + xa[c] / c_skip;
+        x0m = (float)(half_t)((float)nm[c] * c_out) + xm[c] / c_skip;
+      } else {
+        x0a = xa[c] - (float)(half_t)((float)na[c] * sigma);
+        x0m = xm[c] - (float)(half_t)((float)nm[c] * sigma);
+      }
+      const float xb = x0a * w + x0m * wc;
+      latents[la + (long long)c * HW] = (LT)(xa[c] + (xa[c] - xb) / sigma * dt);
+      latents[lm + (long long)c * HW] = (LT)(xm[c] + (xm[c] - xb) / sigma * dt);
+    }
+  }
+}
+
 // ---- layout converters at the UNet.forward API boundary
 __global__ __launch_bounds__(256) void tokens_to_nchw_kernel(const half_t* __restrict__ tok, int ld, long long N,
                                                              int C, int HW, half_t* __restrict__ out) {
@@ -197,6 +266,28 @@ extern "C" int lkgd_cfg_euler_step(const void* noise_tokens, void* latents, int3
     hipLaunchKernelGGL(cfg_euler_kernel<half_t>, dim3(grid_for(total, 256)), dim3(256), 0, (hipStream_t)stream,
                        (const half_t*)noise_tokens, (half_t*)latents, guidance, B, F, H * W, cfg, sigma, sigma_next,
                        prediction_type);
+  return hipGetLastError() == hipSuccess ? LKGD_OK : LKGD_E_LAUNCH;
+}
+
+extern "C" int lkgd_cfg_fusion_euler_step(const void* noise_tokens, void* latents, int32_t latents_is_f32,
+                                          const float* guidance, const float* weight, int32_t B, int32_t F, int32_t H,
+                                          int32_t W, int32_t cfg, float sigma, float sigma_next,
+                                          int32_t prediction_type, lkgd_stream_t stream) {
+  if (!noise_tokens || !latents || !weight) return LKGD_E_NULL;
+  if (cfg == 2 && !guidance) return LKGD_E_NULL;
+  if (B <= 0 || (B & 1) || F <= 0 || H <= 0 || W <= 0 || (cfg != 1 && cfg != 2) || !(sigma > 0.f))
+    return LKGD_E_SHAPE;
+  if (prediction_type != 0 && prediction_type != 1) return LKGD_E_MODE;
+  if ((uintptr_t)noise_tokens & 7) return LKGD_E_ALIGN;
+  const long long pairs = (long long)(B / 2) * F * H * W;
+  if (latents_is_f32)
+    hipLaunchKernelGGL(cfg_fusion_euler_kernel<float>, dim3(grid_for(pairs, 256)), dim3(256), 0, (hipStream_t)stream,
+                       (const half_t*)noise_tokens, (float*)latents, guidance, weight, B, F, H * W, cfg, sigma,
+                       sigma_next, prediction_type);
+  else
+    hipLaunchKernelGGL(cfg_fusion_euler_kernel<half_t>, dim3(grid_for(pairs, 256)), dim3(256), 0, (hipStream_t)stream,
+                       (const half_t*)noise_tokens, (half_t*)latents, guidance, weight, B, F, H * W, cfg, sigma,
+                       sigma_next, prediction_type);
   return hipGetLastError() == hipSuccess ? LKGD_OK : LKGD_E_LAUNCH;
 }
 

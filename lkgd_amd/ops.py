@@ -543,6 +543,28 @@ def cfg_euler_step(noise_tokens: torch.Tensor, latents: torch.Tensor, guidance: 
     return latents
 
 
+def cfg_fusion_euler_step(noise_tokens: torch.Tensor, latents: torch.Tensor, guidance: Optional[torch.Tensor],
+                          weight: torch.Tensor, cfg: int, sigma: float, sigma_next: float,
+                          v_prediction: bool = True) -> torch.Tensor:
+    """direct-fusion Euler step (lkgd_cfg_fusion_euler_step): in-place update of ``latents`` [B,F,4,H,W] (B = 2P clips, clip
+    b + P the backward partner of clip b) from channels-last noise tokens [cfg*B*F*H*W, 4]; ``weight`` fp32 [F] on the device
+    (torch.linspace(1, 0, F)), ``guidance`` fp32 [F] on the device (or None when cfg == 1)"""
+    B, F, _, H, W = latents.shape
+    _req(noise_tokens, torch.float16, "noise_tokens")
+    _req(weight, torch.float32, "weight")
+    if guidance is not None:
+        _req(guidance, torch.float32, "guidance")
+    if not latents.is_cuda or latents.dtype not in (torch.float16, torch.float32):
+        raise _lib.LkgdHipError("latents must be a GPU fp16/fp32 tensor")
+    assert latents.is_contiguous() and noise_tokens.is_contiguous() and weight.is_contiguous()
+    assert weight.numel() == F and (guidance is None or guidance.numel() == F)
+    check(_L().lkgd_cfg_fusion_euler_step(noise_tokens.data_ptr(), latents.data_ptr(),
+                                          int(latents.dtype == torch.float32), _ptr(guidance), weight.data_ptr(), B, F,
+                                          H, W, cfg, sigma, sigma_next, 1 if v_prediction else 0, _stream()),
+          "lkgd_cfg_fusion_euler_step")
+    return latents
+
+
 def shard_rows(src: torch.Tensor, dst: torch.Tensor, fl: int, HW: int, C_: int, px, pack: bool) -> torch.Tensor:
     """pack: src [fl, HW, C] -> dst rows grouped by destination pixel shard (px = pixels per shard); not pack: the inverse
     (lkgd_shard_rows).  Both contiguous fp16."""

@@ -245,17 +245,25 @@ class StableVideoDiffusionPipeline:
                 max_guidance_scale: float = 3.0, domain_features: Optional[torch.Tensor] = None,
                 flow_features: Optional[torch.Tensor] = None, callback_on_step_end: Optional[Callable] = None,
                 callback_on_step_end_tensor_inputs: List[str] = ["latents"],
-                controlnet_condition: Optional[torch.Tensor] = None, controlnet_cond_scale: float = 1.0) -> torch.Tensor:
+                controlnet_condition: Optional[torch.Tensor] = None, controlnet_cond_scale: float = 1.0,
+                start_step: int = 0, direct_fusion: bool = False, controlnet_scale: float = 1.0) -> torch.Tensor:
         """Reference loop :503-640.  ``latents`` [B,F,4,h,w] already scaled by init_noise_sigma (fp16 or fp32, updated
         in place and returned); ``image_latents`` [cfg*B,F,4,h,w] fp16; ``image_embeddings`` [cfg*B,1,1024].
         ``controlnet_condition`` [cfg*B,F,3,8h,8w] (already preprocessed and duplicated for CFG) runs ``self.controlnet``
-        before the UNet every step and feeds its residuals in (pipeline_stable_video_diffusion_controlnet.py:582-607)."""
+        before the UNet every step and feeds its residuals in (pipeline_stable_video_diffusion_controlnet.py:582-607).
+        pipeline_stable_video_diffusion_trans_controlnet.py adds (defaults = the loop above): ``start_step`` skips the first
+        Euler steps and their callbacks (:571-574); ``controlnet_scale`` multiplies every residual on top of
+        ``controlnet_cond_scale`` (:594-598), folded into the zero-convolution epilogue; ``direct_fusion`` switches the joint
+        hooks off (:568) and fuses clip b with the frame-reversed clip b + B/2 through their x0 once per step (:637-667,
+        lkgd_cfg_fusion_euler_step)."""
         unet, sch = self.unet, self.scheduler
         dev = unet.device
         B, F, _, H, W = latents.shape
         cfg = 2 if max_guidance_scale > 1 else 1
         if image_latents.shape[0] != cfg * B or image_embeddings.shape[0] != cfg * B:
             raise ValueError("image_latents / image_embeddings must carry cfg*batch entries (uncond first)")
+        if direct_fusion and B % 2:
+            raise ValueError(f"direct_fusion pairs clip b with clip b + B/2: the clip count must be even, got {B}")
         latents = latents.to(dev).contiguous()
         image_latents = image_latents.to(device=dev, dtype=torch.float16).contiguous()
         sch.set_timesteps(num_inference_steps, device=None)
@@ -271,7 +279,11 @@ class StableVideoDiffusionPipeline:
         ids = added_time_ids.to(dev)
         vpred = sch.config.prediction_type == "v_prediction"
         from . import patch as _patch
-        _patch.set_joint_attention(unet, enable=True)           # reference :555 (no-op unless the model is patched)
+        _patch.set_joint_attention(unet, enable=not direct_fusion)     # reference :555 / trans_controlnet :568 (no-op unless
+                                                                       # the model is patched)
+        # trans_controlnet :660: torch.linspace(1, 0, F) in fp32, made once per clip on the host and copied to the device
+        fusion_w = torch.linspace(1, 0, F, dtype=torch.float32).to(dev) if direct_fusion else None
+        ctrl_scale = float(controlnet_cond_scale) * float(controlnet_scale)    # both scale accumulator and bias (s_acc)
         ctrl = None
         if controlnet_condition is not None:
             if self.controlnet is None:
@@ -298,13 +310,15 @@ class StableVideoDiffusionPipeline:
                 down = mid = None
                 if ctrl is not None:
                     down, mid, _ = self.controlnet.forward_tokens(tok_buf, cfg * B, F, H, W, t_dev, enc_r, ids_r, ctrl,
-                                                                  controlnet_cond_scale)
+                                                                  ctrl_scale)
                 return unet.forward_tokens(tok_buf, cfg * B, F, H, W, t_dev, enc_r, ids_r, down, mid)[0]
         timers = _trace.StepTimers() if _trace.STEP_TIMERS else None      # LKGD_STEP_TIMERS=1: device ms per Euler step
         self.last_step_timers = timers
         recorded = None
         try:
             for i, t in enumerate(sch.timesteps_host):
+                if i < start_step:          # trans_controlnet :571-574: skipped steps run nothing, not even the callback
+                    continue
                 sigma, sigma_next = sch.sigmas_host[i], sch.sigmas_host[i + 1]
                 _trace.push(f"euler_step_{i}")                                  # roctx range (LKGD_ROCTX=1), else a no-op
                 t_ev = timers.start() if timers is not None else None
@@ -325,9 +339,13 @@ class StableVideoDiffusionPipeline:
                     down = mid = None
                     if ctrl is not None:      # residuals stay channels-last token matrices between the two models
                         down, mid, _ = self.controlnet.forward_tokens(tok, cfg * B, F, H, W, t, enc, ids, ctrl,
-                                                                      controlnet_cond_scale)
+                                                                      ctrl_scale)
                     noise_tok, _ = unet.forward_tokens(tok, cfg * B, F, H, W, t, enc, ids, down, mid)
-                ops.cfg_euler_step(noise_tok, latents, guidance_dev, cfg, sigma, sigma_next, v_prediction=vpred)
+                if direct_fusion:
+                    ops.cfg_fusion_euler_step(noise_tok, latents, guidance_dev, fusion_w, cfg, sigma, sigma_next,
+                                              v_prediction=vpred)
+                else:
+                    ops.cfg_euler_step(noise_tok, latents, guidance_dev, cfg, sigma, sigma_next, v_prediction=vpred)
                 if timers is not None:
                     timers.stop(t_ev)
                 _trace.pop()
@@ -357,14 +375,28 @@ class StableVideoDiffusionPipeline:
         """hook between the loop and the VAE decode (identity here; the flow pipeline un-normalises)"""
         return latents
 
+    def _controlnet_condition_batch(self, cc, height: int, width: int, device, cfg: bool) -> torch.Tensor:
+        """reference pipeline_stable_video_diffusion_controlnet.py:546-550: VaeImageProcessor.preprocess ([0,1] -> [-1,1]), add
+        the batch axis, duplicate for CFG"""
+        if isinstance(cc, torch.Tensor) and cc.dim() == 5:      # already batched [1,F,3,H,W] in [0,1]
+            cc = 2.0 * cc.to(device) - 1.0
+        else:
+            cc = self.image_processor.preprocess(cc, height=height, width=width).to(device)
+        if cc.dim() == 4:
+            cc = cc.unsqueeze(0)
+        return torch.cat([cc] * 2) if cfg else cc
+
     def _graphed_forward(self, Bc: int, F: int, H: int, W: int, enc: torch.Tensor, ids: torch.Tensor):
         """HIP-graph replay of ``unet.forward_tokens`` for fixed shapes / conditioning.  Static buffers: input tokens,
         timestep scalar; the captured kernels are exactly the ones the eager path launches (same stream semantics:
         everything in lkgd_amd/csrc is capturable - no allocation or sync inside).  Re-captured when shapes, weights or
         the conditioning tensors change."""
         unet = self.unet
+        # the joint hooks' on/off state is part of the captured launch sequence: a graph captured with them on never replays
+        # with them off (direct_fusion switches them off)
+        joint = tuple(bool(m.enable_joint_attention) for m in unet.modules() if hasattr(m, "enable_joint_attention"))
         key = (Bc, F, H, W, enc.data_ptr(), enc._version, ids.data_ptr(), ids._version, id(unet._pk),
-               getattr(unet, "_joint_attn_mask", None) is not None)
+               getattr(unet, "_joint_attn_mask", None) is not None, joint)
         g = self._graph
         if g is not None and g.key == key:
             return g
@@ -407,7 +439,10 @@ class StableVideoDiffusionPipeline:
                  image_embeddings: Optional[torch.Tensor] = None, image_latents: Optional[torch.Tensor] = None,
                  domain_features: Optional[torch.Tensor] = None, flow_features: Optional[torch.Tensor] = None,
                  # pipeline_stable_video_diffusion_controlnet.py:356-380: a [F,3,H,W] (or [1,F,3,H,W]) tensor in [0,1]
-                 controlnet_condition: Optional[torch.Tensor] = None, controlnet_cond_scale: float = 1.0):
+                 controlnet_condition: Optional[torch.Tensor] = None, controlnet_cond_scale: float = 1.0,
+                 # pipeline_stable_video_diffusion_trans_controlnet.py:354-380 (StableVideoDiffusionPipelineTransControlNet)
+                 original_latents: Optional[torch.Tensor] = None, start_step: int = 0, direct_fusion: bool = False,
+                 controlnet_scale: float = 1.0):
         height = height or self.unet.config.sample_size * self.vae_scale_factor
         width = width or self.unet.config.sample_size * self.vae_scale_factor
         num_frames = num_frames if num_frames is not None else self.unet.config.num_frames
@@ -461,20 +496,25 @@ class StableVideoDiffusionPipeline:
         self.scheduler.set_timesteps(num_inference_steps, device=None)
         lat = self.prepare_latents(batch_size * num_videos_per_prompt, num_frames, self.unet.config.in_channels,
                                    height, width, torch.float16, device, generator, latents)
+        if direct_fusion:
+            # trans_controlnet :660-666: the fp32 linspace weight promotes the reference's latents to fp32 at the first fused
+            # step; here they are carried in fp32 from the start (prepare_unet_input and the fused step both take fp32)
+            lat = lat.float()
+        if original_latents is not None:
+            # trans_controlnet :528-529: scheduler.add_noise(original_latents, randn_like(latents), timesteps[[start_step]]) -
+            # an SDEdit start; the noise comes from the global RNG of the latents' device, as the reference draws it.  Once per
+            # clip, before the loop
+            noise = torch.randn_like(lat)
+            orig = original_latents.to(device)
+            lat = (orig + noise * torch.tensor(self.scheduler.sigmas_host[start_step], dtype=orig.dtype,
+                                               device=device)).to(lat.dtype).contiguous()
         if controlnet_condition is not None:
-            # reference :546-550: VaeImageProcessor.preprocess ([0,1] -> [-1,1]), add the batch axis, duplicate for CFG
-            cc = controlnet_condition
-            if isinstance(cc, torch.Tensor) and cc.dim() == 5:      # already batched [1,F,3,H,W] in [0,1]
-                cc = 2.0 * cc.to(device) - 1.0
-            else:
-                cc = self.image_processor.preprocess(cc, height=height, width=width).to(device)
-            if cc.dim() == 4:
-                cc = cc.unsqueeze(0)
-            controlnet_condition = torch.cat([cc] * 2) if cfg else cc
+            controlnet_condition = self._controlnet_condition_batch(controlnet_condition, height, width, device, cfg)
         lat = self.denoise(lat, image_latents.contiguous(), image_embeddings, added_time_ids, num_inference_steps,
                            min_guidance_scale, max_guidance_scale, domain_features, flow_features,
                            callback_on_step_end, callback_on_step_end_tensor_inputs, controlnet_condition,
-                           controlnet_cond_scale)
+                           controlnet_cond_scale, start_step=start_step, direct_fusion=direct_fusion,
+                           controlnet_scale=controlnet_scale)
         if output_type != "latent":
             frames = self.decode_latents(self._latents_for_decode(lat), num_frames, decode_chunk_size)
             frames = tensor2vid(frames, self.image_processor, output_type=output_type)               # reference :644
@@ -504,6 +544,40 @@ class StableVideoDiffusionPipelineControlNet(StableVideoDiffusionPipeline):
 
     def _condition(self, controlnet_condition):
         return controlnet_condition
+
+
+class StableVideoDiffusionPipelineTransControlNet(StableVideoDiffusionPipeline):
+    """/root/reference/pipeline/pipeline_stable_video_diffusion_trans_controlnet.py: the joint-attention pair pipeline with the
+    ControlNet (signature :354-380).  ``controlnet_condition`` is one [F,C,H,W] condition or a list with one per clip
+    (:531-541); ``original_latents`` + ``start_step`` start from noised latents and skip the first steps (:528-529, :571-574);
+    ``controlnet_scale`` multiplies every residual on top of ``controlnet_cond_scale`` (:594-598); ``direct_fusion`` switches
+    the joint hooks off and fuses clip b with the frame-reversed clip b + B/2 through their x0 once per step (:637-667).
+    Its fused branch also draws ``randn_tensor(..., generator=generator)`` every step (:648-650); that noise is never read and
+    nothing downstream uses the generator, so it is not drawn here.  Single-GPU only: under frame sharding the blend pairs
+    frame f with frame F-1-f, which another rank holds (lkgd_amd/dist_run.py does not take these arguments)."""
+
+    def __call__(self, image, controlnet_condition=None, height: int = 576, width: int = 1024, num_frames=None,
+                 num_inference_steps: int = 25, min_guidance_scale: float = 1.0, max_guidance_scale: float = 3.0,
+                 fps: int = 7, motion_bucket_id: int = 127, noise_aug_strength: float = 0.02, decode_chunk_size=None,
+                 num_videos_per_prompt=1, generator=None, latents=None, output_type="pil", callback_on_step_end=None,
+                 callback_on_step_end_tensor_inputs=["latents"], return_dict: bool = True, controlnet_cond_scale=1.0,
+                 original_latents=None, start_step=0, direct_fusion=False, controlnet_scale=1.0, **extensions):
+        return super().__call__(image, height, width, num_frames, num_inference_steps, min_guidance_scale,
+                                max_guidance_scale, fps, motion_bucket_id, noise_aug_strength, decode_chunk_size,
+                                num_videos_per_prompt, generator, latents, output_type, callback_on_step_end,
+                                callback_on_step_end_tensor_inputs, return_dict,
+                                controlnet_condition=controlnet_condition, controlnet_cond_scale=controlnet_cond_scale,
+                                original_latents=original_latents, start_step=start_step, direct_fusion=direct_fusion,
+                                controlnet_scale=controlnet_scale, **extensions)
+
+    def _controlnet_condition_batch(self, cc, height: int, width: int, device, cfg: bool) -> torch.Tensor:
+        """:531-541: every entry preprocessed and given a batch axis, then ``torch.cat(conds * 2)``: under CFG that lines up with
+        [uncond clips..., cond clips...].  Without CFG the reference's batch would be twice the latent batch (its call cannot
+        run); one copy per clip is passed instead (deviations)"""
+        if not isinstance(cc, list):
+            cc = [cc]
+        conds = [self.image_processor.preprocess(c, height=height, width=width).unsqueeze(0) for c in cc]
+        return torch.cat(conds * 2 if cfg else conds).to(device)
 
 
 class StableVideoDiffusionPipelineControlNetFlow(StableVideoDiffusionPipelineControlNet):

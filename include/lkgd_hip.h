@@ -13,6 +13,32 @@
  *   - no allocation, no synchronisation, no global state inside; safe on any stream; graph-capturable (the debug
  *     knobs declared at the end of this file are the one exception and say so).
  *   - return value: 0 = launched; negative = LKGD_E_* (nothing was launched).
+ *
+ * Footprint contract (enforced per entry point by tests/test_footprint_gpu.py): callers hand these functions VIEWS - column
+ * blocks of a wider matrix, a frame slice of a token matrix - that sit packed against other live tensors.  An entry point
+ * therefore WRITES only the logical [rows, width] elements of each output at the given leading dimension: not the `ld - width`
+ * gap of any row, not a row before the first or after the last, not the dead rows or columns of a ragged last tile; scratch
+ * buffers (`partial`, `workspace`, `colstats`) are written only within the size their parameter documents.  And whatever it
+ * READS outside the logical window of an input - a clamped or masked lane, the padding channel of a wide load - never
+ * influences a result: the output is bit for bit the one the same call gives on compact, exactly-sized operands, as long as
+ * alignment leaves the choice of program the same (see below).
+ *
+ * Alignment.  Unless noted, fp16 matrices are 16-byte aligned with ld % 8 == 0 (LKGD_E_ALIGN otherwise) and ld >= width.  The
+ * entry points whose rule differs, as their checks state it:
+ *     lkgd_gemm_f16            a0 / a1 / w / zeros / bias 16 bytes, lda % 8; out 8 bytes, ldc / ldr1 / ldr2 / ldrb % 4, N % 4
+ *                              (rows that are not 16-byte pieces - N, ldc or ldr % 8 != 0, out / res not 16-byte aligned - keep
+ *                              the persistent programs out: the 128-row tile programs run); LKGD_A_CONV3X3_C8: lda0 == 8
+ *     lkgd_attn_spatial(_qk)   q / k / v 16 bytes, ld % 8; out 8 bytes, ldo % 4
+ *     lkgd_attn_dense          q / k / v 16 bytes, ld % 8; out 4 bytes, ldo % 2
+ *     lkgd_time_conv_out       tokens 8 bytes, ld % 4, ld >= 4 (every load takes 4 channels: the 4th is never used)
+ *     lkgd_cfg_euler_step, lkgd_cfg_fusion_euler_step   noise tokens 8 bytes (ld = 4 by definition); latents: element aligned
+ *     lkgd_prepare_unet_input  tokens_out 16 bytes (ld = 8 by definition); latents: element aligned
+ *     lkgd_groupnorm_finalize_parts  parts 4 bytes;  lkgd_groupnorm_apply_segments  the table 8 bytes, ld % 8
+ *     lkgd_groupnorm_stats_cols      fp32 column sums: ldcs % 2 (column pairs)
+ *     lkgd_gelu_tanh           16 bytes and n % 8 == 0 (LKGD_E_SHAPE);  lkgd_silu / lkgd_add: 16 bytes, any n
+ *     lkgd_tokens_to_nchw, lkgd_nchw_to_tokens, lkgd_timestep_embedding, lkgd_scale, lkgd_euler_step(_churn),
+ *     lkgd_conv1d_reflect, lkgd_resize_bicubic_ac, lkgd_vit_patchify, lkgd_lk_fuse: element aligned, any ld >= width
+ *     lkgd_gated_add           x / res / out / gate 16 bytes
  */
 #ifndef LKGD_HIP_H
 #define LKGD_HIP_H

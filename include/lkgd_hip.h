@@ -119,7 +119,7 @@ typedef struct lkgd_gemm_desc {
                               and one zero row / column at the bottom / right - F.pad(x, (0,1,0,1)) + stride-2 conv with
                               padding 0, the VAE encoder's Downsample2D [EXT diffusers downsampling.py] */
   void* workspace;         /* optional fp32 scratch for split-K partial sums (NULL = never split).  Few-row problems */
-  int64_t workspace_bytes; /* (M < 8192: the 18x32 / 9x16 levels, or a frame-sharded rank's slice) fill a fraction of
+  int64_t workspace_bytes; /* (M < 12288: the 18x32 / 9x16 levels, or a frame-sharded rank's slice) fill a fraction of
                               the CUs with 128x128 tiles; K is then cut into up to 16 slices whose fp32 partial tiles
                               go to [slice][M][N] here and a second kernel adds them in slice order and runs the
                               epilogue - deterministic, no atomics.  One GEMM at a time may use a workspace. */
@@ -146,6 +146,20 @@ int lkgd_gemm_f16(const lkgd_gemm_desc* d, lkgd_stream_t stream);
 /* rows per `colstats` block of the tile program lkgd_gemm_f16 will run for this descriptor (its colstats field is ignored);
  * 0 = that program does not produce column statistics */
 int lkgd_gemm_colstats_block(const lkgd_gemm_desc* d);
+/* what lkgd_gemm_f16 decides on the host for this descriptor - the same code path it launches from, so the answer is what runs.
+ * cus = compute units to plan for; 0 = ask the current device.  With cus != 0 nothing touches the device and no pointer of the
+ * descriptor is dereferenced: only NULL-ness and alignment of the pointers matter (introspection for tests and tools; honours the
+ * calling thread's debug knobs like the launch does).  Returns 0 or the LKGD_E_* lkgd_gemm_f16 would return before launching. */
+typedef struct lkgd_gemm_plan_info {
+  int32_t program;        /* 1 = 128x128 two-stage, 2 = 256x128 ring, 3 = persistent 256x128, 4 = 256x320 family, 5 = row-panel,
+                             6 = resident-weight, 7 = 128x128 on the four-stage ring */
+  int32_t k_slices;       /* 1 = K not cut; > 1: that many partial launches + the reduce pass (programs 1, 4, 7) */
+  int32_t tile_m, tile_n; /* rows x columns of one tile: program 4's form (256 | 192) x (320 | 256); 128x128, 256x128, the
+                             row-panel's 256x64, the resident-weight program's 32 rows per wave x 160-column slab */
+  int32_t colstats_block; /* = lkgd_gemm_colstats_block(d) at this cus */
+  int32_t lds_out;        /* program 4: 1 = output rows leave through LDS, 0 = direct stores (always 0 for other programs) */
+} lkgd_gemm_plan_info;
+int lkgd_gemm_plan(const lkgd_gemm_desc* d, int32_t cus, lkgd_gemm_plan_info* out);
 /* tile columns of the widest tile program for an output of N columns: 320, or 256 where 256 divides N and 320-column tiles would
  * idle more than a tenth of their columns (N = 256, 512, 768: the temporal VAE decoder's widths, diffusers
  * AutoencoderKLTemporalDecoder block_out_channels (128, 256, 512, 512)) - introspection for tests and tools */

@@ -41,6 +41,12 @@ class GemmDesc(C.Structure):
     ]
 
 
+class GemmPlanInfo(C.Structure):
+    """struct lkgd_gemm_plan_info (include/lkgd_hip.h)."""
+    _fields_ = [("program", C.c_int32), ("k_slices", C.c_int32), ("tile_m", C.c_int32), ("tile_n", C.c_int32),
+                ("colstats_block", C.c_int32), ("lds_out", C.c_int32)]
+
+
 #: every symbol include/lkgd_hip.h declares: name -> (restype, argtypes)
 _vp, _i32, _i64, _f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_float
 class FsmDesc(C.Structure):
@@ -59,6 +65,7 @@ class FsmDesc(C.Structure):
 SYMBOLS = {
     "lkgd_gemm_f16": (_i32, [C.POINTER(GemmDesc), _vp]),
     "lkgd_gemm_colstats_block": (_i32, [C.POINTER(GemmDesc)]),
+    "lkgd_gemm_plan": (_i32, [C.POINTER(GemmDesc), _i32, C.POINTER(GemmPlanInfo)]),
     "lkgd_gemm_wide_tile_n": (_i32, [_i32]),
     "lkgd_groupnorm_stats_cols": (_i32, [_vp, _i32, _i32, _i32, _vp, _i32, _i32, _i32, _i64, _i64, _f32, _i32, _vp, _vp]),
     "lkgd_groupnorm_chunks": (_i32, [_i64, _i32]),

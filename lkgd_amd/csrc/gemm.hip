@@ -685,20 +685,119 @@ static void gemm_wide_form(const lkgd_gemm_desc* d, int cus, int slices, int* wn
   }
 }
 
-extern "C" int lkgd_gemm_colstats_block(const lkgd_gemm_desc* d) {
-  if (!d || check_desc(d) != LKGD_OK || d->geglu || d->N % 8) return 0;
-  int cus = 0;
-  if (gemm_cus(&cus) != LKGD_OK) return 0;
+extern "C" int lkgd_gemm_wide_lds_out(const lkgd_gemm_desc* d, int ksplit, int wn);   // gemm_wide.hip: 1 rows through LDS, 0 direct, < 0 LKGD_E_*
+
+// K slices of the two-stage 128x128 program.  Split-K when the tiles leave workgroup slots (2 per CU) idle: the smallest slice
+// count whose blocks fill >= 85 % of the rounds they occupy, slices of >= 4 K-tiles when less than half the slots are filled
+// (few-row problems: the reduce pass is tiny) and of >= 32 K-tiles otherwise (the 3x3 convs of the full model's 9x16 level:
+// 320 tiles on 512 slots -> 3 slices, 0.172 -> 0.150 ms; its K = 3840 temporal convs lose more in the reduce pass than they
+// gain); bounded by the caller's workspace (include/lkgd_hip.h: lkgd_gemm_desc.workspace).  *per_out = K-tiles per slice
+static int tile128_split(const lkgd_gemm_desc* d, long long nwg, int cus, int* per_out) {
+  int ksplit = 1, per = d->K / BK;
+  const int nk = d->K / BK;
+  const long long slots = 2LL * cus;
+  if (gemm_splitk_enabled && d->workspace && aligned16(d->workspace) && d->N % 4 == 0 && nk >= 8 &&
+      nwg * 10 < slots * 7) {
+    const bool few = nwg * 2 <= slots;
+    const int min_slice = few ? 4 : 32;
+    long long cap = nk / min_slice;
+    if (cap > 16) cap = 16;
+    const long long fit = d->workspace_bytes / ((long long)d->M * d->N * 4);
+    if (cap > fit) cap = fit;
+    long long want = 1;
+    for (long long ks = 2; ks <= cap; ++ks) {
+      const long long blocks = nwg * ks, rounds = (blocks + slots - 1) / slots;
+      if (blocks * 100 >= rounds * slots * 85 || (few && ks == cap)) { want = ks; break; }
+    }
+    if (few && slots / nwg > want && slots / nwg <= cap) want = slots / nwg;   // fill one whole round
+    if (want >= 2) {
+      per = (int)((nk + want - 1) / want);
+      ksplit = (nk + per - 1) / per;           // every slice non-empty
+    }
+  }
+  *per_out = per;
+  return ksplit;
+}
+
+// Everything lkgd_gemm_f16 decides on the host for a CHECKED descriptor, in one place: lkgd_gemm_f16 launches from it and
+// lkgd_gemm_plan / lkgd_gemm_colstats_block report it, so what they say is what runs.
+struct gemm_plan {
+  int pick;        // 1..7 (gemm_pick)
+  int ks, per;     // K slices (1 = none) and K-tiles per slice (programs 1 and 7; the 256x320 program's slices are equal)
+  int wm, wn;      // tile rows x columns
+  int cs_blk;      // rows per colstats block, 0 = no column sums
+  int lds_out;     // 256x320 program: rows leave through LDS
+};
+
+static int gemm_make_plan(const lkgd_gemm_desc* d, int cus, gemm_plan* pl) {
   int wide_ks = 1;
   const int pick = gemm_pick(d, cus, &wide_ks);
-  if (pick == 6) return lkgd_gemm_resw_colstats_ok(d) ? 32 : 0;
-  // the 256x320 program sums the columns of the row segments it parks in LDS: whole 320-column tiles, unsliced K
-  if (pick == 4 && gemm_wide_slices(d, cus, pick, wide_ks) == 1 && d->ldc % 8 == 0 && aligned16(d->out)) {
-    int wn, wm;
-    gemm_wide_form(d, cus, 1, &wn, &wm);
-    return d->N % wn == 0 ? wm : 0;
+  if (pick < 0) return pick;
+  pl->pick = pick;
+  pl->ks = 1;
+  pl->per = d->K / BK;
+  pl->wm = BM;
+  pl->wn = BN;
+  pl->cs_blk = 0;
+  pl->lds_out = 0;
+  const bool cs_shape = !d->geglu && d->N % 8 == 0;
+  if (pick == 6) {
+    pl->wm = 32; pl->wn = 160;                   // a wave's 32 token rows x a 160-row weight slab (gemm_resw.hip)
+    if (cs_shape && lkgd_gemm_resw_colstats_ok(d)) pl->cs_blk = 32;
+  } else if (pick == 5) {
+    pl->wm = 256; pl->wn = 64;                   // gemm_rowpanel.hip
+  } else if (pick == 4) {
+    pl->ks = gemm_wide_slices(d, cus, pick, wide_ks);
+    gemm_wide_form(d, cus, pl->ks, &pl->wn, &pl->wm);
+    pl->per = (d->K / BK) / pl->ks;
+    // the 256x320 program sums the columns of the row segments it parks in LDS: whole 320-column tiles, unsliced K
+    if (cs_shape && pl->ks == 1 && d->ldc % 8 == 0 && aligned16(d->out) && d->N % pl->wn == 0) pl->cs_blk = pl->wm;
+    const int lo = lkgd_gemm_wide_lds_out(d, pl->ks, pl->wn);
+    pl->lds_out = lo > 0 ? 1 : 0;
+  } else if (pick == 3 || pick == 2) {
+    pl->wm = 256;                                // gemm_stream.hip / lkgd_gemm_kernel_256
+    if (pick == 2 && (long long)((d->M + BM2 - 1) / BM2) * ((d->N + BN - 1) / BN) > 0x7fffffffLL) return LKGD_E_SHAPE;
+  } else {
+    const long long nwg = (long long)((d->M + BM - 1) / BM) * ((d->N + BN - 1) / BN);
+    if (nwg > 0x7fffffffLL) return LKGD_E_SHAPE;
+    const int nk = d->K / BK;
+    if (pick == 7) {
+      const int ksplit = mid_split(d, nwg, nk, cus);
+      if (ksplit > 1) {
+        pl->per = (nk + ksplit - 1) / ksplit;
+        pl->ks = (nk + pl->per - 1) / pl->per;           // every slice non-empty
+      }
+    } else {
+      pl->ks = tile128_split(d, nwg, cus, &pl->per);
+    }
   }
-  return 0;
+  return LKGD_OK;
+}
+
+extern "C" int lkgd_gemm_plan(const lkgd_gemm_desc* d, int32_t cus, lkgd_gemm_plan_info* out) {
+  if (!out) return LKGD_E_NULL;
+  int rc = check_desc(d);
+  if (rc != LKGD_OK) return rc;
+  if (cus < 0) return LKGD_E_SHAPE;
+  int n = cus;
+  if (n == 0 && (rc = gemm_cus(&n)) != LKGD_OK) return rc;
+  gemm_plan pl;
+  if ((rc = gemm_make_plan(d, n, &pl)) != LKGD_OK) return rc;
+  out->program = pl.pick;
+  out->k_slices = pl.ks;
+  out->tile_m = pl.wm;
+  out->tile_n = pl.wn;
+  out->colstats_block = pl.cs_blk;
+  out->lds_out = pl.lds_out;
+  return LKGD_OK;
+}
+
+extern "C" int lkgd_gemm_colstats_block(const lkgd_gemm_desc* d) {
+  if (!d || check_desc(d) != LKGD_OK) return 0;
+  int cus = 0;
+  if (gemm_cus(&cus) != LKGD_OK) return 0;
+  gemm_plan pl;
+  return gemm_make_plan(d, cus, &pl) == LKGD_OK ? pl.cs_blk : 0;
 }
 
 extern "C" int lkgd_gemm_f16(const lkgd_gemm_desc* d, lkgd_stream_t stream) {
@@ -715,17 +814,15 @@ extern "C" int lkgd_gemm_f16(const lkgd_gemm_desc* d, lkgd_stream_t stream) {
   LKGD_DEVICE_ONCE_END
   int cus = 0;
   if ((rc = gemm_cus(&cus)) != LKGD_OK) return rc;
-  int wide_ks = 1;
-  const int pick = gemm_pick(d, cus, &wide_ks);
-  if (pick < 0) return pick;
-  if (d->colstats && lkgd_gemm_colstats_block(d) == 0) return LKGD_E_SHAPE;   // the chosen program produces no column sums
+  gemm_plan pl;
+  if ((rc = gemm_make_plan(d, cus, &pl)) != LKGD_OK) return rc;
+  const int pick = pl.pick;
+  if (d->colstats && pl.cs_blk == 0) return LKGD_E_SHAPE;   // the chosen program produces no column sums
   if (pick == 6) return lkgd_gemm_resw_launch(d, (hipStream_t)stream, cus);
   if (pick == 5) return lkgd_gemm_rowpanel_launch(d, (hipStream_t)stream, cus);
   if (pick == 4) {
-    const int ks = gemm_wide_slices(d, cus, pick, wide_ks);
-    int wn, wm;
-    gemm_wide_form(d, cus, ks, &wn, &wm);
-    rc = lkgd_gemm_wide_launch(d, (hipStream_t)stream, cus, ks, wn, wm);
+    const int ks = pl.ks;
+    rc = lkgd_gemm_wide_launch(d, (hipStream_t)stream, cus, ks, pl.wn, pl.wm);
     if (rc != LKGD_OK || ks == 1) return rc;
     const int tn128 = (d->N + BN - 1) / BN;
     const unsigned rblocks = (unsigned)(((d->M + 31) / 32) * tn128);
@@ -734,78 +831,31 @@ extern "C" int lkgd_gemm_f16(const lkgd_gemm_desc* d, lkgd_stream_t stream) {
     return hipGetLastError() == hipSuccess ? LKGD_OK : LKGD_E_LAUNCH;
   }
   if (pick == 3) return lkgd_gemm_stream_launch(d, (hipStream_t)stream, cus);
-  int tiles_n = (d->N + BN - 1) / BN;
-  if (pick == 7) {
-    const int tiles_m = (d->M + BM - 1) / BM;
-    const long long nwg = (long long)tiles_m * tiles_n;
-    if (nwg > 0x7fffffffLL) return LKGD_E_SHAPE;
-    const int nk = d->K / BK;
-    const int ksplit = mid_split(d, nwg, nk, cus);
-    if (ksplit > 1) {
-      const int per = (nk + ksplit - 1) / ksplit;
-      const int ks = (nk + per - 1) / per;           // every slice non-empty
-      hipLaunchKernelGGL(lkgd_gemm_mid_kernel, dim3((unsigned)nwg, (unsigned)ks), dim3(MID_NT), MID_LDS, (hipStream_t)stream, *d,
-                         tiles_m, tiles_n, ks, per, (float*)d->workspace);
-      const unsigned rblocks = (unsigned)(((d->M + 31) / 32) * tiles_n);
-      hipLaunchKernelGGL(lkgd_gemm_splitk_reduce, dim3(rblocks), dim3(256), 0, (hipStream_t)stream, *d, tiles_n, ks,
-                         (const float*)d->workspace);
-    } else {
-      hipLaunchKernelGGL(lkgd_gemm_mid_kernel, dim3((unsigned)nwg), dim3(MID_NT), MID_LDS, (hipStream_t)stream, *d, tiles_m,
-                         tiles_n, 1, nk, (float*)nullptr);
-    }
-    return hipGetLastError() == hipSuccess ? LKGD_OK : LKGD_E_LAUNCH;
-  }
+  const int tiles_n = (d->N + BN - 1) / BN;
   // deep-K problems (3x3 / temporal convs, K >= 960) take the 256x128 three-stage ring: its two K-tiles in flight hide
   // the HBM latency the two-stage kernel exposes every K-step.  Short-K GEMMs (K = 320/640 projections at 258k rows) are
   // epilogue-bound; they keep 128x128 tiles at two workgroups per CU so one workgroup's epilogue overlaps the other's
   // main loop (measured per shape: tools/gemm_shapes_bench.py, profiles/r01_gemm_shapes.txt).
   if (pick == 2) {
-    int tiles_m = (d->M + BM2 - 1) / BM2;
-    long long nwg = (long long)tiles_m * tiles_n;
-    if (nwg > 0x7fffffffLL) return LKGD_E_SHAPE;
-    hipLaunchKernelGGL(lkgd_gemm_kernel_256, dim3((unsigned)nwg), dim3(NT2), GEMM2_LDS, (hipStream_t)stream, *d,
+    const int tiles_m = (d->M + BM2 - 1) / BM2;
+    hipLaunchKernelGGL(lkgd_gemm_kernel_256, dim3((unsigned)(tiles_m * tiles_n)), dim3(NT2), GEMM2_LDS, (hipStream_t)stream, *d,
                        tiles_m, tiles_n);
-  } else {
-    int tiles_m = (d->M + BM - 1) / BM;
-    long long nwg = (long long)tiles_m * tiles_n;
-    if (nwg > 0x7fffffffLL) return LKGD_E_SHAPE;
-    // split-K when the tiles leave workgroup slots (2 per CU) idle: the smallest slice count whose blocks fill >= 85 % of
-    // the rounds they occupy, slices of >= 4 K-tiles when less than half the slots are filled (few-row problems: the reduce
-    // pass is tiny) and of >= 32 K-tiles otherwise (the 3x3 convs of the full model's 9x16 level: 320 tiles on 512 slots
-    // -> 3 slices, 0.172 -> 0.150 ms; its K = 3840 temporal convs lose more in the reduce pass than they gain);
-    // bounded by the caller's workspace (include/lkgd_hip.h: lkgd_gemm_desc.workspace)
-    int ksplit = 1, per = d->K / BK;
-    const int nk = d->K / BK;
-    const long long slots = 2LL * cus;
-    if (gemm_splitk_enabled && d->workspace && aligned16(d->workspace) && d->N % 4 == 0 && nk >= 8 &&
-        nwg * 10 < slots * 7) {
-      const bool few = nwg * 2 <= slots;
-      const int min_slice = few ? 4 : 32;
-      long long cap = nk / min_slice;
-      if (cap > 16) cap = 16;
-      const long long fit = d->workspace_bytes / ((long long)d->M * d->N * 4);
-      if (cap > fit) cap = fit;
-      long long want = 1;
-      for (long long ks = 2; ks <= cap; ++ks) {
-        const long long blocks = nwg * ks, rounds = (blocks + slots - 1) / slots;
-        if (blocks * 100 >= rounds * slots * 85 || (few && ks == cap)) { want = ks; break; }
-      }
-      if (few && slots / nwg > want && slots / nwg <= cap) want = slots / nwg;   // fill one whole round
-      if (want >= 2) {
-        per = (int)((nk + want - 1) / want);
-        ksplit = (nk + per - 1) / per;           // every slice non-empty
-      }
-    }
-    if (ksplit > 1) {
-      hipLaunchKernelGGL(lkgd_gemm_kernel, dim3((unsigned)nwg, (unsigned)ksplit), dim3(256), GEMM_LDS,
-                         (hipStream_t)stream, *d, tiles_m, tiles_n, ksplit, per, (float*)d->workspace);
-      const unsigned rblocks = (unsigned)(((d->M + 31) / 32) * tiles_n);
-      hipLaunchKernelGGL(lkgd_gemm_splitk_reduce, dim3(rblocks), dim3(256), 0, (hipStream_t)stream, *d, tiles_n, ksplit,
-                         (const float*)d->workspace);
-    } else {
-      hipLaunchKernelGGL(lkgd_gemm_kernel, dim3((unsigned)nwg), dim3(256), GEMM_LDS, (hipStream_t)stream, *d, tiles_m,
-                         tiles_n, 1, nk, (float*)nullptr);
-    }
+    return hipGetLastError() == hipSuccess ? LKGD_OK : LKGD_E_LAUNCH;
+  }
+  // programs 1 (two LDS stages) and 7 (four-stage ring): 128x128 tiles, pl.ks K slices of pl.per K-tiles + the reduce pass
+  const int tiles_m = (d->M + BM - 1) / BM;
+  const unsigned nwg = (unsigned)(tiles_m * tiles_n);
+  float* ws = pl.ks > 1 ? (float*)d->workspace : (float*)nullptr;
+  const dim3 grid = pl.ks > 1 ? dim3(nwg, (unsigned)pl.ks) : dim3(nwg);
+  if (pick == 7)
+    hipLaunchKernelGGL(lkgd_gemm_mid_kernel, grid, dim3(MID_NT), MID_LDS, (hipStream_t)stream, *d, tiles_m, tiles_n, pl.ks, pl.per,
+                       ws);
+  else
+    hipLaunchKernelGGL(lkgd_gemm_kernel, grid, dim3(256), GEMM_LDS, (hipStream_t)stream, *d, tiles_m, tiles_n, pl.ks, pl.per, ws);
+  if (pl.ks > 1) {
+    const unsigned rblocks = (unsigned)(((d->M + 31) / 32) * tiles_n);
+    hipLaunchKernelGGL(lkgd_gemm_splitk_reduce, dim3(rblocks), dim3(256), 0, (hipStream_t)stream, *d, tiles_n, pl.ks,
+                       (const float*)d->workspace);
   }
   return hipGetLastError() == hipSuccess ? LKGD_OK : LKGD_E_LAUNCH;
 }

@@ -607,6 +607,16 @@ static bool wide_set_lds(const void* split_fn) {
   return true;
 }
 
+// do the output rows of this launch leave through LDS?  1 = yes, 0 = direct 8-byte stores, LKGD_E_SHAPE = column sums asked for
+// where the rows cannot go through LDS (host-side: also what lkgd_gemm_plan reports)
+extern "C" int lkgd_gemm_wide_lds_out(const lkgd_gemm_desc* d, int ksplit, int wn) {
+  // plain linears without GEGLU, whole tile columns, 16-byte aligned output rows: the rows leave through LDS (see the epilogue)
+  // (the convolutions only when column statistics are asked for: they are summed from the rows in LDS)
+  const bool lds_ok = ksplit == 1 && !d->geglu && d->N % wn == 0 && d->ldc % 8 == 0 && aligned16(d->out);
+  if (d->colstats && !lds_ok) return LKGD_E_SHAPE;
+  return lds_ok && (d->colstats ? true : (wide_lds_out_override != 0 && d->mode == LKGD_A_PLAIN)) ? 1 : 0;
+}
+
 // wn = tile columns (320 | 256), wm = tile rows (256 | 192): the caller's choice (gemm.hip: gemm_wide_form)
 extern "C" int lkgd_gemm_wide_launch(const lkgd_gemm_desc* d, hipStream_t stream, int cus, int ksplit, int wn, int wm) {
   LKGD_DEVICE_ONCE_BEGIN
@@ -625,11 +635,9 @@ extern "C" int lkgd_gemm_wide_launch(const lkgd_gemm_desc* d, hipStream_t stream
   int grid = ntiles < cus ? (int)ntiles : cus;
   if (d->M >= (1 << 24)) return LKGD_E_SHAPE;            // float-reciprocal row decomposition (gemm_common.h)
   float* ws = (float*)d->workspace;
-  // plain linears without GEGLU, whole tile columns, 16-byte aligned output rows: the rows leave through LDS (see the epilogue)
-  // (the convolutions only when column statistics are asked for: they are summed from the rows in LDS)
-  const bool lds_ok = ksplit == 1 && !d->geglu && d->N % wn == 0 && d->ldc % 8 == 0 && aligned16(d->out);
-  if (d->colstats && !lds_ok) return LKGD_E_SHAPE;
-  const bool lds_out = lds_ok && (d->colstats ? true : (wide_lds_out_override != 0 && d->mode == LKGD_A_PLAIN));
+  const int lo = lkgd_gemm_wide_lds_out(d, ksplit, wn);
+  if (lo < 0) return lo;
+  const bool lds_out = lo != 0;
 #define WIDE_LAUNCH(MODE_)                                                                                              \
   {                                                                                                                     \
     if (ksplit > 1)                                                                                                     \

@@ -110,24 +110,22 @@ def rowmap_div_mod(div: int, mod: int) -> RowMap:
     return (div, 1, 1, mod)
 
 
-def gemm(a0: torch.Tensor, w: torch.Tensor, out: torch.Tensor, *, M: int, N: int, K: int,
-         bias: Optional[torch.Tensor] = None, a1: Optional[torch.Tensor] = None, csplit: Optional[int] = None,
-         mode: int = A_PLAIN, Cin: int = 0, conv: Optional[Tuple[int, int, int, int, int, int]] = None,
-         tconv: Optional[Tuple[int, int]] = None, rowbias: Optional[torch.Tensor] = None,
-         rowmap: Optional[RowMap] = None, res1: Optional[torch.Tensor] = None, r1: float = 1.0,
-         res2: Optional[torch.Tensor] = None, r2: float = 1.0, s_acc: float = 1.0, geglu: int = 0,
-         colstats: int = 0, ln: Optional[Tuple[torch.Tensor, float]] = None) -> torch.Tensor:
-    """out = epilogue(A(.) @ w.T) - see include/lkgd_hip.h section 1.  ``conv`` = (Hout, Wout, Hin, Win, stride, ups);
-    ``tconv`` = (F, HW).  ``colstats`` = rows per GroupNorm sample (0 = off): ``out`` feeds a GroupNorm next - where the
-    tile program that will run supports it and its row blocks tile the samples, the GEMM leaves the per-(row block, channel
-    pair) sums of its rounded outputs and ``out`` carries them (``out._lkgd_colstats``) to :func:`groupnorm_stats`, which
-    then skips its read pass over the tensor."""
-    _req(a0, torch.float16, "a0"); _req(w, torch.float16, "w"); _req(out, torch.float16, "out")
+_FAKE_PTR = 1 << 12     # gemm_plan off the device: a non-NULL, 16-byte aligned stand-in for buffers the query never dereferences
+
+
+def _gemm_desc(a0, w, out, *, M, N, K, bias=None, a1=None, csplit=None, mode=A_PLAIN, Cin=0, conv=None, tconv=None,
+               rowbias=None, rowmap=None, res1=None, r1=1.0, res2=None, r2=1.0, s_acc=1.0, geglu=0, colstats=0, ln=None,
+               plan_cus=None):
+    """the lkgd_gemm_desc of a :func:`gemm` call.  ``plan_cus`` None: for launching (device tensors, the workspace and the column
+    sum buffer are allocated); an int: for :func:`gemm_plan` - the same fields and pointer classes, nothing allocated."""
+    launch = plan_cus is None
+    req = _req if launch or a0.is_cuda else (lambda t, dtype, name: None)
+    req(a0, torch.float16, "a0"); req(w, torch.float16, "w"); req(out, torch.float16, "out")
     d = GemmDesc()
     d.a0, d.w, d.out = a0.data_ptr(), w.data_ptr(), out.data_ptr()
     d.a1 = _ptr(a1)
     d.bias = _ptr(bias)
-    d.zeros = zeros_page(a0.device).data_ptr()
+    d.zeros = zeros_page(a0.device).data_ptr() if a0.is_cuda else _FAKE_PTR
     d.M, d.N, d.K = M, N, K
     d.lda0 = _ld(a0)
     d.lda1 = _ld(a1) if a1 is not None else 0
@@ -143,34 +141,62 @@ def gemm(a0: torch.Tensor, w: torch.Tensor, out: torch.Tensor, *, M: int, N: int
         d.F, d.HW = tconv[0], tconv[1]
         d.Floc, d.f_off = (tconv[2], tconv[3]) if len(tconv) == 4 else (tconv[0], 0)
     if rowbias is not None:
-        _req(rowbias, torch.float16, "rowbias")
+        req(rowbias, torch.float16, "rowbias")
         d.rowbias, d.ldrb = rowbias.data_ptr(), _ld(rowbias)
         d.rb_d1, d.rb_m1, d.rb_d2, d.rb_md = rowmap[:4]
         d.rb_c0 = rowmap[4] if len(rowmap) > 4 else 0
     if res1 is not None:
-        _req(res1, torch.float16, "res1")
+        req(res1, torch.float16, "res1")
         d.res1, d.ldr1 = res1.data_ptr(), _ld(res1)
     if res2 is not None:
-        _req(res2, torch.float16, "res2")
+        req(res2, torch.float16, "res2")
         d.res2, d.ldr2 = res2.data_ptr(), _ld(res2)
     d.ldc = _ld(out)
     d.s_acc, d.r1, d.r2 = s_acc, r1, r2
     d.geglu = int(geglu)        # 0 off, 32 / 80 = interleave width the weights were packed with
     if M < 12288:               # few-row problems may cut K into slices (lkgd_hip.h: lkgd_gemm_desc.workspace)
-        ws = splitk_workspace(out.device)
-        d.workspace, d.workspace_bytes = ws.data_ptr(), ws.numel() * 4
+        if launch or out.is_cuda:
+            ws = splitk_workspace(out.device)
+            d.workspace, d.workspace_bytes = ws.data_ptr(), ws.numel() * 4
+        else:
+            d.workspace, d.workspace_bytes = _FAKE_PTR, SPLITK_WORKSPACE_BYTES
     if ln is not None:           # LayerNorm of the A rows folded into the GEMM (lkgd_gemm_desc.ln_colsum)
-        _req(ln[0], torch.float32, "ln colsum")
+        req(ln[0], torch.float32, "ln colsum")
         d.ln_colsum, d.ln_eps = ln[0].data_ptr(), float(ln[1])
     if colstats and COLSTATS and out.shape[0] == M and out.shape[1] == N:
         d.cs_rows = int(colstats)        # the tile-form choice keeps to tile rows that divide a sample
-        blk = _L().lkgd_gemm_colstats_block(C.byref(d))
+        if launch:
+            blk = _L().lkgd_gemm_colstats_block(C.byref(d))
+        else:
+            info = _lib.GemmPlanInfo()
+            blk = info.colstats_block if _lib.lib().lkgd_gemm_plan(C.byref(d), int(plan_cus), C.byref(info)) == 0 else 0
         if blk > 0 and int(colstats) % blk == 0:
-            buf = torch.empty((M + blk - 1) // blk, N // 2, 2, dtype=torch.float32, device=out.device)   # channel pairs
-            d.colstats = buf.data_ptr()
-            out._lkgd_colstats = (buf, blk, out._version)      # see _stats_from_cols: void once `out` is written again
+            if launch:
+                buf = torch.empty((M + blk - 1) // blk, N // 2, 2, dtype=torch.float32, device=out.device)   # channel pairs
+                d.colstats = buf.data_ptr()
+                out._lkgd_colstats = (buf, blk, out._version)      # see _stats_from_cols: void once `out` is written again
+            else:
+                d.colstats = _FAKE_PTR
         else:
             d.cs_rows = 0                # no sums attached: the tile-form choice is not restricted either
+    return d
+
+
+def gemm(a0: torch.Tensor, w: torch.Tensor, out: torch.Tensor, *, M: int, N: int, K: int,
+         bias: Optional[torch.Tensor] = None, a1: Optional[torch.Tensor] = None, csplit: Optional[int] = None,
+         mode: int = A_PLAIN, Cin: int = 0, conv: Optional[Tuple[int, int, int, int, int, int]] = None,
+         tconv: Optional[Tuple[int, int]] = None, rowbias: Optional[torch.Tensor] = None,
+         rowmap: Optional[RowMap] = None, res1: Optional[torch.Tensor] = None, r1: float = 1.0,
+         res2: Optional[torch.Tensor] = None, r2: float = 1.0, s_acc: float = 1.0, geglu: int = 0,
+         colstats: int = 0, ln: Optional[Tuple[torch.Tensor, float]] = None) -> torch.Tensor:
+    """out = epilogue(A(.) @ w.T) - see include/lkgd_hip.h section 1.  ``conv`` = (Hout, Wout, Hin, Win, stride, ups);
+    ``tconv`` = (F, HW).  ``colstats`` = rows per GroupNorm sample (0 = off): ``out`` feeds a GroupNorm next - where the
+    tile program that will run supports it and its row blocks tile the samples, the GEMM leaves the per-(row block, channel
+    pair) sums of its rounded outputs and ``out`` carries them (``out._lkgd_colstats``) to :func:`groupnorm_stats`, which
+    then skips its read pass over the tensor."""
+    d = _gemm_desc(a0, w, out, M=M, N=N, K=K, bias=bias, a1=a1, csplit=csplit, mode=mode, Cin=Cin, conv=conv, tconv=tconv,
+                   rowbias=rowbias, rowmap=rowmap, res1=res1, r1=r1, res2=res2, r2=r2, s_acc=s_acc, geglu=geglu,
+                   colstats=colstats, ln=ln)
     ev = GEMM_EVENTS
     if ev is not None:
         s_ev, e_ev = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -181,6 +207,19 @@ def gemm(a0: torch.Tensor, w: torch.Tensor, out: torch.Tensor, *, M: int, N: int
         return out
     check(_L().lkgd_gemm_f16(C.byref(d), _stream()), "lkgd_gemm_f16")
     return out
+
+
+def gemm_plan(a0: torch.Tensor, w: torch.Tensor, out: torch.Tensor, *, cus: int = 0, **kwargs):
+    """what :func:`gemm` would run for the same arguments (lkgd_gemm_plan): a ``_lib.GemmPlanInfo`` - tile program 1..7, K slices,
+    tile rows x columns, colstats block, rows-through-LDS.  Nothing is launched or allocated.  ``cus`` = compute units to plan for
+    (0 = the current device's); with ``cus`` given the tensors may live anywhere - on the CPU too, only their strides and the
+    alignment of their addresses matter - and no GPU is needed.  The calling thread's debug knobs apply as they do to a launch."""
+    if cus == 0 and not a0.is_cuda:
+        raise _lib.LkgdHipError("gemm_plan: cus=0 asks the device, which needs GPU tensors (pass cus=... to plan without one)")
+    d = _gemm_desc(a0, w, out, plan_cus=int(cus), **kwargs)
+    info = _lib.GemmPlanInfo()
+    check(_lib.lib().lkgd_gemm_plan(C.byref(d), int(cus), C.byref(info)), "lkgd_gemm_plan")
+    return info
 
 
 #: A/B switch of the GroupNorm statistics from the producing GEMM's epilogue (False = always the separate read pass)

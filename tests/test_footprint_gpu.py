@@ -23,11 +23,12 @@ DEV = "cuda:0"
 # ------------------------------------------------------------------------------------------------------------ the registry
 #: every name in lkgd_amd._lib.SYMBOLS -> its footprint tests in this module, or "exempt: <reason>".  Only entry points that launch
 #: no kernel may be exempt (EXEMPT_ALLOWED, enforced literally by test_registry_covers_every_export).
-EXEMPT_ALLOWED = {"lkgd_gemm_colstats_block", "lkgd_gemm_wide_tile_n", "lkgd_groupnorm_chunks", "lkgd_version"}
+EXEMPT_ALLOWED = {"lkgd_gemm_colstats_block", "lkgd_gemm_plan", "lkgd_gemm_wide_tile_n", "lkgd_groupnorm_chunks", "lkgd_version"}
 REGISTRY = {
     "lkgd_gemm_f16": ["test_gemm_plain_and_epilogue", "test_gemm_two_source_geglu_ln_colstats", "test_gemm_conv_modes",
                       "test_gemm_unaligned_rows_fall_back", "test_gemm_split_k_workspace", "test_gemm_wide_forms"],
     "lkgd_gemm_colstats_block": "exempt: host-side query of the dispatcher, launches nothing",
+    "lkgd_gemm_plan": "exempt: host-side query of the dispatcher, launches nothing (writes its own lkgd_gemm_plan_info only)",
     "lkgd_gemm_wide_tile_n": "exempt: host-side query, launches nothing",
     "lkgd_groupnorm_chunks": "exempt: host-side size query, launches nothing",
     "lkgd_version": "exempt: returns a string",

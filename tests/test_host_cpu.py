@@ -390,3 +390,116 @@ def test_clip_module_takes_transformers_state_dict_names(tmp_path):
         m2(torch.zeros(1, 3, 28, 28))
     with pytest.raises(LkgdHipError):
         CLIPVisionModelWithProjection(CLIPVisionConfig(hidden_size=128, num_attention_heads=2, hidden_act="relu"))
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# lkgd_gemm_plan: the dispatcher's decision, asked without a GPU
+
+GEMM_CLASSES = ("plain", "rowmap", "two-source", "geglu", "conv3x3 stride 1 ups 0", "conv3x3 stride 2 ups 0", "conv3x3 stride 1 ups 1",
+                "tconv")
+#: the operand / epilogue classes each forced variant supports (lkgd_amd/csrc/gemm.hip::gemm_pick: the row-panel and resident-weight
+#: programs take a plain single-source A with K <= 320; the 80-wide GEGLU interleave exists on the 256x320 and resident-weight
+#: programs only, the 32-wide one on the others)
+VARIANT_CLASSES = {1: GEMM_CLASSES, 2: GEMM_CLASSES, 3: GEMM_CLASSES, 4: GEMM_CLASSES, 5: ("plain", "rowmap", "geglu"),
+                   6: ("plain", "rowmap", "geglu"), 7: GEMM_CLASSES}
+
+
+def test_gemm_plan_reports_what_the_front_end_would_launch():
+    from lkgd_amd import _lib, ops
+    e = lambda *s, dt=torch.float16: torch.empty(*s, dtype=dt)       # noqa: E731
+    M, N, K = 4032, 1280, 3840
+    p = ops.gemm_plan(e(M, K), e(N, K), e(M, N), M=M, N=N, K=K, bias=e(N, dt=torch.float32), cus=256)
+    assert (p.program, p.k_slices, p.tile_m, p.tile_n) == (4, 4, 256, 320)       # 64 tiles, deep K: four equal K slices
+    # without the workspace ops.gemm hands to problems below 12288 rows there is nothing to slice into
+    p = ops.gemm_plan(e(12288, K), e(N, K), e(12288, N), M=12288, N=N, K=K, cus=256)
+    assert p.program == 4 and p.k_slices == 1
+    # column sums: asked for -> the tile rows divide the sample, the rows leave through LDS, the block is the tile's rows
+    p = ops.gemm_plan(e(16128, 640), e(640, 640), e(16128, 640), M=16128, N=640, K=640, colstats=576, cus=256)
+    assert p.program == 4 and p.colstats_block == p.tile_m and 576 % p.tile_m == 0 and p.lds_out == 1
+    # rows that are not 16-byte pieces keep the persistent programs out
+    p = ops.gemm_plan(e(40000, 320), e(324, 320), e(40000, 324), M=40000, N=324, K=320, cus=256)
+    assert p.program in (1, 2, 7)
+    # the CU count is an input: fewer CUs, fewer idle ones to fill with K slices
+    p64 = ops.gemm_plan(e(M, K), e(N, K), e(M, N), M=M, N=N, K=K, cus=64)
+    assert p64.program == 4 and p64.k_slices == 1
+    with pytest.raises(_lib.LkgdHipError):
+        ops.gemm_plan(e(M, K), e(N, K), e(M, N), M=M, N=N, K=K)                 # cus = 0 asks a device
+    with pytest.raises(_lib.LkgdHipError):
+        ops.gemm_plan(e(M, K + 8), e(N, K + 8), e(M, N), M=M, N=N, K=K + 8, cus=256)     # K % 64: the launch's own LKGD_E_SHAPE
+    info = _lib.GemmPlanInfo()
+    assert _lib.lib().lkgd_gemm_plan(None, 256, ctypes.byref(info)) == -1
+    assert _lib.lib().lkgd_gemm_plan(ctypes.byref(_lib.GemmDesc()), 256, None) == -1
+
+
+def test_forced_variant_matrix_reaches_every_program():
+    """tests/test_kernels_gpu.py runs its GEMM tests under every forced variant, and a forced variant falls back to another program
+    where it does not apply.  For every variant and every operand / epilogue class it supports, at least one shape of those tests
+    must really run THAT program (at 256 CUs) - otherwise the class is tested on the 128x128 program seven times."""
+    import test_kernels_gpu as tk
+    from lkgd_amd import _lib, ops
+    lib = _lib.lib()
+    cases = tk.gemm_plan_cases(ops)
+    assert {c for c, _ in cases} == set(GEMM_CLASSES)
+    reached = {}
+    try:
+        for v in sorted(tk.VARIANTS.values()):
+            lib.lkgd_debug_set_gemm_variant(v)
+            for cls, kw in cases:
+                kw = dict(kw)
+                p = ops.gemm_plan(kw.pop("a0"), kw.pop("w"), kw.pop("out"), cus=256, **kw)
+                assert 1 <= p.program <= 7
+                if p.program == v:
+                    reached.setdefault(v, set()).add(cls)
+    finally:
+        lib.lkgd_debug_set_gemm_variant(0)
+    missing = {v: sorted(set(cl) - reached.get(v, set())) for v, cl in VARIANT_CLASSES.items() if set(cl) - reached.get(v, set())}
+    assert not missing, f"forced variant -> classes that only ever fall back: {missing}"
+    # and nothing runs where it is documented not to apply
+    for v, cl in VARIANT_CLASSES.items():
+        assert reached[v] <= set(cl), (v, reached[v] - set(cl))
+
+
+def test_gemm_census_plans_reproduce_from_the_stored_fields():
+    """tests/golden/gemm_census.json: every lkgd_gemm_f16 signature of the real forwards with the plan at 256 CUs.  The stored
+    plan must be what lkgd_gemm_plan says for the stored fields today - a dispatch change shows up as a diff of that file
+    (tools/gemm_census.py --write on a GPU box), reviewed, not as a silent change of what the suite exercises."""
+    from tools import gemm_census as gc
+    rows = gc.load_table()
+    keys = [gc.sig_key(e) for e in rows]
+    assert keys == sorted(set(keys)) and len(rows) > 300
+    for e in rows:
+        assert gc.plan(gc.desc_from_signature(e), gc.PLAN_CUS) == e["plan"], gc.sig_key(e)
+        variant, why = gc.second_program(e)
+        assert variant == e["second_program"] and why == e.get("no_second_program"), gc.sig_key(e)
+        assert set(e["launches"]) <= set(gc.FORWARDS) and all(n > 0 for n in e["launches"].values())
+    # the real rows: the four levels of the full forward and a rank's slices
+    ms = {e["fields"]["M"] for e in rows}
+    assert {258048, 64512, 16128, 4032, 36864, 9216, 2304} <= ms
+
+
+#: programs / 256x320 tile forms no signature of the census selects, with the reason - everything else must be selected by one
+CENSUS_NOT_COVERED = {
+    "program 5": "row-panel: the K <= 320 projections it was tuned for run in the fused LayerNorm + projection / feed-forward / "
+                 "temporal-attention kernels or, with a residual, on the resident-weight program; no forward issues a LayerNorm-fold "
+                 "descriptor at these geometries (tests/test_kernels_gpu.py::test_gemm_layernorm_fold and the forced `rowpanel` "
+                 "variant cover the program)",
+    "form 256x256": "256-column tiles serve N = 256 / 512 / 768, the VAE decoder's widths: at the census' 96x128-pixel VAE geometry "
+                    "every such launch is a one-round problem, where the 192-row form is modelled cheaper "
+                    "(test_gemm_wide_256_column_tiles forces 256 rows)",
+}
+
+
+def test_gemm_census_covers_every_program_and_tile_form():
+    from tools import gemm_census as gc
+    rows = gc.load_table()
+    progs = {e["plan"]["program"] for e in rows}
+    forms = {(e["plan"]["tile_m"], e["plan"]["tile_n"]) for e in rows if e["plan"]["program"] == 4}
+    want = {f"program {p}" for p in range(1, 8)} | {f"form {m}x{n}" for m in (256, 192) for n in (320, 256)}
+    have = {f"program {p}" for p in progs} | {f"form {m}x{n}" for m, n in forms}
+    assert have | set(CENSUS_NOT_COVERED) == want, sorted(want - have - set(CENSUS_NOT_COVERED))
+    assert not have & set(CENSUS_NOT_COVERED), f"now covered, drop from the list: {sorted(have & set(CENSUS_NOT_COVERED))}"
+    # all three split-K schemes, both output paths of the 256x320 program, both colstats block sizes
+    sliced = {e["plan"]["program"] for e in rows if e["plan"]["k_slices"] > 1}
+    assert {4, 7} <= sliced, sliced
+    assert {e["plan"]["lds_out"] for e in rows if e["plan"]["program"] == 4} == {0, 1}
+    assert {256, 192, 32} <= {e["plan"]["colstats_block"] for e in rows}

@@ -24,18 +24,88 @@ def _close(got, ref, rtol=4e-3, what=""):
     assert rel < 3e-3, f"{what}: relative L2 {rel:.4g}"
 
 
-@pytest.fixture(scope="module", params=["tile128", "tile256", "stream", "wide", "rowpanel", "resw", "mid"])
+VARIANTS = {"tile128": 1, "tile256": 2, "stream": 3, "wide": 4, "rowpanel": 5, "resw": 6, "mid": 7}
+
+# Shapes of the tests that run under the `ops` fixture (every forced variant).  Module constants, so that
+# tests/test_host_cpu.py::test_forced_variant_matrix_reaches_every_program can ask lkgd_gemm_plan - without a GPU - which program
+# each (variant, shape) really runs: a forced variant falls back where it does not apply, and a class of operand / epilogue that
+# only ever fell back would be tested on the 128x128 program seven times.
+PLAIN_SHAPES = [(128, 128, 64), (300, 320, 320), (1000, 64, 1280), (2, 1280, 320), (4032, 960, 640)]
+MANY_TILES_SHAPES = [(256 * 70 + 37, 320, 64), (256 * 41 + 200, 704, 128), (256 * 300, 128, 192), (256 * 33 + 5, 960, 320)]
+ROWPANEL_SHAPES = [(256 * 300 + 77, 320, 320), (256 * 9 + 1, 960, 320), (4100, 200, 256), (70000, 64, 64)]
+TWO_SOURCE_SHAPES = [(520, 192, 128, 192)]        # M, N, K0, K1
+ROWBIAS_MAPS_GEOMETRY = (2, 3, 20, 64)            # B, F, HW, C
+ROWBIAS_LONG_SHAPES = [(700, 320, 64, 300, 1 << 30, 0), (1500, 640, 128, 257, 3, 0), (1024, 320, 64, 256, 2, 1),
+                       (900, 320, 320, 4096, 1 << 30, 0)]        # M, N, K, d1, md, c0
+GEGLU_SHAPES = [(260, 128, 32), (256 * 20 + 9, 320, 32), (700, 320, 80)]      # M, C (N = 8C, K = C), interleave
+CONV3X3_SHAPES = {(1, 0): [(3, 64, 128, 10, 12)],             # (stride, ups): [(images, Cin, Cout, H, W)]
+                  (2, 0): [(3, 64, 128, 10, 12), (3, 64, 128, 40, 48)],     # 20x24 outputs: 1440 rows - the persistent
+                                                                            # 256x128 program needs more than 256
+                  (1, 1): [(3, 64, 128, 10, 12)]}
+TCONV_SHAPES = [(2, 5, 64, 6, 7)]                 # B, F, C, H, W
+
+
+def _e(*shape, dtype=torch.float16):
+    return torch.empty(*shape, dtype=dtype)
+
+
+def gemm_plan_cases(ops):
+    """(operand / epilogue class, ops.gemm_plan keyword arguments on CPU tensors) for the shapes above, as their tests call
+    ops.gemm"""
+    f32 = torch.float32
+    cases = []
+    for M, N, K in PLAIN_SHAPES + MANY_TILES_SHAPES:
+        cases.append(("plain", dict(a0=_e(M, K), w=_e(N, K), out=_e(M, N), M=M, N=N, K=K, bias=_e(N, dtype=f32), res1=_e(M, N))))
+    for M, N, K in ROWPANEL_SHAPES:
+        cases.append(("rowmap", dict(a0=_e(M, K), w=_e(N, K), out=_e(M, N), M=M, N=N, K=K, bias=_e(N, dtype=f32),
+                                     rowbias=_e(7, N), rowmap=ops.rowmap_div_mod(100, 7), s_acc=0.7, res1=_e(M, N), r1=0.7,
+                                     res2=_e(M, N), r2=0.3)))
+    B, Fr, HW, C = ROWBIAS_MAPS_GEOMETRY
+    cases.append(("rowmap", dict(a0=_e(B * Fr * HW, C), w=_e(C, C), out=_e(B * Fr * HW, C), M=B * Fr * HW, N=C, K=C,
+                                 rowbias=_e(B * Fr, C), rowmap=ops.rowmap_div(HW))))
+    for M, N, K, d1, md, c0 in ROWBIAS_LONG_SHAPES:
+        cases.append(("rowmap", dict(a0=_e(M, K), w=_e(N, K), out=_e(M, N), M=M, N=N, K=K, bias=_e(N, dtype=f32),
+                                     rowbias=_e(8, N + 64)[:, 32:32 + N], rowmap=(d1, 1, 1, md, c0))))
+    for M, N, K0, K1 in TWO_SOURCE_SHAPES:
+        cases.append(("two-source", dict(a0=_e(M, K0), w=_e(N, K0 + K1), out=_e(M, N), M=M, N=N, K=K0 + K1, a1=_e(M, K1), csplit=K0,
+                                         bias=_e(N, dtype=f32), s_acc=0.7, res1=_e(M, N), r1=0.7, res2=_e(M, N), r2=0.3)))
+    for M, C, half in GEGLU_SHAPES:
+        cases.append(("geglu", dict(a0=_e(M, C), w=_e(8 * C, C), out=_e(M, 4 * C), M=M, N=8 * C, K=C, bias=_e(8 * C, dtype=f32),
+                                    geglu=half)))
+    for (stride, ups), shapes in CONV3X3_SHAPES.items():
+        for n, Cin, Cout, H, W in shapes:
+            Ho, Wo = ((H << ups) - 1) // stride + 1, ((W << ups) - 1) // stride + 1
+            cases.append((f"conv3x3 stride {stride} ups {ups}",
+                          dict(a0=_e(n * H * W, Cin), w=_e(Cout, 9 * Cin), out=_e(n * Ho * Wo, Cout), M=n * Ho * Wo, N=Cout, K=9 * Cin,
+                               bias=_e(Cout, dtype=f32), mode=ops.A_CONV3X3, Cin=Cin, conv=(Ho, Wo, H, W, stride, ups))))
+    for B, Fr, C, H, W in TCONV_SHAPES:
+        M = B * Fr * H * W
+        cases.append(("tconv", dict(a0=_e(M, C), w=_e(C, 3 * C), out=_e(M, C), M=M, N=C, K=3 * C, bias=_e(C, dtype=f32),
+                                    mode=ops.A_TCONV3, Cin=C, tconv=(Fr, H * W))))
+    return cases
+
+
+def _gemm_as(ops, expect, a0, w, out, **kw):
+    """ops.gemm, after asserting that the dispatcher's plan for this very call (lkgd_gemm_plan, the code lkgd_gemm_f16 launches
+    from) is the program the test is about: a variant that silently fell back would test another kernel"""
+    plan = ops.gemm_plan(a0, w, out, **kw)
+    got = {k: getattr(plan, k) for k in expect}
+    assert got == expect, f"plan {got}, the test is about {expect}"
+    return ops.gemm(a0, w, out, **kw)
+
+
+@pytest.fixture(scope="module", params=list(VARIANTS))
 def ops(request):
     """every GEMM/conv test runs against ALL kernel variants (128x128 two-stage, 256x128 three-stage ring, persistent
     streaming kernel with register epilogue, 256x320, row-panel, resident-weight, 128x128 on the four-stage ring; a forced variant falls back to the 128x128
     program on shapes it does not cover)"""
     from lkgd_amd import _lib, ops
-    _lib.lib().lkgd_debug_set_gemm_variant({"tile128": 1, "tile256": 2, "stream": 3, "wide": 4, "rowpanel": 5, "resw": 6, "mid": 7}[request.param])
+    _lib.lib().lkgd_debug_set_gemm_variant(VARIANTS[request.param])
     yield ops
     _lib.lib().lkgd_debug_set_gemm_variant(0)
 
 
-@pytest.mark.parametrize("M,N,K", [(128, 128, 64), (300, 320, 320), (1000, 64, 1280), (2, 1280, 320), (4032, 960, 640)])
+@pytest.mark.parametrize("M,N,K", PLAIN_SHAPES)
 def test_gemm_plain_bias_residual(ops, M, N, K):
     g = torch.Generator().manual_seed(M + N + K)
     a, w = _h(torch.randn(M, K, generator=g)), _h(torch.randn(N, K, generator=g) / K ** 0.5)
@@ -50,8 +120,7 @@ def test_gemm_plain_bias_residual(ops, M, N, K):
 def test_gemm_many_tiles_short_k(ops):
     """> 256 output tiles with K = 64/128 (epilogue every 1-2 K-steps), ragged M and N: stresses the streaming ring"""
     g = torch.Generator().manual_seed(77)
-    for M, N, K in ((256 * 70 + 37, 320, 64), (256 * 41 + 200, 704, 128), (256 * 300, 128, 192),
-                    (256 * 33 + 5, 960, 320)):
+    for M, N, K in MANY_TILES_SHAPES:
         a, w = _h(torch.randn(M, K, generator=g)), _h(torch.randn(N, K, generator=g) / K ** 0.5)
         bias = torch.randn(N, generator=g)
         res = _h(torch.randn(M, N, generator=g))
@@ -67,7 +136,7 @@ def test_gemm_many_tiles_short_k(ops):
 def test_gemm_rowpanel_shapes(ops):
     """the short-K projection shapes (K = 64..320, several panels per workgroup, ragged M/N, residual + row bias + blend)"""
     g = torch.Generator().manual_seed(55)
-    for M, N, K in ((256 * 300 + 77, 320, 320), (256 * 9 + 1, 960, 320), (4100, 200, 256), (70000, 64, 64)):
+    for M, N, K in ROWPANEL_SHAPES:
         a, w = _h(torch.randn(M, K, generator=g)), _h(torch.randn(N, K, generator=g) / K ** 0.5)
         bias = torch.randn(N, generator=g)
         r1, r2 = _h(torch.randn(M, N, generator=g)), _h(torch.randn(M, N, generator=g))
@@ -82,22 +151,22 @@ def test_gemm_rowpanel_shapes(ops):
 
 def test_gemm_two_source_and_blend(ops):
     g = torch.Generator().manual_seed(5)
-    M, N, K0, K1 = 520, 192, 128, 192
-    a0, a1 = _h(torch.randn(M, K0, generator=g)), _h(torch.randn(M, K1, generator=g))
-    w = _h(torch.randn(N, K0 + K1, generator=g) / 18)
-    bias = torch.randn(N, generator=g)
-    r1, r2 = _h(torch.randn(M, N, generator=g)), _h(torch.randn(M, N, generator=g))
-    alpha = 0.3
-    ref = (1 - alpha) * (torch.cat([a0, a1], 1).float() @ w.float().T + bias) + (1 - alpha) * r1.float() + alpha * r2.float()
-    out = torch.empty(M, N, dtype=torch.float16, device=DEV)
-    ops.gemm(a0.to(DEV), w.to(DEV), out, M=M, N=N, K=K0 + K1, a1=a1.to(DEV), csplit=K0, bias=bias.to(DEV),
-             s_acc=1 - alpha, res1=r1.to(DEV), r1=1 - alpha, res2=r2.to(DEV), r2=alpha)
-    _close(out, ref, what="gemm 2-source blend")
+    for M, N, K0, K1 in TWO_SOURCE_SHAPES:
+        a0, a1 = _h(torch.randn(M, K0, generator=g)), _h(torch.randn(M, K1, generator=g))
+        w = _h(torch.randn(N, K0 + K1, generator=g) / 18)
+        bias = torch.randn(N, generator=g)
+        r1, r2 = _h(torch.randn(M, N, generator=g)), _h(torch.randn(M, N, generator=g))
+        alpha = 0.3
+        ref = (1 - alpha) * (torch.cat([a0, a1], 1).float() @ w.float().T + bias) + (1 - alpha) * r1.float() + alpha * r2.float()
+        out = torch.empty(M, N, dtype=torch.float16, device=DEV)
+        ops.gemm(a0.to(DEV), w.to(DEV), out, M=M, N=N, K=K0 + K1, a1=a1.to(DEV), csplit=K0, bias=bias.to(DEV),
+                 s_acc=1 - alpha, res1=r1.to(DEV), r1=1 - alpha, res2=r2.to(DEV), r2=alpha)
+        _close(out, ref, what=f"gemm 2-source blend {M}x{N}")
 
 
 def test_gemm_rowbias_maps(ops):
     g = torch.Generator().manual_seed(6)
-    B, Fr, HW, C = 2, 3, 20, 64
+    B, Fr, HW, C = ROWBIAS_MAPS_GEOMETRY
     M = B * Fr * HW
     a, w = _h(torch.randn(M, C, generator=g)), _h(torch.randn(C, C, generator=g) / 8)
     rows = torch.arange(M)
@@ -119,8 +188,7 @@ def test_gemm_rowbias_long_periods(ops):
     kernel serves them from two LDS strips per tile - tiles that straddle a boundary, ragged last tile, N = 320 / 640,
     table rows reached through the modulo, a table that is a column slice of a wider one"""
     g = torch.Generator().manual_seed(16)
-    for M, N, K, d1, md, c0 in [(700, 320, 64, 300, 1 << 30, 0), (1500, 640, 128, 257, 3, 0), (1024, 320, 64, 256, 2, 1),
-                                (900, 320, 320, 4096, 1 << 30, 0)]:
+    for M, N, K, d1, md, c0 in ROWBIAS_LONG_SHAPES:
         a, w = _h(torch.randn(M, K, generator=g)), _h(torch.randn(N, K, generator=g) / K ** 0.5)
         rows = torch.arange(M)
         idx = (rows // d1 + c0) % md
@@ -137,7 +205,7 @@ def test_gemm_rowbias_long_periods(ops):
 def test_gemm_geglu(ops):
     from lkgd_amd.packing import pack_geglu
     g = torch.Generator().manual_seed(7)
-    M, C = 260, 128
+    M, C = GEGLU_SHAPES[0][:2]
     a = _h(torch.randn(M, C, generator=g))
     w = torch.randn(8 * C, C, generator=g) / C ** 0.5
     b = torch.randn(8 * C, generator=g) * 0.1
@@ -151,14 +219,14 @@ def test_gemm_geglu(ops):
     ops.gemm(a.to(DEV), wp.to(DEV), out, M=M, N=8 * C, K=C, bias=bp.to(DEV), geglu=half)
     _close(out, ref, what="geglu")
     # C = 320: 8C = 2560 is a multiple of 320 -> interleave 80, always served by the 256x320-tile kernel
-    M, C = 700, 320
+    M, C = GEGLU_SHAPES[2][:2]
     a = _h(torch.randn(M, C, generator=g))
     w = torch.randn(8 * C, C, generator=g) / C ** 0.5
     b = torch.randn(8 * C, generator=g) * 0.1
     y = a.float() @ _h(w).float().T + b
     hid, gate = y.chunk(2, dim=-1)
     wp32, bp32, _ = pack_geglu(w, b, half=32)
-    M2 = 256 * 20 + 9
+    M2 = GEGLU_SHAPES[1][0]
     a2 = _h(torch.randn(M2, C, generator=g))
     y2 = a2.float() @ _h(w).float().T + b
     h2, g2 = y2.chunk(2, dim=-1)
@@ -183,17 +251,17 @@ def _untokens(t, N, H, W):
 def test_conv3x3(ops, stride, ups):
     from lkgd_amd.packing import pack_conv3x3
     g = torch.Generator().manual_seed(10 + stride + ups)
-    N, Cin, Cout, H, W = 3, 64, 128, 10, 12
-    x = _h(torch.randn(N, Cin, H, W, generator=g))
-    w = _h(torch.randn(Cout, Cin, 3, 3, generator=g) / (9 * Cin) ** 0.5)
-    b = torch.randn(Cout, generator=g)
-    xin = F.interpolate(x.float(), scale_factor=2.0, mode="nearest") if ups else x.float()
-    ref = F.conv2d(xin, w.float(), b, stride=stride, padding=1)
-    Ho, Wo = ref.shape[-2:]
-    out = torch.empty(N * Ho * Wo, Cout, dtype=torch.float16, device=DEV)
-    ops.gemm(_tokens(x).to(DEV), pack_conv3x3(w).to(DEV), out, M=N * Ho * Wo, N=Cout, K=9 * Cin, bias=b.to(DEV),
-             mode=ops.A_CONV3X3, Cin=Cin, conv=(Ho, Wo, H, W, stride, ups))
-    _close(_untokens(out.cpu(), N, Ho, Wo), ref, what=f"conv3x3 s{stride} u{ups}")
+    for N, Cin, Cout, H, W in CONV3X3_SHAPES[(stride, ups)]:
+        x = _h(torch.randn(N, Cin, H, W, generator=g))
+        w = _h(torch.randn(Cout, Cin, 3, 3, generator=g) / (9 * Cin) ** 0.5)
+        b = torch.randn(Cout, generator=g)
+        xin = F.interpolate(x.float(), scale_factor=2.0, mode="nearest") if ups else x.float()
+        ref = F.conv2d(xin, w.float(), b, stride=stride, padding=1)
+        Ho, Wo = ref.shape[-2:]
+        out = torch.empty(N * Ho * Wo, Cout, dtype=torch.float16, device=DEV)
+        ops.gemm(_tokens(x).to(DEV), pack_conv3x3(w).to(DEV), out, M=N * Ho * Wo, N=Cout, K=9 * Cin, bias=b.to(DEV),
+                 mode=ops.A_CONV3X3, Cin=Cin, conv=(Ho, Wo, H, W, stride, ups))
+        _close(_untokens(out.cpu(), N, Ho, Wo), ref, what=f"conv3x3 s{stride} u{ups} {H}x{W}")
 
 
 def test_conv3x3_concat_temb_residual(ops):
@@ -237,7 +305,7 @@ def test_conv_in_c8_and_conv_out(ops):
 def test_temporal_conv(ops):
     from lkgd_amd.packing import pack_tconv3
     g = torch.Generator().manual_seed(16)
-    B, Fr, C, H, W = 2, 5, 64, 6, 7
+    B, Fr, C, H, W = TCONV_SHAPES[0]
     x5 = _h(torch.randn(B, C, Fr, H, W, generator=g))
     w = _h(torch.randn(C, C, 3, 1, 1, generator=g) / (3 * C) ** 0.5)
     b = torch.randn(C, generator=g)
@@ -600,7 +668,9 @@ def test_gemm_four_stage_ring_k_slices():
                 L.lkgd_debug_set_mid_model(0.0, 0.0, 0.0, 0.0, f)
                 L.lkgd_debug_set_gemm_splitk(1 if f else 0)
                 out = torch.empty(M, N, dtype=torch.float16, device=DEV)
-                ops.gemm(a.to(DEV), w.to(DEV), out, M=M, N=N, K=K, bias=b.to(DEV), res1=res.to(DEV), r1=0.5)
+                per = -(-(K // 64) // f) if f else K // 64            # K-tiles per slice; every slice non-empty
+                _gemm_as(ops, dict(program=7, k_slices=-(-(K // 64) // per)), a.to(DEV), w.to(DEV), out, M=M, N=N, K=K,
+                         bias=b.to(DEV), res1=res.to(DEV), r1=0.5)
                 outs.append(out.cpu())
             _close(outs[0], ref, what=f"four-stage ring, {forced} K slices, {M}x{N}x{K}")
             _close(outs[1], ref, what=f"four-stage ring, unsplit, {M}x{N}x{K}")
@@ -633,14 +703,17 @@ def test_gemm_split_k_on_256x320_tiles():
         L.lkgd_debug_set_wide_ksplit(ks)
         L.lkgd_debug_set_gemm_splitk(1 if ks else 0)
         out = torch.empty(M, N, dtype=torch.float16, device=DEV)
-        ops.gemm(a.to(DEV), w.to(DEV), out, M=M, N=N, K=K, bias=b.to(DEV), res1=res.to(DEV), r1=0.5)
+        _gemm_as(ops, dict(program=4, k_slices=ks or 1), a.to(DEV), w.to(DEV), out, M=M, N=N, K=K, bias=b.to(DEV),
+                 res1=res.to(DEV), r1=0.5)
         outs.append(out.cpu())
     L.lkgd_debug_set_gemm_splitk(1)
     _close(outs[0][rows], ref, what="256x320 split-K plain")
     assert (outs[0].float() - outs[1].float()).abs().max().item() <= 4e-3 * ref.abs().max().item()
     assert not torch.equal(outs[0], outs[1])        # another fp32 summation order: the sliced path really ran
-    # 3x3 conv, two sources (the slice boundary falls inside a tap): 3 images of 64x64, 128 + 128 channels -> K = 2304
-    Nimg, C0, C1, Cout, H, W = 3, 128, 128, 320, 64, 64
+    # 3x3 conv, two sources (the slice boundary falls inside a tap): 3 images of 60x64, 128 + 128 channels -> K = 2304
+    # (11 520 rows: until the plan was asserted here this leg had 3 x 64 x 64 = 12 288 rows, one more than ops.gemm hands a
+    # workspace to, and compared the unsliced program with itself)
+    Nimg, C0, C1, Cout, H, W = 3, 128, 128, 320, 60, 64
     x0, x1 = _h(torch.randn(Nimg, C0, H, W, generator=g)), _h(torch.randn(Nimg, C1, H, W, generator=g))
     wc = _h(torch.randn(Cout, C0 + C1, 3, 3, generator=g) / 48)
     bc = torch.randn(Cout, generator=g)
@@ -650,8 +723,8 @@ def test_gemm_split_k_on_256x320_tiles():
         L.lkgd_debug_set_wide_ksplit(ks)
         L.lkgd_debug_set_gemm_splitk(1 if ks else 0)
         out = torch.empty(Nimg * H * W, Cout, dtype=torch.float16, device=DEV)
-        ops.gemm(_tokens(x0).to(DEV), pack_conv3x3(wc).to(DEV), out, M=Nimg * H * W, N=Cout, K=9 * (C0 + C1),
-                 a1=_tokens(x1).to(DEV), csplit=C0, bias=bc.to(DEV), mode=ops.A_CONV3X3, Cin=C0 + C1,
+        _gemm_as(ops, dict(program=4, k_slices=ks or 1), _tokens(x0).to(DEV), pack_conv3x3(wc).to(DEV), out, M=Nimg * H * W, N=Cout,
+                 K=9 * (C0 + C1), a1=_tokens(x1).to(DEV), csplit=C0, bias=bc.to(DEV), mode=ops.A_CONV3X3, Cin=C0 + C1,
                  conv=(H, W, H, W, 1, 0))
         outs.append(out.cpu())
     L.lkgd_debug_set_gemm_splitk(1)
@@ -659,14 +732,15 @@ def test_gemm_split_k_on_256x320_tiles():
     L.lkgd_debug_set_gemm_variant(0)
     _close(_untokens(outs[0], Nimg, H, W), refc, what="256x320 split-K conv3x3")
     assert (outs[0].float() - outs[1].float()).abs().max().item() <= 4e-3 * refc.abs().max().item()
+    assert not torch.equal(outs[0], outs[1])        # another fp32 summation order: the sliced path really ran
     # the dispatcher's own choices (fill rule of wide_split): 4032 x 1280 x 3840 (64 tiles -> 4 slices), 8064 rows (128 tiles
     # -> 2 slices), 2304 rows (36 tiles -> 6 slices of 10 K-tiles): against fp32 on sampled rows
-    for M, N, K in ((4032, 1280, 3840), (8064, 1280, 3840), (2304, 1280, 3840)):
+    for M, N, K, slices in ((4032, 1280, 3840, 4), (8064, 1280, 3840, 2), (2304, 1280, 3840, 6)):
         a, w = _h(torch.randn(M, K, generator=g)), _h(torch.randn(N, K, generator=g) / K ** 0.5)
         b = torch.randn(N, generator=g)
         rows = torch.arange(0, M, 37)
         out = torch.empty(M, N, dtype=torch.float16, device=DEV)
-        ops.gemm(a.to(DEV), w.to(DEV), out, M=M, N=N, K=K, bias=b.to(DEV))
+        _gemm_as(ops, dict(program=4, k_slices=slices), a.to(DEV), w.to(DEV), out, M=M, N=N, K=K, bias=b.to(DEV))
         _close(out.cpu()[rows], a[rows].float() @ w.float().T + b, what=f"auto split {M}x{N}x{K}")
 
 
@@ -682,10 +756,13 @@ def test_gemm_wide_rows_through_lds_match_direct_stores(tile_rows):
     L = _lib.lib()
     g = torch.Generator().manual_seed(29)
 
+    path = {}
+
     def both(fn, shape, cols=None):
         outs = []
         for on in (0, 1):
             L.lkgd_debug_set_wide_lds_out(on)
+            path["lds_out"] = on
             buf = torch.full(shape, -7.0, dtype=torch.float16, device=DEV)
             fn(buf if cols is None else buf[:, cols[0]:cols[1]])
             outs.append(buf.cpu())
@@ -703,9 +780,12 @@ def test_gemm_wide_rows_through_lds_match_direct_stores(tile_rows):
         res = _h(torch.randn(M, N, generator=g))
         table = _h(torch.randn(5, N, generator=g))
         idx = (torch.arange(M) // 300) % 5
-        out = both(lambda o: ops.gemm(a.to(DEV), w.to(DEV), o, M=M, N=N, K=K, bias=b.to(DEV), res1=res.to(DEV), r1=0.5,
-                                      rowbias=table.to(DEV), rowmap=(300, 1, 1, 5, 0)), (M + 3, 768), cols=(64, 64 + N))
+        form = dict(program=4, k_slices=1, tile_m=tile_rows, tile_n=320)
+        out = both(lambda o: _gemm_as(ops, dict(form, lds_out=path["lds_out"]), a.to(DEV), w.to(DEV), o, M=M, N=N, K=K,
+                                      bias=b.to(DEV), res1=res.to(DEV), r1=0.5, rowbias=table.to(DEV), rowmap=(300, 1, 1, 5, 0)),
+                   (M + 3, 768), cols=(64, 64 + N))
         _close(out[:M, 64:64 + N], a.float() @ w.float().T + b + table.float()[idx] + 0.5 * res.float(), what="wide via LDS")
+        form["lds_out"] = 0                      # GEGLU and the convolutions: direct stores under either setting
         assert (out[M:] == -7).all() and (out[:, :64] == -7).all() and (out[:, 64 + N:] == -7).all()
         # GEGLU at C = 320 (interleave 80): output 1280 columns
         M, C = 256 * 3 + 130, 320
@@ -713,7 +793,8 @@ def test_gemm_wide_rows_through_lds_match_direct_stores(tile_rows):
         w = torch.randn(8 * C, C, generator=g) / C ** 0.5
         b = torch.randn(8 * C, generator=g) * 0.1
         wp, bp, half = pack_geglu(w, b, half=80)
-        out = both(lambda o: ops.gemm(a.to(DEV), wp.to(DEV), o, M=M, N=8 * C, K=C, bias=bp.to(DEV), geglu=half), (M + 1, 4 * C))
+        out = both(lambda o: _gemm_as(ops, form, a.to(DEV), wp.to(DEV), o, M=M, N=8 * C, K=C, bias=bp.to(DEV), geglu=half),
+                   (M + 1, 4 * C))
         hid, gate = (a.float() @ _h(w).float().T + b).chunk(2, dim=-1)
         _close(out[:M], hid * F.gelu(gate), what="wide geglu via LDS")
         assert (out[M:] == -7).all()
@@ -722,7 +803,7 @@ def test_gemm_wide_rows_through_lds_match_direct_stores(tile_rows):
         x = _h(torch.randn(Nimg, Cin, H, W, generator=g))
         wc = _h(torch.randn(Cout, Cin, 3, 3, generator=g) / 24)
         bc = torch.randn(Cout, generator=g)
-        out = both(lambda o: ops.gemm(_tokens(x).to(DEV), pack_conv3x3(wc).to(DEV), o, M=Nimg * H * W, N=Cout, K=9 * Cin,
+        out = both(lambda o: _gemm_as(ops, form, _tokens(x).to(DEV), pack_conv3x3(wc).to(DEV), o, M=Nimg * H * W, N=Cout, K=9 * Cin,
                                       bias=bc.to(DEV), mode=ops.A_CONV3X3, Cin=Cin, conv=(H, W, H, W, 1, 0)),
                    (Nimg * H * W, Cout))
         _close(_untokens(out, Nimg, H, W), F.conv2d(x.float(), wc.float(), bc, padding=1), what="wide conv via LDS")
@@ -732,8 +813,8 @@ def test_gemm_wide_rows_through_lds_match_direct_stores(tile_rows):
         wt = _h(torch.randn(C, C, 3, 1, 1, generator=g) / (3 * C) ** 0.5)
         bt = torch.randn(C, generator=g)
         tok = x5.permute(0, 2, 3, 4, 1).reshape(-1, C).contiguous()
-        out = both(lambda o: ops.gemm(tok.to(DEV), pack_tconv3(wt).to(DEV), o, M=Bc * Fr * Ht * Wt, N=C, K=3 * C, bias=bt.to(DEV),
-                                      mode=ops.A_TCONV3, Cin=C, tconv=(Fr, Ht * Wt)), (Bc * Fr * Ht * Wt, C))
+        out = both(lambda o: _gemm_as(ops, form, tok.to(DEV), pack_tconv3(wt).to(DEV), o, M=Bc * Fr * Ht * Wt, N=C, K=3 * C,
+                                      bias=bt.to(DEV), mode=ops.A_TCONV3, Cin=C, tconv=(Fr, Ht * Wt)), (Bc * Fr * Ht * Wt, C))
         reft = F.conv3d(x5.float(), wt.float(), bt, padding=(1, 0, 0)).permute(0, 2, 3, 4, 1).reshape(-1, C)
         _close(out, reft, what="wide tconv via LDS")
     finally:
@@ -755,10 +836,13 @@ def test_gemm_wide_256_column_tiles(tile_rows):
     assert L.lkgd_gemm_wide_tile_n(640) == 320 and L.lkgd_gemm_wide_tile_n(3072) == 320 and L.lkgd_gemm_wide_tile_n(128) == 320
     g = torch.Generator().manual_seed(256)
 
+    path = {}
+
     def both(fn, shape, cols=None):
         outs = []
         for on in (0, 1):
             L.lkgd_debug_set_wide_lds_out(on)
+            path["lds_out"] = on
             buf = torch.full(shape, -7.0, dtype=torch.float16, device=DEV)
             fn(buf if cols is None else buf[:, cols[0]:cols[1]])
             outs.append(buf.cpu())
@@ -775,8 +859,10 @@ def test_gemm_wide_256_column_tiles(tile_rows):
             res = _h(torch.randn(M, N, generator=g))
             table = _h(torch.randn(5, N, generator=g))
             idx = (torch.arange(M) // d1) % 5
-            out = both(lambda o: ops.gemm(a.to(DEV), w.to(DEV), o, M=M, N=N, K=K, bias=b.to(DEV), res1=res.to(DEV), r1=0.5,
-                                          rowbias=table.to(DEV), rowmap=(d1, 1, 1, 5, 0)), (M + 3, N + 128), cols=(64, 64 + N))
+            form = dict(program=4, k_slices=1, tile_m=tile_rows, tile_n=256)
+            out = both(lambda o: _gemm_as(ops, dict(form, lds_out=path["lds_out"]), a.to(DEV), w.to(DEV), o, M=M, N=N, K=K,
+                                          bias=b.to(DEV), res1=res.to(DEV), r1=0.5, rowbias=table.to(DEV), rowmap=(d1, 1, 1, 5, 0)),
+                       (M + 3, N + 128), cols=(64, 64 + N))
             _close(out[:M, 64:64 + N], a.float() @ w.float().T + b + table.float()[idx] + 0.5 * res.float(),
                    what=f"256-column tiles {M}x{N}x{K}")
             assert (out[M:] == -7).all() and (out[:, :64] == -7).all() and (out[:, 64 + N:] == -7).all()
@@ -787,9 +873,9 @@ def test_gemm_wide_256_column_tiles(tile_rows):
             wc = _h(torch.randn(Cout, Cin, 3, 3, generator=g) / (9 * Cin) ** 0.5)
             bc = torch.randn(Cout, generator=g)
             Ho, Wo = H << ups, W << ups
-            out = both(lambda o: ops.gemm(_tokens(x).to(DEV), pack_conv3x3(wc).to(DEV), o, M=Nimg * Ho * Wo, N=Cout, K=9 * Cin,
-                                          bias=bc.to(DEV), mode=ops.A_CONV3X3, Cin=Cin, conv=(Ho, Wo, H, W, 1, ups)),
-                       (Nimg * Ho * Wo, Cout))
+            out = both(lambda o: _gemm_as(ops, dict(form, lds_out=0), _tokens(x).to(DEV), pack_conv3x3(wc).to(DEV), o,
+                                          M=Nimg * Ho * Wo, N=Cout, K=9 * Cin, bias=bc.to(DEV), mode=ops.A_CONV3X3, Cin=Cin,
+                                          conv=(Ho, Wo, H, W, 1, ups)), (Nimg * Ho * Wo, Cout))
             xin = F.interpolate(x.float(), scale_factor=2.0, mode="nearest") if ups else x.float()
             _close(_untokens(out, Nimg, Ho, Wo), F.conv2d(xin, wc.float(), bc, padding=1), what=f"256-column conv {Cin}->{Cout}")
         Bc, Fr, C, Ht, Wt = 1, 5, 256, 23, 10
@@ -797,8 +883,8 @@ def test_gemm_wide_256_column_tiles(tile_rows):
         wt = _h(torch.randn(C, C, 3, 1, 1, generator=g) / (3 * C) ** 0.5)
         bt = torch.randn(C, generator=g)
         tok = x5.permute(0, 2, 3, 4, 1).reshape(-1, C).contiguous()
-        out = both(lambda o: ops.gemm(tok.to(DEV), pack_tconv3(wt).to(DEV), o, M=Bc * Fr * Ht * Wt, N=C, K=3 * C, bias=bt.to(DEV),
-                                      mode=ops.A_TCONV3, Cin=C, tconv=(Fr, Ht * Wt)), (Bc * Fr * Ht * Wt, C))
+        out = both(lambda o: _gemm_as(ops, dict(form, lds_out=0), tok.to(DEV), pack_tconv3(wt).to(DEV), o, M=Bc * Fr * Ht * Wt, N=C,
+                                      K=3 * C, bias=bt.to(DEV), mode=ops.A_TCONV3, Cin=C, tconv=(Fr, Ht * Wt)), (Bc * Fr * Ht * Wt, C))
         reft = F.conv3d(x5.float(), wt.float(), bt, padding=(1, 0, 0)).permute(0, 2, 3, 4, 1).reshape(-1, C)
         _close(out, reft, what="256-column tconv")
         # GroupNorm sums from the epilogue: conv 128 -> 512 on 4 images of 16x32 (two tiles per image), against the read pass
@@ -807,8 +893,9 @@ def test_gemm_wide_256_column_tiles(tile_rows):
         x = _h(torch.randn(T, 128, generator=g)).to(DEV)
         w = torch.randn(512, 128, 3, 3, generator=g) / (9 * 128) ** 0.5
         out = torch.empty(T, 512, dtype=torch.float16, device=DEV)
-        ops.gemm(x, pack_conv3x3(w).to(DEV), out, M=T, N=512, K=9 * 128, bias=torch.randn(512, generator=g).to(DEV),
-                 mode=ops.A_CONV3X3, Cin=128, conv=(H, W, H, W, 1, 0), colstats=H * W)
+        bcs = torch.randn(512, generator=g)
+        _gemm_as(ops, dict(form, lds_out=1, colstats_block=tile_rows), x, pack_conv3x3(w).to(DEV), out, M=T, N=512, K=9 * 128,
+                 bias=bcs.to(DEV), mode=ops.A_CONV3X3, Cin=128, conv=(H, W, H, W, 1, 0), colstats=H * W)
         assert out._lkgd_colstats[1] == tile_rows
         got = ops.groupnorm_stats(out, None, Nimg, H * W, 1e-6)
         ops.COLSTATS = False
@@ -817,8 +904,9 @@ def test_gemm_wide_256_column_tiles(tile_rows):
         finally:
             ops.COLSTATS = True
         assert torch.allclose(got.cpu(), two_pass.cpu(), rtol=2e-5, atol=2e-6)
-        ref = F.conv2d(_untokens(x.cpu(), Nimg, H, W).float(), _h(w).float(), None, padding=1)
+        ref = F.conv2d(_untokens(x.cpu(), Nimg, H, W).float(), _h(w).float(), bcs, padding=1)
         assert out.shape == (T, 512) and torch.isfinite(out).all() and ref.shape[1] == 512
+        _close(_untokens(out.cpu(), Nimg, H, W), ref, what="256-column conv with column sums")
     finally:
         L.lkgd_debug_set_gemm_variant(0)
         L.lkgd_debug_set_wide_lds_out(-1)
@@ -882,7 +970,9 @@ def test_attn_spatial_fewer_queries_than_keys(ops):
 
 def test_gemm_resident_weight_kernel():
     """lkgd_gemm_resw_kernel (K <= 320, N % 160 == 0: a 160-channel weight slab resident in LDS, waves independent): every
-    epilogue source combination, ragged M (partial 32-row block, fewer blocks than waves, one row), 1 / 2 / 6 slabs,
+    epilogue source combination the program is instantiated for (gemm_resw.hip::resw_has - the ones that fit its 96-register
+    budget: all but both residuals together from K = 256, all pairs but rowbias + a residual below; the plan is asserted, and for
+    the others that the forced variant falls back to the 128x128 program), ragged M (partial 32-row block, fewer blocks than waves, one row), 1 / 2 / 6 slabs,
     K = 64 .. 320, GEGLU with the 80 | 80 interleave - against fp32, and bitwise against the 256x320 kernel where both apply"""
     from lkgd_amd import _lib, ops
     from lkgd_amd.packing import pack_geglu
@@ -912,7 +1002,8 @@ def test_gemm_resident_weight_kernel():
                     ref = ref + 0.3 * r2.float()
                 out = torch.full((M, N), float("nan"), dtype=torch.float16, device=DEV)
                 L.lkgd_debug_set_gemm_variant(6)
-                ops.gemm(ad, wd, out, M=M, N=N, K=K, bias=bias.to(DEV), s_acc=0.7, **kw)
+                has = src <= 5 if K >= 256 else src in (0, 1, 2, 4, 6)
+                _gemm_as(ops, dict(program=6 if has else 1), ad, wd, out, M=M, N=N, K=K, bias=bias.to(DEV), s_acc=0.7, **kw)
                 _close(out, ref, what=f"resw {M}x{N}x{K} src {src}")
                 if N % 320 == 0 and K >= 64:
                     out4 = torch.full((M, N), float("nan"), dtype=torch.float16, device=DEV)
@@ -921,7 +1012,7 @@ def test_gemm_resident_weight_kernel():
                     assert torch.equal(out, out4), f"resw vs 256x320 {M}x{N}x{K} src {src}"
             out = torch.full((M, N), float("nan"), dtype=torch.float16, device=DEV)
             L.lkgd_debug_set_gemm_variant(6)
-            ops.gemm(ad, wd, out, M=M, N=N, K=K)                     # no bias, no sources (QKV)
+            _gemm_as(ops, dict(program=6), ad, wd, out, M=M, N=N, K=K)                     # no bias, no sources (QKV)
             _close(out, acc, what=f"resw bare {M}x{N}x{K}")
         for M, C in ((700, 320), (32 * 300 + 5, 320), (40, 64)):
             a = _h(torch.randn(M, C, generator=g))
@@ -934,7 +1025,7 @@ def test_gemm_resident_weight_kernel():
             wp, bp, half = pack_geglu(w, b, half=80)
             out = torch.full((M, 4 * C), float("nan"), dtype=torch.float16, device=DEV)
             L.lkgd_debug_set_gemm_variant(6)
-            ops.gemm(a.to(DEV), wp.to(DEV), out, M=M, N=8 * C, K=C, bias=bp.to(DEV), geglu=half)
+            _gemm_as(ops, dict(program=6), a.to(DEV), wp.to(DEV), out, M=M, N=8 * C, K=C, bias=bp.to(DEV), geglu=half)
             _close(out, hid * F.gelu(gate), what=f"resw geglu {M}x{C}")
             out4 = torch.full((M, 4 * C), float("nan"), dtype=torch.float16, device=DEV)
             L.lkgd_debug_set_gemm_variant(4)

@@ -35,14 +35,15 @@ Register plan.  Arch VGPRs v[VB ...] are named here and listed as clobbers (the 
 AGPRs (invisible to the compiler): a[0:31] O_A, a[32:63] O_B, a[64:79] Q_A, a[80:95] Q_B (pre-scaled, written by the kernel
 before the statement), a[96:99] bias A operand (1.0 in k-slot 0), a[100:103] / a[104:107] bias B operands (-m_A / -m_B).
 
-The generator keeps an instruction list with register reads / writes and checks it (check()): MFMA result -> any other use
->= 20 wait states, VALU write -> MFMA read >= 3, transcendental -> consumer >= 1, every LDS fragment waited for by a counted
-lgkmcnt before its MFMA, ring slots holding the fragment the MFMA expects.
+The generator keeps an instruction list with register reads / writes and checks it before it writes the file: the rule table
+of tools/asmgen.py (MFMA result -> any other use, VALU write -> MFMA read, transcendental -> consumer, every LDS fragment
+waited for by a counted lgkmcnt before its MFMA, ring slots holding the fragment the MFMA expects, ...).
 """
 import os
-import sys
 
-NL = r"\n\t"
+import asmgen
+from asmgen import R, ar, v, vr
+
 VB = 24
 S_ = {"A": VB, "B": VB + 32}
 PF = {"A": VB + 64, "B": VB + 80}
@@ -73,42 +74,17 @@ PSUM_LIMIT = "0x44800000"   # 1024.0
 MASKED = "mask" in OPT
 
 
-def v(n):
-    return "v%d" % n
-
-
-def vr(a, n):
-    return "v[%d:%d]" % (a, a + n - 1)
-
-
-def ar(a, n):
-    return "a[%d:%d]" % (a, a + n - 1)
-
-
-class Ins:
-    __slots__ = ("text", "kind", "rd", "wr", "meta")
-
-    def __init__(self, text, kind, rd=(), wr=(), **meta):
-        self.text, self.kind, self.rd, self.wr, self.meta = text, kind, tuple(rd), tuple(wr), meta
-
-
-def R(base, n, f="v"):
-    return [(f, base + i) for i in range(n)]
-
-
-class Gen:
-    def __init__(self):
-        self.ins = []
-        self.lbl = 0
-
-    def e(self, text, kind, rd=(), wr=(), **meta):
-        self.ins.append(Ins(text, kind, rd, wr, **meta))
-
-    def label(self, name):
-        self.e(name + "_%=:", "label", name=name)
-
-    def nop(self, n):
-        self.e("s_nop %d" % n, "nop", n=n)
+class Gen(asmgen.Program):
+    MFMA_WS = 1                # distances are counted in issued instructions here (the stricter metric: kept)
+    RING, NRING = RING, 4
+    LOOP, INHERIT = "LOOP", ("TAIL",)
+    # the loop is entered from the prologue (everything landed) and from the back edge (the next phase's first four
+    # fragments in flight): the waits are counted for the back edge, which is also correct for the other entry
+    LOOP_ENTRY = [("K", 1, f, ks) for ks in range(2) for f in range(2)]
+    PRESET = R(QF["A"], 32, "a")        # the Q fragments come from the kernel
+    KNOB_ENV = "ATTN_GEN_KNOB"          # tools/micro/attn_pipe_knobs.sh
+    KNOB_DROPS = {"nowait": ("waitlgkm",), "nomfma": ("mfma",), "nobar": ("barrier", "waitvm", "vmem")}
+    STATS_COST = {"mfma": 8, "trans": 8, "valu": 4}        # vector issue only
 
     def ckpt(self):
         """bisection aid (ATTN_GEN_STOP=k python tools/gen_attn_asm.py): leave the statement at the k-th checkpoint"""
@@ -518,200 +494,27 @@ class Gen:
             self.redo(t, tag, back, ksub)
         self.label("END")
 
-    # ---- resolve the WAITFRAG markers into counted lgkmcnt waits ----------------------------------------------------------
-    def resolve_waits(self):
-        self.loop_entry_fifo = [("K", 1, f, ks) for ks in range(2) for f in range(2)]
-        """Walks the list in emission order (the fall-through path: prologue, loop body, tail).  Branch targets inherit a
-        conservative state: a wait for N outstanding is still correct when fewer are outstanding."""
-        out = []
-        fifo = []          # fragments of outstanding LDS ops, oldest first
-        for i in self.ins:
-            if i.kind == "lds":
-                fifo.append(i.meta["frag"])
-                out.append(i)
-            elif i.kind == "waitall":
-                fifo = []
-                out.append(i)
-            elif i.kind == "waitfrag":
-                fr = i.meta["frag"]
-                idx = [k for k, f in enumerate(fifo) if f == fr]
-                if idx:
-                    keep = len(fifo) - 1 - idx[-1]
-                    assert keep <= 15
-                    out.append(Ins("s_waitcnt lgkmcnt(%d)" % keep, "waitlgkm", n=keep))
-                    fifo = fifo[idx[-1] + 1:]
-                # else: already waited for
-            elif i.kind == "label" and i.meta["name"] == "LOOP":
-                # entered from the prologue (everything landed) and from the back edge (the next phase's first four
-                # fragments in flight): count for the back edge, which is also correct for the other entry
-                assert all(f in self.loop_entry_fifo for f in fifo)
-                fifo = list(self.loop_entry_fifo)
-                out.append(i)
-            elif i.kind == "branch" and i.meta["target"] == "LOOP":
-                assert fifo == self.loop_entry_fifo, (fifo, self.loop_entry_fifo)
-                out.append(i)
-            elif i.kind == "branch" and i.meta["target"] == "TAIL":
-                self.tail_fifo = list(fifo)
-                out.append(i)
-            elif i.kind == "label" and i.meta["name"] == "TAIL":
-                fifo = list(self.tail_fifo)          # the path that reaches TAIL
-                out.append(i)
-            else:
-                out.append(i)
-        self.ins = out
+    def keep(self, i, knob):
+        filler = "cost" in i.meta          # the softmax work that rides in the MFMA gaps
+        if knob != [""] and i.kind == "branch" and i.meta["target"].startswith("REDO"):
+            return []         # every knob build: the reference never moves (removed ingredients leave garbage maxima)
+        if i.kind == "lds" and (("nolds" in knob and i.meta["frag"][0] != "X") or ("nokread" in knob and i.meta["frag"][0] == "K")
+                                or ("novread" in knob and i.meta["frag"][0] == "V")):
+            return []
+        if ("nolds" in knob and i.kind == "waitlgkm") or ("novalu" in knob and filler) or ("noexp" in knob and filler and i.kind == "trans"):
+            return []
+        if ("noadd" in knob and filler and i.text.startswith("v_add_f32")) or ("nocvt" in knob and filler and i.text.startswith("v_cvt_pk")):
+            return []
+        return asmgen.Program.keep(self, i, knob)
 
-    # ---- checks --------------------------------------------------------------------------------------------------------
-    def check(self):
-        """Hazard distances on the straight-line order, with the loop body walked twice (the second walk starts from the
-        state the first leaves).  Distances are counted in issued instructions (s_nop n = n + 1)."""
-        def ws(i):
-            return i.meta["n"] + 1 if i.kind == "nop" else (0 if i.kind in ("label", "comment") else 1)
-
-        seq = [i for i in self.ins]
-        a = next(k for k, i in enumerate(seq) if i.kind == "label" and i.meta["name"] == "LOOP")
-        b = next(k for k, i in enumerate(seq) if i.kind == "branch" and i.meta["target"] == "LOOP")
-        walk = seq[:b] + seq[a:b] + seq[b:]
-        last_mfma_wr, last_valu_wr, last_trans_wr = {}, {}, {}
-        pos = 0
-        nerr = 0
-        for i in walk:
-            if i.kind in ("label", "comment"):
-                continue
-            for r in i.rd + i.wr:
-                if r in last_mfma_wr:
-                    same_chain = i.kind == "mfma" and i.meta.get("acc") and r in i.wr
-                    d = pos - last_mfma_wr[r]
-                    if not same_chain and d < 20:
-                        print("HAZARD mfma->use %s dist %d: %s" % (r, d, i.text))
-                        nerr += 1
-            if i.kind == "mfma":
-                for r in i.rd:
-                    if r in last_valu_wr and pos - last_valu_wr[r] < 3:
-                        print("HAZARD valu->mfma %s: %s" % (r, i.text))
-                        nerr += 1
-            if i.kind in ("valu", "trans"):
-                for r in i.rd:
-                    if r in last_trans_wr and pos - last_trans_wr[r] < 2:
-                        print("HAZARD trans->valu %s: %s" % (r, i.text))
-                        nerr += 1
-            for r in i.wr:
-                last_mfma_wr.pop(r, None)
-                last_valu_wr.pop(r, None)
-                last_trans_wr.pop(r, None)
-                if i.kind == "mfma":
-                    last_mfma_wr[r] = pos
-                elif i.kind == "trans":
-                    last_trans_wr[r] = pos
-                    last_valu_wr[r] = pos
-                elif i.kind == "valu":
-                    last_valu_wr[r] = pos
-            pos += ws(i)
-        # no named register is read before the statement has written it (Q fragments a[64:95] come from the kernel)
-        written = set(("a", i) for i in range(QF["A"], QF["B"] + 16))
-        for i in self.ins:
-            if i.kind in ("label", "comment"):
-                continue
-            for r in i.rd:
-                if r[0] in ("v", "a") and r not in written:
-                    print("UNINITIALISED %s read by: %s" % (r, i.text))
-                    nerr += 1
-                    written.add(r)
-            written.update(i.wr)
-        # ring contents: the fragment an MFMA consumes is the one last read into its slot, and it has been waited for
-        slotfrag, pending = {}, []
-        for i in walk:
-            if i.kind == "lds" and i.meta["frag"][0] != "X":
-                for r in i.wr:
-                    slotfrag[r] = i.meta["frag"]
-                pending.append(i.meta["frag"])
-            elif i.kind == "waitlgkm":
-                n = i.meta["n"]
-                pending = pending[len(pending) - n:] if n else []
-            elif i.kind == "waitall":
-                pending = []
-            elif i.kind == "mfma" and i.meta.get("frag") is not None:
-                regs = [r for r in i.rd if r[0] == "v" and RING <= r[1] < RING + 16]
-                assert len(regs) == 4
-                for r in regs:
-                    if slotfrag.get(r) != i.meta["frag"]:
-                        print("RING slot %s holds %s, MFMA expects %s" % (r, slotfrag.get(r), i.meta["frag"]))
-                        nerr += 1
-                if i.meta["frag"] in pending:
-                    print("RING fragment not waited for: %s" % (i.meta["frag"],))
-                    nerr += 1
-        assert nerr == 0, "%d hazards" % nerr
-
-    def text(self):
-        lines = []
-        knob = os.environ.get("ATTN_GEN_KNOB", "").split("+")    # timing experiments only (tools/micro/attn_pipe_knobs.sh)
-        for i in self.ins:
-            if i.kind == "comment":
-                continue
-            if knob != [""] and i.kind == "branch" and i.meta["target"].startswith("REDO"):
-                continue          # every knob build: the reference never moves (removed ingredients leave garbage maxima)
-            if "nolds" in knob and (i.kind == "waitlgkm" or (i.kind == "lds" and i.meta["frag"][0] != "X")):
-                continue
-            if "nokread" in knob and i.kind == "lds" and i.meta["frag"][0] == "K":
-                continue
-            if "novread" in knob and i.kind == "lds" and i.meta["frag"][0] == "V":
-                continue
-            if "nowait" in knob and i.kind == "waitlgkm":
-                continue
-            if "novalu" in knob and i.kind in ("valu", "trans") and "cost" in i.meta:
-                continue
-            if "noexp" in knob and i.kind == "trans" and "cost" in i.meta:
-                continue
-            for cls, key in (("noadd", "v_add_f32"), ("nocvt", "v_cvt_pk")):
-                if cls in knob and "cost" in i.meta and i.text.startswith(key):
-                    i = None
-                    break
-            if i is None:
-                continue
-            if "nomfma" in knob and i.kind == "mfma":
-                continue
-            if "nobar" in knob and i.kind in ("barrier", "waitvm", "vmem"):
-                continue
-            lines.append('"' + i.text + NL + '"')
-        return " \\\n  ".join(lines)
-
-    def stats(self):
-        cost = {"mfma": 8, "trans": 8, "valu": 4}
-        cur, tot, n = None, {}, {}
-        for i in self.ins:
-            if i.kind == "comment":
-                cur = i.text
-                tot[cur] = 0
-                n[cur] = {}
-            elif cur is not None:
-                tot[cur] += cost.get(i.kind, 0)
-                n[cur][i.kind] = n[cur].get(i.kind, 0) + 1
-        for k in tot:
-            print("%-70s vector-issue cycles %4d  %s" % (k, tot[k], n[k]))
-        print("instructions:", sum(1 for i in self.ins if i.kind not in ("comment", "label")))
-
-
-def main():
-    g = Gen()
-    g.build()
-    g.resolve_waits()
-    g.check()
-    if "--stats" in sys.argv:
-        g.stats()
-    out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "lkgd_amd", "csrc",
-                       "attn_spatial_pipe_masked.inc" if MASKED else "attn_spatial_pipe.inc")
-    P = "ATTN_PIPEM" if MASKED else "ATTN_PIPE"
-    with open(out, "w") as f:
-        f.write("// GENERATED by tools/gen_attn_asm.py - do not edit.  Main loop of attn_spatial_pipe.hip (register plan and\n"
-                "// schedule: see that script).\n")
-        if not MASKED:
-            f.write("#define ATTN_PIPE_VB %d\n#define ATTN_PIPE_VEND %d\n#define ATTN_PIPE_AEND %d\n" % (VB, VEND, AEND))
-            f.write("#define ATTN_PIPE_QF_A %d\n#define ATTN_PIPE_QF_B %d\n#define ATTN_PIPE_O_A %d\n#define ATTN_PIPE_O_B %d\n"
-                    % (QF["A"], QF["B"], OACC["A"], OACC["B"]))
-        f.write("#define %s_ASM \\\n  %s\n\n" % (P, g.text()))
-        clob = ['"v%d"' % i for i in range(VB, VEND)] + ['"a%d"' % i for i in range(AEND)] + ['"s%d"' % i for i in range(SK, SEND)]
-        f.write("#define %s_CLOBBERS " % P + ", ".join(clob) + ', "vcc", "scc", "m0", "memory"\n')
-    print("wrote", out)
+    def inc(self):
+        P = "ATTN_PIPEM" if MASKED else "ATTN_PIPE"
+        D = dict(VB=VB, VEND=VEND, AEND=AEND, QF_A=QF["A"], QF_B=QF["B"], O_A=OACC["A"], O_B=OACC["B"])
+        return dict(script="gen_attn_asm.py", name="attn_spatial_pipe_masked.inc" if MASKED else "attn_spatial_pipe.inc",
+                    blurb="Main loop of attn_spatial_pipe.hip (register plan and\n// schedule: see that script).",
+                    defines=[] if MASKED else [("ATTN_PIPE_" + k, D[k]) for k in D],       # (one set for both files)
+                    macros=[(P + "_ASM", self.text())], clobber=(P + "_CLOBBERS", asmgen.clobbers(VB, VEND, AEND, range(SK, SEND))))
 
 
 if __name__ == "__main__":
-    main()
+    asmgen.main(Gen)

@@ -23,12 +23,11 @@ vector issue per unit - matrix-bound, unlike the attention program.
 
 Register plan (named, clobbered): arch v[24:87] the four H tiles (hidden f0, gate f0, hidden f1, gate f1), v[88:103] g (two
 tiles x 8), v[104:119] fragment ring, v[120:127] GELU temporaries (two elements in flight); a[0:159] Y^T, a[160:239] z^T,
-a[240:243] the ones operand of the bias k-step.  The generator checks what gen_attn_asm.py checks.
+a[240:243] the ones operand of the bias k-step.  Checks: the rule table of tools/asmgen.py.
 """
-import os
-import sys
+import asmgen
+from asmgen import Ins, R, ar, v, vr
 
-NL = r"\n\t"
 VB = 24
 HT = {("h", 0): VB, ("g", 0): VB + 16, ("h", 1): VB + 32, ("g", 1): VB + 48}
 G_ = {0: VB + 64, 1: VB + 72}
@@ -51,46 +50,11 @@ SUNIT = 67
 SP = 68                # s[68:69]: the weight stream pointer (carried across statements through operands)
 
 
-def v(n):
-    return "v%d" % n
-
-
-def vr(a, n):
-    return "v[%d:%d]" % (a, a + n - 1)
-
-
-def ar(a, n):
-    return "a[%d:%d]" % (a, a + n - 1)
-
-
-def R(base, n, f="v"):
-    return [(f, base + i) for i in range(n)]
-
-
-class Ins:
-    __slots__ = ("text", "kind", "rd", "wr", "meta")
-
-    def __init__(self, text, kind, rd=(), wr=(), **meta):
-        self.text, self.kind, self.rd, self.wr, self.meta = text, kind, tuple(rd), tuple(wr), meta
-
-
-def slot_addr(slot):
-    """(address operand, immediate) of byte 0 of an LDS ring slot: three base registers cover the 16-bit offset field"""
-    return "%%[fa%d]" % (slot // 2), (slot % 2) * SLOT
-
-
-class Gen:
-    def __init__(self):
-        self.ins = []
-
-    def e(self, text, kind, rd=(), wr=(), **meta):
-        self.ins.append(Ins(text, kind, rd, wr, **meta))
-
-    def label(self, name):
-        self.e(name + "_%=:", "label", name=name)
-
-    def nop(self, n):
-        self.e("s_nop %d" % n, "nop", n=n)
+class Gen(asmgen.ChunkRing):
+    SLOT, SP, RING, NRING, LOOP = SLOT, SP, RING, NRING, "LOOP"
+    PRESET = R(ZF, 4 * NKS, "a")      # (Y^T a[0:159] needs no entry: the first unit's C = 0 MFMAs write it before any read)
+    KNOB_ENV = "FF_GEN_KNOB"          # tools/micro/ff_knobs.sh
+    KNOB_DROPS = {"nolds": ("lds", "waitlgkm"), "nomfma": ("mfma",), "nodma": ("vmem",), "nobar": ("barrier", "waitvm", "vmem")}
 
     # ---- GELU / GEGLU filler stream of one tile ---------------------------------------------------------------------------
     def geglu_items(self, f):
@@ -128,49 +92,10 @@ class Gen:
                           [("v", hh + r), ("v", hh + r + 1)], [("v", g0 + r // 2)]))
         return items
 
-    # ---- fragment reads ------------------------------------------------------------------------------------------------
-    def read_frag(self, slot, frag_i, ring_slot, tag):
-        reg = RING + 4 * ring_slot
-        base, imm = slot_addr(slot)
-        self.e("ds_read_b128 %s, %s offset:%d" % (vr(reg, 4), base, imm + frag_i * 1024), "lds", wr=R(reg, 4), frag=tag)
-
-    # ---- DMA of one chunk (this wave's pieces) ------------------------------------------------------------------------------
     def dma_items(self, slot, kind, adv):
-        """instructions that copy a chunk ("w1": 21 KiB, "w2": 20 KiB) from the stream pointer s[SP:SP+1] into ring slot
-        `slot` and move the pointer behind it (adv = bytes, or "wrap": back to the stream start).  Pieces w + 4j (j < 5)
-        through the five offset registers; the 21st KiB of a W1 chunk (the bias fragment) by every wave (same bytes, same
-        place).  An s_nop separates every M0 write from its LDS-DMA."""
-        it = []          # pairs (M0 write, LDS-DMA): emitted around an MFMA, which is the wait state between the two
-        for j in range(5):
-            it.append(("s_add_u32 m0, %%[ldsw], %d" % (slot * SLOT + j * 4096),
-                       "global_load_lds_dwordx4 %%[vo%d], s[%d:%d]" % (j, SP, SP + 1)))
-        if kind == "w1":
-            it.append(("s_add_u32 m0, %%[lds0], %d" % (slot * SLOT + 20480),
-                       "global_load_lds_dwordx4 %%[vob], s[%d:%d]" % (SP, SP + 1)))
-        if adv == "wrap":
-            it.append(("s_mov_b32 s%d, %%[sp0lo]" % SP, "s_mov_b32 s%d, %%[sp0hi]" % (SP + 1)))
-        else:
-            it.append(("s_add_u32 s%d, s%d, %d" % (SP, SP, adv), "s_addc_u32 s%d, s%d, 0" % (SP + 1, SP + 1)))
-        return it
-
-    def dma_first(self):
-        """first half of the next pending DMA pair (an M0 write or the pointer's low word): goes in FRONT of an MFMA"""
-        if self.pending_dma:
-            self.e(self.pending_dma[0][0], "salu")
-            self.dma_half = True
-
-    def dma_second(self):
-        """second half (the LDS-DMA itself / the pointer's high word): behind that MFMA"""
-        if getattr(self, "dma_half", False):
-            t = self.pending_dma.pop(0)[1]
-            self.e(t, "vmem" if t.startswith("global_load") else "salu")
-            self.dma_half = False
-
-    def emit_dma_all(self):
-        while self.pending_dma:
-            self.dma_first()
-            self.nop(0)
-            self.dma_second()
+        """the pairs that copy a chunk ("w1": 21 KiB with its bias fragment, "w2": 20 KiB) into ring slot `slot` and move
+        the stream pointer behind it (adv = bytes, or "wrap": back to the stream start)"""
+        return self.dma_pairs(slot, kind == "w1", None if adv == "wrap" else adv)
 
     # ---- one chunk ----------------------------------------------------------------------------------------------------------
     def chunk(self, cname, ctype, f, slot, fillers, nxt, dma, wait_n, first_y=False, fill_from=0, flush=False):
@@ -236,7 +161,6 @@ class Gen:
     def build(self):
         import struct
         e = self.e
-        self.pending_dma = []
         fbits = lambda x: struct.unpack("<I", struct.pack("<f", x))[0]
         consts = {"c1": 0.3275911 * 0.70710678118654752440, "c2": 0.5 * 1.4426950408889634, "a1": 0.5 * 0.254829592,
                   "a2": 0.5 * -0.284496736, "a3": 0.5 * 1.421413741, "a4": 0.5 * -1.453152027, "a5": 0.5 * 1.061405429}
@@ -271,7 +195,6 @@ class Gen:
         # ---- statement start: the DMA of chunk 3 (unit 0's c4) and the first fragments of chunk 0
         self.pending_dma = self.dma_items(3, "w1", W1_BYTES)
         self.emit_dma_all()
-        self.ringpos = 0
         for j in range(NRING):
             self.read_frag(0, j, j, ("c0", j))
 
@@ -333,170 +256,34 @@ class Gen:
         e("s_mov_b32 %%[splo], s%d" % SP, "salu")
         e("s_mov_b32 %%[sphi], s%d" % (SP + 1), "salu")
 
-    # ---- counted lgkmcnt waits ----------------------------------------------------------------------------------------------
-    def resolve_waits(self):
-        out, fifo = [], []
-        loop_fifo = None
-        for i in self.ins:
-            if i.kind == "lds":
-                fifo.append(i.meta["frag"])
-                out.append(i)
-            elif i.kind == "waitfrag":
-                fr = i.meta["frag"]
-                idx = [k for k, f in enumerate(fifo) if f == fr]
-                assert idx, ("fragment never read", fr)
-                keep = len(fifo) - 1 - idx[-1]
-                out.append(Ins("s_waitcnt lgkmcnt(%d)" % keep, "waitlgkm", n=keep))
-                fifo = fifo[idx[-1] + 1:]
-            elif i.kind == "label" and i.meta["name"] == "LOOP":
-                loop_fifo = list(fifo)
-                out.append(i)
-            elif i.kind == "branch" and i.meta["target"] == "LOOP":
-                assert fifo == loop_fifo, (fifo, loop_fifo)
-                out.append(i)
-            else:
-                out.append(i)
-        self.ins = out
+    def keep(self, i, knob):
+        if not asmgen.ChunkRing.keep(self, i, knob):
+            return []
+        geglu = i.kind in ("valu", "trans") and "cost" in i.meta
+        if "novalu" in knob and geglu:
+            return []
+        out = [i]
+        # "dmapad" (round 6): every LDS-DMA issued twice (same bytes to the same place) - the L2 -> LDS fill, its issue slots and
+        # the LDS write traffic of a form whose chunks serve two waves instead of four (the C = 640 wave-pair form);
+        # twice the operations in flight: the counted waits double
+        if "dmapad" in knob and i.kind == "waitvm":
+            out = [Ins("s_waitcnt vmcnt(%d)" % (2 * int(i.text.split("(")[1].rstrip(")"))), "waitvm")]
+        if "dmapad" in knob and i.kind == "vmem":
+            out.append(i)
+        # sensitivity knobs that leave the RESULT (and so the data the MFMAs see, and the clock) unchanged: every GEGLU
+        # instruction followed by a dead move / every fragment read issued twice
+        if "valupad" in knob and geglu:
+            out.append(Ins("v_mov_b32_e32 v%d, v%d" % (VEND - 1, VEND - 1), "valu"))
+        if "ldspad" in knob and i.kind == "lds":
+            out.append(i)
+        return out
 
-    # ---- checks (see gen_attn_asm.py) -----------------------------------------------------------------------------------------
-    def check(self):
-        def ws(i):
-            return i.meta["n"] + 1 if i.kind == "nop" else (0 if i.kind in ("label", "comment") else (8 if i.kind == "mfma" else 1))
-
-        seq = self.ins
-        a = next(k for k, i in enumerate(seq) if i.kind == "label" and i.meta["name"] == "LOOP")
-        b = next(k for k, i in enumerate(seq) if i.kind == "branch" and i.meta["target"] == "LOOP")
-        walk = seq[:b] + seq[a:b] + seq[b:]
-        last_mfma_wr, last_valu_wr, last_trans_wr = {}, {}, {}
-        pos = nerr = 0
-        for i in walk:
-            if i.kind in ("label", "comment"):
-                continue
-            for r in i.rd + i.wr:
-                if r in last_mfma_wr:
-                    same_chain = i.kind == "mfma" and i.meta.get("acc") and r in i.wr
-                    if not same_chain and pos - last_mfma_wr[r] < 20:
-                        print("HAZARD mfma->use %s dist %d: %s" % (r, pos - last_mfma_wr[r], i.text))
-                        nerr += 1
-            if i.kind == "mfma":
-                for r in i.rd:
-                    if r in last_valu_wr and pos - last_valu_wr[r] < 3:
-                        print("HAZARD valu->mfma %s: %s" % (r, i.text))
-                        nerr += 1
-            if i.kind in ("valu", "trans"):
-                for r in i.rd:
-                    if r in last_trans_wr and pos - last_trans_wr[r] < 2:
-                        print("HAZARD trans->valu %s: %s" % (r, i.text))
-                        nerr += 1
-            for r in i.wr:
-                last_mfma_wr.pop(r, None)
-                last_valu_wr.pop(r, None)
-                last_trans_wr.pop(r, None)
-                if i.kind == "mfma":
-                    last_mfma_wr[r] = pos
-                elif i.kind == "trans":
-                    last_trans_wr[r] = pos
-                    last_valu_wr[r] = pos
-                elif i.kind == "valu":
-                    last_valu_wr[r] = pos
-            pos += ws(i)
-        written = set(("a", i) for i in range(ZF, ZF + 80))
-        for i in walk:
-            if i.kind in ("label", "comment"):
-                continue
-            for r in i.rd:
-                if r[0] in ("v", "a") and r not in written and not (r[0] == "a" and r[1] < 160):
-                    print("UNINITIALISED %s read by: %s" % (r, i.text))
-                    nerr += 1
-                    written.add(r)
-            written.update(i.wr)
-        slotfrag, pending = {}, []
-        for i in walk:
-            if i.kind == "lds":
-                for r in i.wr:
-                    slotfrag[r] = i.meta["frag"]
-                pending.append(i.meta["frag"])
-            elif i.kind == "waitlgkm":
-                n = i.meta["n"]
-                pending = pending[len(pending) - n:] if n else []
-            elif i.kind == "mfma":
-                regs = [r for r in i.rd if r[0] == "v" and RING <= r[1] < RING + 4 * NRING]
-                assert len(regs) == 4
-                want = i.meta["frag"]
-                for r in regs:
-                    got = slotfrag.get(r)
-                    if got != want:
-                        print("RING slot %s holds %s, MFMA expects %s" % (r, got, want))
-                        nerr += 1
-                if want in pending:
-                    print("RING fragment not waited for: %s" % (want,))
-                    nerr += 1
-        assert nerr == 0, "%d problems" % nerr
-
-    def text(self):
-        knob = os.environ.get("FF_GEN_KNOB", "").split("+")      # timing experiments only (tools/micro/ff_knobs.sh): results WRONG
-        keep = []
-        for i in self.ins:
-            if i.kind == "comment":
-                continue
-            if "nolds" in knob and i.kind in ("lds", "waitlgkm"):
-                continue
-            if "novalu" in knob and i.kind in ("valu", "trans") and "cost" in i.meta:
-                continue
-            if "nomfma" in knob and i.kind == "mfma":
-                continue
-            if "nodma" in knob and i.kind == "vmem":
-                continue
-            if "nobar" in knob and i.kind in ("barrier", "waitvm", "vmem"):
-                continue
-            if "dmapad" in knob and i.kind == "waitvm":          # (twice the operations in flight: the counted waits double)
-                n = int(i.text.split("(")[1].rstrip(")"))
-                i = Ins("s_waitcnt vmcnt(%d)" % (2 * n), "waitvm")
-            keep.append(i)
-            # "dmapad" (round 6): every LDS-DMA issued twice (same bytes to the same place) - the L2 -> LDS fill, its issue slots and
-            # the LDS write traffic of a form whose chunks serve two waves instead of four (the C = 640 wave-pair form)
-            if "dmapad" in knob and i.kind == "vmem":
-                keep.append(i)
-            # sensitivity knobs that leave the RESULT (and so the data the MFMAs see, and the clock) unchanged: every GEGLU
-            # instruction followed by a dead move / every fragment read issued twice
-            if "valupad" in knob and i.kind in ("valu", "trans") and "cost" in i.meta:
-                keep.append(Ins("v_mov_b32_e32 v%d, v%d" % (VEND - 1, VEND - 1), "valu"))
-            if "ldspad" in knob and i.kind == "lds":
-                keep.append(i)
-        return " \\\n  ".join('"' + i.text + NL + '"' for i in keep)
-
-    def stats(self):
-        cost = {"mfma": 8, "trans": 8, "valu": 4, "salu": 4, "lds": 4, "vmem": 4, "waitlgkm": 4, "waitvm": 4, "barrier": 4}
-        cur, tot, n = None, {}, {}
-        for i in self.ins:
-            if i.kind == "comment":
-                cur = i.text
-                tot[cur], n[cur] = 0, {}
-            elif cur is not None:
-                tot[cur] += cost.get(i.kind, 0)
-                n[cur][i.kind] = n[cur].get(i.kind, 0) + 1
-        for k in tot:
-            print("%-28s issue cycles %5d (matrix pipe %4d)  %s" % (k, tot[k], 32 * n[k].get("mfma", 0), n[k]))
-        print("instructions:", sum(1 for i in self.ins if i.kind not in ("comment", "label")))
-
-
-def main():
-    g = Gen()
-    g.build()
-    g.resolve_waits()
-    g.check()
-    if "--stats" in sys.argv:
-        g.stats()
-    out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "lkgd_amd", "csrc", "ff_fused_loop.inc")
-    with open(out, "w") as f:
-        f.write("// GENERATED by tools/gen_ff_asm.py - do not edit.  Panel loop of ff_fused.hip (plan: see that script).\n")
-        f.write("#define FF_VB %d\n#define FF_VEND %d\n#define FF_AEND %d\n#define FF_YACC %d\n#define FF_ZF %d\n" % (VB, VEND, AEND, YACC, ZF))
-        f.write("#define FF_W1_BYTES %d\n#define FF_W2_BYTES %d\n#define FF_SLOT %d\n#define FF_NSLOT %d\n" % (W1_BYTES, W2_BYTES, SLOT, NSLOT))
-        f.write("#define FF_PANEL_ASM \\\n  %s\n\n" % g.text())
-        clob = ['"v%d"' % i for i in range(VB, VEND)] + ['"a%d"' % i for i in range(AEND)] + ['"s%d"' % i for i in range(60, 70)]
-        f.write("#define FF_CLOBBERS " + ", ".join(clob) + ', "vcc", "scc", "m0", "memory"\n')
-    print("wrote", out)
+    def inc(self):
+        D = dict(VB=VB, VEND=VEND, AEND=AEND, YACC=YACC, ZF=ZF, W1_BYTES=W1_BYTES, W2_BYTES=W2_BYTES, SLOT=SLOT, NSLOT=NSLOT)
+        return dict(script="gen_ff_asm.py", name="ff_fused_loop.inc", blurb="Panel loop of ff_fused.hip (plan: see that script).",
+                    defines=[("FF_" + k, D[k]) for k in D], macros=[("FF_PANEL_ASM", self.text())],
+                    clobber=("FF_CLOBBERS", asmgen.clobbers(VB, VEND, AEND, range(60, 70))))
 
 
 if __name__ == "__main__":
-    main()
+    asmgen.main(Gen)

@@ -14,12 +14,13 @@ MFMA gaps of tile n + 1, from the other of two accumulator sets.  The stores cou
 wait is computed from the statement's own issue log (the statement is straight-line), not from a fixed formula.
 
 Register plan (named, clobbered): v[24:55] two accumulator tiles, v[56:71] two packed tiles (8 registers each), v[72:103]
-fragment ring; a[0:79] z^T, a[80:83] the ones operand of the bias k-step.  Checks as in gen_tblock_asm.py.
+fragment ring; a[0:79] z^T, a[80:83] the ones operand of the bias k-step.  Checks: the rule table of tools/asmgen.py.
 """
 import os
-import sys
 
-NL = r"\n\t"
+import asmgen
+from asmgen import Ins, R, ar, v, vr
+
 VB = 24
 ACC = [VB, VB + 16]
 PK = [VB + 32, VB + 40]
@@ -45,50 +46,24 @@ RATE = 2
 SP = 68                   # s[68:69]: the weight stream pointer
 
 
-def v(n):
-    return "v%d" % n
+class Gen(asmgen.ChunkRing):
+    SLOT, SP, RING, NRING = SLOT, SP, RING, NRING
+    PRESET = R(ZF, 4 * NKS, "a")
+    KNOB_ENV, KNOB_DROPS = "QKV_GEN_KNOB", {"nomfma": ("mfma",)}      # (and "nostore", "norows")
 
-
-def vr(a, n):
-    return "v[%d:%d]" % (a, a + n - 1)
-
-
-def ar(a, n):
-    return "a[%d:%d]" % (a, a + n - 1)
-
-
-def R(base, n, f="v"):
-    return [(f, base + i) for i in range(n)]
-
-
-class Ins:
-    __slots__ = ("text", "kind", "rd", "wr", "meta")
-
-    def __init__(self, text, kind, rd=(), wr=(), **meta):
-        self.text, self.kind, self.rd, self.wr, self.meta = text, kind, tuple(rd), tuple(wr), meta
-
-
-def slot_addr(slot):
-    return "%%[fa%d]" % (slot // 2), (slot % 2) * SLOT
-
-
-class Gen:
     def __init__(self):
-        self.ins = []
+        asmgen.ChunkRing.__init__(self)
         self.queue = []          # Ins or ("GATE", ring-MFMA position)
         self.mpos = 0
-        self.ringpos = 0
-        self.pending_dma = []
-        self.dma_half = False
-        self.vmlog = []          # issue order of vector-memory operations: ("dma", chunk) / ("st", tile)
+        self.vmlog = []          # issue order of vector-memory operations: ("dma", chunk) / ("st", tile) / ("row", k-step)
 
     def e(self, text, kind, rd=(), wr=(), **meta):
-        self.ins.append(Ins(text, kind, rd, wr, **meta))
-        if kind == "vmem":
-            self.vmlog.append(meta["vm"])
+        self.append(Ins(text, kind, rd, wr, **meta))
 
-    def nop(self, n):
-        self.e("s_nop %d" % n, "nop", n=n)
+    def append(self, i):
+        self.ins.append(i)
+        if i.kind == "vmem":
+            self.vmlog.append(i.meta["vm"])
 
     def vm_after(self, chunk):
         """vector-memory operations issued behind the last DMA piece of `chunk` (all of them, if its pieces are older than this
@@ -125,54 +100,13 @@ class Gen:
                     break
                 self.queue.pop(0)
                 continue
-            self.queue.pop(0)
-            self.ins.append(it)
-            if it.kind == "vmem":
-                self.vmlog.append(it.meta["vm"])
+            self.append(self.queue.pop(0))
             k += 1
 
-    # ---- fragment reads / DMA -----------------------------------------------------------------------------------------------
-    def read_frag(self, slot, frag_i, ring_slot, tag):
-        reg = RING + 4 * ring_slot
-        base, imm = slot_addr(slot)
-        self.e("ds_read_b128 %s, %s offset:%d" % (vr(reg, 4), base, imm + frag_i * 1024), "lds", wr=R(reg, 4), frag=tag)
-
     def dma_items(self, chunk, wrap):
-        slot = chunk % NSLOT
         first = chunk % PARTS == 0           # the chunk that opens a tile carries the bias fragment (a 21st KiB)
-        it = []
-        for j in range(5):
-            it.append(("s_add_u32 m0, %%[ldsw], %d" % (slot * SLOT + j * 4096),
-                       "global_load_lds_dwordx4 %%[vo%d], s[%d:%d]" % (j, SP, SP + 1)))
-        if first:
-            it.append(("s_add_u32 m0, %%[lds0], %d" % (slot * SLOT + 20480),
-                       "global_load_lds_dwordx4 %%[vob], s[%d:%d]" % (SP, SP + 1)))
-        if wrap:
-            it.append(("s_mov_b32 s%d, %%[sp0lo]" % SP, "s_mov_b32 s%d, %%[sp0hi]" % (SP + 1)))
-        else:
-            it.append(("s_add_u32 s%d, s%d, %d" % (SP, SP, W1_BYTES if first else W2_BYTES), "s_addc_u32 s%d, s%d, 0" % (SP + 1, SP + 1)))
-        self.dma_chunk = chunk
-        return it
-
-    def dma_first(self):
-        if self.pending_dma:
-            self.e(self.pending_dma[0][0], "salu")
-            self.dma_half = True
-
-    def dma_second(self):
-        if self.dma_half:
-            t = self.pending_dma.pop(0)[1]
-            if t.startswith("global_load"):
-                self.e(t, "vmem", vm=("dma", self.dma_chunk))
-            else:
-                self.e(t, "salu")
-            self.dma_half = False
-
-    def emit_dma_all(self):
-        while self.pending_dma:
-            self.dma_first()
-            self.nop(0)
-            self.dma_second()
+        self.dma_tag = ("dma", chunk)
+        return self.dma_pairs(chunk % NSLOT, first, None if wrap else (W1_BYTES if first else W2_BYTES))
 
     # ---- one chunk = (part of) one 32-channel output tile ---------------------------------------------------------------------
     def chunk(self, c):
@@ -253,9 +187,7 @@ class Gen:
         self.nop(7)
         for it in self.queue:
             if isinstance(it, Ins):
-                self.ins.append(it)
-                if it.kind == "vmem":
-                    self.vmlog.append(it.meta["vm"])
+                self.append(it)
         self.queue = []
         self.nop(1)
         start_vm = self.vm_after(NCH + AHEAD - 1)            # this statement's tail = the next statement's head
@@ -266,99 +198,7 @@ class Gen:
         e("s_mov_b32 %%[splo], s%d" % SP, "salu")
         e("s_mov_b32 %%[sphi], s%d" % (SP + 1), "salu")
 
-    # ---- counted lgkmcnt waits ------------------------------------------------------------------------------------------------
-    def resolve_waits(self):
-        out, fifo = [], []
-        for i in self.ins:
-            if i.kind == "lds":
-                fifo.append(i.meta["frag"])
-                out.append(i)
-            elif i.kind == "waitfrag":
-                fr = i.meta["frag"]
-                idx = [k for k, f in enumerate(fifo) if f == fr]
-                assert idx, ("fragment never read", fr)
-                keep = len(fifo) - 1 - idx[-1]
-                assert keep <= 15
-                out.append(Ins("s_waitcnt lgkmcnt(%d)" % keep, "waitlgkm", n=keep))
-                fifo = fifo[idx[-1] + 1:]
-            else:
-                out.append(i)
-        self.ins = out
-
-    # ---- checks ------------------------------------------------------------------------------------------------------------------
-    def check(self):
-        def ws(i):
-            return i.meta["n"] + 1 if i.kind == "nop" else (0 if i.kind in ("label", "comment") else (8 if i.kind == "mfma" else 1))
-
-        walk = self.ins
-        last_mfma_wr, last_valu_wr, store_rd = {}, {}, {}
-        pos = nerr = 0
-        for i in walk:
-            if i.kind in ("label", "comment"):
-                continue
-            for r in i.rd + i.wr:
-                if r in last_mfma_wr:
-                    same_chain = i.kind == "mfma" and i.meta.get("acc") and r in i.wr and r in i.rd
-                    if not same_chain and pos - last_mfma_wr[r] < 20:
-                        print("HAZARD mfma->use %s dist %d: %s" % (r, pos - last_mfma_wr[r], i.text))
-                        nerr += 1
-            if i.kind == "mfma":
-                for r in i.rd:
-                    if r in last_valu_wr and pos - last_valu_wr[r] < 3:
-                        print("HAZARD valu->mfma %s: %s" % (r, i.text))
-                        nerr += 1
-            if i.kind == "swap":          # VALU write -> v_permlane32_swap read: 2 wait states (LLVM gfx950 hazard rule)
-                for r in i.rd:
-                    if r in last_valu_wr and pos - last_valu_wr[r] < 3:
-                        print("HAZARD valu->permlane swap %s: %s" % (r, i.text))
-                        nerr += 1
-            if i.kind == "vmem":          # a store's data registers: written >= 2 wait states before, not rewritten for 2 after
-                for r in i.rd:
-                    if r in last_valu_wr and pos - last_valu_wr[r] < 2:
-                        print("HAZARD valu->store data %s: %s" % (r, i.text))
-                        nerr += 1
-                    store_rd[r] = pos
-            for r in i.wr:
-                if r in store_rd and pos - store_rd[r] < 3:
-                    print("HAZARD store data rewritten %s: %s" % (r, i.text))
-                    nerr += 1
-                last_mfma_wr.pop(r, None)
-                last_valu_wr.pop(r, None)
-                if i.kind == "mfma":
-                    last_mfma_wr[r] = pos
-                elif i.kind in ("valu", "trans", "swap"):
-                    last_valu_wr[r] = pos
-            pos += ws(i)
-        written = set(("a", i) for i in range(ZF, ZF + 4 * NKS))
-        for i in walk:
-            if i.kind in ("label", "comment"):
-                continue
-            for r in i.rd:
-                if r[0] in ("v", "a") and r not in written:
-                    print("UNINITIALISED %s read by: %s" % (r, i.text))
-                    nerr += 1
-                    written.add(r)
-            written.update(i.wr)
-        slotfrag, pending = {}, []
-        for i in walk:
-            if i.kind == "lds":
-                for r in i.wr:
-                    slotfrag[r] = i.meta["frag"]
-                pending.append(i.meta["frag"])
-            elif i.kind == "waitlgkm":
-                n = i.meta["n"]
-                pending = pending[len(pending) - n:] if n else []
-            elif i.kind == "mfma":
-                regs = [r for r in i.rd if r[0] == "v" and RING <= r[1] < RING + 4 * NRING]
-                assert len(regs) == 4
-                want = i.meta["frag"]
-                for r in regs:
-                    if slotfrag.get(r) != want:
-                        print("RING slot %s holds %s, MFMA expects %s" % (r, slotfrag.get(r), want))
-                        nerr += 1
-                if want in pending:
-                    print("RING fragment not waited for: %s" % (want,))
-                    nerr += 1
+    def check_own(self):
         # the token rows are retired by a counted wait: some DMA piece issued behind them is waited for
         rows = [k for k, t in enumerate(self.vmlog) if t[0] == "row"]
         if rows:
@@ -366,20 +206,11 @@ class Gen:
         # every tile stored exactly once, four pieces
         st = [t for t in self.vmlog if t[0] == "st"]
         assert sorted(st) == sorted([("st", n) for n in range(NTILE) for _ in range(2)]), "stores"
-        assert nerr == 0, "%d problems" % nerr
 
-    def text(self):
-        knob = os.environ.get("QKV_GEN_KNOB", "").split("+")      # timing experiments only: results WRONG
-        keep = []
-        for i in self.ins:
-            if i.kind == "comment":
-                continue
-            if "nostore" in knob and i.kind == "vmem" and i.meta["vm"][0] == "st":
-                continue
-            if "nomfma" in knob and i.kind == "mfma":
-                continue
-            keep.append(i)
-        return " \\\n  ".join('"' + i.text + NL + '"' for i in keep)
+    def keep(self, i, knob):
+        if "nostore" in knob and i.kind == "vmem" and i.meta["vm"][0] == "st":
+            return []
+        return asmgen.ChunkRing.keep(self, i, knob)
 
     def stats(self):
         print("instructions:", sum(1 for i in self.ins if i.kind not in ("comment", "label")),
@@ -387,25 +218,15 @@ class Gen:
               " max counted vmcnt:", max(int(i.text.split("(")[1][:-1]) for i in self.ins if i.kind == "waitvm"))
 
 
-def main():
-    g = Gen()
-    g.build()
-    g.resolve_waits()
-    g.check()
-    if "--stats" in sys.argv:
-        g.stats()
-    out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "lkgd_amd", "csrc",
-                       "qkv_fused_loop.inc" if C_IN == 320 else "qkv%d_fused_loop.inc" % C_IN)
-    P = "QK" if C_IN == 320 else "QK%d" % (C_IN // 100)
-    with open(out, "w") as f:
-        f.write("// GENERATED by tools/gen_qkv_asm.py - do not edit.  Panel statement of qkv_fused.hip (plan: see that script).\n")
-        f.write("#define %s_VB %d\n#define %s_VEND %d\n#define %s_AEND %d\n#define %s_ZF %d\n#define %s_PARTS %d\n" % (P, VB, P, VEND, P, AEND, P, ZF, P, PARTS))
-        f.write("#define %s_W1_BYTES %d\n#define %s_W2_BYTES %d\n#define %s_SLOT %d\n#define %s_NSLOT %d\n#define %s_NTILE %d\n#define %s_AHEAD %d\n" % (P, W1_BYTES, P, W2_BYTES, P, SLOT, P, NSLOT, P, NTILE, P, AHEAD))
-        f.write("#define %s_PANEL_ASM \\\n  %s\n\n" % (P, g.text()))
-        clob = ['"v%d"' % i for i in range(VB, VEND)] + ['"a%d"' % i for i in range(AEND)] + ['"s%d"' % i for i in range(SP, SP + 2)]
-        f.write("#define %s_CLOBBERS " % P + ", ".join(clob) + ', "vcc", "scc", "m0", "memory"\n')
-    print("wrote", out)
+    def inc(self):
+        P = "QK" if C_IN == 320 else "QK%d" % (C_IN // 100)
+        D = dict(VB=VB, VEND=VEND, AEND=AEND, ZF=ZF, PARTS=PARTS, W1_BYTES=W1_BYTES, W2_BYTES=W2_BYTES, SLOT=SLOT, NSLOT=NSLOT,
+                 NTILE=NTILE, AHEAD=AHEAD)
+        return dict(script="gen_qkv_asm.py", name="qkv_fused_loop.inc" if C_IN == 320 else "qkv%d_fused_loop.inc" % C_IN,
+                    blurb="Panel statement of qkv_fused.hip (plan: see that script).",
+                    defines=[("%s_%s" % (P, k), D[k]) for k in D], macros=[(P + "_PANEL_ASM", self.text())],
+                    clobber=(P + "_CLOBBERS", asmgen.clobbers(VB, VEND, AEND, range(SP, SP + 2))))
 
 
 if __name__ == "__main__":
-    main()
+    asmgen.main(Gen)

@@ -17,15 +17,10 @@ Operands of the K-loop statement:
   %14, %15         vmcnt immediates: how many vector-memory operations younger than the token fragments of K-step 0
                    (K-steps >= 1) are certainly in flight - see gemm_resw.hip
 """
-import os
-import sys
+import asmgen
+from asmgen import q
 
-NL = r"\n\t"
 R, D = 10, 9
-
-
-def q(text):
-    return '"' + text + NL + '"'
 
 
 # RESW_RD / RESW_MM / RESW_LX are identity macros in the product build (timing knobs: tools/micro/resw_knobs.sh)
@@ -91,11 +86,13 @@ def loadx(nks):
     return " \\\n  ".join(lines)
 
 
-out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "lkgd_amd", "csrc", "gemm_resw_kloop.inc")
-with open(out, "w") as f:
-    f.write("// GENERATED by tools/gen_resw_asm.py - do not edit.  K-loop of gemm_resw.hip (see that script for operands).\n")
+def main():
+    macros = []
     for nk in (1, 2, 3, 4, 5):
-        f.write("#define RESW_KLOOP_ASM_%d \\\n  %s\n\n" % (nk, kloop(2 * nk)))
-        f.write("#define RESW_LOADX_ASM_%d \\\n  %s\n\n" % (nk, loadx(2 * nk)))
-    f.write("#define RESW_AGPR_CLOBBERS " + ", ".join('"a%d"' % i for i in range(160)) + "\n")
-print("wrote", out)
+        macros += [("RESW_KLOOP_ASM_%d" % nk, kloop(2 * nk)), ("RESW_LOADX_ASM_%d" % nk, loadx(2 * nk))]
+    asmgen.write_inc("gen_resw_asm.py", "gemm_resw_kloop.inc", "K-loop of gemm_resw.hip (see that script for operands).",
+                     macros=macros, clobber=("RESW_AGPR_CLOBBERS", ['"a%d"' % i for i in range(160)]))
+
+
+if __name__ == "__main__":
+    main()

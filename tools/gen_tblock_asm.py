@@ -26,13 +26,11 @@ and the packed O^T is the B operand of the out-projection.  Nothing of q, k, v, 
 Register plan (named, clobbered): v[24:55] Q tiles (packed in place into v[24:39]; S^T in v[40:55]), v[56:87] K tiles (packed
 into v[56:71]; later the O^T accumulators), v[88:119] V tiles (packed in place into v[88:103]), v[120:135] packed O^T,
 v[136:143] P, v[144:159] MASK, v[160:191] fragment ring, v[192:199] temporaries; a[0:159] Y^T, a[160:239] z^T, a[240:243] ones.
-The generator checks MFMA -> use distances, VALU -> MFMA and trans -> VALU wait states, ring contents, counted lgkmcnt waits,
-reads of uninitialised registers, and that no chunk overwrites a register a queued instruction still has to read.
+Checks: the rule table of tools/asmgen.py, and here that no chunk overwrites a register a queued instruction still has to read.
 """
-import os
-import sys
+import asmgen
+from asmgen import Ins, R, ar, v, vr
 
-NL = r"\n\t"
 VB = 24
 QA, KA, VA = VB, VB + 32, VB + 64
 SACC = QA + 16            # S^T accumulators: the upper half of the Q tiles (free once q is packed into the lower half)
@@ -58,33 +56,6 @@ SCL = 70                  # log2(e) / 8: the softmax scale, applied to the fp32 
 NEG = "0xc6ea6000"        # -30000.0f
 
 
-def v(n):
-    return "v%d" % n
-
-
-def vr(a, n):
-    return "v[%d:%d]" % (a, a + n - 1)
-
-
-def ar(a, n):
-    return "a[%d:%d]" % (a, a + n - 1)
-
-
-def R(base, n, f="v"):
-    return [(f, base + i) for i in range(n)]
-
-
-class Ins:
-    __slots__ = ("text", "kind", "rd", "wr", "meta")
-
-    def __init__(self, text, kind, rd=(), wr=(), **meta):
-        self.text, self.kind, self.rd, self.wr, self.meta = text, kind, tuple(rd), tuple(wr), meta
-
-
-def slot_addr(slot):
-    return "%%[fa%d]" % (slot // 2), (slot % 2) * SLOT
-
-
 def stream():
     """the 40 chunks of a panel: (name, type, head, tile).  The out-projection of head h - 1 sits between the q and the k
     chunks of head h (its operand, the packed O^T of head h - 1, is finished under q0 q1 of head h); the last head keeps the
@@ -101,22 +72,18 @@ def stream():
     return cs
 
 
-class Gen:
+class Gen(asmgen.ChunkRing):
+    SLOT, SP, RING, NRING = SLOT, SP, RING, NRING
+    PRESET = R(ZF, 4 * NKS, "a")
+    KNOB_ENV = "TB_GEN_KNOB"          # tools/micro/tblock_knobs.sh
+    KNOB_DROPS = {"nolds": ("lds", "waitlgkm"), "nomfma": ("mfma",), "nobar": ("barrier", "waitvm", "vmem")}
+
     def __init__(self):
-        self.ins = []
+        asmgen.ChunkRing.__init__(self)
         self.queue = []          # instructions waiting for MFMA gaps: Ins, ("GATE", ring-MFMA position) or ("GAP",)
         self.mpos = 0            # ring MFMAs emitted so far
-        self.ringpos = 0
-        self.pending_dma = []
-        self.dma_half = False
         self.xid = 0
         self.chunk_end = {}      # chunk name -> ring-MFMA count at its end
-
-    def e(self, text, kind, rd=(), wr=(), **meta):
-        self.ins.append(Ins(text, kind, rd, wr, **meta))
-
-    def nop(self, n):
-        self.e("s_nop %d" % n, "nop", n=n)
 
     def q(self, text, kind, rd=(), wr=(), **meta):
         self.queue.append(Ins(text, kind, rd, wr, **meta))
@@ -224,42 +191,8 @@ class Gen:
     def gate(self, after):
         self.queue.append(("GATE", self.mpos + after))
 
-    # ---- fragment reads / DMA (as gen_ff_asm.py) ------------------------------------------------------------------------
-    def read_frag(self, slot, frag_i, ring_slot, tag):
-        reg = RING + 4 * ring_slot
-        base, imm = slot_addr(slot)
-        self.e("ds_read_b128 %s, %s offset:%d" % (vr(reg, 4), base, imm + frag_i * 1024), "lds", wr=R(reg, 4), frag=tag)
-
     def dma_items(self, slot, w1, wrap):
-        it = []
-        for j in range(5):
-            it.append(("s_add_u32 m0, %%[ldsw], %d" % (slot * SLOT + j * 4096),
-                       "global_load_lds_dwordx4 %%[vo%d], s[%d:%d]" % (j, SP, SP + 1)))
-        if w1:
-            it.append(("s_add_u32 m0, %%[lds0], %d" % (slot * SLOT + 20480),
-                       "global_load_lds_dwordx4 %%[vob], s[%d:%d]" % (SP, SP + 1)))
-        if wrap:
-            it.append(("s_mov_b32 s%d, %%[sp0lo]" % SP, "s_mov_b32 s%d, %%[sp0hi]" % (SP + 1)))
-        else:
-            it.append(("s_add_u32 s%d, s%d, %d" % (SP, SP, W1_BYTES if w1 else W2_BYTES), "s_addc_u32 s%d, s%d, 0" % (SP + 1, SP + 1)))
-        return it
-
-    def dma_first(self):
-        if self.pending_dma:
-            self.e(self.pending_dma[0][0], "salu")
-            self.dma_half = True
-
-    def dma_second(self):
-        if self.dma_half:
-            t = self.pending_dma.pop(0)[1]
-            self.e(t, "vmem" if t.startswith("global_load") else "salu")
-            self.dma_half = False
-
-    def emit_dma_all(self):
-        while self.pending_dma:
-            self.dma_first()
-            self.nop(0)
-            self.dma_second()
+        return self.dma_pairs(slot, w1, None if wrap else (W1_BYTES if w1 else W2_BYTES))
 
     # ---- one chunk ------------------------------------------------------------------------------------------------------
     def chunk(self, n, cs):
@@ -401,157 +334,19 @@ class Gen:
         e("s_mov_b32 %%[splo], s%d" % SP, "salu")
         e("s_mov_b32 %%[sphi], s%d" % (SP + 1), "salu")
 
-    # ---- counted lgkmcnt waits ------------------------------------------------------------------------------------------------
-    def resolve_waits(self):
-        out, fifo, retired = [], [], set()
-        for i in self.ins:
-            if i.kind == "lds":
-                fifo.append(i.meta["frag"])
-                out.append(i)
-            elif i.kind == "waitfrag":
-                fr = i.meta["frag"]
-                idx = [k for k, f in enumerate(fifo) if f == fr]
-                if not idx:
-                    assert fr in retired, ("fragment never read", fr)
-                    continue
-                keep = len(fifo) - 1 - idx[-1]
-                assert keep <= 15
-                out.append(Ins("s_waitcnt lgkmcnt(%d)" % keep, "waitlgkm", n=keep))
-                retired.update(fifo[:idx[-1] + 1])
-                fifo = fifo[idx[-1] + 1:]
-            else:
-                out.append(i)
-        self.ins = out
+    def keep(self, i, knob):
+        if "novalu" in knob and i.kind in ("valu", "trans") and "head" in i.meta:
+            return []
+        return asmgen.ChunkRing.keep(self, i, knob)
 
-    # ---- checks ------------------------------------------------------------------------------------------------------------------
-    def check(self):
-        def ws(i):
-            return i.meta["n"] + 1 if i.kind == "nop" else (0 if i.kind in ("label", "comment") else (8 if i.kind == "mfma" else 1))
-
-        walk = self.ins
-        last_mfma_wr, last_valu_wr, last_trans_wr = {}, {}, {}
-        pos = nerr = 0
-        for i in walk:
-            if i.kind in ("label", "comment"):
-                continue
-            for r in i.rd + i.wr:
-                if r in last_mfma_wr:
-                    same_chain = i.kind == "mfma" and i.meta.get("acc") and r in i.wr and r in i.rd
-                    if not same_chain and pos - last_mfma_wr[r] < 20:
-                        print("HAZARD mfma->use %s dist %d: %s" % (r, pos - last_mfma_wr[r], i.text))
-                        nerr += 1
-            if i.kind == "mfma":
-                for r in i.rd:
-                    if r in last_valu_wr and pos - last_valu_wr[r] < 3:
-                        print("HAZARD valu->mfma %s: %s" % (r, i.text))
-                        nerr += 1
-            if i.kind in ("valu", "trans", "lds"):
-                for r in i.rd:
-                    if r in last_trans_wr and pos - last_trans_wr[r] < 2:
-                        print("HAZARD trans->valu %s: %s" % (r, i.text))
-                        nerr += 1
-            for r in i.wr:
-                last_mfma_wr.pop(r, None)
-                last_valu_wr.pop(r, None)
-                last_trans_wr.pop(r, None)
-                if i.kind == "mfma":
-                    last_mfma_wr[r] = pos
-                elif i.kind == "trans":
-                    last_trans_wr[r] = pos
-                    last_valu_wr[r] = pos
-                elif i.kind == "valu":
-                    last_valu_wr[r] = pos
-            pos += ws(i)
-        written = set(("a", i) for i in range(ZF, ZF + 80))
-        for i in walk:
-            if i.kind in ("label", "comment"):
-                continue
-            for r in i.rd:
-                if r[0] in ("v", "a") and r not in written:
-                    print("UNINITIALISED %s read by: %s" % (r, i.text))
-                    nerr += 1
-                    written.add(r)
-            written.update(i.wr)
-        slotfrag, pending = {}, []
-        for i in walk:
-            if i.kind == "lds":
-                for r in i.wr:
-                    slotfrag[r] = i.meta["frag"]
-                pending.append(i.meta["frag"])
-            elif i.kind == "waitlgkm":
-                n = i.meta["n"]
-                pending = pending[len(pending) - n:] if n else []
-            elif i.kind == "mfma" and not i.meta.get("inline"):
-                regs = [r for r in i.rd if r[0] == "v" and RING <= r[1] < RING + 4 * NRING]
-                assert len(regs) == 4
-                want = i.meta["frag"]
-                for r in regs:
-                    if slotfrag.get(r) != want:
-                        print("RING slot %s holds %s, MFMA expects %s" % (r, slotfrag.get(r), want))
-                        nerr += 1
-                if want in pending:
-                    print("RING fragment not waited for: %s" % (want,))
-                    nerr += 1
-            elif i.kind in ("valu", "trans"):
-                for r in i.rd:
-                    if slotfrag.get(r) in pending and slotfrag.get(r, ("",))[0] == "X":
-                        print("exchange result not waited for: %s" % i.text)
-                        nerr += 1
-        assert nerr == 0, "%d problems" % nerr
-
-    def text(self):
-        knob = os.environ.get("TB_GEN_KNOB", "").split("+")      # timing experiments only: results WRONG
-        keep = []
-        for i in self.ins:
-            if i.kind == "comment":
-                continue
-            if "nolds" in knob and i.kind in ("lds", "waitlgkm"):
-                continue
-            if "novalu" in knob and i.kind in ("valu", "trans") and "head" in i.meta:
-                continue
-            if "nomfma" in knob and i.kind == "mfma":
-                continue
-            if "nobar" in knob and i.kind in ("barrier", "waitvm", "vmem"):
-                continue
-            keep.append(i)
-        return " \\\n  ".join('"' + i.text + NL + '"' for i in keep)
-
-    def stats(self):
-        cost = {"mfma": 8, "trans": 8, "valu": 4, "salu": 4, "lds": 4, "vmem": 4, "waitlgkm": 4, "waitvm": 4, "barrier": 4}
-        cur, tot, n = None, {}, {}
-        for i in self.ins:
-            if i.kind == "comment":
-                cur = i.text
-                tot[cur], n[cur] = 0, {}
-            elif cur is not None:
-                tot[cur] += cost.get(i.kind, 0)
-                n[cur][i.kind] = n[cur].get(i.kind, 0) + 1
-        for k in tot:
-            print("%-22s issue cycles %5d (matrix pipe %4d)  %s" % (k, tot[k], 32 * n[k].get("mfma", 0), n[k]))
-        print("instructions:", sum(1 for i in self.ins if i.kind not in ("comment", "label")),
-              " MFMAs:", sum(1 for i in self.ins if i.kind == "mfma"))
-
-
-def main():
-    g = Gen()
-    g.build()
-    g.resolve_waits()
-    g.check()
-    if "--stats" in sys.argv:
-        g.stats()
-    out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "lkgd_amd", "csrc", "attn_tblock_loop.inc")
-    if "-o" in sys.argv:
-        out = sys.argv[sys.argv.index("-o") + 1]
-    with open(out, "w") as f:
-        f.write("// GENERATED by tools/gen_tblock_asm.py - do not edit.  Panel statement of attn_tblock.hip (plan: see that script).\n")
-        f.write("#define TB_VB %d\n#define TB_VEND %d\n#define TB_AEND %d\n#define TB_YACC %d\n#define TB_ZF %d\n" % (VB, VEND, AEND, YACC, ZF))
-        f.write("#define TB_W1_BYTES %d\n#define TB_W2_BYTES %d\n#define TB_SLOT %d\n#define TB_NSLOT %d\n#define TB_NCHUNK %d\n" %
-                (W1_BYTES, W2_BYTES, SLOT, NSLOT, len(stream())))
-        f.write("#define TB_PANEL_ASM \\\n  %s\n\n" % g.text())
-        clob = ['"v%d"' % i for i in range(VB, VEND)] + ['"a%d"' % i for i in range(AEND)] + ['"s%d"' % i for i in range(SP, SCL + 1)]
-        f.write("#define TB_CLOBBERS " + ", ".join(clob) + ', "vcc", "scc", "m0", "memory"\n')
-    print("wrote", out)
+    def inc(self):
+        D = dict(VB=VB, VEND=VEND, AEND=AEND, YACC=YACC, ZF=ZF, W1_BYTES=W1_BYTES, W2_BYTES=W2_BYTES, SLOT=SLOT, NSLOT=NSLOT,
+                 NCHUNK=len(stream()))
+        return dict(script="gen_tblock_asm.py", name="attn_tblock_loop.inc",
+                    blurb="Panel statement of attn_tblock.hip (plan: see that script).",
+                    defines=[("TB_" + k, D[k]) for k in D], macros=[("TB_PANEL_ASM", self.text())],
+                    clobber=("TB_CLOBBERS", asmgen.clobbers(VB, VEND, AEND, range(SP, SCL + 1))))
 
 
 if __name__ == "__main__":
-    main()
+    asmgen.main(Gen)

@@ -12,15 +12,11 @@ Register plan (AGPRs, invisible to the compiler):
   a[32:111]  token fragments x[j][ks] (LayerNorm-ed fp16, MFMA operands) = a[32 + (j*10 + ks)*4 .. +3]
 Operands: %0-%5 weight-fragment ring (scratch), %6 LDS byte address of this lane's 16 bytes of fragment 0 of the chunk's stage.
 """
-import os
+import asmgen
+from asmgen import q
 
-NL = r"\n\t"
 R, D = 6, 5
 NKS = 10
-
-
-def q(text):
-    return '"' + text + NL + '"'
 
 
 def chunk(direct):
@@ -61,11 +57,12 @@ def loadx():
     return " \\\n  ".join(lines)
 
 
-out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "lkgd_amd", "csrc", "attn_tfront_kloop.inc")
-with open(out, "w") as f:
-    f.write("// GENERATED by tools/gen_tfront_asm.py - do not edit.  Chunk loop of attn_tfront.hip (see that script for operands).\n")
-    f.write("#define TFRONT_CHUNK_ASM_SWAPPED \\\n  %s\n\n" % chunk(False))
-    f.write("#define TFRONT_CHUNK_ASM_DIRECT \\\n  %s\n\n" % chunk(True))
-    f.write("#define TFRONT_LOADX_ASM \\\n  %s\n\n" % loadx())
-    f.write("#define TFRONT_AGPR_CLOBBERS " + ", ".join('"a%d"' % i for i in range(112)) + "\n")
-print("wrote", out)
+def main():
+    asmgen.write_inc("gen_tfront_asm.py", "attn_tfront_kloop.inc", "Chunk loop of attn_tfront.hip (see that script for operands).",
+                     macros=[("TFRONT_CHUNK_ASM_SWAPPED", chunk(False)), ("TFRONT_CHUNK_ASM_DIRECT", chunk(True)),
+                             ("TFRONT_LOADX_ASM", loadx())],
+                     clobber=("TFRONT_AGPR_CLOBBERS", ['"a%d"' % i for i in range(112)]))
+
+
+if __name__ == "__main__":
+    main()

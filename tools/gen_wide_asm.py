@@ -14,13 +14,8 @@ Operands of the asm statement (see gemm_wide.hip::wide_ktile):
   %24     m_a    LDS destination (other stage, A part) + this wave's 1 KiB slice
 acc[i][j] (weight fragment i < 10, token fragment j < 4) = a[(4i+j)*4 .. +3].
 """
-import os
-
-NL = r"\n\t"
-
-
-def q(text):
-    return '"' + text + NL + '"'
+import asmgen
+from asmgen import q
 
 
 def rd(text):
@@ -86,20 +81,17 @@ def body(first, part, nf=10, mf=4):
     return " \\\n  ".join(lines)
 
 
-out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "lkgd_amd", "csrc", "gemm_wide_ktile.inc")
-with open(out, "w") as f:
-    f.write("// GENERATED by tools/gen_wide_asm.py - do not edit.  K-tile body of gemm_wide.hip (see that script for operands).\n")
-    f.write("#define WIDE_KTILE_ASM_FIRST_A \\\n  " + body(True, 0) + "\n\n")
-    f.write("#define WIDE_KTILE_ASM_NEXT_A \\\n  " + body(False, 0) + "\n\n")
-    f.write("#define WIDE_KTILE_ASM_B \\\n  " + body(False, 1) + "\n\n")
-    # the 256x256 form (wave tile 64 x 128: eight weight fragments, accumulators a[0:127], four weight loads per thread)
-    f.write("#define WIDE8_KTILE_ASM_FIRST_A \\\n  " + body(True, 0, 8) + "\n\n")
-    f.write("#define WIDE8_KTILE_ASM_NEXT_A \\\n  " + body(False, 0, 8) + "\n\n")
-    f.write("#define WIDE8_KTILE_ASM_B \\\n  " + body(False, 1, 8) + "\n\n")
-    # the 192-row forms (wave tile 48 x 160 / 48 x 128: three token fragments, accumulators (4i+j)*4 with j < 3, three token loads)
-    for nf, pre in ((10, "WIDE_M3"), (8, "WIDE8_M3")):
-        f.write("#define %s_KTILE_ASM_FIRST_A \\\n  " % pre + body(True, 0, nf, 3) + "\n\n")
-        f.write("#define %s_KTILE_ASM_NEXT_A \\\n  " % pre + body(False, 0, nf, 3) + "\n\n")
-        f.write("#define %s_KTILE_ASM_B \\\n  " % pre + body(False, 1, nf, 3) + "\n\n")
-    f.write("#define WIDE_AGPR_CLOBBERS " + ", ".join('"a%d"' % i for i in range(160)) + "\n")
-print("wrote", out)
+def main():
+    # WIDE: wave tile 64 x 160.  WIDE8: the 256x256 form (wave tile 64 x 128: eight weight fragments, accumulators a[0:127], four
+    # weight loads per thread).  _M3: the 192-row forms (wave tile 48 x 160 / 48 x 128: three token fragments, accumulators
+    # (4i+j)*4 with j < 3, three token loads)
+    macros = []
+    for pre, nf, mf in (("WIDE", 10, 4), ("WIDE8", 8, 4), ("WIDE_M3", 10, 3), ("WIDE8_M3", 8, 3)):
+        macros += [(pre + "_KTILE_ASM_FIRST_A", body(True, 0, nf, mf)), (pre + "_KTILE_ASM_NEXT_A", body(False, 0, nf, mf)),
+                   (pre + "_KTILE_ASM_B", body(False, 1, nf, mf))]
+    asmgen.write_inc("gen_wide_asm.py", "gemm_wide_ktile.inc", "K-tile body of gemm_wide.hip (see that script for operands).",
+                     macros=macros, clobber=("WIDE_AGPR_CLOBBERS", ['"a%d"' % i for i in range(160)]))
+
+
+if __name__ == "__main__":
+    main()

@@ -110,6 +110,26 @@ def rowmap_div_mod(div: int, mod: int) -> RowMap:
     return (div, 1, 1, mod)
 
 
+def _gemm_family(name: str, args: tuple, flop: float) -> None:
+    """one launch of the GEMM family (the GEMM and the fused kernels built on its skeleton): entry point ``name`` with ``args``
+    and the current stream, ``flop`` its algorithmic FLOP.  Bracketed by events when GEMM_EVENTS is a list; while this thread
+    records, the plan entry of the call carries the same ``flop`` (Plan.run(gemm_events) brackets it on replay)."""
+    plan = current_plan()
+    fn = getattr(plan.lib if plan is not None else _lib.lib(), name)
+    ev = GEMM_EVENTS
+    if ev is None:
+        rc = fn(*args, _stream())
+    else:
+        s_ev, e_ev = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        s_ev.record()
+        rc = fn(*args, _stream())
+        e_ev.record()
+        ev.append((s_ev, e_ev, float(flop)))
+    if plan is not None:
+        plan.gemm_family(flop)
+    check(rc, name)
+
+
 _FAKE_PTR = 1 << 12     # gemm_plan off the device: a non-NULL, 16-byte aligned stand-in for buffers the query never dereferences
 
 
@@ -166,7 +186,7 @@ def _gemm_desc(a0, w, out, *, M, N, K, bias=None, a1=None, csplit=None, mode=A_P
     if colstats and COLSTATS and out.shape[0] == M and out.shape[1] == N:
         d.cs_rows = int(colstats)        # the tile-form choice keeps to tile rows that divide a sample
         if launch:
-            blk = _L().lkgd_gemm_colstats_block(C.byref(d))
+            blk = _lib.lib().lkgd_gemm_colstats_block(C.byref(d))      # (a host query: nothing to record)
         else:
             info = _lib.GemmPlanInfo()
             blk = info.colstats_block if _lib.lib().lkgd_gemm_plan(C.byref(d), int(plan_cus), C.byref(info)) == 0 else 0
@@ -197,15 +217,7 @@ def gemm(a0: torch.Tensor, w: torch.Tensor, out: torch.Tensor, *, M: int, N: int
     d = _gemm_desc(a0, w, out, M=M, N=N, K=K, bias=bias, a1=a1, csplit=csplit, mode=mode, Cin=Cin, conv=conv, tconv=tconv,
                    rowbias=rowbias, rowmap=rowmap, res1=res1, r1=r1, res2=res2, r2=r2, s_acc=s_acc, geglu=geglu,
                    colstats=colstats, ln=ln)
-    ev = GEMM_EVENTS
-    if ev is not None:
-        s_ev, e_ev = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        s_ev.record()
-        check(_L().lkgd_gemm_f16(C.byref(d), _stream()), "lkgd_gemm_f16")
-        e_ev.record()
-        ev.append((s_ev, e_ev, 2.0 * M * N * (72 if mode == A_CONV3X3_C8 else K)))
-        return out
-    check(_L().lkgd_gemm_f16(C.byref(d), _stream()), "lkgd_gemm_f16")
+    _gemm_family("lkgd_gemm_f16", (C.byref(d),), 2.0 * M * N * (72 if mode == A_CONV3X3_C8 else K))
     return out
 
 
@@ -263,7 +275,7 @@ def groupnorm_stats(x0: torch.Tensor, x1: Optional[torch.Tensor], nsamples: int,
     c0 = x0.shape[1]
     c1 = x1.shape[1] if x1 is not None else 0
     L = _L()
-    nchunks = L.lkgd_groupnorm_chunks(rows_per_sample, c0 + c1)
+    nchunks = _lib.lib().lkgd_groupnorm_chunks(rows_per_sample, c0 + c1)      # (a host query: nothing to record)
     partial = torch.empty(nsamples * nchunks * 64, dtype=torch.float32, device=x0.device)
     stats = torch.empty(nsamples, 32, 2, dtype=torch.float32, device=x0.device)
     check(L.lkgd_groupnorm_stats(x0.data_ptr(), c0, _ld(x0), _ptr(x1), c1, _ld(x1) if x1 is not None else 0,
@@ -281,7 +293,7 @@ def groupnorm_sums(x0: torch.Tensor, x1: Optional[torch.Tensor], nsamples: int, 
     c0 = x0.shape[1]
     c1 = x1.shape[1] if x1 is not None else 0
     L = _L()
-    nchunks = L.lkgd_groupnorm_chunks(rows_per_sample, c0 + c1)
+    nchunks = _lib.lib().lkgd_groupnorm_chunks(rows_per_sample, c0 + c1)      # (a host query: nothing to record)
     partial = torch.empty(nsamples * nchunks * 64, dtype=torch.float32, device=x0.device)
     sums = torch.empty(nsamples, 32, 2, dtype=torch.float32, device=x0.device)
     check(L.lkgd_groupnorm_sums(x0.data_ptr(), c0, _ld(x0), _ptr(x1), c1, _ld(x1) if x1 is not None else 0,
@@ -352,7 +364,7 @@ def groupnorm_silu(x0, x1, nsamples, rows_per_sample, gamma, beta, eps, silu=Tru
     c0 = x0.shape[1]
     c1 = x1.shape[1] if x1 is not None else 0
     L = _L()
-    nchunks = L.lkgd_groupnorm_chunks(rows_per_sample, c0 + c1)
+    nchunks = _lib.lib().lkgd_groupnorm_chunks(rows_per_sample, c0 + c1)      # (a host query: nothing to record)
     partial = torch.empty(nsamples * nchunks * 64, dtype=torch.float32, device=x0.device)
     stats = torch.empty(nsamples, 32, 2, dtype=torch.float32, device=x0.device)
     check(L.lkgd_groupnorm_silu(x0.data_ptr(), c0, _ld(x0), _ptr(x1), c1, _ld(x1) if x1 is not None else 0, nsamples,
@@ -382,14 +394,14 @@ def layernorm(x: torch.Tensor, gamma: Optional[torch.Tensor], beta: Optional[tor
 FF_FUSED = os.environ.get("LKGD_NO_FF_FUSED", "0") != "1"
 
 
-#: A/B switch of the one-launch LayerNorm + QKV projection of the 72x128 level (False = the row-panel GEMM with the LayerNorm fold)
+#: A/B switch of the one-launch LayerNorm + QKV projection of the 72x128 level (False = LayerNorm kernel + GEMM)
 LN_QKV = os.environ.get("LKGD_NO_LN_QKV", "0") != "1"
 
 
 def ln_qkv_ok(T: int, N: int, C_: int) -> bool:
     """the fused kernel exists for 320 -> 960 and 640 -> 1920 and pays where its 128-token panels fill the CUs: from one full
     round at C = 640 (a CFG-parallel rank's 32 256 rows: 83 us against 109 for LayerNorm + GEMM; 16 128 rows tie), from two
-    at C = 320, where the alternative is the row-panel GEMM with the LayerNorm folded in (profiles/r05_ln_qkv_rows.txt)"""
+    at C = 320, measured against the row-panel GEMM with the LayerNorm folded in (profiles/r05_ln_qkv_rows.txt)"""
     return LN_QKV and C_ in (320, 640) and N == 3 * C_ and T >= (30000 if C_ == 640 else 60000)
 
 
@@ -399,15 +411,8 @@ def ln_qkv(x: torch.Tensor, wstream: torch.Tensor, out: torch.Tensor, eps: float
     T, C_ = x.shape
     if C_ not in (320, 640):
         raise _lib.LkgdHipError("ln_qkv: 320 or 640 channels")
-    fn = _L().lkgd_ln_qkv_c320 if C_ == 320 else _L().lkgd_ln_qkv_c640
-    ev = GEMM_EVENTS
-    if ev is not None:
-        s_ev, e_ev = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        s_ev.record()
-    check(fn(x.data_ptr(), _ld(x), T, wstream.data_ptr(), eps, out.data_ptr(), _ld(out), _stream()), "lkgd_ln_qkv")
-    if ev is not None:
-        e_ev.record()
-        ev.append((s_ev, e_ev, 2.0 * T * 3 * C_ * C_))
+    _gemm_family("lkgd_ln_qkv_c320" if C_ == 320 else "lkgd_ln_qkv_c640",
+                 (x.data_ptr(), _ld(x), T, wstream.data_ptr(), eps, out.data_ptr(), _ld(out)), 2.0 * T * 3 * C_ * C_)
     return out
 
 
@@ -432,17 +437,12 @@ def ff_fused(x: torch.Tensor, wstream: torch.Tensor, b2: torch.Tensor, out: torc
     d1, m1, d2, md = (rowmap if rowmap is not None else (1, 1, 1, 1))[:4]
     if rowbias is not None and (m1 != 1 or d2 != 1 or (len(rowmap) > 4 and rowmap[4] != 0)):
         raise _lib.LkgdHipError("ff_fused: only (row // d1) % md row maps (no c0 term)")
-    ev = GEMM_EVENTS        # a GEMM-family launch for bench.py's roofline line: 2 T (2560 x 320 + 320 x 1280) algorithmic FLOP
-    if ev is not None:
-        s_ev, e_ev = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        s_ev.record()
-    check(_L().lkgd_ff_fused_c320(x.data_ptr(), _ld(x), x.shape[0], _ptr(rowbias), _ld(rowbias) if rowbias is not None else 0,
-                                  d1, min(md, 1 << 30), wstream.data_ptr(), b2.data_ptr(), eps, s_acc, _ptr(res2),
-                                  _ld(res2) if res2 is not None else 0, r2, out.data_ptr(), _ld(out), _stream()),
-          "lkgd_ff_fused_c320")
-    if ev is not None:
-        e_ev.record()
-        ev.append((s_ev, e_ev, 2.0 * x.shape[0] * (2560 * 320 + 320 * 1280)))
+    # a GEMM-family launch for bench.py's roofline line: 2 T (2560 x 320 + 320 x 1280) algorithmic FLOP
+    _gemm_family("lkgd_ff_fused_c320",
+                 (x.data_ptr(), _ld(x), x.shape[0], _ptr(rowbias), _ld(rowbias) if rowbias is not None else 0, d1,
+                  min(md, 1 << 30), wstream.data_ptr(), b2.data_ptr(), eps, s_acc, _ptr(res2),
+                  _ld(res2) if res2 is not None else 0, r2, out.data_ptr(), _ld(out)),
+                 2.0 * x.shape[0] * (2560 * 320 + 320 * 1280))
     return out
 
 
@@ -493,17 +493,12 @@ def tattn_block(x: torch.Tensor, wstream: torch.Tensor, bo: torch.Tensor, out: t
     c0 = rowmap[4] if rowmap is not None and len(rowmap) > 4 else 0
     if rowbias is not None:
         _req(rowbias, torch.float16, "rowbias")
-    nflop = 2 * x.shape[0] * (960 * 320 + 320 * 320) + 4 * x.shape[0] * 16 * 320
-    ev = GEMM_EVENTS        # a GEMM-family launch for bench.py's roofline line (projections, out-projection, 16 x 16 attention)
-    if ev is not None:
-        s_ev, e_ev = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        s_ev.record()
-    check(_L().lkgd_tattn_block_c320(x.data_ptr(), _ld(x), wstream.data_ptr(), bo.data_ptr(), _ptr(rowbias),
-                                     _ld(rowbias) if rowbias is not None else 0, d1, m1, d2, min(md, 0x7fffffff), c0,
-                                     out.data_ptr(), _ld(out), B, F, HW, eps, _stream()), "lkgd_tattn_block_c320")
-    if ev is not None:
-        e_ev.record()
-        ev.append((s_ev, e_ev, float(nflop)))
+    # a GEMM-family launch for bench.py's roofline line (projections, out-projection, 16 x 16 attention)
+    _gemm_family("lkgd_tattn_block_c320",
+                 (x.data_ptr(), _ld(x), wstream.data_ptr(), bo.data_ptr(), _ptr(rowbias),
+                  _ld(rowbias) if rowbias is not None else 0, d1, m1, d2, min(md, 0x7fffffff), c0, out.data_ptr(), _ld(out),
+                  B, F, HW, eps),
+                 2 * x.shape[0] * (960 * 320 + 320 * 320) + 4 * x.shape[0] * 16 * 320)
     return out
 
 
@@ -531,16 +526,6 @@ def attn_cross(q, k, v, out, heads: int, ncontexts: int, Lk: int, rowmap: RowMap
     check(_L().lkgd_attn_cross(q.data_ptr(), _ld(q), k.data_ptr(), _ld(k), v.data_ptr(), _ld(v), out.data_ptr(), _ld(out),
                                q.shape[0], heads, ncontexts, Lk, d1, m1, d2, md, c0, scale, _stream()), "lkgd_attn_cross")
     return out
-
-
-#: A/B switch of the LayerNorm fold into the row-panel QKV projection (False = LayerNorm kernel + GEMM)
-LNFOLD = os.environ.get("LKGD_NO_LNFOLD", "0") != "1"
-
-
-def gemm_ln_ok(M: int, N: int, K: int) -> bool:
-    """shapes for which gemm(..., ln=...) runs (the row-panel program) AND pays: K = LayerNorm width <= 320 and enough 256-row
-    panels to fill the CUs (a rank of 8 has 144 at the 72x128 level: LayerNorm + 256x320 tiles stay ahead there)"""
-    return LNFOLD and K <= 320 and K % 64 == 0 and K >= 192 and M >= 60000 and N % 8 == 0
 
 
 def attn_dense(q, k, v, out, nbatch: int, S: int, heads: int, head_dim: int, scale: Optional[float] = None):

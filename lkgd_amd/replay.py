@@ -270,25 +270,7 @@ class _RecordingLib:
 
         def call(*args):
             rc = fn(*args)
-            if name in ("lkgd_groupnorm_chunks", "lkgd_gemm_colstats_block"):     # pure host helpers, return a count
-                return rc
-            flop = None
-            if name == "lkgd_gemm_f16":
-                d = args[0]._obj
-                flop = 2.0 * d.M * d.N * (72 if d.mode == 3 else d.K)
-            # the fused kernels of the GEMM family, with the FLOP formulas ops.ff_fused / ops.tattn_block / ops.ln_qkv use for
-            # the eager path's events (bench.py's roofline line counts the same launches replayed or not)
-            elif name in ("lkgd_ff_fused_c320", "lkgd_ff_fused_c640"):
-                c = 320 if name.endswith("c320") else 640
-                flop = 2.0 * args[2] * (8 * c * c + 4 * c * c)
-            elif name in ("lkgd_ln_qkv_c320", "lkgd_ln_qkv_c640"):
-                c = 320 if name.endswith("c320") else 640
-                flop = 2.0 * args[2] * 3 * c * c
-            elif name in ("lkgd_tattn_block_c320", "lkgd_tattn_block_c640"):
-                c = 320 if name.endswith("c320") else 640
-                rows = args[13] * args[14] * args[15]
-                flop = 2.0 * rows * (3 * c * c + c * c) + 4.0 * rows * 16 * c
-            plan.calls.append((fn, args[:-1], name, flop))   # the last argument of every launch is the stream
+            plan.calls.append((fn, args[:-1], name, None))   # the last argument of every launch is the stream
             return rc
         return call
 
@@ -315,6 +297,12 @@ class Plan:
     def python(self, f: Callable[[], None]) -> None:
         """a host-side step (collective, torch copy) to redo at this point of every replay"""
         self.calls.append((None, f, "py", None))
+
+    def gemm_family(self, flop: float) -> None:
+        """the launch just recorded belongs to the GEMM family: ``flop`` = its algorithmic FLOP, as ops counted it for the eager
+        call (``run(gemm_events)`` then brackets it with events - bench.py's roofline line)"""
+        fn, args, name, _ = self.calls[-1]
+        self.calls[-1] = (fn, args, name, float(flop))
 
     def run(self, gemm_events=None):
         from . import trace

@@ -38,7 +38,8 @@ from . import ops
 from . import replay as _replay
 from . import trace as _trace
 from ._lib import LkgdHipError
-from .packing import pack_conv3x3, pack_conv3x3_c8, pack_ff_fused, pack_geglu, pack_linear, pack_tconv3
+from .packing import (pack_conv3x3, pack_conv3x3_c8, pack_ff_fused, pack_geglu, pack_linear, pack_ln_proj, pack_tblock,
+                      pack_tconv3, pack_tfront)
 
 #: row order of the temporal cross-attention context, see SURVEY.md App. C11.  "interleaved_0_27" reproduces
 #: diffusers 0.27.x (rows (pixel, batch)-ordered against (batch, pixel)-ordered hidden rows); "batch_major" = later.
@@ -188,10 +189,7 @@ class Attention(nn.Module):
         if norm is not None:
             w, bqkv = _fold_ln(norm, w, None)
             bqkv = bqkv.contiguous()
-        wq = pack_linear(w)
-        # column sums of the PACKED (fp16) weights: what the LayerNorm fold of ops.gemm(ln=...) subtracts, times the row mean
-        cs = wq.float().sum(dim=1).contiguous() if norm is not None else None
-        return SimpleNamespace(wqkv=wq, bqkv=bqkv, cs=cs,
+        return SimpleNamespace(wqkv=pack_linear(w), bqkv=bqkv,
                                wo=pack_linear(_eff_weight(self.to_out[0], ao)), bo=_f32(self.to_out[0].bias))
 
     def pack_cross(self, norm: nn.LayerNorm):
@@ -218,8 +216,8 @@ def _eff_weight(lin, adapters=()) -> torch.Tensor:
     return lin.weight.detach()
 
 
-def _gemm_runs(ctx: "Ctx", a: torch.Tensor, out: torch.Tensor, pick, *, N: int, K: int, rowmap=None, res1=None,
-               res2=None, rows: Optional[int] = None, **kw) -> None:
+def _gemm_runs(ctx: "Ctx", a: torch.Tensor, out: torch.Tensor, pick, *, rowmap=None, res1=None, res2=None,
+               rows: Optional[int] = None, **kw) -> None:
     """masked-LoRA form of a projection over all T rows: one launch per run of consecutive batch entries that share a
     weight variant (lkgd_amd/lora.py).  pick(i) -> (w, bias, rowbias table or None) of run i; a row map is shifted to the
     run's first row (idx(m) = ((m / d1) * m1 + m % d2 + c0) % md with the run start a multiple of d1 and d2).  ``rows``: token
@@ -235,7 +233,7 @@ def _gemm_runs(ctx: "Ctx", a: torch.Tensor, out: torch.Tensor, pick, *, N: int, 
                 raise LkgdHipError("internal: entry run does not start on a row-map period")
             rm = (rowmap[0], rowmap[1], rowmap[2], rowmap[3],
                   (rowmap[4] if len(rowmap) > 4 else 0) + (r0 // rowmap[0]) * rowmap[1])
-        ops.gemm(a[r0:r1], w, out[r0:r1], M=r1 - r0, N=N, K=K, bias=bias, rowbias=rb, rowmap=rm,
+        ops.gemm(a[r0:r1], w, out[r0:r1], M=r1 - r0, N=w.shape[0], K=w.shape[1], bias=bias, rowbias=rb, rowmap=rm,
                  res1=res1[r0:r1] if res1 is not None else None, res2=res2[r0:r1] if res2 is not None else None, **kw)
 
 
@@ -257,6 +255,130 @@ def _attn_variant(block, which: str, ctx: "Ctx", run: int, spatial: bool):
                 _pack_joint_post(block, v, spatial, key[4])
         pk.var[key] = v
     return v
+
+
+def _project(block, ctx: "Ctx", which: str, part: str, a: torch.Tensor, out: torch.Tensor, *, cross=None,
+             rows: Optional[int] = None, res1=None, **epilogue) -> None:
+    """out = a . W^T + b with the caller's epilogue, where W, b are a named part of the pack of block.attn1 (``which`` "a1") or
+    block.attn1n ("a1n"): "qkv" the whole fused projection, "q" its query rows [:C], "kv" its key | value rows [C:], "out" wo / bo,
+    "joint" the out-projection with the joint branch's post step folded in (jw / jb).  ``cross`` = (first context entry, row
+    map): the folded cross-attention table joins the epilogue as a row bias.
+    One launch with the block's own weights; under masked LoRA one launch per entry run with that run's weight variant and
+    cross-attention table (_attn_variant, _gemm_runs).  ``rows``: token rows per batch entry in the layout of ``a`` where that is
+    not the rank's frames x pixels (the pixel-re-sharded and the gathered layouts of a frame-sharded temporal block)."""
+    pk, Cc = block._pk, a.shape[1]
+    if ctx.lora is None:
+        w, b = _part(pk if part == "joint" else getattr(pk, which), part, Cc)
+        if cross is not None:
+            epilogue.update(rowbias=ctx.xb_all[cross[0]:, pk.xoff:pk.xoff + Cc], rowmap=cross[1])
+        ops.gemm(a, w, out, M=a.shape[0], N=w.shape[0], K=w.shape[1], bias=b, res1=res1, **epilogue)
+        return
+    spatial = isinstance(block, BasicTransformerBlock)
+    vs = [_attn_variant(block, which, ctx, i, spatial) for i in range(len(ctx.lora.runs))]
+    table = (lambda i: None) if cross is None else (lambda i: ctx.xb_runs[i][cross[0]:, pk.xoff:pk.xoff + Cc])
+    _gemm_runs(ctx, a, out, lambda i: (*_part(vs[i], part, Cc), table(i)), rowmap=cross[1] if cross is not None else None,
+               res1=res1, rows=rows, **epilogue)
+
+
+def _part(v, part: str, Cc: int):
+    """(W, b) of a named part of an attention pack (see _project)"""
+    if part == "out":
+        return v.wo, v.bo
+    if part == "joint":
+        return v.jw, v.jb
+    if part == "qkv":
+        return v.wqkv, v.bqkv
+    return (v.wqkv[:Cc], v.bqkv[:Cc]) if part == "q" else (v.wqkv[Cc:], v.bqkv[Cc:])
+
+
+def _first_use(pk, name: str, build):
+    """pk.<name>, packed on first use.  Built once from the weights: a constant of any plan being recorded"""
+    v = getattr(pk, name, None)
+    if v is None:
+        with _replay.invariant():
+            v = build()
+        setattr(pk, name, v)
+    return v
+
+
+def _ln_qkv(block, x: torch.Tensor, qkv: torch.Tensor) -> None:
+    """qkv = attn1's Q | K | V of LayerNorm(x) in one launch of the fused-kernel skeleton (qkv_fused.hip: the 72x128 and 36x64
+    levels); the block's own weights only"""
+    a1 = block._pk.a1
+    ops.ln_qkv(x, _first_use(a1, "wlnqkv", lambda: pack_ln_proj(a1.wqkv, a1.bqkv)), qkv)
+
+
+def _self_qkv(block, ctx: "Ctx", h: torch.Tensor, keep_ln: bool):
+    """Q | K | V of block.attn1 over LayerNorm(h): (qkv, normalised tokens or None).  One launch where the fused kernel pays, the
+    block's own weights run (no masked LoRA) and nobody reads the normalised tokens again (``keep_ln``: the joint branch does);
+    LayerNorm + projection otherwise"""
+    T, Cc = h.shape
+    fused = ctx.lora is None and not keep_ln and ops.ln_qkv_ok(T, 3 * Cc, Cc)
+    ln = None if fused else ops.layernorm(h, None, None, 1e-5)
+    qkv = ctx.new(T, 3 * Cc)
+    if fused:
+        _ln_qkv(block, h, qkv)
+    else:
+        _project(block, ctx, "a1", "qkv", ln, qkv)
+    return qkv, ln
+
+
+def _attend_temporal(block, ctx: "Ctx", which: str, a: torch.Tensor, geom, *, rows: Optional[int] = None, kv_b_map=None,
+                     ln_fused: bool = False) -> torch.Tensor:
+    """attention of block.attn1 / attn1n over the frames of every pixel: allocate [rows, 3C], project, attend on the three
+    column thirds.  ``a``: normalised tokens - or, with ``ln_fused``, the tokens themselves (LayerNorm + Q|K|V in one launch);
+    ``geom`` = (entries, frames, pixels) of a's layout."""
+    T, Cc = a.shape
+    qkv = ctx.new(T, 3 * Cc)
+    if ln_fused:
+        _ln_qkv(block, a, qkv)
+    else:
+        _project(block, ctx, which, "qkv", a, qkv, rows=rows)
+    att = ctx.new(T, Cc)
+    heads = (block.attn1 if which == "a1" else block.attn1n).heads
+    ops.attn_temporal(qkv[:, :Cc], qkv[:, Cc:2 * Cc], qkv[:, 2 * Cc:], att, *geom, heads, kv_b_map=kv_b_map)
+    return att
+
+
+def temporal_path(C_: int, heads: int, F: int, F_total: int, HW: int, T: int, frame_shards: int, *, lora: bool, joint: bool,
+                  gather: bool):
+    """which launch sequence the self-attention of a temporal transformer block takes: (path name, whether the normalised tokens
+    are needed as a tensor).  Pure: scalars in (channels, heads, local / total frames, pixels per frame, token rows, frame
+    shards; masked LoRA on, joint branch on, dist.TEMPORAL_GATHER), nothing allocated or launched
+    (tests/test_host_cpu.py::test_temporal_path_table holds the table).
+      all frames on this rank (F == F_total):
+        block    LayerNorm .. out-projection + residual in one launch (ops.tattn_block); the joint branch normalises apart
+        front    LayerNorm + Q|K|V + attention in one launch (ops.tattn_front), then the out-projection GEMM
+        ln_qkv   LayerNorm + Q|K|V in one launch (ops.ln_qkv: the 36x64 level), then the attention kernel
+        chain    LayerNorm, projection(s), attention kernel - everything else, every masked-LoRA forward
+      frames on several GPUs:
+        pixels   re-shard by pixels around the attention (front or chain form inside), back to frame slices
+        gather   local queries against K | V projected from the gathered normalised tokens (LKGD_TEMPORAL_GATHER=1, and a level
+                 with fewer pixels than shards - the 1x1 level of the tiny test nets)"""
+    if F_total != F:
+        return ("pixels", False) if (not gather and HW >= frame_shards) else ("gather", True)
+    if not lora and ops.tattn_front_ok(C_, heads, F, HW):
+        if ops.tattn_block_ok(C_, heads, F, HW):
+            return "block", joint
+        if not joint:      # the joint branch reads the normalised tokens again: unfused
+            return "front", False
+    if not lora and not joint and ops.ln_qkv_ok(T, 3 * C_, C_):
+        return "ln_qkv", False
+    return "chain", True
+
+
+def _temporal_path_of(block, ctx: "Ctx", T: int, Cc: int, joint: bool):
+    """temporal_path of this block in this forward"""
+    from . import dist as _dist
+    return temporal_path(Cc, block.attn1.heads, ctx.F, ctx.F_total, ctx.HW, T,
+                         ctx.shard.plan.frame_shards if ctx.frames_sharded else 1, lora=ctx.lora is not None, joint=joint,
+                         gather=_dist.TEMPORAL_GATHER)
+
+
+def _front_ok(block, ctx: "Ctx", Cc: int, F: int, HW: int) -> bool:
+    """the fused temporal-attention front can run block.attn1 over (F frames, HW pixels): one weight set for all entries (no masked
+    LoRA) and a geometry the kernel has"""
+    return ctx.lora is None and ops.tattn_front_ok(Cc, block.attn1.heads, F, HW)
 
 
 def _pack_joint_post(block, pk, spatial: bool, out_adapters=()):
@@ -354,11 +476,8 @@ def _cross_literal(block, ctx: Ctx, h1: torch.Tensor, rowmap, first_ctx: int) ->
     """attn2 as written (patch/patch.py:526-549, :660-668) for a context of Lk > 1 tokens: norm2 -> to_q; to_k | to_v of the
     context tokens; every row against the Lk keys of the context `rowmap` selects (counted from entry `first_ctx`);
     to_out + residual.  The one-token case never comes here (folded into a row bias by _cross_tables)."""
-    pk = block._pk
-    if not hasattr(pk, "x2"):
-        with _replay.invariant():      # built once from the weights: a constant of any plan being recorded
-            pk.x2 = block.attn2.pack_cross(block.norm2)
-    x2, (T, Cc), Lk = pk.x2, h1.shape, ctx.cross_Lk
+    x2 = _first_use(block._pk, "x2", lambda: block.attn2.pack_cross(block.norm2))
+    (T, Cc), Lk = h1.shape, ctx.cross_Lk
     ln2 = ops.layernorm(h1, None, None, 1e-5)
     q = ctx.new(T, Cc)
     ops.gemm(ln2, x2.wq, q, M=T, N=Cc, K=Cc, bias=x2.bq)
@@ -406,52 +525,26 @@ class BasicTransformerBlock(nn.Module):
 
     @_trace.traced("spatial_transformer_block")
     def run(self, ctx: Ctx, h: torch.Tensor) -> torch.Tensor:
-        pk, T, Cc = self._pk, h.shape[0], h.shape[1]
-        heads = self.attn1.heads
-        # norm1 folded into the QKV projection where the row-panel program runs it (K = 320 at many rows): the normalised
-        # tokens are never written; the joint branch reads them again and keeps the LayerNorm pass
+        T, Cc = h.shape
+        # the joint branch reads the normalised tokens again and keeps the LayerNorm pass
         joint = self.enable_joint_attention and hasattr(self, "attn1n")
-        fold = ctx.lora is None and pk.a1.cs is not None and ops.gemm_ln_ok(T, 3 * Cc, Cc) and not joint
-        # LayerNorm + Q|K|V in one launch of the fused-kernel skeleton (qkv_fused.hip: the 72x128 and 36x64 levels)
-        one = ctx.lora is None and not joint and ops.ln_qkv_ok(T, 3 * Cc, Cc)
-        ln = None if (fold or one) else ops.layernorm(h, None, None, 1e-5)
-        qkv = ctx.new(T, 3 * Cc)
-        if one:
-            if getattr(pk.a1, "wlnqkv", None) is None:
-                from .packing import pack_ln_proj
-                with _replay.invariant():      # built once from the weights: a constant of any plan being recorded
-                    pk.a1.wlnqkv = pack_ln_proj(pk.a1.wqkv, pk.a1.bqkv)
-            ops.ln_qkv(h, pk.a1.wlnqkv, qkv)
-        elif fold:
-            ops.gemm(h, pk.a1.wqkv, qkv, M=T, N=3 * Cc, K=Cc, bias=pk.a1.bqkv, ln=(pk.a1.cs, 1e-5))
-        elif ctx.lora is None:
-            ops.gemm(ln, pk.a1.wqkv, qkv, M=T, N=3 * Cc, K=Cc, bias=pk.a1.bqkv)
-        else:
-            va = [_attn_variant(self, "a1", ctx, i, True) for i in range(len(ctx.lora.runs))]
-            _gemm_runs(ctx, ln, qkv, lambda i: (va[i].wqkv, va[i].bqkv, None), N=3 * Cc, K=Cc)
+        qkv, ln = _self_qkv(self, ctx, h, keep_ln=joint)
         # flip=True joint attention on a frame-sharded rank: attn1n's K | V rows come from the mirror shard.  Its projection runs FIRST
         # and the exchange is issued here, so that it travels under this branch's attention and out-projection (the one place of the
         # sharded forward where an exchange's consumer is not the very next op)
         pre = self._joint_start(ctx, ln) if (joint and ctx.flip_mirror) else None
         att = ctx.new(T, Cc)
-        ops.attn_spatial(qkv[:, :Cc], qkv[:, Cc:2 * Cc], qkv[:, 2 * Cc:], att, ctx.N, ctx.HW, heads)
+        ops.attn_spatial(qkv[:, :Cc], qkv[:, Cc:2 * Cc], qkv[:, 2 * Cc:], att, ctx.N, ctx.HW, self.attn1.heads)
         h1 = ctx.new(T, Cc)
-        if ctx.lora is not None:
-            if getattr(self, "_lkgd_fsm", False) and self.enable_joint_attention:
-                raise LkgdHipError("masked LoRA together with the FSM hook is not supported")
-            _gemm_runs(ctx, att, h1, lambda i: (va[i].wo, va[i].bo, ctx.xb_runs[i][ctx.b0:, pk.xoff:pk.xoff + Cc]),
-                       N=Cc, K=Cc, rowmap=ops.rowmap_div(ctx.F * ctx.HW), res1=h)
-            if self.enable_joint_attention and hasattr(self, "attn1n"):
-                h1 = self._joint(ctx, ln, h1, pre)
-            return self._tail(ctx, h1)
         if getattr(self, "_lkgd_fsm", False) and self.enable_joint_attention:
+            if ctx.lora is not None:
+                raise LkgdHipError("masked LoRA together with the FSM hook is not supported")
             # the track fuse reads attn1(x) + x BEFORE cross-attention: the folded attn2 bias is added by its last kernels
-            ops.gemm(att, pk.a1.wo, h1, M=T, N=Cc, K=Cc, bias=pk.a1.bo, res1=h)
+            _project(self, ctx, "a1", "out", att, h1, res1=h)
             return self._tail(ctx, self._fsm(ctx, h1))
         # attn1 out-projection + residual + (attn2 == per-batch bias, norm2/Q/K are dead for one key token)
-        ops.gemm(att, pk.a1.wo, h1, M=T, N=Cc, K=Cc, bias=pk.a1.bo, res1=h,
-                 rowbias=ctx.xb_all[ctx.b0:, pk.xoff:pk.xoff + Cc], rowmap=ops.rowmap_div(ctx.F * ctx.HW))
-        if self.enable_joint_attention and hasattr(self, "attn1n"):
+        _project(self, ctx, "a1", "out", att, h1, cross=(ctx.b0, ops.rowmap_div(ctx.F * ctx.HW)), res1=h)
+        if joint:
             h1 = self._joint(ctx, ln, h1, pre)
         return self._tail(ctx, h1)
 
@@ -463,17 +556,12 @@ class BasicTransformerBlock(nn.Module):
 
     def _joint_start(self, ctx: Ctx, ln: torch.Tensor):
         """Q | K | V of attn1n (per-entry LoRA variants where the model carries them); on a flip=True frame-sharded rank also the
-        start of the K | V exchange with the mirror shard.  Returns (qkv, vj, k, v, finish)"""
-        pk, T, Cc = self._pk, ln.shape[0], ln.shape[1]
+        start of the K | V exchange with the mirror shard.  Returns (qkv, k, v, finish)"""
+        T, Cc = ln.shape
         if ctx.spatial_partner is None:
             raise LkgdHipError("joint attention enabled but no joint_attn_mask set (patch.set_joint_attention_mask)")
         qkv = ctx.new(T, 3 * Cc)
-        vj = None
-        if ctx.lora is None:
-            ops.gemm(ln, pk.a1n.wqkv, qkv, M=T, N=3 * Cc, K=Cc, bias=pk.a1n.bqkv)
-        else:
-            vj = [_attn_variant(self, "a1n", ctx, i, True) for i in range(len(ctx.lora.runs))]
-            _gemm_runs(ctx, ln, qkv, lambda i: (vj[i].wqkv, vj[i].bqkv, None), N=3 * Cc, K=Cc)
+        _project(self, ctx, "a1n", "qkv", ln, qkv)
         kk, vv, finish = qkv[:, Cc:2 * Cc], qkv[:, 2 * Cc:], None
         if ctx.flip_mirror:
             # the partner's frame F-1-f lives on the mirror shard: trade the K | V rows of this block with it (one all-to-all whose
@@ -484,14 +572,14 @@ class BasicTransformerBlock(nn.Module):
             _dist._step(lambda: kv_own.copy_(src))
             kv_mirror, finish = ctx.shard.mirror_start(kv_own)
             kk, vv = kv_mirror[:, :Cc], kv_mirror[:, Cc:]
-        return qkv, vj, kk, vv, finish
+        return qkv, kk, vv, finish
 
     def _joint(self, ctx: Ctx, ln: torch.Tensor, h1: torch.Tensor, pre=None) -> torch.Tensor:
         """joint attention attn1n with the partner batch entry's K/V (patch/patch.py:438-501); the post step
         (conv1n / scale1n / conv_fuse) is folded into the out-projection, so the branch ends in ONE GEMM epilogue
         h1 + joint_scale * post(attn1n(...)).  ``pre``: what _joint_start returned when run() called it ahead of the main branch"""
         pk, T, Cc = self._pk, ln.shape[0], ln.shape[1]
-        qkv, vj, kk, vv, finish = pre if pre is not None else self._joint_start(ctx, ln)
+        qkv, kk, vv, finish = pre if pre is not None else self._joint_start(ctx, ln)
         if finish is not None:
             finish()                   # the mirror shard's K | V have arrived (the launch stream waits for the exchange here)
         att = ctx.new(T, Cc)
@@ -499,12 +587,9 @@ class BasicTransformerBlock(nn.Module):
         out = ctx.new(T, Cc)
         js = float(self.joint_scale)
         if pk.post != "conv_fuse":
-            if vj is None:
-                ops.gemm(att, pk.jw, out, M=T, N=Cc, K=Cc, bias=pk.jb, s_acc=js, res1=h1)
-            else:
-                _gemm_runs(ctx, att, out, lambda i: (vj[i].jw, vj[i].jb, None), N=Cc, K=Cc, s_acc=js, res1=h1)
+            _project(self, ctx, "a1n", "joint", att, out, s_acc=js, res1=h1)
             return out
-        if vj is not None:
+        if ctx.lora is not None:
             raise LkgdHipError("masked LoRA with post='conv_fuse' joint layers is not supported")
         # conv_fuse: the i-th masked and i-th unmasked entry blocks are fused pairwise (:488-493) - one two-source GEMM
         # per entry block, own rows | partner rows along K
@@ -587,190 +672,128 @@ class TemporalBasicTransformerBlock(nn.Module):
     @_trace.traced("temporal_transformer_block")
     def run(self, ctx: Ctx, h_s: torch.Tensor, posemb: torch.Tensor, alpha: float, order: str) -> torch.Tensor:
         """h_s: output of the spatial block; returns alpha*h_s + (1-alpha)*temporal(h_s + posemb[f])"""
-        pk, T, Cc = self._pk, h_s.shape[0], h_s.shape[1]
+        T, Cc = h_s.shape
         fmap = ops.rowmap_div_mod(ctx.HW, ctx.F)
-        m1 = _ff_ln(ctx, pk.ffin, h_s, rowbias=posemb, rowmap=fmap)               # ff_in(norm_in(m0)) + m0, m0 = h_s + pos
-        att = ctx.new(T, Cc)
-        va = None
-        att_joint = None       # attn1n's attention output where the sharded paths below compute it (frames on several GPUs)
-        fin_att = fin_joint = None     # pending halves of the re-sharding exchanges that bring attention outputs back to frame slices
-        # LayerNorm + QKV + attention over the frames in one kernel where it exists (C = 320: the 72x128 level); the joint
-        # branch reads the normalised tokens again, masked LoRA runs per-entry weights, a sharded rank gathers frames: unfused
+        m1 = _ff_ln(ctx, self._pk.ffin, h_s, rowbias=posemb, rowmap=fmap)         # ff_in(norm_in(m0)) + m0, m0 = h_s + pos
         joint = self.enable_joint_attention and hasattr(self, "attn1n")
-        base_ok = ctx.lora is None and not ctx.frames_sharded and ops.tattn_front_ok(Cc, self.attn1.heads, ctx.F, ctx.HW)
-        fused = base_ok and not joint
-        from . import dist as _dist
-        # (a level with fewer pixels than shards - the 1x1 level of the tiny test nets - keeps the gathered form)
-        resharded = ctx.frames_sharded and not _dist.TEMPORAL_GATHER and ctx.HW >= ctx.shard.plan.frame_shards
-        # ... and the out-projection, its residual and the folded cross-attention table in the same launch (attn_tblock.hip);
-        # with the joint branch on, the main branch still runs that way and only the joint branch's input is normalised apart
-        one_launch = base_ok and ops.tattn_block_ok(Cc, self.attn1.heads, ctx.F, ctx.HW)
-        # (the 36x64 level: LayerNorm + Q|K|V in one launch, then the attention kernel)
-        ln_qkv_one = (not (fused or resharded or one_launch) and ctx.lora is None and not ctx.frames_sharded and not joint and
-                      ops.ln_qkv_ok(T, 3 * Cc, Cc))
-        ln1 = None if (((fused or resharded or one_launch) and not (one_launch and joint)) or ln_qkv_one) else \
-            ops.layernorm(m1, None, None, 1e-5)
-        if one_launch:
-            pass
-        elif fused:
-            if getattr(pk.a1, "wfront", None) is None:
-                from .packing import pack_tfront
-                with _replay.invariant():      # built once from the weights: a constant of any plan being recorded
-                    pk.a1.wfront = pack_tfront(pk.a1.wqkv, self.attn1.heads)
-            ops.tattn_front(m1, pk.a1.wfront, pk.a1.bqkv, att, ctx.B, ctx.F, ctx.HW, self.attn1.heads)
-        elif ctx.lora is not None and not ctx.frames_sharded:
-            va = [_attn_variant(self, "a1", ctx, i, False) for i in range(len(ctx.lora.runs))]
-            qkv = ctx.new(T, 3 * Cc)
-            _gemm_runs(ctx, ln1, qkv, lambda i: (va[i].wqkv, va[i].bqkv, None), N=3 * Cc, K=Cc)
-            ops.attn_temporal(qkv[:, :Cc], qkv[:, Cc:2 * Cc], qkv[:, 2 * Cc:], att, ctx.B, ctx.F, ctx.HW,
-                              self.attn1.heads)
-        elif not ctx.frames_sharded:
-            qkv = ctx.new(T, 3 * Cc)
-            if ln_qkv_one:
-                if getattr(pk.a1, "wlnqkv", None) is None:
-                    from .packing import pack_ln_proj
-                    with _replay.invariant():      # built once from the weights: a constant of any plan being recorded
-                        pk.a1.wlnqkv = pack_ln_proj(pk.a1.wqkv, pk.a1.bqkv)
-                ops.ln_qkv(m1, pk.a1.wlnqkv, qkv)
-            else:
-                ops.gemm(ln1, pk.a1.wqkv, qkv, M=T, N=3 * Cc, K=Cc, bias=pk.a1.bqkv)
-            ops.attn_temporal(qkv[:, :Cc], qkv[:, Cc:2 * Cc], qkv[:, 2 * Cc:], att, ctx.B, ctx.F, ctx.HW,
-                              self.attn1.heads)
-        elif resharded:
-            # frames of the clip live on several GPUs: re-shard by PIXELS around the attention (all-to-all), so that this rank
-            # holds all F frames of its pixel slice - LayerNorm, Q|K|V and the attention then run once per token, fused where
-            # the kernel applies - and bring the attention output back to frame slices (lkgd_amd/dist.py)
-            m1p = ctx.shard.to_pixels(m1, ctx.HW)              # rows (entry, frame, pixel of this rank's slice)
-            Tp, Ft = m1p.shape[0], ctx.F_total
-            pxl = Tp // (Ft * ctx.B)
+        path, need_ln = _temporal_path_of(self, ctx, T, Cc, joint)
+        ln1 = ops.layernorm(m1, None, None, 1e-5) if need_ln else None
+        attend = self._attend_pixels if path == "pixels" else self._attend_gathered if path == "gather" else self._attend_local
+        att, fin_att, att_joint, fin_joint = attend(ctx, m1, ln1, path, joint)
+        return self._finish(ctx, h_s, m1, ln1, path, att, fin_att, att_joint, fin_joint, alpha, order)
+
+    def _attend_local(self, ctx: Ctx, m1: torch.Tensor, ln1: Optional[torch.Tensor], path: str, joint: bool):
+        """all frames on this rank.  Every layout method returns (attention output, its pending finish, attn1n's attention
+        output where the layout computes it, its pending finish); here the joint branch runs in the tail"""
+        pk, (T, Cc) = self._pk, m1.shape
+        if path == "block":          # LayerNorm .. out-projection in one launch: issued by the tail, which knows the context rows
+            return None, None, None, None
+        if path == "front":
+            # LayerNorm + QKV + attention over the frames in one kernel where it exists (C = 320: the 72x128 level)
+            att = ctx.new(T, Cc)
+            ops.tattn_front(m1, _first_use(pk.a1, "wfront", lambda: pack_tfront(pk.a1.wqkv, self.attn1.heads)), pk.a1.bqkv, att,
+                            ctx.B, ctx.F, ctx.HW, self.attn1.heads)
+            return att, None, None, None
+        fused = path == "ln_qkv"     # (the 36x64 level: LayerNorm + Q|K|V in one launch, then the attention kernel)
+        return _attend_temporal(self, ctx, "a1", m1 if fused else ln1, (ctx.B, ctx.F, ctx.HW), ln_fused=fused), None, None, None
+
+    def _attend_pixels(self, ctx: Ctx, m1: torch.Tensor, ln1, path: str, joint: bool):
+        """frames of the clip live on several GPUs: re-shard by PIXELS around the attention (all-to-all), so that this rank
+        holds all F frames of its pixel slice - LayerNorm, Q|K|V and the attention then run once per token, fused where
+        the kernel applies - and bring the attention output back to frame slices (lkgd_amd/dist.py)"""
+        pk, Cc = self._pk, m1.shape[1]
+        m1p = ctx.shard.to_pixels(m1, ctx.HW)              # rows (entry, frame, pixel of this rank's slice)
+        Tp, Ft = m1p.shape[0], ctx.F_total
+        pxl = Tp // (Ft * ctx.B)
+        ln1p = None
+        if _front_ok(self, ctx, Cc, Ft, pxl):
             attp = ctx.new(Tp, Cc)
-            ln1p = None
-            if ctx.lora is not None:
-                # masked LoRA (round 6): a rank holds its slice of every clip of its CFG half, so the per-entry weight variants
-                # apply to its entries unchanged - one launch per entry run, rows per entry = all F frames of the pixel slice
-                va = [_attn_variant(self, "a1", ctx, i, False) for i in range(len(ctx.lora.runs))]
-                ln1p = ops.layernorm(m1p, None, None, 1e-5)
-                qkv = ctx.new(Tp, 3 * Cc)
-                _gemm_runs(ctx, ln1p, qkv, lambda i: (va[i].wqkv, va[i].bqkv, None), N=3 * Cc, K=Cc, rows=Ft * pxl)
-                ops.attn_temporal(qkv[:, :Cc], qkv[:, Cc:2 * Cc], qkv[:, 2 * Cc:], attp, ctx.B, Ft, pxl, self.attn1.heads)
-            elif ops.tattn_front_ok(Cc, self.attn1.heads, Ft, pxl):
-                if getattr(pk.a1, "wfront", None) is None:
-                    from .packing import pack_tfront
-                    with _replay.invariant():      # built once from the weights: a constant of any plan being recorded
-                        pk.a1.wfront = pack_tfront(pk.a1.wqkv, self.attn1.heads)
-                ops.tattn_front(m1p, pk.a1.wfront, pk.a1.bqkv, attp, ctx.B, Ft, pxl, self.attn1.heads)
-            else:
-                ln1p = ops.layernorm(m1p, None, None, 1e-5)
-                qkv = ctx.new(Tp, 3 * Cc)
-                ops.gemm(ln1p, pk.a1.wqkv, qkv, M=Tp, N=3 * Cc, K=Cc, bias=pk.a1.bqkv)
-                ops.attn_temporal(qkv[:, :Cc], qkv[:, Cc:2 * Cc], qkv[:, 2 * Cc:], attp, ctx.B, Ft, pxl, self.attn1.heads)
-            # the attention output goes back to frame slices: issued here, awaited right before the out-projection reads it - with the
-            # joint branch on, that branch's projection and attention run beside the transfer (RCCL: an asynchronous all-to-all)
-            att, fin_att = ctx.shard.to_frames_start(attp, ctx.HW)
-            if joint:
-                # the joint branch in the same pixel layout: all frames of the partner ENTRY's pixels are on this rank (a rank
-                # holds its slice of every clip of its CFG half), so attn1n needs no exchange beyond bringing its output back
-                if ctx.temporal_partner is None:
-                    raise LkgdHipError("joint attention enabled but no joint_attn_mask set")
-                if ln1p is None:
-                    ln1p = ops.layernorm(m1p, None, None, 1e-5)
-                qkvj, attjp = ctx.new(Tp, 3 * Cc), ctx.new(Tp, Cc)
-                if ctx.lora is None:
-                    ops.gemm(ln1p, pk.a1n.wqkv, qkvj, M=Tp, N=3 * Cc, K=Cc, bias=pk.a1n.bqkv)
-                else:
-                    vjp = [_attn_variant(self, "a1n", ctx, i, False) for i in range(len(ctx.lora.runs))]
-                    _gemm_runs(ctx, ln1p, qkvj, lambda i: (vjp[i].wqkv, vjp[i].bqkv, None), N=3 * Cc, K=Cc, rows=Ft * pxl)
-                ops.attn_temporal(qkvj[:, :Cc], qkvj[:, Cc:2 * Cc], qkvj[:, 2 * Cc:], attjp, ctx.B, Ft, pxl, self.attn1n.heads,
-                                  kv_b_map=ctx.temporal_partner)
-                att_joint, fin_joint = ctx.shard.to_frames_start(attjp, ctx.HW)    # ... and this one beside the main out-projection
+            ops.tattn_front(m1p, _first_use(pk.a1, "wfront", lambda: pack_tfront(pk.a1.wqkv, self.attn1.heads)), pk.a1.bqkv, attp,
+                            ctx.B, Ft, pxl, self.attn1.heads)
         else:
-            # LKGD_TEMPORAL_GATHER=1: local queries against the keys / values of ALL frames.  The
-            # normalised hidden states are gathered (C channels) and K|V projected here for every frame: half the
-            # bytes of gathering K|V, for a 2C x C GEMM on F*HW rows
-            ln1f = ctx.shard.gather(ln1)
-            Tf = ln1f.shape[0]
-            q, kvf = ctx.new(T, Cc), ctx.new(Tf, 2 * Cc)
-            if ctx.lora is None:
-                ops.gemm(ln1, pk.a1.wqkv[:Cc], q, M=T, N=Cc, K=Cc, bias=pk.a1.bqkv[:Cc])
-                ops.gemm(ln1f, pk.a1.wqkv[Cc:], kvf, M=Tf, N=2 * Cc, K=Cc, bias=pk.a1.bqkv[Cc:])
-            else:
-                va = [_attn_variant(self, "a1", ctx, i, False) for i in range(len(ctx.lora.runs))]
-                _gemm_runs(ctx, ln1, q, lambda i: (va[i].wqkv[:Cc], va[i].bqkv[:Cc], None), N=Cc, K=Cc)
-                _gemm_runs(ctx, ln1f, kvf, lambda i: (va[i].wqkv[Cc:], va[i].bqkv[Cc:], None), N=2 * Cc, K=Cc,
-                           rows=ctx.F_total * ctx.HW)
-            ops.attn_temporal(q, kvf[:, :Cc], kvf[:, Cc:], att, ctx.B, ctx.F_total, ctx.HW, self.attn1.heads,
-                              Fq=ctx.F)
-            if joint:         # attn1n: local query frames against the partner entry's keys / values of ALL frames
-                if ctx.temporal_partner is None:
-                    raise LkgdHipError("joint attention enabled but no joint_attn_mask set")
-                qj, kvj, att_joint = ctx.new(T, Cc), ctx.new(Tf, 2 * Cc), ctx.new(T, Cc)
-                if ctx.lora is None:
-                    ops.gemm(ln1, pk.a1n.wqkv[:Cc], qj, M=T, N=Cc, K=Cc, bias=pk.a1n.bqkv[:Cc])
-                    ops.gemm(ln1f, pk.a1n.wqkv[Cc:], kvj, M=Tf, N=2 * Cc, K=Cc, bias=pk.a1n.bqkv[Cc:])
-                else:
-                    vjg = [_attn_variant(self, "a1n", ctx, i, False) for i in range(len(ctx.lora.runs))]
-                    _gemm_runs(ctx, ln1, qj, lambda i: (vjg[i].wqkv[:Cc], vjg[i].bqkv[:Cc], None), N=Cc, K=Cc)
-                    _gemm_runs(ctx, ln1f, kvj, lambda i: (vjg[i].wqkv[Cc:], vjg[i].bqkv[Cc:], None), N=2 * Cc, K=Cc,
-                               rows=ctx.F_total * ctx.HW)
-                ops.attn_temporal(qj, kvj[:, :Cc], kvj[:, Cc:], att_joint, ctx.B, ctx.F_total, ctx.HW, self.attn1n.heads,
-                                  kv_b_map=ctx.temporal_partner, Fq=ctx.F)
-        xtab = ctx.xb_all[:, pk.xoff:pk.xoff + Cc]
+            # (masked LoRA, round 6: a rank holds its slice of every clip of its CFG half, so the per-entry weight variants
+            # apply to its entries unchanged - one launch per entry run, rows per entry = all F frames of the pixel slice)
+            ln1p = ops.layernorm(m1p, None, None, 1e-5)
+            attp = _attend_temporal(self, ctx, "a1", ln1p, (ctx.B, Ft, pxl), rows=Ft * pxl)
+        # the attention output goes back to frame slices: issued here, awaited right before the out-projection reads it - with the
+        # joint branch on, that branch's projection and attention run beside the transfer (RCCL: an asynchronous all-to-all)
+        att, fin_att = ctx.shard.to_frames_start(attp, ctx.HW)
+        if not joint:
+            return att, fin_att, None, None
+        # the joint branch in the same pixel layout: all frames of the partner ENTRY's pixels are on this rank (a rank
+        # holds its slice of every clip of its CFG half), so attn1n needs no exchange beyond bringing its output back
+        if ctx.temporal_partner is None:
+            raise LkgdHipError("joint attention enabled but no joint_attn_mask set")
+        if ln1p is None:
+            ln1p = ops.layernorm(m1p, None, None, 1e-5)
+        attjp = _attend_temporal(self, ctx, "a1n", ln1p, (ctx.B, Ft, pxl), rows=Ft * pxl, kv_b_map=ctx.temporal_partner)
+        att_joint, fin_joint = ctx.shard.to_frames_start(attjp, ctx.HW)    # ... and this one beside the main out-projection
+        return att, fin_att, att_joint, fin_joint
+
+    def _attend_gathered(self, ctx: Ctx, m1: torch.Tensor, ln1: torch.Tensor, path: str, joint: bool):
+        """LKGD_TEMPORAL_GATHER=1: local queries against the keys / values of ALL frames.  The normalised hidden states are
+        gathered (C channels) and K|V projected here for every frame: half the bytes of gathering K|V, for a 2C x C GEMM on
+        F*HW rows"""
+        ln1f = ctx.shard.gather(ln1)
+        att, att_joint = self._attend_all_frames(ctx, "a1", ln1, ln1f), None
+        if joint:         # attn1n: local query frames against the partner entry's keys / values of ALL frames
+            if ctx.temporal_partner is None:
+                raise LkgdHipError("joint attention enabled but no joint_attn_mask set")
+            att_joint = self._attend_all_frames(ctx, "a1n", ln1, ln1f, ctx.temporal_partner)
+        return att, None, att_joint, None
+
+    def _attend_all_frames(self, ctx: Ctx, which: str, ln1: torch.Tensor, ln1f: torch.Tensor, kv_b_map=None) -> torch.Tensor:
+        (T, Cc), Tf = ln1.shape, ln1f.shape[0]
+        q, kvf, att = ctx.new(T, Cc), ctx.new(Tf, 2 * Cc), ctx.new(T, Cc)
+        _project(self, ctx, which, "q", ln1, q)
+        _project(self, ctx, which, "kv", ln1f, kvf, rows=ctx.F_total * ctx.HW)
+        ops.attn_temporal(q, kvf[:, :Cc], kvf[:, Cc:], att, ctx.B, ctx.F_total, ctx.HW,
+                          (self.attn1 if which == "a1" else self.attn1n).heads, kv_b_map=kv_b_map, Fq=ctx.F)
+        return att
+
+    def _finish(self, ctx: Ctx, h_s, m1, ln1, path: str, att, fin_att, att_joint, fin_joint, alpha: float, order) -> torch.Tensor:
+        """the tail every layout shares: context-row map from ``order``, out-projection (or the one-launch block), joint branch,
+        literal cross-attention, feed-forward with the AlphaBlender"""
+        pk, (T, Cc) = self._pk, m1.shape
+        b_off = 0                             # first context entry of the folded cross-attention table
         if isinstance(order, tuple):
             xmap = order                      # explicit context-row map (tests drive single blocks this way)
         elif order == "interleaved_0_27":
             # global row i = (b0 + b)*HW + s of the [B_total*HW, F, C] regroup uses context i % B_total
             xmap = (ctx.F * ctx.HW, ctx.HW, ctx.HW, ctx.B_total, (ctx.b0 * ctx.HW) % ctx.B_total)
         elif order == "batch_major":
-            xmap, xtab = ops.rowmap_div(ctx.F * ctx.HW), ctx.xb_all[ctx.b0:, pk.xoff:pk.xoff + Cc]
+            xmap, b_off = ops.rowmap_div(ctx.F * ctx.HW), ctx.b0
         else:
             raise ValueError(order)
         m2 = ctx.new(T, Cc)
         if fin_att is not None:
             fin_att()
-        if one_launch:
-            if getattr(pk.a1, "wblock", None) is None:
-                from .packing import pack_tblock
-                with _replay.invariant():      # built once from the weights: a constant of any plan being recorded
-                    pk.a1.wblock = pack_tblock(pk.a1.wqkv, pk.a1.bqkv, pk.a1.wo, self.attn1.heads)
-            ops.tattn_block(m1, pk.a1.wblock, pk.a1.bo, m2, ctx.B, ctx.F, ctx.HW, rowbias=xtab, rowmap=xmap)
-        elif va is None:
-            ops.gemm(att, pk.a1.wo, m2, M=T, N=Cc, K=Cc, bias=pk.a1.bo, res1=m1, rowbias=xtab, rowmap=xmap)
+        if path == "block":
+            # ... and the out-projection, its residual and the folded cross-attention table in the same launch (attn_tblock.hip);
+            # with the joint branch on, the main branch still runs that way and only the joint branch's input is normalised apart
+            wblock = _first_use(pk.a1, "wblock", lambda: pack_tblock(pk.a1.wqkv, pk.a1.bqkv, pk.a1.wo, self.attn1.heads))
+            ops.tattn_block(m1, wblock, pk.a1.bo, m2, ctx.B, ctx.F, ctx.HW,
+                            rowbias=ctx.xb_all[b_off:, pk.xoff:pk.xoff + Cc], rowmap=xmap)
         else:
-            b_off = ctx.b0 if order == "batch_major" else 0
-            _gemm_runs(ctx, att, m2, lambda i: (va[i].wo, va[i].bo, ctx.xb_runs[i][b_off:, pk.xoff:pk.xoff + Cc]),
-                       N=Cc, K=Cc, rowmap=xmap, res1=m1)
+            _project(self, ctx, "a1", "out", att, m2, cross=(b_off, xmap), res1=m1)
         if fin_joint is not None:
             fin_joint()
         if self.enable_joint_attention and hasattr(self, "attn1n"):
             m2 = self._joint(ctx, ln1, m2, att_joint)
         if ctx.cross_Lk > 1:                  # literal attn2 over the time context (same row -> context map as the folded bias)
-            m2 = _cross_literal(self, ctx, m2, xmap, ctx.b0 if order == "batch_major" else 0)
+            m2 = _cross_literal(self, ctx, m2, xmap, b_off)
         # ff(norm3(m2)) + m2, then AlphaBlender with the spatial branch - one epilogue
         return _ff_ln(ctx, pk.ff, m2, s_acc=1.0 - alpha, res2=h_s, r2=alpha)
 
     def _joint(self, ctx: Ctx, ln1: Optional[torch.Tensor], m2: torch.Tensor, att: Optional[torch.Tensor] = None) -> torch.Tensor:
         """temporal joint branch (patch/patch.py:616-658): attn1n over the partner batch entry's frames; ``att``: the attention
         output where the caller computed it already (frame-sharded ranks: over all frames, run())"""
-        pk, T, Cc = self._pk, m2.shape[0], m2.shape[1]
         if ctx.temporal_partner is None:
             raise LkgdHipError("joint attention enabled but no joint_attn_mask set")
-        vj = None
-        if ctx.lora is not None:
-            vj = [_attn_variant(self, "a1n", ctx, i, False) for i in range(len(ctx.lora.runs))]
         if att is None:
-            qkv = ctx.new(T, 3 * Cc)
-            if vj is None:
-                ops.gemm(ln1, pk.a1n.wqkv, qkv, M=T, N=3 * Cc, K=Cc, bias=pk.a1n.bqkv)
-            else:
-                _gemm_runs(ctx, ln1, qkv, lambda i: (vj[i].wqkv, vj[i].bqkv, None), N=3 * Cc, K=Cc)
-            att = ctx.new(T, Cc)
-            ops.attn_temporal(qkv[:, :Cc], qkv[:, Cc:2 * Cc], qkv[:, 2 * Cc:], att, ctx.B, ctx.F, ctx.HW,
-                              self.attn1n.heads, kv_b_map=ctx.temporal_partner)
-        out = ctx.new(T, Cc)
-        if vj is None:   # post folded in; joint_scale is not applied here
-            ops.gemm(att, pk.jw, out, M=T, N=Cc, K=Cc, bias=pk.jb, res1=m2)
-        else:
-            _gemm_runs(ctx, att, out, lambda i: (vj[i].jw, vj[i].jb, None), N=Cc, K=Cc, res1=m2)
+            att = _attend_temporal(self, ctx, "a1n", ln1, (ctx.B, ctx.F, ctx.HW), kv_b_map=ctx.temporal_partner)
+        out = ctx.new(*m2.shape)
+        _project(self, ctx, "a1n", "joint", att, out, res1=m2)      # post folded in; joint_scale is not applied here
         return out
 
 

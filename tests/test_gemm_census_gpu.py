@@ -360,3 +360,46 @@ def test_census_notices_a_wrong_oracle(monkeypatch):
     bad = check_signature(conv)[0]
     print("taps shifted by one pixel:", bad[0][:300])
     assert bad and "over the bound" in bad[0]
+
+
+def test_gemm_family_flop_replayed_equals_eager(c1_hip_model):
+    """bench.py's roofline line reads the algorithmic FLOP of every GEMM-family launch from `ops.GEMM_EVENTS` in an eager forward
+    and from `Plan.run(events)` in a replayed one: the full forward gives the same list both ways, element by element, and the
+    fused kernels of the family are in it with the FLOP of their matrix products"""
+    from lkgd_amd import ops, replay
+    unet = c1_hip_model
+    tok, emb, ids, t = gc._unet_inputs(unet.device, 2, 14)
+    run = lambda: unet.forward_tokens(tok, 2, 14, gc.H, gc.W, t, emb, ids)      # noqa: E731
+    run()                                       # (first-use packs and cached tables)
+    torch.cuda.synchronize()
+    eager = []
+    ops.GEMM_EVENTS = eager
+    try:
+        run()
+    finally:
+        ops.GEMM_EVENTS = None
+    torch.cuda.synchronize()
+    with replay.strict(False):
+        with replay.record(replay.Arena()) as plan:
+            plan.result = run()
+    try:
+        replayed = []
+        plan.run(replayed)
+        torch.cuda.synchronize()
+        family = [(name, flop) for fn, args, name, flop in plan.calls if flop is not None]
+    finally:
+        plan.release()
+        torch.cuda.empty_cache()
+    assert len(eager) == len(replayed) == len(family) > 200
+    assert [f for _, _, f in eager] == [f for _, _, f in replayed] == [f for _, f in family]
+    assert all(e.elapsed_time(e2) >= 0 for e, e2, _ in replayed[:4])
+    T320, T640 = 2 * 14 * gc.H * gc.W, 2 * 14 * (gc.H // 2) * (gc.W // 2)
+    want = {"lkgd_ff_fused_c320": 2.0 * T320 * (2560 * 320 + 320 * 1280),
+            "lkgd_tattn_block_c320": 2.0 * T320 * (960 * 320 + 320 * 320) + 4.0 * T320 * 16 * 320,
+            "lkgd_ln_qkv_c320": 2.0 * T320 * 3 * 320 * 320,
+            "lkgd_ln_qkv_c640": 2.0 * T640 * 3 * 640 * 640}
+    for name, flop in want.items():
+        got = {f for n, f in family if n == name}
+        assert got == {flop}, (name, got, flop)
+    # conv_in (A_CONV3X3_C8: K = 128 zero padded in memory) counts its 72 real taps
+    assert 2.0 * T320 * 320 * 72 in {f for n, f in family if n == "lkgd_gemm_f16"}

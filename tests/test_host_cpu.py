@@ -503,3 +503,77 @@ def test_gemm_census_covers_every_program_and_tile_form():
     assert {4, 7} <= sliced, sliced
     assert {e["plan"]["lds_out"] for e in rows if e["plan"]["program"] == 4} == {0, 1}
     assert {256, 192, 32} <= {e["plan"]["colstats_block"] for e in rows}
+
+
+#: the launch sequence of a temporal transformer block's self-attention, written out from the path table of DESIGN.md ("Which launches a transformer block issues"), not computed:
+#: (C, heads, F local, F total, HW, token rows, frame shards, masked LoRA, joint, TEMPORAL_GATHER) -> (path, normalised tokens needed)
+TEMPORAL_PATHS = [
+    # the headline geometries: 72x128 at C = 320 (2 x 14 frames), 36x64 at C = 640, 18x32 and 9x16 at C = 1280
+    ((320, 5, 14, 14, 9216, 258048, 1, False, False, False), ("block", False)),
+    ((640, 10, 14, 14, 2304, 64512, 1, False, False, False), ("ln_qkv", False)),
+    ((1280, 20, 14, 14, 576, 16128, 1, False, False, False), ("chain", True)),
+    ((1280, 20, 14, 14, 144, 4032, 1, False, False, False), ("chain", True)),
+    # the joint branch reads the normalised tokens: the one-launch block keeps its main branch, everything else runs the chain
+    ((320, 5, 14, 14, 9216, 258048, 1, False, True, False), ("block", True)),
+    ((640, 10, 14, 14, 2304, 64512, 1, False, True, False), ("chain", True)),
+    # masked LoRA: per-entry weights, always the chain
+    ((320, 5, 14, 14, 9216, 258048, 1, True, False, False), ("chain", True)),
+    ((320, 5, 14, 14, 9216, 258048, 1, True, True, False), ("chain", True)),
+    ((640, 10, 14, 14, 2304, 64512, 1, True, False, False), ("chain", True)),
+    # F = 16 / 17: the fused temporal kernels hold at most 16 frames
+    ((320, 5, 16, 16, 9216, 294912, 1, False, False, False), ("block", False)),
+    ((320, 5, 17, 17, 9216, 313344, 1, False, False, False), ("ln_qkv", False)),
+    ((320, 5, 17, 17, 64, 2176, 1, False, False, False), ("chain", True)),
+    # HW % 16
+    ((320, 5, 14, 14, 9224, 258272, 1, False, False, False), ("ln_qkv", False)),
+    ((320, 5, 14, 14, 16, 448, 1, False, False, False), ("block", False)),
+    ((320, 5, 14, 14, 24, 672, 1, False, False, False), ("chain", True)),
+    # heads != 5 at C = 320: no fused temporal kernel; LayerNorm + Q|K|V in one launch from 60 000 rows
+    ((320, 4, 14, 14, 9216, 258048, 1, False, False, False), ("ln_qkv", False)),
+    ((320, 4, 14, 14, 9216, 60000, 1, False, False, False), ("ln_qkv", False)),
+    ((320, 4, 14, 14, 9216, 59999, 1, False, False, False), ("chain", True)),
+    # ... and from 30 000 rows at C = 640
+    ((640, 10, 14, 14, 2304, 30000, 1, False, False, False), ("ln_qkv", False)),
+    ((640, 10, 14, 14, 2304, 29999, 1, False, False, False), ("chain", True)),
+    # frames on several GPUs.  A rank of 8 (2 CFG halves x 4 frame shards; 4 of 14 frames): re-sharded by pixels
+    ((320, 5, 4, 14, 9216, 36864, 4, False, False, False), ("pixels", False)),
+    ((640, 10, 3, 14, 2304, 6912, 4, False, False, False), ("pixels", False)),
+    ((320, 5, 4, 14, 9216, 36864, 4, True, True, False), ("pixels", False)),
+    ((320, 5, 4, 14, 9216, 36864, 4, False, False, True), ("gather", True)),
+    ((320, 5, 4, 14, 9216, 36864, 4, True, True, True), ("gather", True)),
+    # HW just below / at frame_shards: a level with fewer pixels than shards keeps the gathered form
+    ((64, 1, 2, 4, 3, 6, 4, False, False, False), ("gather", True)),
+    ((64, 1, 2, 4, 4, 8, 4, False, False, False), ("pixels", False)),
+    ((64, 1, 2, 4, 1, 4, 2, False, True, False), ("gather", True)),
+    ((64, 1, 2, 4, 2, 8, 2, False, True, False), ("pixels", False)),
+]
+
+#: with LKGD_NO_TBLOCK=1 (the A/B switch tests use as a reference) the `front` path takes the one-launch block's geometries
+TEMPORAL_PATHS_NO_TBLOCK = [
+    ((320, 5, 14, 14, 9216, 258048, 1, False, False, False), ("front", False)),
+    ((320, 5, 16, 16, 16, 512, 1, False, False, False), ("front", False)),
+    ((320, 5, 14, 14, 9216, 258048, 1, False, True, False), ("chain", True)),
+    ((320, 5, 14, 14, 9216, 258048, 1, True, False, False), ("chain", True)),
+    ((320, 5, 17, 17, 9216, 313344, 1, False, False, False), ("ln_qkv", False)),
+    ((320, 5, 4, 14, 9216, 36864, 4, False, False, False), ("pixels", False)),
+]
+
+
+def test_temporal_path_table(monkeypatch):
+    """lkgd_amd.unet.temporal_path - which launch sequence TemporalBasicTransformerBlock.run takes - returns every row of the
+    table: every path, both sides of every threshold, the headline geometries"""
+    from lkgd_amd import ops
+    from lkgd_amd.unet import temporal_path
+    for sw in ("TBLOCK", "TFRONT", "LN_QKV"):          # the table is the shipped configuration, whatever the environment says
+        monkeypatch.setattr(ops, sw, True)
+
+    def got(row):
+        C_, heads, F, Ft, HW, T, shards, lora, joint, gather = row
+        return temporal_path(C_, heads, F, Ft, HW, T, shards, lora=lora, joint=joint, gather=gather)
+
+    for row, want in TEMPORAL_PATHS:
+        assert got(row) == want, row
+    assert {w[0] for _, w in TEMPORAL_PATHS} == {"block", "ln_qkv", "chain", "pixels", "gather"}
+    monkeypatch.setattr(ops, "TBLOCK", False)
+    for row, want in TEMPORAL_PATHS_NO_TBLOCK:
+        assert got(row) == want, row

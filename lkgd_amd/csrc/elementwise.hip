@@ -1,5 +1,6 @@
-// Loop glue and small elementwise kernels (include/lkgd_hip.h sections 6, 7).  All HBM/latency-bound.
+// Loop glue and small elementwise kernels (include/lkgd_hip.h sections 6, 7; include/lkgd_hip_window.h).  All HBM/latency-bound.
 #include "common.h"
+#include "../../include/lkgd_hip_window.h"
 
 // ---- CFG duplicate + scale_model_input + channel concat, NCHW planes -> channels-last tokens [.., 8]
 // reference: pipeline_stable_video_diffusion_trans.py:549-553, scheduler scale_model_input :284-285
@@ -26,6 +27,27 @@ __global__ __launch_bounds__(256) void prepare_input_kernel(const LT* __restrict
   }
 }
 
+// ---- per-frame CFG  uncond + g[f] * (cond - uncond)  of one token row, on fp16 values as the reference's fp16 tensors form it
+// (pipeline :578-592): the difference, the product and the sum are each rounded to fp16.  Contraction is off here: fused into
+// one fp16 multiply-add the product would skip its rounding, and one fp16 ulp of the noise is sigma / 1024 in an epsilon-
+// prediction x0 - more than an fp16 ulp of the latents at the high-noise steps.
+__device__ __forceinline__ half4_t cfg_combine(const half_t* __restrict__ noise, long long i, long long total, int cfg,
+                                               const float* __restrict__ guidance, int f) {
+#pragma clang fp contract(off)
+  half4_t u = *(const half4_t*)(noise + i * 4);
+  if (cfg != 2) return u;
+  half4_t c = *(const half4_t*)(noise + (i + total) * 4);
+  const half_t g = (half_t)guidance[f];
+  half4_t n;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    half_t d = (half_t)((float)c[e] - (float)u[e]);
+    half_t gd = (half_t)((float)g * (float)d);
+    n[e] = (half_t)((float)u[e] + (float)gd);
+  }
+  return n;
+}
+
 // ---- per-frame CFG + Euler step (pipeline :578-592; scheduler.step :481-520).  fp16 rounding points follow the
 // reference's tensor dtypes: CFG arithmetic on fp16 tensors, model_output * c_out stays fp16 (0-dim fp32 scalar does
 // not promote), everything after the upcast of `sample` is fp32.
@@ -42,18 +64,7 @@ __global__ __launch_bounds__(256) void cfg_euler_kernel(const half_t* __restrict
     const long long bf = i / HW;
     const int f = (int)(bf % F);
     const int b = (int)(bf / F);
-    half4_t u = *(const half4_t*)(noise + i * 4);
-    half4_t n = u;
-    if (cfg == 2) {
-      half4_t c = *(const half4_t*)(noise + (i + total) * 4);
-      const half_t g = (half_t)guidance[f];
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        half_t d = (half_t)((float)c[e] - (float)u[e]);
-        half_t gd = (half_t)((float)g * (float)d);
-        n[e] = (half_t)((float)u[e] + (float)gd);
-      }
-    }
+    const half4_t n = cfg_combine(noise, i, total, cfg, guidance, f);
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
       const long long li = (((long long)b * F + f) * 4 + c) * HW + p;
@@ -68,26 +79,10 @@ __global__ __launch_bounds__(256) void cfg_euler_kernel(const half_t* __restrict
 }
 
 // ---- direct-fusion Euler step of the trans-ControlNet pipeline (pipeline_stable_video_diffusion_trans_controlnet.py
-// :637-667): per-frame CFG and x0 of every clip as cfg_euler_kernel forms them, then the forward clip b and the
+// :637-667): per-frame CFG (cfg_combine) and x0 of every clip as cfg_euler_kernel forms them, then the forward clip b and the
 // frame-reversed backward clip b+P are blended through their x0 with weight[f] = linspace(1, 0, F)[f] (fp32), and both
 // clips take the Euler step from the blend (clip b+P at frame F-1-f from xb[b, f]).  One thread owns element (b, f, ., p)
 // and its mirror (b+P, F-1-f, ., p): it reads both latents before it writes either, so the in-place update is race-free.
-__device__ __forceinline__ half4_t cfg_combine(const half_t* __restrict__ noise, long long i, long long total, int cfg,
-                                               const float* __restrict__ guidance, int f) {
-  half4_t u = *(const half4_t*)(noise + i * 4);
-  if (cfg != 2) return u;
-  half4_t c = *(const half4_t*)(noise + (i + total) * 4);
-  const half_t g = (half_t)guidance[f];
-  half4_t n;
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    half_t d = (half_t)((float)c[e] - (float)u[e]);
-    half_t gd = (half_t)((float)g * (float)d);
-    n[e] = (half_t)((float)u[e] + (float)gd);
-  }
-  return n;
-}
-
 template <typename LT>
 __global__ __launch_bounds__(256) void cfg_fusion_euler_kernel(const half_t* __restrict__ noise,
                                                                LT* __restrict__ latents,
@@ -288,6 +283,103 @@ extern "C" int lkgd_cfg_fusion_euler_step(const void* noise_tokens, void* latent
     hipLaunchKernelGGL(cfg_fusion_euler_kernel<half_t>, dim3(grid_for(pairs, 256)), dim3(256), 0, (hipStream_t)stream,
                        (const half_t*)noise_tokens, (half_t*)latents, guidance, weight, B, F, H * W, cfg, sigma,
                        sigma_next, prediction_type);
+  return hipGetLastError() == hipSuccess ? LKGD_OK : LKGD_E_LAUNCH;
+}
+
+// ---- windowed loop glue of the long-video smoothing pipeline (include/lkgd_hip_window.h; pipeline_stable_video_diffusion_
+// smooth.py:545-594).  A window is frames f0 .. f0+L-1 of latents [T,4,H,W]; the UNet batch is entry e = 2*k + d, k = CFG half,
+// d = 0 the window, d = 1 the window reversed in time.  Same rounding points, 16-byte token rows, plane-coalesced reads and grid
+// rule as prepare_input_kernel / cfg_euler_kernel.
+template <typename LT>
+__global__ __launch_bounds__(256) void window_prepare_kernel(const LT* __restrict__ latents,
+                                                             const half_t* __restrict__ image_latents, int f0, int L,
+                                                             int HW, int cfg, float inv_scale,
+                                                             half_t* __restrict__ out) {
+  const long long total = 2ll * cfg * L * HW;
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
+    const int p = (int)(i % HW);
+    const long long ej = i / HW;          // e*L + j
+    const int j = (int)(ej % L);
+    const int e = (int)(ej / L);
+    const int d = e & 1;
+    const bool cond = (e >> 1) == cfg - 1;                // torch.cat([latents_chunk] * 2): the uncond entries come first
+    const long long lf = f0 + (d ? L - 1 - j : j);        // latents_chunk.flip(dims=[1]) for the reversed clip (:551)
+    const long long cf = d ? f0 + L - 1 : f0;             // first_frame_ids (:554): the clip's own first frame conditions it
+    half8_t o;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      float x = (float)latents[(lf * 4 + c) * HW + p];
+      o[c] = (half_t)(x * inv_scale);
+      o[4 + c] = cond ? image_latents[(cf * 4 + c) * HW + p] : (half_t)0.0f;
+    }
+    *(half8_t*)(out + i * 8) = o;
+  }
+}
+
+template <typename LT>
+__global__ __launch_bounds__(256) void window_cfg_euler_kernel(const half_t* __restrict__ noise, LT* __restrict__ latents,
+                                                               const float* __restrict__ guidance, int f0, int L, int HW,
+                                                               int cfg, float sigma, float sigma_next, int vpred) {
+  const long long total = (long long)L * HW;             // token rows of one batch entry; entry 2 = the forward clip's cond
+  const float c_out = -sigma / sqrtf(sigma * sigma + 1.0f);
+  const float c_skip = sigma * sigma + 1.0f;
+  const float dt = sigma_next - sigma;
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
+    const int p = (int)(i % HW);
+    const int j = (int)(i / HW);
+    const half4_t n = cfg_combine(noise, i, 2 * total, cfg, guidance, j);
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      const long long li = (((long long)f0 + j) * 4 + c) * HW + p;
+      const float x = (float)latents[li];
+      float x0;
+      if (vpred) x0 = (float)(half_t)((float)n[c] * c_out) + x / c_skip;
+      else x0 = x - (float)(half_t)((float)n[c] * sigma);
+      const float deriv = (x - x0) / sigma;
+      latents[li] = (LT)(x + deriv * dt);
+    }
+  }
+}
+
+static int window_shape_ok(int32_t T, int32_t f0, int32_t L, int32_t H, int32_t W, int32_t cfg, float sigma) {
+  return T > 0 && H > 0 && W > 0 && L > 0 && f0 >= 0 && (long long)f0 + L <= T && (cfg == 1 || cfg == 2) && sigma > 0.f;
+}
+
+extern "C" int lkgd_window_prepare_input(const void* latents, int32_t latents_is_f32, const void* image_latents, int32_t T,
+                                         int32_t f0, int32_t L, int32_t H, int32_t W, int32_t cfg, float sigma,
+                                         void* tokens_out, lkgd_stream_t stream) {
+  if (!latents || !image_latents || !tokens_out) return LKGD_E_NULL;
+  if (!window_shape_ok(T, f0, L, H, W, cfg, sigma)) return LKGD_E_SHAPE;
+  if (!aligned16(tokens_out)) return LKGD_E_ALIGN;
+  const float inv = 1.0f / sqrtf(sigma * sigma + 1.0f);
+  const long long total = 2ll * cfg * L * H * W;
+  if (latents_is_f32)
+    hipLaunchKernelGGL(window_prepare_kernel<float>, dim3(grid_for(total, 256)), dim3(256), 0, (hipStream_t)stream,
+                       (const float*)latents, (const half_t*)image_latents, f0, L, H * W, cfg, inv, (half_t*)tokens_out);
+  else
+    hipLaunchKernelGGL(window_prepare_kernel<half_t>, dim3(grid_for(total, 256)), dim3(256), 0, (hipStream_t)stream,
+                       (const half_t*)latents, (const half_t*)image_latents, f0, L, H * W, cfg, inv, (half_t*)tokens_out);
+  return hipGetLastError() == hipSuccess ? LKGD_OK : LKGD_E_LAUNCH;
+}
+
+extern "C" int lkgd_window_cfg_euler_step(const void* noise_tokens, void* latents, int32_t latents_is_f32,
+                                          const float* guidance, int32_t T, int32_t f0, int32_t L, int32_t H, int32_t W,
+                                          int32_t cfg, float sigma, float sigma_next, int32_t prediction_type,
+                                          lkgd_stream_t stream) {
+  if (!noise_tokens || !latents) return LKGD_E_NULL;
+  if (cfg == 2 && !guidance) return LKGD_E_NULL;
+  if (!window_shape_ok(T, f0, L, H, W, cfg, sigma)) return LKGD_E_SHAPE;
+  if (prediction_type != 0 && prediction_type != 1) return LKGD_E_MODE;
+  if ((uintptr_t)noise_tokens & 7) return LKGD_E_ALIGN;
+  const long long total = (long long)L * H * W;
+  if (latents_is_f32)
+    hipLaunchKernelGGL(window_cfg_euler_kernel<float>, dim3(grid_for(total, 256)), dim3(256), 0, (hipStream_t)stream,
+                       (const half_t*)noise_tokens, (float*)latents, guidance, f0, L, H * W, cfg, sigma, sigma_next,
+                       prediction_type);
+  else
+    hipLaunchKernelGGL(window_cfg_euler_kernel<half_t>, dim3(grid_for(total, 256)), dim3(256), 0, (hipStream_t)stream,
+                       (const half_t*)noise_tokens, (half_t*)latents, guidance, f0, L, H * W, cfg, sigma, sigma_next,
+                       prediction_type);
   return hipGetLastError() == hipSuccess ? LKGD_OK : LKGD_E_LAUNCH;
 }
 

@@ -589,6 +589,60 @@ def cfg_fusion_euler_step(noise_tokens: torch.Tensor, latents: torch.Tensor, gui
     return latents
 
 
+def _window(latents: torch.Tensor, f0: int, L: int):
+    if not latents.is_cuda or latents.dtype not in (torch.float16, torch.float32):
+        raise _lib.LkgdHipError("latents must be a GPU fp16/fp32 tensor")
+    if latents.dim() == 5 and latents.shape[0] == 1:
+        latents = latents[0]
+    if latents.dim() != 4 or latents.shape[1] != 4 or not latents.is_contiguous():
+        raise _lib.LkgdHipError(f"latents must be contiguous [T,4,H,W] (or [1,T,4,H,W]), got {tuple(latents.shape)}")
+    T, _, H, W = latents.shape
+    if not (0 <= f0 and 0 < L and f0 + L <= T):
+        raise _lib.LkgdHipError(f"window of {L} frames at {f0} does not lie inside the {T} frames")
+    return T, H, W
+
+
+def window_prepare_input(latents: torch.Tensor, image_latents: torch.Tensor, f0: int, L: int, cfg: int, sigma: float,
+                         out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """frames f0 .. f0+L-1 of ``latents`` [T,4,H,W] (or [1,T,4,H,W]) + per-frame conditional ``image_latents`` [T,4,H,W] ->
+    channels-last tokens [2*cfg*L*H*W, 8] of the UNet batch [window, reversed window] x [uncond, cond]
+    (lkgd_window_prepare_input); ``out`` may be the leading rows of a larger token buffer"""
+    T, H, W = _window(latents, f0, L)
+    _req(image_latents, torch.float16, "image_latents")
+    if tuple(image_latents.shape) != (T, 4, H, W) or not image_latents.is_contiguous():
+        raise _lib.LkgdHipError(f"image_latents must be contiguous [T,4,H,W] = {(T, 4, H, W)}, got {tuple(image_latents.shape)}")
+    rows = 2 * cfg * L * H * W
+    if out is None:
+        out = torch.empty(rows, 8, dtype=torch.float16, device=latents.device)
+    else:
+        _req(out, torch.float16, "out")
+        if out.dim() != 2 or out.shape[1] != 8 or not out.is_contiguous() or out.shape[0] < rows:
+            raise _lib.LkgdHipError(f"out must be a contiguous [>= {rows}, 8] token buffer, got {tuple(out.shape)}")
+        out = out[:rows]
+    check(_L().lkgd_window_prepare_input(latents.data_ptr(), int(latents.dtype == torch.float32), image_latents.data_ptr(),
+                                         T, f0, L, H, W, cfg, sigma, out.data_ptr(), _stream()), "lkgd_window_prepare_input")
+    return out
+
+
+def window_cfg_euler_step(noise_tokens: torch.Tensor, latents: torch.Tensor, guidance: Optional[torch.Tensor], f0: int, L: int,
+                          cfg: int, sigma: float, sigma_next: float, v_prediction: bool = True) -> torch.Tensor:
+    """in-place Euler update of frames f0 .. f0+L-1 of ``latents`` [T,4,H,W] (or [1,T,4,H,W]) from the forward clip's entries of
+    the window's noise tokens [2*cfg*L*H*W, 4]; ``guidance`` fp32 [L] on the device, or None when cfg == 1
+    (lkgd_window_cfg_euler_step)"""
+    T, H, W = _window(latents, f0, L)
+    _req(noise_tokens, torch.float16, "noise_tokens")
+    if tuple(noise_tokens.shape) != (2 * cfg * L * H * W, 4) or not noise_tokens.is_contiguous():
+        raise _lib.LkgdHipError(f"noise_tokens must be contiguous [{2 * cfg * L * H * W}, 4], got {tuple(noise_tokens.shape)}")
+    if guidance is not None:
+        _req(guidance, torch.float32, "guidance")
+        if guidance.numel() != L or not guidance.is_contiguous():
+            raise _lib.LkgdHipError(f"guidance must hold one contiguous fp32 value per window frame ({L})")
+    check(_L().lkgd_window_cfg_euler_step(noise_tokens.data_ptr(), latents.data_ptr(), int(latents.dtype == torch.float32),
+                                          _ptr(guidance), T, f0, L, H, W, cfg, sigma, sigma_next, 1 if v_prediction else 0,
+                                          _stream()), "lkgd_window_cfg_euler_step")
+    return latents
+
+
 def shard_rows(src: torch.Tensor, dst: torch.Tensor, fl: int, HW: int, C_: int, px, pack: bool) -> torch.Tensor:
     """pack: src [fl, HW, C] -> dst rows grouped by destination pixel shard (px = pixels per shard); not pack: the inverse
     (lkgd_shard_rows).  Both contiguous fp16."""

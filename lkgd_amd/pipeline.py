@@ -17,6 +17,7 @@ from __future__ import annotations
 from dataclasses import dataclass
 from typing import Callable, Dict, List, Optional, Union
 
+import numpy as np
 import torch
 
 from . import ops
@@ -53,6 +54,22 @@ def _append_dims(x, target_dims):
     if dims_to_append < 0:
         raise ValueError(f"input has {x.ndim} dims but target_dims is {target_dims}, which is less")
     return x[(...,) + (None,) * dims_to_append]
+
+
+def smooth_chunks(total_frames: int, num_frames: int, rng=np.random):
+    """the frame windows of one Euler step of the smoothing pipeline, as (f0, L) pairs: ``get_chunks`` of
+    pipeline_stable_video_diffusion_smooth.py:526-533 restated.  The first window has a random length of 1..num_frames, the
+    others ``num_frames`` frames and the last one the remainder.  One ``rng.randint(0, num_frames)`` is drawn per call, as the
+    reference draws it, so seeding ``np.random`` reproduces its windows."""
+    if total_frames <= 0 or num_frames <= 0:
+        raise ValueError(f"smooth_chunks needs positive frame counts, got {total_frames} and {num_frames}")
+    first = min(int(rng.randint(0, num_frames)) + 1, total_frames)
+    chunks, f0 = [(0, first)], first
+    while f0 < total_frames:
+        n = min(num_frames, total_frames - f0)
+        chunks.append((f0, n))
+        f0 += n
+    return chunks
 
 
 class StableVideoDiffusionPipeline:
@@ -224,6 +241,37 @@ class StableVideoDiffusionPipeline:
         if do_classifier_free_guidance:
             lat = torch.cat([torch.zeros_like(lat), lat])
         return lat.repeat(num_videos_per_prompt, 1, 1, 1)
+
+    def _encode_vae_boundary(self, img, device, num_videos_per_prompt, do_classifier_free_guidance, dtype, chunk=None):
+        """the VAE encode of ``__call__`` with what the reference wraps around it; ``chunk``: encode in slices of that many images
+        (pipeline_stable_video_diffusion_smooth.py:458-464)"""
+        # reference :470-484: an fp16 VAE with `force_upcast` encodes in fp32 and is cast back right after (so the
+        # decode at the end runs in fp16 again, :643-645).  The HIP VAE computes fp16 activations with fp32 accumulation
+        # whatever the module dtype says (lkgd_amd/vae.py), so casting it there and back would only re-pack its weights
+        # twice per call: the module is left alone, and what the upcast protects against - an fp16 overflow in the
+        # encoder - is checked instead (INTEGRATION.md, deviations)
+        vae_dtype = getattr(self.vae, "dtype", None)
+        from .vae import AutoencoderKLTemporalDecoder
+        hip_vae = isinstance(self.vae, AutoencoderKLTemporalDecoder)
+        needs_upcasting = (not hip_vae and vae_dtype == torch.float16 and
+                           bool(getattr(self.vae.config, "force_upcast", False)))
+        if needs_upcasting:
+            self.vae.to(dtype=torch.float32)
+        elif vae_dtype is not None and vae_dtype != img.dtype:
+            img = img.to(vae_dtype)
+        if chunk is None:
+            image_latents = self._encode_vae_image(img, device, num_videos_per_prompt, do_classifier_free_guidance)
+        else:
+            image_latents = torch.cat([self._encode_vae_image(img[i:i + chunk], device, num_videos_per_prompt,
+                                                              do_classifier_free_guidance)
+                                       for i in range(0, img.shape[0], chunk)], dim=0)
+        image_latents = image_latents.to(dtype)                                                   # reference :480
+        if needs_upcasting:
+            self.vae.to(dtype=torch.float16)
+        if hip_vae and not bool(torch.isfinite(image_latents).all()):
+            raise LkgdHipError("VAE encode produced non-finite latents (fp16 range exceeded in the encoder): the reference "
+                               "encodes in fp32 under force_upcast; scale the input or encode outside and pass image_latents")
+        return image_latents
 
     def decode_latents(self, latents, num_frames, decode_chunk_size=14):
         if self.vae is None:
@@ -467,27 +515,7 @@ class StableVideoDiffusionPipeline:
             img = self.image_processor.preprocess(image, height=height, width=width).to(device)      # reference :466
             noise = _randn_tensor(img.shape, generator, device, img.dtype)      # drawn for the execution device (:467)
             img = img + noise_aug_strength * noise
-            # reference :470-484: an fp16 VAE with `force_upcast` encodes in fp32 and is cast back right after (so the
-            # decode at the end runs in fp16 again, :643-645).  The HIP VAE computes fp16 activations with fp32 accumulation
-            # whatever the module dtype says (lkgd_amd/vae.py), so casting it there and back would only re-pack its weights
-            # twice per call: the module is left alone, and what the upcast protects against - an fp16 overflow in the
-            # encoder - is checked instead (deviations)
-            vae_dtype = getattr(self.vae, "dtype", None)
-            from .vae import AutoencoderKLTemporalDecoder
-            hip_vae = isinstance(self.vae, AutoencoderKLTemporalDecoder)
-            needs_upcasting = (not hip_vae and vae_dtype == torch.float16 and
-                               bool(getattr(self.vae.config, "force_upcast", False)))
-            if needs_upcasting:
-                self.vae.to(dtype=torch.float32)
-            elif vae_dtype is not None and vae_dtype != img.dtype:
-                img = img.to(vae_dtype)
-            image_latents = self._encode_vae_image(img, device, num_videos_per_prompt, cfg)
-            image_latents = image_latents.to(image_embeddings.dtype)                                  # reference :480
-            if needs_upcasting:
-                self.vae.to(dtype=torch.float16)
-            if hip_vae and not bool(torch.isfinite(image_latents).all()):
-                raise LkgdHipError("VAE encode produced non-finite latents (fp16 range exceeded in the encoder): the reference "
-                                   "encodes in fp32 under force_upcast; scale the input or encode outside and pass image_latents")
+            image_latents = self._encode_vae_boundary(img, device, num_videos_per_prompt, cfg, image_embeddings.dtype)
         image_latents = image_latents.to(device=device, dtype=torch.float16)
         if image_latents.dim() == 4:      # [cfg*B,4,h,w] -> repeat over frames (:488)
             image_latents = image_latents.unsqueeze(1).repeat(1, num_frames, 1, 1, 1)
@@ -578,6 +606,174 @@ class StableVideoDiffusionPipelineTransControlNet(StableVideoDiffusionPipeline):
             cc = [cc]
         conds = [self.image_processor.preprocess(c, height=height, width=width).unsqueeze(0) for c in cc]
         return torch.cat(conds * 2 if cfg else conds).to(device)
+
+
+class StableVideoDiffusionPipelineSmooth(StableVideoDiffusionPipeline):
+    """pipeline/pipeline_stable_video_diffusion_smooth.py (driven by run_models/run_inference_svd_smooth.py): an input video of
+    any length T is noised to ``start_step`` and denoised in frame windows of at most ``num_frames`` frames.  ``__call__`` has
+    the reference's parameter list (:320-341); ``image`` is the list or tensor of the T frames.  Every Euler step cuts the
+    frames into windows (``smooth_chunks``) and runs the UNet per window on [window, reversed window] x [uncond, cond]; the
+    window's first and last frame condition the forward and the reversed clip (:549-577); only the forward clip's CFG result
+    steps the window's frames (:579-594).  The run script patches the UNet with ``apply_patch(flip=True)`` and the joint mask
+    [0, 1, 0, 1] (utils/util.py:408-438): the joint hooks are left as the model has them.  The loop is ``denoise_smooth``: two
+    glue launches per window (lkgd_window_prepare_input, lkgd_window_cfg_euler_step) around the UNet forward.
+    Refused, with the reason: ``max_guidance_scale <= 1`` (the reference's own no-CFG branch feeds the whole latents tensor to
+    the UNet, :565, and cannot run with more than one window), ``num_videos_per_prompt != 1``, ``num_frames > 16`` (the fused
+    temporal kernels' limit), a ``controlnet_condition`` and sharded runs."""
+
+    SCALING_FACTOR = 0.18215       # AutoencoderKLTemporalDecoder's config value, used when the pipeline carries no VAE
+
+    def _refuse(self, num_frames, max_guidance_scale, num_videos_per_prompt=1, controlnet_condition=None, shard=None):
+        if not max_guidance_scale > 1:
+            raise ValueError("the smoothing pipeline needs classifier-free guidance (max_guidance_scale > 1): the reference's "
+                             "no-CFG branch feeds the whole latents tensor to the UNet and cannot run with more than one window")
+        if num_videos_per_prompt != 1:
+            raise ValueError(f"the smoothing pipeline denoises one video: num_videos_per_prompt must be 1, got {num_videos_per_prompt}")
+        if not 1 <= num_frames <= 16:
+            raise ValueError(f"window length num_frames must be 1..16 (the fused temporal kernels' limit), got {num_frames}")
+        if controlnet_condition is not None:
+            raise ValueError("the smoothing pipeline runs no ControlNet: controlnet_condition is not taken")
+        if shard is not None:
+            raise ValueError("the smoothing loop is single-GPU: sharded runs are not supported")
+
+    def _noisy_start(self, image_latents: torch.Tensor, noise: torch.Tensor, start_step: int) -> torch.Tensor:
+        """:466, :516-518: scheduler.add_noise(image_latents * scaling_factor, noise, timesteps[[start_step]]) as [1,T,4,h,w]
+        fp16 (the reference's latents dtype); needs ``scheduler.set_timesteps``"""
+        sf = self.vae.config.scaling_factor if self.vae is not None else self.SCALING_FACTOR
+        orig = (image_latents.float() * sf).unsqueeze(0)
+        noise = noise.to(device=orig.device, dtype=torch.float16).reshape(orig.shape)
+        start = self.scheduler.add_noise(orig, noise, [self.scheduler.timesteps_host[start_step]])
+        return start.to(torch.float16).contiguous()
+
+    @torch.no_grad()
+    def denoise_smooth(self, latents: torch.Tensor, image_latents: torch.Tensor, image_embeddings: torch.Tensor,
+                       added_time_ids: torch.Tensor, num_frames: int, num_inference_steps: int = 25,
+                       min_guidance_scale: float = 1.0, max_guidance_scale: float = 3.0, start_step: int = 0,
+                       callback_on_step_end: Optional[Callable] = None,
+                       callback_on_step_end_tensor_inputs: List[str] = ["latents"], controlnet_condition=None,
+                       shard=None) -> torch.Tensor:
+        """Reference loop :535-605.  ``latents`` [1,T,4,h,w] noised to ``start_step`` (fp16 or fp32, updated in place and
+        returned); ``image_latents`` [T,4,h,w]: the VAE latent of every input frame (the unconditional zeros are never
+        materialised); ``image_embeddings`` [T,1,1024]: the CLIP embedding of every input frame; ``added_time_ids`` [1,3] (or the
+        reference's 4 equal rows).  Per window: one glue kernel (gather + flip + CFG duplicate + scale_model_input + channel
+        concat -> tokens of the batch of four), the UNet forward at (4, L, h, w) with the embedding rows [0, 0, emb[f0],
+        emb[f0+L-1]], one glue kernel (per-frame CFG of the forward clip + Euler update of the window's frames).  The forward is
+        recorded once per call at L == num_frames and replayed for the later windows of that length (token buffer, timestep and
+        embedding rows are updated in place); windows of other lengths walk the modules, so the call holds one plan's arena."""
+        unet, sch = self.unet, self.scheduler
+        dev = unet.device
+        self._refuse(num_frames, max_guidance_scale, controlnet_condition=controlnet_condition, shard=shard)
+        if latents.dim() != 5 or latents.shape[0] != 1 or latents.shape[2] != 4:
+            raise ValueError(f"latents must be [1,T,4,h,w] (the smoothing pipeline denoises one video), got {tuple(latents.shape)}")
+        _, T, _, H, W = latents.shape
+        if tuple(image_latents.shape) != (T, 4, H, W) or image_embeddings.shape[0] != T or image_embeddings.dim() != 3:
+            raise ValueError("image_latents [T,4,h,w] and image_embeddings [T,1,C] must carry one conditional entry per input frame")
+        cfg, nf = 2, int(num_frames)
+        latents = latents.to(dev).contiguous()
+        image_latents = image_latents.to(device=dev, dtype=torch.float16).contiguous()
+        emb = image_embeddings.to(device=dev, dtype=torch.float16).contiguous()
+        ids = added_time_ids.to(device=dev, dtype=torch.float32).reshape(-1, added_time_ids.shape[-1])
+        if 2 * cfg % ids.shape[0]:
+            raise ValueError(f"added_time_ids must be built for one clip (1, 2 or 4 equal rows), got {ids.shape[0]} rows")
+        ids = ids.repeat(2 * cfg // ids.shape[0], 1).contiguous()           # :539 and the CFG duplicate of _get_add_time_ids
+        sch.set_timesteps(num_inference_steps, device=None)
+        self._num_timesteps = len(sch.timesteps_host)
+        self._guidance_scale = max_guidance_scale
+        # :581: torch.linspace(min, max, len(chunk)) per window - one device table for the call, row L-1 holds the L values
+        gtab = torch.zeros(nf, nf, dtype=torch.float32)
+        for n in range(1, nf + 1):
+            gtab[n - 1, :n] = torch.linspace(min_guidance_scale, max_guidance_scale, n, dtype=torch.float32)
+        gtab = gtab.to(dev)
+        vpred = sch.config.prediction_type == "v_prediction"
+        HW = H * W
+        # static inputs of the window forward: the tokens of the largest window, the timestep and the embedding rows of the batch
+        # [uncond fwd, uncond rev, cond fwd, cond rev] (:554-561); rows 0 / 1 stay zero
+        tok_buf = torch.empty(2 * cfg * nf * HW, 8, dtype=torch.float16, device=dev)
+        t_dev = torch.zeros(2 * cfg, dtype=torch.float32, device=dev)
+        enc = torch.zeros(2 * cfg, emb.shape[1], emb.shape[2], dtype=torch.float16, device=dev)
+        recorded = None
+        try:
+            for i, t in enumerate(sch.timesteps_host):
+                if i < start_step:
+                    continue
+                sigma, sigma_next = sch.sigmas_host[i], sch.sigmas_host[i + 1]
+                _trace.push(f"euler_step_{i}")
+                for f0, n in smooth_chunks(T, nf):
+                    tok = ops.window_prepare_input(latents, image_latents, f0, n, cfg, sigma, out=tok_buf)
+                    enc[2].copy_(emb[f0])
+                    enc[3].copy_(emb[f0 + n - 1])
+                    if self.use_replay and n == nf:
+                        t_dev.fill_(float(t))
+                        if recorded is not None:
+                            noise_tok = recorded.run(ops.GEMM_EVENTS)
+                        else:
+                            with _replay.record(self._arenas.take(dev, ("smooth", 2 * cfg, nf, H, W, id(unet._pk)))) as recorded:
+                                recorded.result = unet.forward_tokens(tok, 2 * cfg, nf, H, W, t_dev, enc, ids)[0]
+                            noise_tok = recorded.result
+                    else:
+                        noise_tok, _ = unet.forward_tokens(tok, 2 * cfg, n, H, W, t, enc, ids)
+                    ops.window_cfg_euler_step(noise_tok, latents, gtab[n - 1, :n], f0, n, cfg, sigma, sigma_next,
+                                              v_prediction=vpred)
+                _trace.pop()
+                if callback_on_step_end is not None:
+                    kw = {k: {"latents": latents}[k] for k in callback_on_step_end_tensor_inputs}
+                    out = callback_on_step_end(self, i, t, kw)
+                    latents = out.pop("latents", latents) if isinstance(out, dict) else latents
+        finally:
+            if recorded is not None:
+                recorded.release()
+        sch._step_index = num_inference_steps
+        return latents
+
+    @torch.no_grad()
+    def __call__(self, image, height: int = 576, width: int = 1024, num_frames: Optional[int] = None,
+                 num_inference_steps: int = 25, min_guidance_scale: float = 1.0, max_guidance_scale: float = 3.0,
+                 fps: int = 7, motion_bucket_id: int = 127, noise_aug_strength: float = 0.02,
+                 decode_chunk_size: Optional[int] = None, num_videos_per_prompt: Optional[int] = 1,
+                 generator=None, latents: Optional[torch.Tensor] = None, output_type: Optional[str] = "pil",
+                 callback_on_step_end: Optional[Callable[[int, int, Dict], None]] = None,
+                 callback_on_step_end_tensor_inputs: List[str] = ["latents"], return_dict: bool = True, start_step=0,
+                 # extensions: per-frame boundary outputs computed outside ([T,1,1024] / [T,4,h,w]) and the start noise [1,T,4,h,w]
+                 image_embeddings: Optional[torch.Tensor] = None, image_latents: Optional[torch.Tensor] = None,
+                 noise: Optional[torch.Tensor] = None, controlnet_condition=None):
+        height = height or self.unet.config.sample_size * self.vae_scale_factor
+        width = width or self.unet.config.sample_size * self.vae_scale_factor
+        num_frames = num_frames if num_frames is not None else self.unet.config.num_frames
+        decode_chunk_size = decode_chunk_size if decode_chunk_size is not None else num_frames
+        self._refuse(num_frames, max_guidance_scale, num_videos_per_prompt, controlnet_condition)
+        if image is not None:
+            self.check_inputs(image, height, width)
+        device = self._execution_device
+        self._guidance_scale = max_guidance_scale
+        if image_embeddings is None:
+            # one CLIP embedding per input frame (:442); the unconditional zeros are rows 0 / 1 of every window's batch
+            image_embeddings = self._encode_image(image, device, 1, False)
+        if image_latents is None:
+            img = self.image_processor.preprocess(image, height=height, width=width).to(device)      # :450-452
+            img = img + noise_aug_strength * _randn_tensor(img.shape, generator, device, img.dtype)
+            # :458-464: the T frames go through the VAE in slices of decode_chunk_size
+            image_latents = self._encode_vae_boundary(img, device, 1, False, torch.float32, chunk=decode_chunk_size)
+        image_latents = image_latents.to(device)
+        total_frames = image_latents.shape[0]
+        added_time_ids = self._get_add_time_ids(fps - 1, motion_bucket_id, noise_aug_strength, torch.float32, 1, 1,
+                                                False).to(device)
+        self.scheduler.set_timesteps(num_inference_steps, device=None)
+        if noise is None:
+            # the reference draws this noise from torch's global RNG (torch.randn_like, :518) and ignores `generator` and
+            # `latents` there; here it comes from `generator` (INTEGRATION.md, deviations)
+            noise = _randn_tensor((1, total_frames) + tuple(image_latents.shape[1:]), generator, device, torch.float16)
+        lat = self._noisy_start(image_latents, noise, start_step)
+        lat = self.denoise_smooth(lat, image_latents.to(torch.float16), image_embeddings, added_time_ids, num_frames,
+                                  num_inference_steps, min_guidance_scale, max_guidance_scale, start_step,
+                                  callback_on_step_end, callback_on_step_end_tensor_inputs)
+        if output_type != "latent":
+            frames = self.decode_latents(lat, total_frames, decode_chunk_size)                       # :611-612
+            frames = tensor2vid(frames, self.image_processor, output_type=output_type)
+        else:
+            frames = lat
+        if not return_dict:
+            return frames
+        return StableVideoDiffusionPipelineOutput(frames=frames)
 
 
 class StableVideoDiffusionPipelineControlNetFlow(StableVideoDiffusionPipelineControlNet):

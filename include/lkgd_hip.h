@@ -219,7 +219,7 @@ int lkgd_groupnorm_silu(const void* x0, int32_t c0, int32_t ld0, const void* x1,
 
 /* ---------------------------------------------------------------------------------------------------------------
  * 3. LayerNorm over the channel dimension of a token matrix, optional row-indexed bias added BEFORE normalising
- *    (frame positional embedding: x + emb[idx(row)]), idx as in (1); C % 8 == 0, C <= 2048.  gamma == beta == NULL: no affine (the UNet folds
+ *    (frame positional embedding: x + emb[idx(row)]), idx as in (1); C % 8 == 0, C <= 3072.  gamma == beta == NULL: no affine (the UNet folds
  *    gamma/beta of every LayerNorm into the Linear that consumes it: W' = W*diag(gamma), b' = b + W*beta).
  *    Replaces: F.layer_norm - BasicTransformerBlock.norm1/3, TemporalBasicTransformerBlock.norm_in/1/3
  *    (patch/patch.py:416,556,600,610,670) and `hidden_states_mix + emb` [EXT transformer_temporal.py].
@@ -455,7 +455,7 @@ int lkgd_vit_patchify(const float* in, int64_t nimg, int32_t C, int32_t H, int32
 
 /* ---------------------------------------------------------------------------------------------------------------
  * 14. DiT glue (the CogVideoX blocks; CogVideo-main/finetune/models/cogvideox_i2v/
- *     cogvideox_transformer_3d.py:126-158): everything else of a block is lkgd_gemm_f16 / lkgd_layernorm (rows up to 2048
+ *     cogvideox_transformer_3d.py:126-158): everything else of a block is lkgd_gemm_f16 / lkgd_layernorm (rows up to 3072
  *     channels) / lkgd_attn_spatial.
  *     `lkgd_gelu_tanh`: F.gelu(approximate="tanh") of the feed-forward [EXT diffusers GELU], fp16, n % 8 == 0, in place allowed.
  *     `lkgd_gated_add`: out = res + gate[g(row)] * x, gate fp32 [2 * batch, C]: the adaLN-zero gates of the text stream (rows

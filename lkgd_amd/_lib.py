@@ -124,6 +124,12 @@ WINDOW_SYMBOLS = {
     "lkgd_window_cfg_euler_step": (_i32, [_vp, _vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _f32, _i32, _vp]),
 }
 
+#: every symbol include/lkgd_hip_dit.h declares (attention glue of the rotary CogVideoX DiT), bound on the same library object;
+#: tests/test_cogvideox_rope_cpu.py pins header, table and library to one another, tests/test_cogvideox_rope_gpu.py the footprint cases
+DIT_SYMBOLS = {
+    "lkgd_qk_norm_rope": (_i32, [_vp, _i32, _vp, _i32, _i64, _i32, _vp, _vp, _vp, _vp, _f32, _vp, _vp, _i32, _i32, _i32, _vp]),
+}
+
 #: include/lkgd_hip_debug.h: A/B and test knobs, per host thread; bound on the same library object, not part of the product interface
 DEBUG_SYMBOLS = {
     "lkgd_debug_set_wide_tile_n": (None, [_i32]),
@@ -158,7 +164,7 @@ def lib() -> C.CDLL:
             l = C.CDLL(LIB_PATH)
         except OSError as e:
             raise LkgdHipError(f"cannot load {LIB_PATH}: {e}") from e
-        for table in (SYMBOLS, WINDOW_SYMBOLS, DEBUG_SYMBOLS):
+        for table in (SYMBOLS, WINDOW_SYMBOLS, DIT_SYMBOLS, DEBUG_SYMBOLS):
             for name, (res, args) in table.items():
                 fn = getattr(l, name)       # AttributeError here = header / library mismatch
                 fn.restype, fn.argtypes = res, args

@@ -22,6 +22,10 @@ MI355X design - the UNet's kernels, one joint token buffer:
 * feed-forward: GEMM + ``lkgd_gelu_tanh`` + GEMM;
 * the latent-knowledge fuse acts on the TEXT embeddings and is step-invariant: evaluated once per clip in fp32 (as the SVD
   fuse, lkgd_amd/lk_fuse.py); the 3-D sin-cos position table is added in the patch-embedding GEMM's epilogue (row-indexed bias);
+* rotary models (CogVideoX-5B-I2V: ``use_rotary_positional_embeddings``, 48 heads, 3072 channels): no sin-cos table; the
+  learned joint position table, when the checkpoint has one, rides the same row-indexed bias of BOTH embedding GEMMs (text
+  rows included); the per-head q / k norms and the rotation of the video rows are one launch per layer
+  (``lkgd_qk_norm_rope``, include/lkgd_hip_dit.h) over tables built once per clip (``rotary_tables``);
 * patch unfold / un-patchify at the API edge, CFG combine and the DDIM update on the 1-M-element latents are tensor plumbing
   (PyTorch-ROCm elementwise ops, < 0.1 % of a step).
 """
@@ -46,7 +50,8 @@ from .unet import QuaternionLinearAutograd, TimestepEmbedding
 
 @dataclass
 class DiTConfig:
-    """constructor keywords of CogVideoXTransformer3DModel (cogvideox_transformer_3d.py:224-255) used by the 2B models"""
+    """constructor keywords of CogVideoXTransformer3DModel (cogvideox_transformer_3d.py:224-255) used by the 2B and the 5B
+    1.0 models (5B-I2V: 48 heads, 42 layers, in_channels 32, rotary embeddings + a learned position table)"""
     num_attention_heads: int = 30
     attention_head_dim: int = 64
     in_channels: int = 16
@@ -64,6 +69,8 @@ class DiTConfig:
     temporal_interpolation_scale: float = 1.0
     norm_eps: float = 1e-5
     attention_bias: bool = True
+    use_rotary_positional_embeddings: bool = False
+    use_learned_positional_embeddings: bool = False
 
 
 def _f32(p):
@@ -87,6 +94,47 @@ def sincos_pos_embed_3d(embed_dim, width, height, frames, spatial_scale, tempora
     temporal = _sincos_1d(dt, np.arange(frames, dtype=np.float32) / temporal_scale)
     pe = np.concatenate([np.repeat(temporal[:, None], height * width, axis=1), np.repeat(spatial[None], frames, axis=0)], axis=-1)
     return torch.from_numpy(pe).float().flatten(0, 1)
+
+
+def _rope_1d(dim: int, pos: torch.Tensor, theta: float = 10000.0):
+    """[EXT diffusers embeddings.py get_1d_rotary_pos_embed, use_real] -> cos, sin [len(pos), dim], every frequency twice"""
+    freqs = 1.0 / (theta ** (torch.arange(0, dim, 2, dtype=torch.float32)[: dim // 2] / dim))
+    ang = torch.outer(pos.to(torch.float32), freqs)
+    return ang.cos().repeat_interleave(2, dim=1), ang.sin().repeat_interleave(2, dim=1)
+
+
+def rope_crop_region(grid_h: int, grid_w: int, base_w: int, base_h: int):
+    """[EXT diffusers get_resize_crop_region_for_grid((grid_h, grid_w), base_w, base_h)] -> (top, left), (bottom, right): the grid
+    resized into the base grid keeping its aspect ratio, centred"""
+    if grid_h / grid_w > base_h / base_w:
+        rh, rw = base_h, int(round(base_h / grid_h * grid_w))
+    else:
+        rw, rh = base_w, int(round(base_w / grid_w * grid_h))
+    top, left = int(round((base_h - rh) / 2.0)), int(round((base_w - rw) / 2.0))
+    return (top, left), (top + rh, left + rw)
+
+
+def rotary_tables(config, frames: int, h: int, w: int):
+    """the pipeline's ``_prepare_rotary_positional_embeddings`` for ``patch_size_t is None``
+    (pipeline_cogvideox_image2video.py:544-571) -> (cos, sin) fp32 [frames * h * w, attention_head_dim]; frames / h / w are the
+    TOKEN grid (latent frames, latent size // patch_size).  PARITY UNPINNED: restates diffusers' [EXT]
+    ``get_resize_crop_region_for_grid`` and ``get_3d_rotary_pos_embed`` (linspace grid over the crop region of the configured
+    sample grid, theta 10 000): dim/4 temporal channels, then 3 dim/8 for the height and 3 dim/8 for the width (16 + 24 + 24 of
+    64), each frequency repeated for the pair (2i, 2i+1) it rotates.  Tested by its properties only."""
+    if getattr(config, "patch_size_t", None) is not None:
+        raise LkgdHipError("rotary_tables: patch_size_t (the CogVideoX 1.5 models) is not implemented")
+    d = config.attention_head_dim
+    p = config.patch_size
+    (top, left), (bottom, right) = rope_crop_region(h, w, config.sample_width // p, config.sample_height // p)
+    gh = torch.linspace(top, bottom * (h - 1) / h, h, dtype=torch.float32)
+    gw = torch.linspace(left, right * (w - 1) / w, w, dtype=torch.float32)
+    gt = torch.arange(frames, dtype=torch.float32)
+    dt, ds = d // 4, d // 8 * 3
+    out = []
+    for ct, ch, cw in zip(_rope_1d(dt, gt), _rope_1d(ds, gh), _rope_1d(ds, gw)):
+        out.append(torch.cat([ct[:, None, None, :].expand(frames, h, w, dt), ch[None, :, None, :].expand(frames, h, w, ds),
+                              cw[None, None, :, :].expand(frames, h, w, ds)], dim=-1).reshape(frames * h * w, d).contiguous())
+    return out[0], out[1]
 
 
 # ------------------------------------------------------------------------------------------------ parameter holders
@@ -155,6 +203,16 @@ class CogVideoXPatchEmbed(nn.Module):
         super().__init__()
         self.proj = nn.Conv2d(cfg.in_channels, dim, kernel_size=(cfg.patch_size, cfg.patch_size), stride=cfg.patch_size)
         self.text_proj = nn.Linear(cfg.text_embed_dim, dim)
+        if cfg.use_learned_positional_embeddings:
+            # [EXT diffusers CogVideoXPatchEmbed]: a persistent buffer over the JOINT sequence (text rows included), present in
+            # the checkpoint; initialised as diffusers does, with the sin-cos table under zero text rows
+            f = (cfg.sample_frames - 1) // cfg.temporal_compression_ratio + 1
+            h, w = cfg.sample_height // cfg.patch_size, cfg.sample_width // cfg.patch_size
+            joint = torch.zeros(1, cfg.max_text_seq_length + f * h * w, dim)
+            if joint.device.type != "meta":
+                joint[0, cfg.max_text_seq_length:] = sincos_pos_embed_3d(dim, w, h, f, cfg.spatial_interpolation_scale,
+                                                                         cfg.temporal_interpolation_scale)
+            self.register_buffer("pos_embedding", joint, persistent=True)
 
 
 @dataclass
@@ -166,12 +224,16 @@ class CogVideoXTransformer3DModel(nn.Module):
     def __init__(self, config: Optional[DiTConfig] = None, **kw):
         super().__init__()
         cfg = config if config is not None else DiTConfig(**kw)
-        self.config = SimpleNamespace(**cfg.__dict__, patch_size_t=None, use_rotary_positional_embeddings=False,
-                                      ofs_embed_dim=None)
+        self.config = SimpleNamespace(**cfg.__dict__, patch_size_t=None, ofs_embed_dim=None)
+        if not cfg.use_rotary_positional_embeddings and cfg.use_learned_positional_embeddings:
+            raise ValueError(                                                                   # cogvideox_transformer_3d.py:258-263
+                "There are no CogVideoX checkpoints available with disable rotary embeddings and learned positional "
+                "embeddings. If you're using a custom model and/or believe this should be supported, please open an "
+                "issue at https://github.com/huggingface/diffusers/issues.")
         d = cfg.num_attention_heads * cfg.attention_head_dim
         if d % 64 or (cfg.in_channels * cfg.patch_size ** 2) % 64 or cfg.time_embed_dim % 64 or cfg.text_embed_dim % 64 \
-                or d > 2048 or (cfg.patch_size ** 2 * cfg.out_channels) % 8:
-            raise LkgdHipError("DiT on the HIP path: dims multiples of 64 (K granularity), inner dim <= 2048")
+                or d > 3072 or (cfg.patch_size ** 2 * cfg.out_channels) % 8:
+            raise LkgdHipError("DiT on the HIP path: dims multiples of 64 (K granularity), inner dim <= 3072")
         self.inner_dim = d
         self.patch_embed = CogVideoXPatchEmbed(cfg, d)
         self.time_embedding = TimestepEmbedding(d, cfg.time_embed_dim)
@@ -227,10 +289,10 @@ class CogVideoXTransformer3DModel(nn.Module):
                         variant: Optional[str] = None, **_ignored):
         from .loading import build_from_pretrained, load_config, load_state_dict
         raw = load_config(pretrained_model_name_or_path, subfolder)
-        for key in ("use_rotary_positional_embeddings", "patch_size_t", "ofs_embed_dim"):
-            if raw.get(key):        # the 5B / 1.5 variants (rotary embeddings, temporal patches, ofs embedding) are not built
+        for key in ("patch_size_t", "ofs_embed_dim"):
+            if raw.get(key):        # the 1.5 variants (temporal patches, ofs embedding) are not built
                 raise LkgdHipError(f"CogVideoXTransformer3DModel.from_pretrained: config has {key}={raw[key]!r}; only the "
-                                   "2B architecture (learned positional embedding, 2-D patches) is implemented")
+                                   "1.0 architectures (2B, 5B: 2-D patches, no ofs embedding) are implemented")
         # stock checkpoints have no quaternion_lora_* modules: those may be missing; anything else missing or unexpected
         # (a truncated shard, renamed parameters) would leave meta-initialised garbage behind a non-strict load
         sd_keys = set(load_state_dict(pretrained_model_name_or_path, subfolder, variant).keys())
@@ -273,8 +335,21 @@ class CogVideoXTransformer3DModel(nn.Module):
         pk.w_pe, pk.b_pe = pack_linear(pe.proj.weight.detach()), _f32(pe.proj.bias)          # [D, C*p*p], k = (c, ky, kx)
         pk.w_tx, pk.b_tx = pack_linear(pe.text_proj.weight), _f32(pe.text_proj.bias)
         pk.w_po, pk.b_po = pack_linear(self.proj_out.weight), _f32(self.proj_out.bias)
+        pk.learned = pe.pos_embedding[0].detach().to(torch.float16).contiguous() if self.config.use_learned_positional_embeddings else None
         self._pk = pk
         self._pos = {}
+
+    def _learned_table(self, Tt: int, f: int, h: int, w: int) -> torch.Tensor:
+        """the learned joint table [max_text_seq_length + T h w, D] fp16; it has rows for the configured grid only, so any
+        other clip raises (diffusers raises for another resolution and silently falls back to the sin-cos table for another
+        frame count; here both are refused)"""
+        c = self.config
+        want = (c.max_text_seq_length, (c.sample_frames - 1) // c.temporal_compression_ratio + 1, c.sample_height // c.patch_size,
+                c.sample_width // c.patch_size)
+        if (Tt, f, h, w) != want:
+            raise ValueError(f"learned positional embeddings cover (text, frames, h, w) tokens = {want} only, got {(Tt, f, h, w)}: "
+                             "it is not possible to run a clip of another size with this checkpoint")
+        return self._pk.learned
 
     def _pos_table(self, f: int, h: int, w: int) -> torch.Tensor:
         key = (f, h, w)
@@ -323,9 +398,12 @@ class CogVideoXTransformer3DModel(nn.Module):
 
     # ---- the per-step forward ------------------------------------------------------------------------------------
     @torch.no_grad()
-    def forward_tokens(self, hidden_states: torch.Tensor, fused_text: torch.Tensor, timestep, shard=None) -> torch.Tensor:
+    def forward_tokens(self, hidden_states: torch.Tensor, fused_text: torch.Tensor, timestep, shard=None,
+                       image_rotary_emb=None) -> torch.Tensor:
         """hidden_states [B, F, C, h, w]; fused_text [B, L, 4096] fp16 (``fused_text`` of the prompt embeddings) ->
-        [B, F, out_channels, h, w] fp16.  ``shard`` (lkgd_amd.dist_run.ShardInfo): this rank holds ONE batch entry (its CFG
+        [B, F, out_channels, h, w] fp16.  ``image_rotary_emb`` = (cos, sin) fp32 [F h w tokens, 64] (``rotary_tables``): every
+        layer's per-head q / k norms and the rotation of their video rows are then ONE launch of ``lkgd_qk_norm_rope``; None =
+        the two LayerNorm launches of the 2B path.  ``shard`` (lkgd_amd.dist_run.ShardInfo): this rank holds ONE batch entry (its CFG
         half) and the latent frames [f0, f0 + F) of the clip; everything is row-local except the attention, whose local
         queries (the replicated text rows + the rank's video rows) attend to the keys / values of ALL frames, all-gathered
         over the frame group every layer."""
@@ -339,6 +417,21 @@ class CogVideoXTransformer3DModel(nn.Module):
         Tt, Tv = fused_text.shape[1], Fr * h * w
         L = Tt + Tv
         heads = cfg.num_attention_heads
+        rotary = cfg.use_rotary_positional_embeddings
+        if rotary != (image_rotary_emb is not None):
+            raise LkgdHipError("image_rotary_emb is given exactly when the model has use_rotary_positional_embeddings "
+                               "(rotary_tables builds it)")
+        rope = None
+        F_all = Fr if shard is None else shard.F_total          # latent frames of the whole clip
+        v0 = 0 if shard is None else shard.f0 * h * w            # the rank's first video row in the clip
+        if rotary:
+            # to the device once per call; every layer reads the same two tables.  A frame-sharded rank is handed the tables of
+            # the WHOLE clip and rotates its local q and k (before the K gather) with the rows of its frames
+            rope = tuple(t.to(device=dev, dtype=torch.float32) for t in image_rotary_emb)
+            if any(tuple(t.shape) != (F_all * h * w, 64) for t in rope):
+                raise LkgdHipError(f"image_rotary_emb: (cos, sin) must each be [{F_all * h * w}, 64], got "
+                                   f"{[tuple(t.shape) for t in rope]}")
+            rope = tuple(t[v0:v0 + Tv].contiguous() for t in rope)
         # time embedding -> all modulation vectors of the step (one GEMM)
         t = timestep if torch.is_tensor(timestep) else torch.tensor([timestep])
         t = t.to(device=dev, dtype=torch.float32).reshape(-1).expand(B).contiguous()
@@ -360,16 +453,22 @@ class CogVideoXTransformer3DModel(nn.Module):
         txt = fused_text.to(device=dev, dtype=torch.float16).reshape(B * Tt, -1).contiguous()
         xh = hidden_states.to(device=dev, dtype=torch.float16)
         patches = xh.reshape(B, Fr, C_, h, p, w, p).permute(0, 1, 3, 5, 2, 4, 6).reshape(B, Tv, C_ * p * p).contiguous()
-        if shard is None:
-            pos = self._pos_table(Fr, h, w)
+        pos_txt = None
+        if not rotary:
+            pos = self._pos_table(F_all, h, w)[v0:v0 + Tv]
+        elif cfg.use_learned_positional_embeddings:     # the learned joint table covers the text rows as well
+            tab = self._learned_table(Tt, F_all, h, w)
+            pos_txt, pos = tab[:Tt], tab[Tt + v0:Tt + v0 + Tv]
         else:
-            pos = self._pos_table(shard.F_total, h, w)[shard.f0 * h * w:(shard.f0 + Fr) * h * w]
-            Tv_all = shard.F_total * h * w
+            pos = None
+        if shard is not None:
+            Tv_all = F_all * h * w
             KV = [torch.empty(Tt + Tv_all, D, dtype=torch.float16, device=dev) for _ in range(2)]
+        rb_t = dict(rowbias=pos_txt, rowmap=(1, 1, 1, 1 << 30)) if pos_txt is not None else {}
+        rb_v = dict(rowbias=pos, rowmap=(1, 1, 1, 1 << 30)) if pos is not None else {}
         for b in range(B):
-            ops.gemm(txt[b * Tt:(b + 1) * Tt], pk.w_tx, X[b * L:b * L + Tt], M=Tt, N=D, K=txt.shape[1], bias=pk.b_tx)
-            ops.gemm(patches[b], pk.w_pe, X[b * L + Tt:(b + 1) * L], M=Tv, N=D, K=C_ * p * p, bias=pk.b_pe, rowbias=pos,
-                     rowmap=(1, 1, 1, 1 << 30))
+            ops.gemm(txt[b * Tt:(b + 1) * Tt], pk.w_tx, X[b * L:b * L + Tt], M=Tt, N=D, K=txt.shape[1], bias=pk.b_tx, **rb_t)
+            ops.gemm(patches[b], pk.w_pe, X[b * L + Tt:(b + 1) * L], M=Tv, N=D, K=C_ * p * p, bias=pk.b_pe, **rb_v)
         T = B * L
         eps = cfg.norm_eps
 
@@ -386,8 +485,11 @@ class CogVideoXTransformer3DModel(nn.Module):
             q, k, v = (torch.empty(T, D, dtype=torch.float16, device=dev) for _ in range(3))
             for dst, (wgt, bias) in ((q, bp.q), (k, bp.k), (v, bp.v)):
                 ops.gemm(n, wgt, dst, M=T, N=D, K=D, bias=bias)
-            ops.layernorm(q.view(T * heads, 64), bp.nq[0], bp.nq[1], 1e-6, out=q.view(T * heads, 64))     # per-head qk norm
-            ops.layernorm(k.view(T * heads, 64), bp.nk[0], bp.nk[1], 1e-6, out=k.view(T * heads, 64))
+            if rope is not None:    # per-head qk norm + rotation of the video rows, q and k in one launch
+                ops.qk_norm_rope(q, k, heads, bp.nq, bp.nk, 1e-6, rope, L, Tt)
+            else:
+                ops.layernorm(q.view(T * heads, 64), bp.nq[0], bp.nq[1], 1e-6, out=q.view(T * heads, 64))     # per-head qk norm
+                ops.layernorm(k.view(T * heads, 64), bp.nk[0], bp.nk[1], 1e-6, out=k.view(T * heads, 64))
             a = torch.empty(T, D, dtype=torch.float16, device=dev)
             if shard is None:
                 ops.attn_spatial(q, k, v, a, B, L, heads)
@@ -422,10 +524,10 @@ class CogVideoXTransformer3DModel(nn.Module):
     def forward(self, hidden_states, encoder_hidden_states, timestep, domain_features, flow_features, timestep_cond=None,
                 ofs=None, image_rotary_emb=None, attention_kwargs=None, return_dict: bool = True):
         """cogvideox_transformer_3d.py:473-486 - ``domain_features`` / ``flow_features`` are positional"""
-        if image_rotary_emb is not None or ofs is not None or timestep_cond is not None:
-            raise LkgdHipError("rotary embeddings / ofs / timestep_cond belong to the 5B and 1.5 models, not to CogVideoX-2B")
+        if ofs is not None or timestep_cond is not None:
+            raise LkgdHipError("ofs belongs to the CogVideoX 1.5 models and timestep_cond to none of the released ones: not built")
         text = self.fused_text(encoder_hidden_states, domain_features, flow_features)
-        out = self.forward_tokens(hidden_states, text, timestep)
+        out = self.forward_tokens(hidden_states, text, timestep, image_rotary_emb=image_rotary_emb)
         if not return_dict:
             return (out,)
         return Transformer2DModelOutput(sample=out)
@@ -481,8 +583,9 @@ def dynamic_guidance(guidance_scale: float, num_inference_steps: int, t: int) ->
 @torch.no_grad()
 def denoise(transformer: CogVideoXTransformer3DModel, scheduler: CogVideoXDDIMScheduler, latents, image_latents, prompt_embeds,
             domain_features, flow_features, num_inference_steps: int = 50, guidance_scale: float = 6.0,
-            use_dynamic_cfg: bool = True, callback=None) -> torch.Tensor:
-    """the loop of pipeline_cogvideox_image2video.py:829-885.  latents / image_latents [B, F, C, h, w]; prompt_embeds
+            use_dynamic_cfg: bool = True, callback=None, image_rotary_emb=None) -> torch.Tensor:
+    """the loop of pipeline_cogvideox_image2video.py:829-885 (the rotary tables are built once per clip when the config asks for
+    them and none are given, :819-823).  latents / image_latents [B, F, C, h, w]; prompt_embeds
     [2B, L, 4096] (negative first) when guidance_scale > 1.  The latents stay fp32 between steps (``noise_pred.float()`` :863,
     the reference casts them back to the prompt dtype :881 - reproduced)."""
     dev = transformer.device
@@ -492,10 +595,15 @@ def denoise(transformer: CogVideoXTransformer3DModel, scheduler: CogVideoXDDIMSc
     latents = latents.to(device=dev, dtype=torch.float16)
     img = image_latents.to(device=dev, dtype=torch.float16)
     img2 = torch.cat([img] * 2) if cfg else img
+    tc = transformer.config
+    if tc.use_rotary_positional_embeddings:
+        if image_rotary_emb is None:
+            image_rotary_emb = rotary_tables(tc, latents.shape[1], latents.shape[3] // tc.patch_size, latents.shape[4] // tc.patch_size)
+        image_rotary_emb = tuple(t.to(device=dev, dtype=torch.float32).contiguous() for t in image_rotary_emb)
     for i, t in enumerate(scheduler.timesteps.tolist()):
         x = torch.cat([latents] * 2) if cfg else latents
         x = torch.cat([x, img2], dim=2)
-        noise = transformer.forward_tokens(x, text, float(t)).float()
+        noise = transformer.forward_tokens(x, text, float(t), image_rotary_emb=image_rotary_emb).float()
         g = dynamic_guidance(guidance_scale, num_inference_steps, t) if use_dynamic_cfg else guidance_scale
         if cfg:
             u, c = noise.chunk(2)

@@ -1,6 +1,7 @@
 // GroupNorm(32)+SiLU and LayerNorm on channels-last fp16 token matrices (include/lkgd_hip.h sections 2, 3).
 // HBM-bound kernels: 16-byte loads/stores, fp32 statistics, deterministic reductions (no float atomics to HBM).
 #include "common.h"
+#include "../../include/lkgd_hip_dit.h"
 
 // rows of one sample handled by one workgroup.  Large maps: ~32 KiB of activations per apply workgroup, 128 KiB per
 // statistics workgroup (fewer, larger partial sums; measured best at the 72x128 level).  Small maps - the 18x32 / 9x16
@@ -585,6 +586,7 @@ extern "C" int lkgd_groupnorm_silu(const void* x0, int32_t c0, int32_t ld0, cons
 // 62 % with one row per wave); reductions are log2(L) shuffle steps inside the group.  gamma/beta stay in registers.
 #define LN_MAXV 3          // 16-byte vectors per lane: rows up to 64 * 8 * 3 = 1536 channels
 #define LN_MAXV_WIDE 4     // the DiT's 1920-channel rows (L = 64 lanes x 4 vectors = 2048)
+#define LN_MAXV_XWIDE 6    // the 5B DiT's 3072-channel rows (L = 64 lanes x 6 vectors)
 template <int L, bool AFF, int NV = LN_MAXV>
 __global__ __launch_bounds__(256) void layernorm_kernel(const half_t* x, int ldx, long long T, int C,
                                                         const float* gamma, const float* beta, float eps,
@@ -681,7 +683,7 @@ extern "C" int lkgd_layernorm(const void* x, int32_t ldx, int64_t T, int32_t C, 
                               lkgd_stream_t stream) {
   if (!x || !out) return LKGD_E_NULL;
   if ((gamma == nullptr) != (beta == nullptr)) return LKGD_E_NULL;     // both or neither (neither = no affine)
-  if (T <= 0 || C <= 0 || C % 8 || C > 64 * 8 * LN_MAXV_WIDE) return LKGD_E_SHAPE;
+  if (T <= 0 || C <= 0 || C % 8 || C > 64 * 8 * LN_MAXV_XWIDE) return LKGD_E_SHAPE;
   if (ldx % 8 || ldo % 8 || !aligned16(x) || !aligned16(out)) return LKGD_E_ALIGN;
   if (rowbias && (ldrb % 8 || !aligned16(rowbias) || rb_d1 <= 0 || rb_d2 <= 0 || rb_md <= 0)) return LKGD_E_SHAPE;
   const int C8 = C / 8;
@@ -699,6 +701,17 @@ extern "C" int lkgd_layernorm(const void* x, int32_t ldx, int64_t T, int32_t C, 
     hipLaunchKernelGGL((layernorm_kernel<LL, false>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, \
                        (const half_t*)x, ldx, (long long)T, C, gamma, beta, eps, (const half_t*)rowbias, ldrb,   \
                        rb_d1, rb_m1, rb_d2, rb_md, 0, (half_t*)out, ldo)
+  if (C8 > 64 * LN_MAXV_WIDE) {     // 2048 < C <= 3072: one row per wave, six vectors per lane
+    if (gamma)
+      hipLaunchKernelGGL((layernorm_kernel<64, true, LN_MAXV_XWIDE>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream,
+                         (const half_t*)x, ldx, (long long)T, C, gamma, beta, eps, (const half_t*)rowbias, ldrb, rb_d1, rb_m1,
+                         rb_d2, rb_md, 0, (half_t*)out, ldo);
+    else
+      hipLaunchKernelGGL((layernorm_kernel<64, false, LN_MAXV_XWIDE>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream,
+                         (const half_t*)x, ldx, (long long)T, C, gamma, beta, eps, (const half_t*)rowbias, ldrb, rb_d1, rb_m1,
+                         rb_d2, rb_md, 0, (half_t*)out, ldo);
+    return hipGetLastError() == hipSuccess ? LKGD_OK : LKGD_E_LAUNCH;
+  }
   if (C8 > 64 * LN_MAXV) {          // 1536 < C <= 2048: one row per wave, four vectors per lane
     if (gamma)
       hipLaunchKernelGGL((layernorm_kernel<64, true, LN_MAXV_WIDE>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream,
@@ -718,5 +731,149 @@ extern "C" int lkgd_layernorm(const void* x, int32_t ldx, int64_t T, int32_t C, 
     default: LN_LAUNCH(64); break;
   }
 #undef LN_LAUNCH
+  return hipGetLastError() == hipSuccess ? LKGD_OK : LKGD_E_LAUNCH;
+}
+
+// ------------------------------------------------------------------------- per-head q/k LayerNorm + rotary embedding (DiT)
+// include/lkgd_hip_dit.h.  One wave per token; a head's 64 channels are held by 4 lanes x 2 vectors, exactly as
+// lkgd_layernorm dispatches a 64-channel row (layernorm_kernel<4, AFF>: lane li holds channels [8 li, 8 li + 8) and
+// [32 + 8 li, 40 + 8 li), sums them in that order, then xor-shuffles 2, 1), so the norm is bit for bit that kernel's and a
+// rotation pair (2i, 2i+1) never leaves a lane.  The wave walks the token's heads 16 at a time (2 KB of the row per step,
+// masked tail), q's and k's loads of a step issued together; gamma / beta of q and k live in registers for the whole launch,
+// the token's cos / sin row is loaded once and serves every head of q and of k.
+__device__ __forceinline__ half8_t qk_rope8(half8_t x, const float* __restrict__ cs, const float* __restrict__ sn) {
+#pragma clang fp contract(off)
+  half8_t y;      // apply_rotary_emb in fp32 on the fp16-rounded norm: two products and one sum, each rounded, then fp16
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const float a = (float)x[2 * i], b = (float)x[2 * i + 1];
+    const float pa = a * cs[2 * i], pb = b * sn[2 * i];
+    const float qa = b * cs[2 * i + 1], qb = a * sn[2 * i + 1];
+    y[2 * i] = (half_t)(pa - pb);
+    y[2 * i + 1] = (half_t)(qa + qb);
+  }
+  return y;
+}
+
+// one head's share of a lane: the two vectors already in registers -> norm (+ rotation) -> the two stores
+__device__ __forceinline__ void qk_norm_rope_head(half_t* __restrict__ p, bool live, const half8_t (&hv)[2],
+                                                  const float (&g)[2][8], const float (&b)[2][8], float eps, bool rot,
+                                                  const float (&cs)[2][8], const float (&sn)[2][8]) {
+  const float invC = 1.0f / 64.0f;
+  float xv[2][8];
+  float s = 0.f;
+#pragma unroll
+  for (int v = 0; v < 2; ++v) {
+    if (live) {
+#pragma unroll
+      for (int e = 0; e < 8; ++e) { xv[v][e] = (float)hv[v][e]; s += xv[v][e]; }
+    } else {
+#pragma unroll
+      for (int e = 0; e < 8; ++e) xv[v][e] = 0.f;
+    }
+  }
+#pragma unroll
+  for (int o = 2; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+  const float mean = s * invC;
+  float q = 0.f;
+#pragma unroll
+  for (int v = 0; v < 2; ++v) {
+#pragma unroll
+    for (int e = 0; e < 8; ++e) { float d = xv[v][e] - mean; q += d * d; }
+  }
+#pragma unroll
+  for (int o = 2; o > 0; o >>= 1) q += __shfl_xor(q, o, 64);
+  const float rstd = rsqrtf(q * invC + eps);
+#pragma unroll
+  for (int v = 0; v < 2; ++v) {
+    if (live) {
+      half8_t o;
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        float y = (xv[v][e] - mean) * rstd;
+        y = y * g[v][e] + b[v][e];
+        o[e] = (half_t)y;
+      }
+      if (rot) o = qk_rope8(o, cs[v], sn[v]);
+      *(half8_t*)(p + 32 * v) = o;
+    }
+  }
+}
+
+__global__ __launch_bounds__(256) void qk_norm_rope_kernel(half_t* q, int ldq, half_t* k, int ldk, long long rows, int heads,
+                                                           const float* __restrict__ gamma_q, const float* __restrict__ beta_q,
+                                                           const float* __restrict__ gamma_k, const float* __restrict__ beta_k,
+                                                           float eps, const float* __restrict__ cos_t,
+                                                           const float* __restrict__ sin_t, int ldt, int rows_per_batch,
+                                                           int split) {
+  const int lane = threadIdx.x & 63;
+  const int wave = threadIdx.x >> 6;
+  const int sub = lane >> 2, li = lane & 3;         // head slot inside the wave, lane inside the head
+  float gq[2][8], bq[2][8], gk[2][8], bk[2][8];
+#pragma unroll
+  for (int v = 0; v < 2; ++v) {
+    const int c = (li + 4 * v) * 8;
+#pragma unroll
+    for (int e = 0; e < 8; e += 4) {
+      const float4_t a0 = *(const float4_t*)(gamma_q + c + e), a1 = *(const float4_t*)(beta_q + c + e);
+      const float4_t a2 = *(const float4_t*)(gamma_k + c + e), a3 = *(const float4_t*)(beta_k + c + e);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) { gq[v][e + j] = a0[j]; bq[v][e + j] = a1[j]; gk[v][e + j] = a2[j]; bk[v][e + j] = a3[j]; }
+    }
+  }
+  for (long long tok = (long long)blockIdx.x * 4 + wave; tok < rows; tok += (long long)gridDim.x * 4) {
+    // 64-bit division costs more than the norm: the usual case is 32-bit unsigned
+    const int r = rows < (1LL << 31) ? (int)((unsigned)tok % (unsigned)rows_per_batch) : (int)(tok % rows_per_batch);
+    const bool rot = cos_t != nullptr && r >= split;
+    float cs[2][8], sn[2][8];
+#pragma unroll
+    for (int v = 0; v < 2; ++v) {
+#pragma unroll
+      for (int e = 0; e < 8; ++e) { cs[v][e] = 1.f; sn[v][e] = 0.f; }
+      if (rot) {
+        const long long t0 = (long long)(r - split) * ldt + (li + 4 * v) * 8;
+#pragma unroll
+        for (int e = 0; e < 8; e += 4) {
+          const float4_t c4 = *(const float4_t*)(cos_t + t0 + e), s4 = *(const float4_t*)(sin_t + t0 + e);
+#pragma unroll
+          for (int j = 0; j < 4; ++j) { cs[v][e + j] = c4[j]; sn[v][e + j] = s4[j]; }
+        }
+      }
+    }
+    for (int h0 = 0; h0 < heads; h0 += 16) {       // q's and k's loads of the step are in flight together
+      const int h = h0 + sub;
+      const bool live = h < heads;
+      half_t* pq = q + tok * ldq + h * 64 + li * 8;
+      half_t* pk = k + tok * ldk + h * 64 + li * 8;
+      half8_t hq[2], hk[2];
+      if (live) {
+#pragma unroll
+        for (int v = 0; v < 2; ++v) { hq[v] = *(const half8_t*)(pq + 32 * v); hk[v] = *(const half8_t*)(pk + 32 * v); }
+      }
+      qk_norm_rope_head(pq, live, hq, gq, bq, eps, rot, cs, sn);
+      qk_norm_rope_head(pk, live, hk, gk, bk, eps, rot, cs, sn);
+    }
+  }
+}
+
+extern "C" int lkgd_qk_norm_rope(void* q, int32_t ldq, void* k, int32_t ldk, int64_t rows, int32_t heads,
+                                 const float* gamma_q, const float* beta_q, const float* gamma_k, const float* beta_k,
+                                 float eps, const float* cos_t, const float* sin_t, int32_t ldt, int32_t rows_per_batch,
+                                 int32_t split, lkgd_stream_t stream) {
+  if (!q || !k || !gamma_q || !beta_q || !gamma_k || !beta_k) return LKGD_E_NULL;
+  if ((cos_t == nullptr) != (sin_t == nullptr)) return LKGD_E_NULL;      // both or neither (neither = norm only)
+  if (rows <= 0 || heads <= 0 || rows_per_batch <= 0 || rows % rows_per_batch || split < 0 || split > rows_per_batch)
+    return LKGD_E_SHAPE;
+  if ((long long)heads * 64 > ldq || (long long)heads * 64 > ldk) return LKGD_E_SHAPE;
+  if (cos_t && ldt < 64) return LKGD_E_SHAPE;
+  if (ldq % 8 || ldk % 8 || !aligned16(q) || !aligned16(k) || !aligned16(gamma_q) || !aligned16(beta_q) ||
+      !aligned16(gamma_k) || !aligned16(beta_k))
+    return LKGD_E_ALIGN;
+  if (cos_t && (ldt % 4 || !aligned16(cos_t) || !aligned16(sin_t))) return LKGD_E_ALIGN;
+  long long blocks = (rows + 3) / 4;
+  if (blocks > 256 * 16) blocks = 256 * 16;
+  hipLaunchKernelGGL(qk_norm_rope_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, (half_t*)q, ldq,
+                     (half_t*)k, ldk, (long long)rows, heads, gamma_q, beta_q, gamma_k, beta_k, eps, cos_t, sin_t, ldt,
+                     rows_per_batch, split);
   return hipGetLastError() == hipSuccess ? LKGD_OK : LKGD_E_LAUNCH;
 }

@@ -797,6 +797,35 @@ def gated_add(x: torch.Tensor, gate: torch.Tensor, res: torch.Tensor, rows_per_b
     return out
 
 
+def qk_norm_rope(q: torch.Tensor, k: torch.Tensor, heads: int, nq, nk, eps: float, rope, rows_per_batch: int,
+                 split: int) -> None:
+    """per-head LayerNorm of q and k, then the rotary embedding of their video rows, in place and in one launch
+    (include/lkgd_hip_dit.h).  q, k fp16 [rows, >= heads * 64] (column windows allowed); nq / nk = (gamma, beta) fp32 [64];
+    rope = (cos, sin) fp32 [rows_per_batch - split, 64], or None for the norm alone; rows r with r % rows_per_batch < split
+    are text rows (never rotated)"""
+    _req(q, torch.float16, "q"); _req(k, torch.float16, "k")
+    for name, t in (("gamma_q", nq[0]), ("beta_q", nq[1]), ("gamma_k", nk[0]), ("beta_k", nk[1])):
+        _req(t, torch.float32, name)
+        if t.numel() != 64 or not t.is_contiguous():
+            raise _lib.LkgdHipError(f"qk_norm_rope: {name} must be a contiguous fp32 [64] vector")
+    if q.dim() != 2 or k.dim() != 2 or q.shape[0] != k.shape[0] or q.shape[1] != heads * 64 or k.shape[1] != heads * 64:
+        raise _lib.LkgdHipError(f"qk_norm_rope: q and k must both be [rows, heads * 64], got {tuple(q.shape)} / {tuple(k.shape)}")
+    cos = sin = None
+    ldt = 0
+    if rope is not None:
+        cos, sin = rope
+        _req(cos, torch.float32, "cos"); _req(sin, torch.float32, "sin")
+        if cos.shape != sin.shape or cos.dim() != 2 or cos.shape[1] != 64 or cos.shape[0] != rows_per_batch - split:
+            raise _lib.LkgdHipError(f"qk_norm_rope: cos / sin must both be [rows_per_batch - split, 64], got {tuple(cos.shape)} / "
+                                    f"{tuple(sin.shape)}")
+        if _ld(cos) != _ld(sin):
+            raise _lib.LkgdHipError("qk_norm_rope: cos and sin must share one row stride")
+        ldt = _ld(cos)
+    check(_L().lkgd_qk_norm_rope(q.data_ptr(), _ld(q), k.data_ptr(), _ld(k), q.shape[0], heads, nq[0].data_ptr(), nq[1].data_ptr(),
+                                 nk[0].data_ptr(), nk[1].data_ptr(), eps, _ptr(cos), _ptr(sin), ldt, rows_per_batch, split,
+                                 _stream()), "lkgd_qk_norm_rope")
+
+
 def scale(x: torch.Tensor, s: float) -> torch.Tensor:
     _req(x, torch.float16, "x")
     x = x.contiguous()

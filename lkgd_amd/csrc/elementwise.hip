@@ -1,4 +1,8 @@
 // Loop glue and small elementwise kernels (include/lkgd_hip.h sections 6, 7; include/lkgd_hip_window.h).  All HBM/latency-bound.
+// Every kernel that takes an Euler step does it through ONE core (euler_setup / euler_x0 / euler_advance), and the plain and the
+// windowed CFG + Euler entry points launch ONE step kernel (cfg_euler_kernel).
+#include <type_traits>
+
 #include "common.h"
 #include "../../include/lkgd_hip_window.h"
 
@@ -31,12 +35,12 @@ __global__ __launch_bounds__(256) void prepare_input_kernel(const LT* __restrict
 // (pipeline :578-592): the difference, the product and the sum are each rounded to fp16.  Contraction is off here: fused into
 // one fp16 multiply-add the product would skip its rounding, and one fp16 ulp of the noise is sigma / 1024 in an epsilon-
 // prediction x0 - more than an fp16 ulp of the latents at the high-noise steps.
-__device__ __forceinline__ half4_t cfg_combine(const half_t* __restrict__ noise, long long i, long long total, int cfg,
+__device__ __forceinline__ half4_t cfg_combine(const half_t* __restrict__ noise, long long i, long long cond_off, int cfg,
                                                const float* __restrict__ guidance, int f) {
 #pragma clang fp contract(off)
   half4_t u = *(const half4_t*)(noise + i * 4);
   if (cfg != 2) return u;
-  half4_t c = *(const half4_t*)(noise + (i + total) * 4);
+  half4_t c = *(const half4_t*)(noise + (i + cond_off) * 4);
   const half_t g = (half_t)guidance[f];
   half4_t n;
 #pragma unroll
@@ -48,32 +52,48 @@ __device__ __forceinline__ half4_t cfg_combine(const half_t* __restrict__ noise,
   return n;
 }
 
-// ---- per-frame CFG + Euler step (pipeline :578-592; scheduler.step :481-520).  fp16 rounding points follow the
-// reference's tensor dtypes: CFG arithmetic on fp16 tensors, model_output * c_out stays fp16 (0-dim fp32 scalar does
-// not promote), everything after the upcast of `sample` is fp32.
+// ---- the Euler core (scheduler.step :481-520).  fp16 rounding points follow the reference's tensor dtypes: model_output *
+// c_out (or * sigma) stays fp16 (a 0-dim fp32 scalar does not promote), everything after the upcast of `sample` is fp32.
+// `sigma_hat` is sigma itself everywhere but in the standalone scheduler's churn step.
+struct euler_t { float c_out, c_skip, sigma_hat, dt; };
+__device__ __forceinline__ euler_t euler_setup(float sigma, float sigma_hat, float sigma_next) {
+  euler_t e;
+  e.c_out = -sigma / sqrtf(sigma * sigma + 1.0f);
+  e.c_skip = sigma * sigma + 1.0f;
+  e.sigma_hat = sigma_hat;
+  e.dt = sigma_next - sigma_hat;
+  return e;
+}
+__device__ __forceinline__ float euler_x0(const euler_t& e, int vpred, half_t n, float x) {
+  if (vpred) return (float)(half_t)((float)n * e.c_out) + x / e.c_skip;
+  return x - (float)(half_t)((float)n * e.sigma_hat);
+}
+__device__ __forceinline__ float euler_advance(const euler_t& e, float x, float x0) {
+  const float deriv = (x - x0) / e.sigma_hat;
+  return x + deriv * e.dt;
+}
+
+// ---- per-frame CFG + Euler step (pipeline :578-592): CFG arithmetic on fp16 tensors (cfg_combine), then the core.  `cond_off`:
+// token rows from an unconditional row to its conditional one - B*F*HW for the whole batch; 2*L*HW for a window of the smoothing
+// pipeline, which is this kernel with B = 1, F = L and `latents` advanced to the window's first frame.
 template <typename LT>
 __global__ __launch_bounds__(256) void cfg_euler_kernel(const half_t* __restrict__ noise, LT* __restrict__ latents,
                                                         const float* __restrict__ guidance, int B, int F, int HW,
-                                                        int cfg, float sigma, float sigma_next, int vpred) {
+                                                        int cfg, long long cond_off, float sigma, float sigma_next,
+                                                        int vpred) {
   const long long total = (long long)B * F * HW;
-  const float c_out = -sigma / sqrtf(sigma * sigma + 1.0f);
-  const float c_skip = sigma * sigma + 1.0f;
-  const float dt = sigma_next - sigma;
+  const euler_t e = euler_setup(sigma, sigma, sigma_next);
   for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
     const int p = (int)(i % HW);
     const long long bf = i / HW;
     const int f = (int)(bf % F);
     const int b = (int)(bf / F);
-    const half4_t n = cfg_combine(noise, i, total, cfg, guidance, f);
+    const half4_t n = cfg_combine(noise, i, cond_off, cfg, guidance, f);
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
       const long long li = (((long long)b * F + f) * 4 + c) * HW + p;
       const float x = (float)latents[li];
-      float x0;
-      if (vpred) x0 = (float)(half_t)((float)n[c] * c_out) + x / c_skip;
-      else x0 = x - (float)(half_t)((float)n[c] * sigma);
-      const float deriv = (x - x0) / sigma;
-      latents[li] = (LT)(x + deriv * dt);
+      latents[li] = (LT)euler_advance(e, x, euler_x0(e, vpred, n[c], x));
     }
   }
 }
@@ -92,9 +112,7 @@ __global__ __launch_bounds__(256) void cfg_fusion_euler_kernel(const half_t* __r
   const int P = B / 2;
   const long long total = (long long)B * F * HW;         // token rows of one CFG half
   const long long pairs = (long long)P * F * HW;         // threads: one per (b < P, f, p)
-  const float c_out = -sigma / sqrtf(sigma * sigma + 1.0f);
-  const float c_skip = sigma * sigma + 1.0f;
-  const float dt = sigma_next - sigma;
+  const euler_t e = euler_setup(sigma, sigma, sigma_next);
   for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < pairs; i += (long long)gridDim.x * 256) {
     const int p = (int)(i % HW);
     const long long bf = i / HW;
@@ -116,17 +134,9 @@ __global__ __launch_bounds__(256) void cfg_fusion_euler_kernel(const half_t* __r
     }
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
-      float x0a, x0m;
-      if (vpred) {
-        x0a = (float)(half_t)((float)na[c] * c_out) + xa[c] / c_skip;
-        x0m = (float)(half_t)((float)nm[c] * c_out) + xm[c] / c_skip;
-      } else {
-        x0a = xa[c] - (float)(half_t)((float)na[c] * sigma);
-        x0m = xm[c] - (float)(half_t)((float)nm[c] * sigma);
-      }
-      const float xb = x0a * w + x0m * wc;
-      latents[la + (long long)c * HW] = (LT)(xa[c] + (xa[c] - xb) / sigma * dt);
-      latents[lm + (long long)c * HW] = (LT)(xm[c] + (xm[c] - xb) / sigma * dt);
+      const float xb = euler_x0(e, vpred, na[c], xa[c]) * w + euler_x0(e, vpred, nm[c], xm[c]) * wc;
+      latents[la + (long long)c * HW] = (LT)euler_advance(e, xa[c], xb);
+      latents[lm + (long long)c * HW] = (LT)euler_advance(e, xm[c], xb);
     }
   }
 }
@@ -205,16 +215,11 @@ __global__ __launch_bounds__(256) void euler_kernel(const half_t* __restrict__ m
                                                     int vpred) {
   // sigma_hat = sigma * (gamma + 1); gamma > 0 ("churn", scheduling_euler_discrete_karras_fix.py:485-497) first adds
   // noise * s_noise * sqrt(sigma_hat^2 - sigma^2) to the sample, each product rounded to fp16 as the reference's tensors are
-  const float c_out = -sigma / sqrtf(sigma * sigma + 1.0f);
-  const float c_skip = sigma * sigma + 1.0f;
-  const float dt = sigma_next - sigma_hat;
+  const euler_t e = euler_setup(sigma, sigma_hat, sigma_next);
   for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
     float x = (float)sample[i];
     if (noise) x += (float)(half_t)((float)(half_t)((float)noise[i] * s_noise) * churn);
-    float x0;
-    if (vpred) x0 = (float)(half_t)((float)mo[i] * c_out) + x / c_skip;
-    else x0 = x - (float)(half_t)((float)mo[i] * sigma_hat);
-    prev[i] = (half_t)(x + (x - x0) / sigma_hat * dt);
+    prev[i] = (half_t)euler_advance(e, x, euler_x0(e, vpred, mo[i], x));
   }
 }
 
@@ -225,71 +230,91 @@ static unsigned grid_for(long long work_items, int per_block) {
   return (unsigned)g;
 }
 
+// ---- shared by the loop-glue entry points.  The order of the checks is part of the ABI: null, guidance for cfg 2, shape, mode,
+// alignment.
+static int batch_shape_ok(int32_t B, int32_t F, int32_t H, int32_t W, int32_t cfg) {
+  return B > 0 && F > 0 && H > 0 && W > 0 && (cfg == 1 || cfg == 2);
+}
+static int window_shape_ok(int32_t T, int32_t f0, int32_t L, int32_t H, int32_t W, int32_t cfg, float sigma) {
+  return T > 0 && H > 0 && W > 0 && L > 0 && f0 >= 0 && (long long)f0 + L <= T && (cfg == 1 || cfg == 2) && sigma > 0.f;
+}
+static int prepare_check(const void* latents, const void* image_latents, const void* tokens_out, int shape_ok) {
+  if (!latents || !image_latents || !tokens_out) return LKGD_E_NULL;
+  if (!shape_ok) return LKGD_E_SHAPE;
+  return aligned16(tokens_out) ? LKGD_OK : LKGD_E_ALIGN;
+}
+static int step_check(const void* noise_tokens, const void* latents, const float* guidance, int32_t cfg, int shape_ok,
+                      int32_t prediction_type) {
+  if (!noise_tokens || !latents) return LKGD_E_NULL;
+  if (cfg == 2 && !guidance) return LKGD_E_NULL;
+  if (!shape_ok) return LKGD_E_SHAPE;
+  if (prediction_type != 0 && prediction_type != 1) return LKGD_E_MODE;
+  return ((uintptr_t)noise_tokens & 7) ? LKGD_E_ALIGN : LKGD_OK;
+}
+// launch(tag) with a float* or half_t* tag: the one place an entry point spells its launch, for both latent dtypes
+template <typename Launch>
+static int launch_typed(int32_t is_f32, Launch&& launch) {
+  if (is_f32) launch((float*)nullptr);
+  else launch((half_t*)nullptr);
+  return hipGetLastError() == hipSuccess ? LKGD_OK : LKGD_E_LAUNCH;
+}
+
 extern "C" int lkgd_prepare_unet_input(const void* latents, int32_t latents_is_f32, const void* image_latents,
                                        int32_t B, int32_t F, int32_t H, int32_t W, int32_t cfg, float sigma,
                                        void* tokens_out, lkgd_stream_t stream) {
-  if (!latents || !image_latents || !tokens_out) return LKGD_E_NULL;
-  if (B <= 0 || F <= 0 || H <= 0 || W <= 0 || (cfg != 1 && cfg != 2)) return LKGD_E_SHAPE;
-  if (!aligned16(tokens_out)) return LKGD_E_ALIGN;
+  if (int rc = prepare_check(latents, image_latents, tokens_out, batch_shape_ok(B, F, H, W, cfg))) return rc;
   const float inv = 1.0f / sqrtf(sigma * sigma + 1.0f);
   const long long total = (long long)cfg * B * F * H * W;
-  if (latents_is_f32)
-    hipLaunchKernelGGL(prepare_input_kernel<float>, dim3(grid_for(total, 256)), dim3(256), 0, (hipStream_t)stream,
-                       (const float*)latents, (const half_t*)image_latents, B, F, H * W, cfg, inv,
-                       (half_t*)tokens_out);
-  else
-    hipLaunchKernelGGL(prepare_input_kernel<half_t>, dim3(grid_for(total, 256)), dim3(256), 0, (hipStream_t)stream,
-                       (const half_t*)latents, (const half_t*)image_latents, B, F, H * W, cfg, inv,
-                       (half_t*)tokens_out);
-  return hipGetLastError() == hipSuccess ? LKGD_OK : LKGD_E_LAUNCH;
+  return launch_typed(latents_is_f32, [&](auto* tag) {
+    using LT = std::remove_pointer_t<decltype(tag)>;
+    hipLaunchKernelGGL(prepare_input_kernel<LT>, dim3(grid_for(total, 256)), dim3(256), 0, (hipStream_t)stream,
+                       (const LT*)latents, (const half_t*)image_latents, B, F, H * W, cfg, inv, (half_t*)tokens_out);
+  });
+}
+
+// the plain step and the window step: `latents` + first_elem is frame 0 of the B x F frames to step, one thread per (b, f, pixel)
+static int cfg_euler_launch(const void* noise_tokens, void* latents, int32_t latents_is_f32, const float* guidance,
+                            long long first_elem, int32_t B, int32_t F, int32_t HW, int32_t cfg, long long cond_off,
+                            int shape_ok, float sigma, float sigma_next, int32_t prediction_type, lkgd_stream_t stream) {
+  if (int rc = step_check(noise_tokens, latents, guidance, cfg, shape_ok, prediction_type)) return rc;
+  const long long total = (long long)B * F * HW;
+  return launch_typed(latents_is_f32, [&](auto* tag) {
+    using LT = std::remove_pointer_t<decltype(tag)>;
+    hipLaunchKernelGGL(cfg_euler_kernel<LT>, dim3(grid_for(total, 256)), dim3(256), 0, (hipStream_t)stream,
+                       (const half_t*)noise_tokens, (LT*)latents + first_elem, guidance, B, F, HW, cfg, cond_off, sigma,
+                       sigma_next, prediction_type);
+  });
 }
 
 extern "C" int lkgd_cfg_euler_step(const void* noise_tokens, void* latents, int32_t latents_is_f32,
                                    const float* guidance, int32_t B, int32_t F, int32_t H, int32_t W, int32_t cfg,
                                    float sigma, float sigma_next, int32_t prediction_type, lkgd_stream_t stream) {
-  if (!noise_tokens || !latents) return LKGD_E_NULL;
-  if (cfg == 2 && !guidance) return LKGD_E_NULL;
-  if (B <= 0 || F <= 0 || H <= 0 || W <= 0 || (cfg != 1 && cfg != 2) || !(sigma > 0.f)) return LKGD_E_SHAPE;
-  if (prediction_type != 0 && prediction_type != 1) return LKGD_E_MODE;
-  if ((uintptr_t)noise_tokens & 7) return LKGD_E_ALIGN;
-  const long long total = (long long)B * F * H * W;
-  if (latents_is_f32)
-    hipLaunchKernelGGL(cfg_euler_kernel<float>, dim3(grid_for(total, 256)), dim3(256), 0, (hipStream_t)stream,
-                       (const half_t*)noise_tokens, (float*)latents, guidance, B, F, H * W, cfg, sigma, sigma_next,
-                       prediction_type);
-  else
-    hipLaunchKernelGGL(cfg_euler_kernel<half_t>, dim3(grid_for(total, 256)), dim3(256), 0, (hipStream_t)stream,
-                       (const half_t*)noise_tokens, (half_t*)latents, guidance, B, F, H * W, cfg, sigma, sigma_next,
-                       prediction_type);
-  return hipGetLastError() == hipSuccess ? LKGD_OK : LKGD_E_LAUNCH;
+  return cfg_euler_launch(noise_tokens, latents, latents_is_f32, guidance, 0, B, F, H * W, cfg, (long long)B * F * H * W,
+                          batch_shape_ok(B, F, H, W, cfg) && sigma > 0.f, sigma, sigma_next, prediction_type, stream);
 }
 
 extern "C" int lkgd_cfg_fusion_euler_step(const void* noise_tokens, void* latents, int32_t latents_is_f32,
                                           const float* guidance, const float* weight, int32_t B, int32_t F, int32_t H,
                                           int32_t W, int32_t cfg, float sigma, float sigma_next,
                                           int32_t prediction_type, lkgd_stream_t stream) {
-  if (!noise_tokens || !latents || !weight) return LKGD_E_NULL;
-  if (cfg == 2 && !guidance) return LKGD_E_NULL;
-  if (B <= 0 || (B & 1) || F <= 0 || H <= 0 || W <= 0 || (cfg != 1 && cfg != 2) || !(sigma > 0.f))
-    return LKGD_E_SHAPE;
-  if (prediction_type != 0 && prediction_type != 1) return LKGD_E_MODE;
-  if ((uintptr_t)noise_tokens & 7) return LKGD_E_ALIGN;
+  if (!weight) return LKGD_E_NULL;
+  if (int rc = step_check(noise_tokens, latents, guidance, cfg, batch_shape_ok(B, F, H, W, cfg) && !(B & 1) && sigma > 0.f,
+                          prediction_type))
+    return rc;
   const long long pairs = (long long)(B / 2) * F * H * W;
-  if (latents_is_f32)
-    hipLaunchKernelGGL(cfg_fusion_euler_kernel<float>, dim3(grid_for(pairs, 256)), dim3(256), 0, (hipStream_t)stream,
-                       (const half_t*)noise_tokens, (float*)latents, guidance, weight, B, F, H * W, cfg, sigma,
-                       sigma_next, prediction_type);
-  else
-    hipLaunchKernelGGL(cfg_fusion_euler_kernel<half_t>, dim3(grid_for(pairs, 256)), dim3(256), 0, (hipStream_t)stream,
-                       (const half_t*)noise_tokens, (half_t*)latents, guidance, weight, B, F, H * W, cfg, sigma,
-                       sigma_next, prediction_type);
-  return hipGetLastError() == hipSuccess ? LKGD_OK : LKGD_E_LAUNCH;
+  return launch_typed(latents_is_f32, [&](auto* tag) {
+    using LT = std::remove_pointer_t<decltype(tag)>;
+    hipLaunchKernelGGL(cfg_fusion_euler_kernel<LT>, dim3(grid_for(pairs, 256)), dim3(256), 0, (hipStream_t)stream,
+                       (const half_t*)noise_tokens, (LT*)latents, guidance, weight, B, F, H * W, cfg, sigma, sigma_next,
+                       prediction_type);
+  });
 }
 
 // ---- windowed loop glue of the long-video smoothing pipeline (include/lkgd_hip_window.h; pipeline_stable_video_diffusion_
 // smooth.py:545-594).  A window is frames f0 .. f0+L-1 of latents [T,4,H,W]; the UNet batch is entry e = 2*k + d, k = CFG half,
-// d = 0 the window, d = 1 the window reversed in time.  Same rounding points, 16-byte token rows, plane-coalesced reads and grid
-// rule as prepare_input_kernel / cfg_euler_kernel.
+// d = 0 the window, d = 1 the window reversed in time.  The gather is a kernel of its own (frame flip, zero unconditional half),
+// with the rounding points, 16-byte token rows, plane-coalesced reads and grid rule of prepare_input_kernel; the step is
+// cfg_euler_kernel on the window's frames.
 template <typename LT>
 __global__ __launch_bounds__(256) void window_prepare_kernel(const LT* __restrict__ latents,
                                                              const half_t* __restrict__ image_latents, int f0, int L,
@@ -316,71 +341,28 @@ __global__ __launch_bounds__(256) void window_prepare_kernel(const LT* __restric
   }
 }
 
-template <typename LT>
-__global__ __launch_bounds__(256) void window_cfg_euler_kernel(const half_t* __restrict__ noise, LT* __restrict__ latents,
-                                                               const float* __restrict__ guidance, int f0, int L, int HW,
-                                                               int cfg, float sigma, float sigma_next, int vpred) {
-  const long long total = (long long)L * HW;             // token rows of one batch entry; entry 2 = the forward clip's cond
-  const float c_out = -sigma / sqrtf(sigma * sigma + 1.0f);
-  const float c_skip = sigma * sigma + 1.0f;
-  const float dt = sigma_next - sigma;
-  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
-    const int p = (int)(i % HW);
-    const int j = (int)(i / HW);
-    const half4_t n = cfg_combine(noise, i, 2 * total, cfg, guidance, j);
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-      const long long li = (((long long)f0 + j) * 4 + c) * HW + p;
-      const float x = (float)latents[li];
-      float x0;
-      if (vpred) x0 = (float)(half_t)((float)n[c] * c_out) + x / c_skip;
-      else x0 = x - (float)(half_t)((float)n[c] * sigma);
-      const float deriv = (x - x0) / sigma;
-      latents[li] = (LT)(x + deriv * dt);
-    }
-  }
-}
-
-static int window_shape_ok(int32_t T, int32_t f0, int32_t L, int32_t H, int32_t W, int32_t cfg, float sigma) {
-  return T > 0 && H > 0 && W > 0 && L > 0 && f0 >= 0 && (long long)f0 + L <= T && (cfg == 1 || cfg == 2) && sigma > 0.f;
-}
-
 extern "C" int lkgd_window_prepare_input(const void* latents, int32_t latents_is_f32, const void* image_latents, int32_t T,
                                          int32_t f0, int32_t L, int32_t H, int32_t W, int32_t cfg, float sigma,
                                          void* tokens_out, lkgd_stream_t stream) {
-  if (!latents || !image_latents || !tokens_out) return LKGD_E_NULL;
-  if (!window_shape_ok(T, f0, L, H, W, cfg, sigma)) return LKGD_E_SHAPE;
-  if (!aligned16(tokens_out)) return LKGD_E_ALIGN;
+  if (int rc = prepare_check(latents, image_latents, tokens_out, window_shape_ok(T, f0, L, H, W, cfg, sigma))) return rc;
   const float inv = 1.0f / sqrtf(sigma * sigma + 1.0f);
   const long long total = 2ll * cfg * L * H * W;
-  if (latents_is_f32)
-    hipLaunchKernelGGL(window_prepare_kernel<float>, dim3(grid_for(total, 256)), dim3(256), 0, (hipStream_t)stream,
-                       (const float*)latents, (const half_t*)image_latents, f0, L, H * W, cfg, inv, (half_t*)tokens_out);
-  else
-    hipLaunchKernelGGL(window_prepare_kernel<half_t>, dim3(grid_for(total, 256)), dim3(256), 0, (hipStream_t)stream,
-                       (const half_t*)latents, (const half_t*)image_latents, f0, L, H * W, cfg, inv, (half_t*)tokens_out);
-  return hipGetLastError() == hipSuccess ? LKGD_OK : LKGD_E_LAUNCH;
+  return launch_typed(latents_is_f32, [&](auto* tag) {
+    using LT = std::remove_pointer_t<decltype(tag)>;
+    hipLaunchKernelGGL(window_prepare_kernel<LT>, dim3(grid_for(total, 256)), dim3(256), 0, (hipStream_t)stream,
+                       (const LT*)latents, (const half_t*)image_latents, f0, L, H * W, cfg, inv, (half_t*)tokens_out);
+  });
 }
 
+// the window's frames are a [1, L] clip that starts f0 frames into the latents; of the batch [fwd, rev] x [uncond, cond] only the
+// forward clip steps: its unconditional rows are entry 0, its conditional rows entry 2
 extern "C" int lkgd_window_cfg_euler_step(const void* noise_tokens, void* latents, int32_t latents_is_f32,
                                           const float* guidance, int32_t T, int32_t f0, int32_t L, int32_t H, int32_t W,
                                           int32_t cfg, float sigma, float sigma_next, int32_t prediction_type,
                                           lkgd_stream_t stream) {
-  if (!noise_tokens || !latents) return LKGD_E_NULL;
-  if (cfg == 2 && !guidance) return LKGD_E_NULL;
-  if (!window_shape_ok(T, f0, L, H, W, cfg, sigma)) return LKGD_E_SHAPE;
-  if (prediction_type != 0 && prediction_type != 1) return LKGD_E_MODE;
-  if ((uintptr_t)noise_tokens & 7) return LKGD_E_ALIGN;
-  const long long total = (long long)L * H * W;
-  if (latents_is_f32)
-    hipLaunchKernelGGL(window_cfg_euler_kernel<float>, dim3(grid_for(total, 256)), dim3(256), 0, (hipStream_t)stream,
-                       (const half_t*)noise_tokens, (float*)latents, guidance, f0, L, H * W, cfg, sigma, sigma_next,
-                       prediction_type);
-  else
-    hipLaunchKernelGGL(window_cfg_euler_kernel<half_t>, dim3(grid_for(total, 256)), dim3(256), 0, (hipStream_t)stream,
-                       (const half_t*)noise_tokens, (half_t*)latents, guidance, f0, L, H * W, cfg, sigma, sigma_next,
-                       prediction_type);
-  return hipGetLastError() == hipSuccess ? LKGD_OK : LKGD_E_LAUNCH;
+  return cfg_euler_launch(noise_tokens, latents, latents_is_f32, guidance, (long long)f0 * 4 * H * W, 1, L, H * W, cfg,
+                          2ll * L * H * W, window_shape_ok(T, f0, L, H, W, cfg, sigma), sigma, sigma_next, prediction_type,
+                          stream);
 }
 
 // ---- rows of a frame shard regrouped by destination pixel shard (and back): the pack / unpack around the all-to-all that
@@ -485,15 +467,12 @@ static int euler_launch(const void* model_output, const void* sample, int32_t sa
   if (!model_output || !sample || !prev) return LKGD_E_NULL;
   if (n <= 0 || !(sigma > 0.f) || !(sigma_hat >= sigma)) return LKGD_E_SHAPE;
   if (prediction_type != 0 && prediction_type != 1) return LKGD_E_MODE;
-  if (sample_is_f32)
-    hipLaunchKernelGGL(euler_kernel<float>, dim3(grid_for(n, 256)), dim3(256), 0, (hipStream_t)stream,
-                       (const half_t*)model_output, (const float*)sample, (const half_t*)noise, (half_t*)prev, (long long)n,
+  return launch_typed(sample_is_f32, [&](auto* tag) {
+    using ST = std::remove_pointer_t<decltype(tag)>;
+    hipLaunchKernelGGL(euler_kernel<ST>, dim3(grid_for(n, 256)), dim3(256), 0, (hipStream_t)stream,
+                       (const half_t*)model_output, (const ST*)sample, (const half_t*)noise, (half_t*)prev, (long long)n,
                        sigma, sigma_hat, s_noise, churn, sigma_next, prediction_type);
-  else
-    hipLaunchKernelGGL(euler_kernel<half_t>, dim3(grid_for(n, 256)), dim3(256), 0, (hipStream_t)stream,
-                       (const half_t*)model_output, (const half_t*)sample, (const half_t*)noise, (half_t*)prev, (long long)n,
-                       sigma, sigma_hat, s_noise, churn, sigma_next, prediction_type);
-  return hipGetLastError() == hipSuccess ? LKGD_OK : LKGD_E_LAUNCH;
+  });
 }
 
 extern "C" int lkgd_euler_step(const void* model_output, const void* sample, int32_t sample_is_f32, void* prev,

@@ -245,38 +245,31 @@ class DistDenoiser:
                 down, mid, _ = pipe.controlnet.forward_tokens(tok_local, b_local, fl, H, W, t_dev, enc, ids_local, ctrl_local,
                                                               controlnet_cond_scale, shard=self.shard)
             return unet.forward_tokens(tok_local, b_local, fl, H, W, t_dev, enc, ids_local, down, mid, shard=self.shard)[0]
-        recorded = None
         events_all = ops.GEMM_EVENTS
         try:
-            for i, t in enumerate(sch.timesteps_host):
-                sigma, sigma_next = sch.sigmas_host[i], sch.sigmas_host[i + 1]
-                ops.GEMM_EVENTS = events_all if (events_all is not None and i % self.event_stride == self.event_stride // 2) else None
-                ops.prepare_unet_input(latents, image_latents, cfg, sigma, out=tok)     # [cfg*F*HW, 8], replicated
-                if pick is not None:
-                    pick[0].copy_(pick[1])
-                t_dev.fill_(float(t))
-                if recorded is not None:
-                    noise_local = recorded.run(ops.GEMM_EVENTS)
-                elif self.use_replay:
-                    with replay.record(self._arenas.take(dev, (b_local, fl, H, W, ctrl_local is not None, id(unet._pk)))) as recorded:   # the first step runs for real and is recorded
-                        recorded.result = forward()
-                    noise_local = recorded.result
-                else:
-                    noise_local = forward()
-                # ---- exchange the noise prediction over all ranks (padded equal counts), compact, replicate the update
-                send[:, :fl * HW].copy_(noise_local.reshape(b_local, fl * HW, 4))
-                all_gather_into(buf.reshape(-1, 4), send.reshape(-1, 4))
-                nf = noise_full.reshape(cfg * B, F * HW, 4)
-                for r in range(plan.world):
-                    ci, si = divmod(r, plan.frame_shards)
-                    n, fs = plan.splits[si], sum(plan.splits[:si])
-                    er = ci * b_local if plan.cfg_groups == 2 else 0
-                    nf[er:er + b_local, fs * HW:(fs + n) * HW].copy_(buf[r, :, :n * HW])
-                ops.cfg_euler_step(noise_full, latents, guidance, cfg, sigma, sigma_next, v_prediction=vpred)
-        finally:          # whatever ended the loop: the bench's event list is restored, the plan's activations are freed
+            # the first step runs for real and is recorded, the others replay it; the plan's activations are freed on the way out
+            with replay.Replayed(self._arenas, dev, lambda: (b_local, fl, H, W, ctrl_local is not None, id(unet._pk)), forward,
+                                 enabled=self.use_replay) as step_forward:
+                for i, t in enumerate(sch.timesteps_host):
+                    sigma, sigma_next = sch.sigmas_host[i], sch.sigmas_host[i + 1]
+                    ops.GEMM_EVENTS = events_all if (events_all is not None and i % self.event_stride == self.event_stride // 2) else None
+                    ops.prepare_unet_input(latents, image_latents, cfg, sigma, out=tok)     # [cfg*F*HW, 8], replicated
+                    if pick is not None:
+                        pick[0].copy_(pick[1])
+                    t_dev.fill_(float(t))
+                    noise_local = step_forward(ops.GEMM_EVENTS)
+                    # ---- exchange the noise prediction over all ranks (padded equal counts), compact, replicate the update
+                    send[:, :fl * HW].copy_(noise_local.reshape(b_local, fl * HW, 4))
+                    all_gather_into(buf.reshape(-1, 4), send.reshape(-1, 4))
+                    nf = noise_full.reshape(cfg * B, F * HW, 4)
+                    for r in range(plan.world):
+                        ci, si = divmod(r, plan.frame_shards)
+                        n, fs = plan.splits[si], sum(plan.splits[:si])
+                        er = ci * b_local if plan.cfg_groups == 2 else 0
+                        nf[er:er + b_local, fs * HW:(fs + n) * HW].copy_(buf[r, :, :n * HW])
+                    ops.cfg_euler_step(noise_full, latents, guidance, cfg, sigma, sigma_next, v_prediction=vpred)
+        finally:          # whatever ended the loop, the bench's event list is restored
             ops.GEMM_EVENTS = events_all
-            if recorded is not None:
-                recorded.release()
         sch._step_index = num_inference_steps
         return latents
 

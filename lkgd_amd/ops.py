@@ -87,6 +87,14 @@ def _req(t: torch.Tensor, dtype, name: str):
         raise _lib.LkgdHipError(f"{name}: expected {dtype}, got {t.dtype}")
 
 
+def _req_latents(t: torch.Tensor, name: str = "latents") -> None:
+    """the loop glue's in-place operand: a contiguous GPU tensor of fp16 or fp32 (the kernels take its bare pointer)"""
+    if not t.is_cuda or t.dtype not in (torch.float16, torch.float32):
+        raise _lib.LkgdHipError(f"{name} must be a GPU fp16/fp32 tensor")
+    if not t.is_contiguous():
+        raise _lib.LkgdHipError(f"{name} must be contiguous, got strides {tuple(t.stride())}")
+
+
 def _ptr(t: Optional[torch.Tensor]) -> Optional[int]:
     return None if t is None else t.data_ptr()
 
@@ -542,10 +550,9 @@ def prepare_unet_input(latents: torch.Tensor, image_latents: torch.Tensor, cfg: 
                        out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """[B,F,4,H,W] latents (+ [cfg*B,F,4,H,W] image latents) -> channels-last tokens [cfg*B*F*H*W, 8]"""
     B, F, _, H, W = latents.shape
+    _req_latents(latents)
     _req(image_latents, torch.float16, "image_latents")
-    if not latents.is_cuda or latents.dtype not in (torch.float16, torch.float32):
-        raise _lib.LkgdHipError("latents must be a GPU fp16/fp32 tensor")
-    assert latents.is_contiguous() and image_latents.is_contiguous()
+    assert image_latents.is_contiguous()
     assert image_latents.shape == (cfg * B, F, 4, H, W), image_latents.shape
     if out is None:
         out = torch.empty(cfg * B * F * H * W, 8, dtype=torch.float16, device=latents.device)
@@ -559,8 +566,9 @@ def cfg_euler_step(noise_tokens: torch.Tensor, latents: torch.Tensor, guidance: 
                    sigma: float, sigma_next: float, v_prediction: bool = True) -> torch.Tensor:
     """in-place Euler update of ``latents`` [B,F,4,H,W] from channels-last noise tokens [cfg*B*F*H*W, 4]"""
     B, F, _, H, W = latents.shape
+    _req_latents(latents)
     _req(noise_tokens, torch.float16, "noise_tokens")
-    assert latents.is_contiguous() and noise_tokens.is_contiguous()
+    assert noise_tokens.is_contiguous()
     check(_L().lkgd_cfg_euler_step(noise_tokens.data_ptr(), latents.data_ptr(),
                                          int(latents.dtype == torch.float32), _ptr(guidance), B, F, H, W, cfg, sigma,
                                          sigma_next, 1 if v_prediction else 0, _stream()), "lkgd_cfg_euler_step")
@@ -574,13 +582,12 @@ def cfg_fusion_euler_step(noise_tokens: torch.Tensor, latents: torch.Tensor, gui
     b + P the backward partner of clip b) from channels-last noise tokens [cfg*B*F*H*W, 4]; ``weight`` fp32 [F] on the device
     (torch.linspace(1, 0, F)), ``guidance`` fp32 [F] on the device (or None when cfg == 1)"""
     B, F, _, H, W = latents.shape
+    _req_latents(latents)
     _req(noise_tokens, torch.float16, "noise_tokens")
     _req(weight, torch.float32, "weight")
     if guidance is not None:
         _req(guidance, torch.float32, "guidance")
-    if not latents.is_cuda or latents.dtype not in (torch.float16, torch.float32):
-        raise _lib.LkgdHipError("latents must be a GPU fp16/fp32 tensor")
-    assert latents.is_contiguous() and noise_tokens.is_contiguous() and weight.is_contiguous()
+    assert noise_tokens.is_contiguous() and weight.is_contiguous()
     assert weight.numel() == F and (guidance is None or guidance.numel() == F)
     check(_L().lkgd_cfg_fusion_euler_step(noise_tokens.data_ptr(), latents.data_ptr(),
                                           int(latents.dtype == torch.float32), _ptr(guidance), weight.data_ptr(), B, F,
@@ -590,11 +597,10 @@ def cfg_fusion_euler_step(noise_tokens: torch.Tensor, latents: torch.Tensor, gui
 
 
 def _window(latents: torch.Tensor, f0: int, L: int):
-    if not latents.is_cuda or latents.dtype not in (torch.float16, torch.float32):
-        raise _lib.LkgdHipError("latents must be a GPU fp16/fp32 tensor")
+    _req_latents(latents)
     if latents.dim() == 5 and latents.shape[0] == 1:
         latents = latents[0]
-    if latents.dim() != 4 or latents.shape[1] != 4 or not latents.is_contiguous():
+    if latents.dim() != 4 or latents.shape[1] != 4:
         raise _lib.LkgdHipError(f"latents must be contiguous [T,4,H,W] (or [1,T,4,H,W]), got {tuple(latents.shape)}")
     T, _, H, W = latents.shape
     if not (0 <= f0 and 0 < L and f0 + L <= T):

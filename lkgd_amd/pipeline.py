@@ -314,8 +314,6 @@ class StableVideoDiffusionPipeline:
             raise ValueError(f"direct_fusion pairs clip b with clip b + B/2: the clip count must be even, got {B}")
         latents = latents.to(dev).contiguous()
         image_latents = image_latents.to(device=dev, dtype=torch.float16).contiguous()
-        sch.set_timesteps(num_inference_steps, device=None)
-        self._num_timesteps = len(sch.timesteps_host)
         guidance = torch.linspace(min_guidance_scale, max_guidance_scale, F, dtype=torch.float32)
         self._guidance_scale = _append_dims(guidance.unsqueeze(0).repeat(B, 1), latents.ndim)
         guidance_dev = guidance.to(dev)
@@ -339,14 +337,9 @@ class StableVideoDiffusionPipeline:
             if controlnet_condition.shape[0] != cfg * B:
                 raise ValueError("controlnet_condition must carry cfg*batch entries")
             ctrl = controlnet_condition.to(device=dev, dtype=torch.float16).contiguous()
-        fwd = self._graphed_forward(cfg * B, F, H, W, enc, ids) if (self.use_hip_graph and ctrl is None) else None
-        # The step's forward is shape-static over the Euler steps: the first step runs for real and is RECORDED as a flat list of
-        # C-ABI launches (lkgd_amd/replay.py), the other 24 replay it between in-place updates of its inputs (token buffer,
-        # timestep) - bit-identical, and the Python module walk (64 ms of host time per forward against 90 ms of device time)
-        # stops leaving the queue dry at the 18x32 / 9x16 levels: +1.1 % frames/s on one GPU (profiles/r05_bench_pair_replay.txt).
-        # LKGD_NO_REPLAY=1 walks the modules every step.
-        use_replay = fwd is None and self.use_replay
-        if use_replay:
+        graph = self._graphed_forward(cfg * B, F, H, W, enc, ids) if (self.use_hip_graph and ctrl is None) else None
+        forward_static = None
+        if graph is None:
             tok_buf = torch.empty(cfg * B * F * H * W, 8, dtype=torch.float16, device=dev)
             t_dev = torch.zeros(cfg * B, dtype=torch.float32, device=dev)
             enc_r, ids_r = enc.to(torch.float16).contiguous(), ids.to(torch.float32).contiguous()
@@ -354,58 +347,59 @@ class StableVideoDiffusionPipeline:
                 self.controlnet.prepare()
                 self.controlnet._cond_tokens(ctrl, cfg * B, F, H, W)       # once per clip, outside the recorded forward
 
-            def forward_static():
+            def forward_static():      # residuals stay channels-last token matrices between the two models
                 down = mid = None
                 if ctrl is not None:
                     down, mid, _ = self.controlnet.forward_tokens(tok_buf, cfg * B, F, H, W, t_dev, enc_r, ids_r, ctrl,
                                                                   ctrl_scale)
                 return unet.forward_tokens(tok_buf, cfg * B, F, H, W, t_dev, enc_r, ids_r, down, mid)[0]
-        timers = _trace.StepTimers() if _trace.STEP_TIMERS else None      # LKGD_STEP_TIMERS=1: device ms per Euler step
-        self.last_step_timers = timers
-        recorded = None
-        try:
-            for i, t in enumerate(sch.timesteps_host):
-                if i < start_step:          # trans_controlnet :571-574: skipped steps run nothing, not even the callback
-                    continue
-                sigma, sigma_next = sch.sigmas_host[i], sch.sigmas_host[i + 1]
-                _trace.push(f"euler_step_{i}")                                  # roctx range (LKGD_ROCTX=1), else a no-op
-                t_ev = timers.start() if timers is not None else None
-                if fwd is not None:
-                    ops.prepare_unet_input(latents, image_latents, cfg, sigma, out=fwd.tok)
-                    noise_tok = fwd.run(t)
-                elif use_replay:
+        # The step's forward is shape-static over the Euler steps: the first step runs for real and is RECORDED as a flat list of
+        # C-ABI launches (lkgd_amd/replay.py), the other 24 replay it between in-place updates of its inputs (token buffer,
+        # timestep) - bit-identical, and the Python module walk (64 ms of host time per forward against 90 ms of device time)
+        # stops leaving the queue dry at the 18x32 / 9x16 levels: +1.1 % frames/s on one GPU (profiles/r05_bench_pair_replay.txt).
+        # LKGD_NO_REPLAY=1 walks the modules every step, on the same static inputs.
+        with _replay.Replayed(self._arenas, dev, lambda: (cfg * B, F, H, W, ctrl is not None, id(unet._pk)), forward_static,
+                              enabled=self.use_replay) as forward:
+            def step(latents, t, sigma, sigma_next):
+                if graph is not None:
+                    ops.prepare_unet_input(latents, image_latents, cfg, sigma, out=graph.tok)
+                    noise_tok = graph.run(t)
+                else:
                     ops.prepare_unet_input(latents, image_latents, cfg, sigma, out=tok_buf)
                     t_dev.fill_(float(t))
-                    if recorded is not None:
-                        noise_tok = recorded.run(ops.GEMM_EVENTS)
-                    else:
-                        with _replay.record(self._arenas.take(dev, (cfg * B, F, H, W, ctrl is not None, id(unet._pk)))) as recorded:
-                            recorded.result = forward_static()
-                        noise_tok = recorded.result
-                else:
-                    tok = ops.prepare_unet_input(latents, image_latents, cfg, sigma)
-                    down = mid = None
-                    if ctrl is not None:      # residuals stay channels-last token matrices between the two models
-                        down, mid, _ = self.controlnet.forward_tokens(tok, cfg * B, F, H, W, t, enc, ids, ctrl,
-                                                                      ctrl_scale)
-                    noise_tok, _ = unet.forward_tokens(tok, cfg * B, F, H, W, t, enc, ids, down, mid)
+                    noise_tok = forward(ops.GEMM_EVENTS)
                 if direct_fusion:
                     ops.cfg_fusion_euler_step(noise_tok, latents, guidance_dev, fusion_w, cfg, sigma, sigma_next,
                                               v_prediction=vpred)
                 else:
                     ops.cfg_euler_step(noise_tok, latents, guidance_dev, cfg, sigma, sigma_next, v_prediction=vpred)
-                if timers is not None:
-                    timers.stop(t_ev)
-                _trace.pop()
-                if callback_on_step_end is not None:
-                    kw = {k: {"latents": latents}[k] for k in callback_on_step_end_tensor_inputs}
-                    out = callback_on_step_end(self, i, t, kw)
-                    latents = out.pop("latents", latents) if isinstance(out, dict) else latents
-        finally:
-            # the recorded forward's activations go back to the allocator whatever ended the loop (a callback's exception, a
-            # launch error, KeyboardInterrupt): the plan and its recording stand-in reference each other
-            if recorded is not None:
-                recorded.release()
+            return self._euler_loop(latents, step, num_inference_steps, start_step, callback_on_step_end,
+                                    callback_on_step_end_tensor_inputs)
+
+    def _euler_loop(self, latents: torch.Tensor, step: Callable, num_inference_steps: int, start_step: int,
+                    callback_on_step_end: Optional[Callable], callback_on_step_end_tensor_inputs: List[str]) -> torch.Tensor:
+        """the skeleton of every denoising loop here (reference :545-640): ``step(latents, t, sigma, sigma_next)`` takes one Euler
+        step in place; around it the timestep table, the ``start_step`` skip (trans_controlnet :571-574: skipped steps run
+        nothing, not even the callback), the roctx range (LKGD_ROCTX=1), the device timers (LKGD_STEP_TIMERS=1: ms per Euler
+        step) and the callback, whose returned ``latents`` replace the loop's"""
+        sch = self.scheduler
+        sch.set_timesteps(num_inference_steps, device=None)
+        self._num_timesteps = len(sch.timesteps_host)
+        timers = _trace.StepTimers() if _trace.STEP_TIMERS else None
+        self.last_step_timers = timers
+        for i, t in enumerate(sch.timesteps_host):
+            if i < start_step:
+                continue
+            _trace.push(f"euler_step_{i}")
+            t_ev = timers.start() if timers is not None else None
+            step(latents, t, sch.sigmas_host[i], sch.sigmas_host[i + 1])
+            if timers is not None:
+                timers.stop(t_ev)
+            _trace.pop()
+            if callback_on_step_end is not None:
+                kw = {k: {"latents": latents}[k] for k in callback_on_step_end_tensor_inputs}
+                out = callback_on_step_end(self, i, t, kw)
+                latents = out.pop("latents", latents) if isinstance(out, dict) else latents
         sch._step_index = num_inference_steps
         if timers is not None:
             timers.finish()
@@ -676,8 +670,6 @@ class StableVideoDiffusionPipelineSmooth(StableVideoDiffusionPipeline):
         if 2 * cfg % ids.shape[0]:
             raise ValueError(f"added_time_ids must be built for one clip (1, 2 or 4 equal rows), got {ids.shape[0]} rows")
         ids = ids.repeat(2 * cfg // ids.shape[0], 1).contiguous()           # :539 and the CFG duplicate of _get_add_time_ids
-        sch.set_timesteps(num_inference_steps, device=None)
-        self._num_timesteps = len(sch.timesteps_host)
         self._guidance_scale = max_guidance_scale
         # :581: torch.linspace(min, max, len(chunk)) per window - one device table for the call, row L-1 holds the L values
         gtab = torch.zeros(nf, nf, dtype=torch.float32)
@@ -691,39 +683,23 @@ class StableVideoDiffusionPipelineSmooth(StableVideoDiffusionPipeline):
         tok_buf = torch.empty(2 * cfg * nf * HW, 8, dtype=torch.float16, device=dev)
         t_dev = torch.zeros(2 * cfg, dtype=torch.float32, device=dev)
         enc = torch.zeros(2 * cfg, emb.shape[1], emb.shape[2], dtype=torch.float16, device=dev)
-        recorded = None
-        try:
-            for i, t in enumerate(sch.timesteps_host):
-                if i < start_step:
-                    continue
-                sigma, sigma_next = sch.sigmas_host[i], sch.sigmas_host[i + 1]
-                _trace.push(f"euler_step_{i}")
+        with _replay.Replayed(self._arenas, dev, lambda: ("smooth", 2 * cfg, nf, H, W, id(unet._pk)),
+                              lambda: unet.forward_tokens(tok_buf, 2 * cfg, nf, H, W, t_dev, enc, ids)[0],
+                              enabled=self.use_replay) as full_window:
+            def step(latents, t, sigma, sigma_next):
                 for f0, n in smooth_chunks(T, nf):
                     tok = ops.window_prepare_input(latents, image_latents, f0, n, cfg, sigma, out=tok_buf)
                     enc[2].copy_(emb[f0])
                     enc[3].copy_(emb[f0 + n - 1])
-                    if self.use_replay and n == nf:
+                    if n == nf:
                         t_dev.fill_(float(t))
-                        if recorded is not None:
-                            noise_tok = recorded.run(ops.GEMM_EVENTS)
-                        else:
-                            with _replay.record(self._arenas.take(dev, ("smooth", 2 * cfg, nf, H, W, id(unet._pk)))) as recorded:
-                                recorded.result = unet.forward_tokens(tok, 2 * cfg, nf, H, W, t_dev, enc, ids)[0]
-                            noise_tok = recorded.result
+                        noise_tok = full_window(ops.GEMM_EVENTS)
                     else:
                         noise_tok, _ = unet.forward_tokens(tok, 2 * cfg, n, H, W, t, enc, ids)
                     ops.window_cfg_euler_step(noise_tok, latents, gtab[n - 1, :n], f0, n, cfg, sigma, sigma_next,
                                               v_prediction=vpred)
-                _trace.pop()
-                if callback_on_step_end is not None:
-                    kw = {k: {"latents": latents}[k] for k in callback_on_step_end_tensor_inputs}
-                    out = callback_on_step_end(self, i, t, kw)
-                    latents = out.pop("latents", latents) if isinstance(out, dict) else latents
-        finally:
-            if recorded is not None:
-                recorded.release()
-        sch._step_index = num_inference_steps
-        return latents
+            return self._euler_loop(latents, step, num_inference_steps, start_step, callback_on_step_end,
+                                    callback_on_step_end_tensor_inputs)
 
     @torch.no_grad()
     def __call__(self, image, height: int = 576, width: int = 1024, num_frames: Optional[int] = None,
@@ -784,14 +760,6 @@ class StableVideoDiffusionPipelineControlNetFlow(StableVideoDiffusionPipelineCon
 
     def _condition(self, controlnet_condition):
         return None
-
-    def release_arena(self) -> None:
-        """return the recorded forwards' working-set pool(s) to the driver (they are kept between calls otherwise)"""
-        self._arenas.clear()
-
-    def arena_reserved_bytes(self) -> int:
-        """device memory the recorded forward's private pool holds (the plan's working set)"""
-        return self._arenas.reserved_bytes()
 
     def _latents_for_decode(self, latents: torch.Tensor) -> torch.Tensor:
         from .optical_flow import optical_flow_latent_unnormalize

@@ -366,3 +366,34 @@ class record:
         finally:
             ops.set_plan(None)
         return False
+
+
+class Replayed:
+    """a shape-static forward that a loop calls once per step: ``with Replayed(arenas, device, key, forward) as f`` and then
+    ``f(gemm_events)`` per step.  The first call runs ``forward()`` for real and records it from ``arenas.take(device, key())``
+    (``key`` is called then: what it names may be built by an earlier eager forward); later calls replay the plan.  Leaving the
+    block releases the plan whatever ended it - a callback's exception, a launch error, KeyboardInterrupt: the plan and its
+    recording stand-in reference each other, and its arena stays busy until then.  ``enabled=False``: every call just
+    runs ``forward()`` and no arena is taken."""
+
+    def __init__(self, arenas: ArenaSet, device, key: Callable[[], tuple], forward: Callable[[], object], enabled: bool = True):
+        self.arenas, self.device, self.key, self.forward, self.enabled = arenas, device, key, forward, enabled
+        self.plan: Optional[Plan] = None
+
+    def __call__(self, gemm_events=None):
+        if not self.enabled:
+            return self.forward()
+        if self.plan is not None:
+            return self.plan.run(gemm_events)
+        with record(self.arenas.take(self.device, self.key())) as self.plan:
+            self.plan.result = self.forward()
+        return self.plan.result
+
+    def __enter__(self) -> "Replayed":
+        return self
+
+    def __exit__(self, *exc):
+        if self.plan is not None:
+            self.plan.release()
+            self.plan = None
+        return False

@@ -577,3 +577,50 @@ def test_temporal_path_table(monkeypatch):
     monkeypatch.setattr(ops, "TBLOCK", False)
     for row, want in TEMPORAL_PATHS_NO_TBLOCK:
         assert got(row) == want, row
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# loop glue: the wrappers' latents checker and the record-then-replay helper, without a GPU
+
+def test_loop_glue_wrappers_refuse_cpu_latents_before_any_library_call(monkeypatch):
+    """the five loop-glue wrappers hand the kernels the bare pointer of ``latents``: a CPU tensor is refused by name before the
+    library (or a plan's recording stand-in) is reached"""
+    from lkgd_amd import ops
+    from lkgd_amd._lib import LkgdHipError
+
+    def reached():
+        raise AssertionError("the library was reached")
+    monkeypatch.setattr(ops, "_L", reached)
+    B, F, H, W, T = 2, 3, 2, 2, 5
+    h = lambda *s: torch.zeros(*s, dtype=torch.float16)       # noqa: E731
+    lat, win = h(B, F, 4, H, W), h(T, 4, H, W)
+    gs = torch.ones(F)
+    calls = {
+        "prepare_unet_input": lambda x: ops.prepare_unet_input(x, h(2 * B, F, 4, H, W), 2, 1.0),
+        "cfg_euler_step": lambda x: ops.cfg_euler_step(h(2 * B * F * H * W, 4), x, gs, 2, 1.0, 0.5),
+        "cfg_fusion_euler_step": lambda x: ops.cfg_fusion_euler_step(h(2 * B * F * H * W, 4), x, gs, gs, 2, 1.0, 0.5),
+        "window_prepare_input": lambda x: ops.window_prepare_input(x, h(T, 4, H, W), 1, F, 2, 1.0),
+        "window_cfg_euler_step": lambda x: ops.window_cfg_euler_step(h(4 * F * H * W, 4), x, gs, 1, F, 2, 1.0, 0.5),
+    }
+    for name, call in calls.items():
+        for x in ((win if name.startswith("window") else lat), (win if name.startswith("window") else lat).double()):
+            with pytest.raises(LkgdHipError, match="latents"):
+                call(x)
+
+
+def test_replayed_disabled_runs_the_forward_every_call():
+    """replay.Replayed(enabled=False): every call is the forward itself, and no arena is taken (so no GPU is needed)"""
+    from lkgd_amd import ops, replay
+
+    class NoArenas:
+        def take(self, *a, **k):
+            raise AssertionError("an arena was taken")
+    runs = []
+
+    def forward():
+        runs.append(len(runs))
+        return runs[-1]
+    with replay.Replayed(NoArenas(), "cuda:0", lambda: ("key",), forward, enabled=False) as f:
+        assert [f(None), f([]), f()] == [0, 1, 2]
+        assert f.plan is None and ops.PLAN is None
+    assert runs == [0, 1, 2] and f.plan is None

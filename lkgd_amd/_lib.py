@@ -130,6 +130,16 @@ DIT_SYMBOLS = {
     "lkgd_qk_norm_rope": (_i32, [_vp, _i32, _vp, _i32, _i64, _i32, _vp, _vp, _vp, _vp, _f32, _vp, _vp, _i32, _i32, _i32, _vp]),
 }
 
+#: every symbol include/lkgd_hip_dit_loop.h declares (the latent-knowledge fuse of the DiT's text tokens and the glue of its sampling
+#: loop), bound on the same library object; tests/test_cogvideox_loop_cpu.py pins header, table and library to one another,
+#: tests/test_cogvideox_loop_gpu.py the footprint cases
+DIT_LOOP_SYMBOLS = {
+    "lkgd_lk_fuse_tokens": (_i32, [_vp, _i32, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _i32, _vp]),
+    "lkgd_dit_patch_rows": (_i32, [_vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _vp]),
+    "lkgd_dit_cfg_ddim_step": (_i32, [_vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _f32, _f32, _f32, _f32,
+                                      _vp]),
+}
+
 #: include/lkgd_hip_debug.h: A/B and test knobs, per host thread; bound on the same library object, not part of the product interface
 DEBUG_SYMBOLS = {
     "lkgd_debug_set_wide_tile_n": (None, [_i32]),
@@ -164,7 +174,7 @@ def lib() -> C.CDLL:
             l = C.CDLL(LIB_PATH)
         except OSError as e:
             raise LkgdHipError(f"cannot load {LIB_PATH}: {e}") from e
-        for table in (SYMBOLS, WINDOW_SYMBOLS, DIT_SYMBOLS, DEBUG_SYMBOLS):
+        for table in (SYMBOLS, WINDOW_SYMBOLS, DIT_SYMBOLS, DIT_LOOP_SYMBOLS, DEBUG_SYMBOLS):
             for name, (res, args) in table.items():
                 fn = getattr(l, name)       # AttributeError here = header / library mismatch
                 fn.restype, fn.argtypes = res, args

@@ -20,14 +20,18 @@ MI355X design - the UNet's kernels, one joint token buffer:
 * attention: three projections (bias), per-head LayerNorm of q and k as the LayerNorm kernel over [tokens * heads, 64] rows in
   place, then the head_dim-64 flash kernel over the joint sequence (S = 226 + 17 550, ragged last tile);
 * feed-forward: GEMM + ``lkgd_gelu_tanh`` + GEMM;
-* the latent-knowledge fuse acts on the TEXT embeddings and is step-invariant: evaluated once per clip in fp32 (as the SVD
-  fuse, lkgd_amd/lk_fuse.py); the 3-D sin-cos position table is added in the patch-embedding GEMM's epilogue (row-indexed bias);
+* the latent-knowledge fuse acts on the TEXT embeddings and is step-invariant: one launch per clip, fp32
+  (``lkgd_lk_fuse_tokens``, include/lkgd_hip_dit_loop.h; lkgd_amd/lk_fuse.py); the 3-D sin-cos position table is added in the
+  patch-embedding GEMM's epilogue (row-indexed bias);
 * rotary models (CogVideoX-5B-I2V: ``use_rotary_positional_embeddings``, 48 heads, 3072 channels): no sin-cos table; the
   learned joint position table, when the checkpoint has one, rides the same row-indexed bias of BOTH embedding GEMMs (text
   rows included); the per-head q / k norms and the rotation of the video rows are one launch per layer
   (``lkgd_qk_norm_rope``, include/lkgd_hip_dit.h) over tables built once per clip (``rotary_tables``);
-* patch unfold / un-patchify at the API edge, CFG combine and the DDIM update on the 1-M-element latents are tensor plumbing
-  (PyTorch-ROCm elementwise ops, < 0.1 % of a step).
+* the sampling loop's glue is two launches per step (include/lkgd_hip_dit_loop.h): ``lkgd_dit_patch_rows`` writes the patch rows
+  of latents | image latents ONCE for both CFG entries (no duplicated batch, no channel concat), ``forward_rows`` runs the DiT on
+  them, ``lkgd_dit_cfg_ddim_step`` takes proj_out's token rows through the CFG combine and the DDIM update into the latents in
+  place.  ``forward_tokens`` / ``forward`` keep the [B, F, C, H, W] interface: their patch unfold / un-patchify are torch permutes
+  (data movement at the API edge).
 """
 from __future__ import annotations
 
@@ -39,11 +43,10 @@ from typing import Optional
 import numpy as np
 import torch
 import torch.nn as nn
-import torch.nn.functional as F
 
 from . import ops
 from ._lib import LkgdHipError
-from .lk_fuse import hamilton
+from .lk_fuse import lk_fuse_tokens, pack_lk_tokens
 from .packing import pack_linear
 from .unet import QuaternionLinearAutograd, TimestepEmbedding
 
@@ -363,45 +366,44 @@ class CogVideoXTransformer3DModel(nn.Module):
     # ---- latent-knowledge fuse on the text embeddings (:519-582), once per clip -----------------------------------
     @torch.no_grad()
     def fused_text(self, encoder_hidden_states, domain_features, flow_features) -> torch.Tensor:
-        dev = self.device
-        e = encoder_hidden_states.to(device=dev, dtype=torch.float32)
-
-        def dw(conv, x, per):       # Conv1d(k=1, groups=256) on the channel axis: `per` inputs per group
-            w = conv.weight.detach().float().reshape(256, per)
-            return (x.reshape(*x.shape[:-1], 256, per) * w).sum(-1)
-
-        def qlin(q, x):
-            return x @ hamilton(q) + q.bias.detach().float()
-        low = dw(self.quaternion_lora_lconv, e, 16)
-        d = F.interpolate(domain_features.to(device=dev, dtype=torch.float32), size=1024, mode="linear")
-        f = F.interpolate(flow_features.to(device=dev, dtype=torch.float32), size=1024, mode="linear")
-        low_d = dw(self.quaternion_lora_dconv, d, 4).expand_as(low)
-        low_f = dw(self.quaternion_lora_fconv, f, 4).expand_as(low)
-        ctx = self.quaternion_lora_texts.detach().float().expand_as(low)
-        spatial = qlin(self.quaternion_lora_fuse, torch.cat([low, low_d, low_f, ctx], -1))
-        hf, df, ff = (torch.fft.rfft(t.contiguous(), dim=-1) for t in (low, low_d, low_f))
-        mags = [hf.abs(), df.abs(), ff.abs(), self.quaternion_lora_texts_fft_mag.detach().float().expand_as(hf.real)]
-        phas = [hf.angle(), df.angle(), ff.angle(), self.quaternion_lora_texts_fft_pha.detach().float().expand_as(hf.real)]
-        mag = qlin(self.quaternion_lora_fuse_fft_mag, torch.cat([m[..., :-1] for m in mags], -1))
-        pha = qlin(self.quaternion_lora_fuse_fft_pha, torch.cat([p[..., :-1] for p in phas], -1))
-        l0m, l0p = self.quaternion_lora_fuse_fft_mag0, self.quaternion_lora_fuse_fft_pha0
-        mag0 = torch.cat([m[..., -1:] for m in mags], -1) @ l0m.weight.detach().float().T + l0m.bias.detach().float()
-        pha0 = torch.cat([p[..., -1:] for p in phas], -1) @ l0p.weight.detach().float().T + l0p.bias.detach().float()
-        spec = torch.cat([torch.complex(mag * torch.cos(pha), mag * torch.sin(pha)),
-                          torch.complex(mag0 * torch.cos(pha0), mag0 * torch.sin(pha0))], -1)
-        freq = torch.fft.irfft(spec, dim=-1)
-        sf = self.quaternion_lora_fuse_sf
-        x = torch.cat([spatial, freq], -1)
-        x = F.leaky_relu(x @ sf[0].weight.detach().float().T + sf[0].bias.detach().float(), 0.1)
-        x = x @ sf[2].weight.detach().float().T + sf[2].bias.detach().float()
-        return x.to(torch.float16)
+        """[B, L, 4096] prompt embeddings, [1 or B, 1, 1000] domain / flow logits -> fp16 [B, L, 4096]: one launch of
+        ``lkgd_lk_fuse_tokens`` over operands packed once per weight version"""
+        if self.device.type != "cuda":
+            raise LkgdHipError("the latent-knowledge fuse runs on the GPU (lkgd_amd has no CPU path)")
+        if self.config.text_embed_dim != 4096:
+            raise LkgdHipError(f"the latent-knowledge fuse is built for text_embed_dim 4096, got {self.config.text_embed_dim}")
+        if encoder_hidden_states.dim() != 3 or encoder_hidden_states.shape[2] != 4096:
+            raise LkgdHipError(f"fused_text: encoder_hidden_states must be [batch, tokens, 4096], got "
+                               f"{tuple(encoder_hidden_states.shape)}")
+        self.prepare()
+        pk = self._pk
+        if getattr(pk, "lk_tokens", None) is None:
+            pk.lk_tokens = pack_lk_tokens(self)
+        return lk_fuse_tokens(pk.lk_tokens, encoder_hidden_states, domain_features, flow_features)
 
     # ---- the per-step forward ------------------------------------------------------------------------------------
     @torch.no_grad()
     def forward_tokens(self, hidden_states: torch.Tensor, fused_text: torch.Tensor, timestep, shard=None,
                        image_rotary_emb=None) -> torch.Tensor:
         """hidden_states [B, F, C, h, w]; fused_text [B, L, 4096] fp16 (``fused_text`` of the prompt embeddings) ->
-        [B, F, out_channels, h, w] fp16.  ``image_rotary_emb`` = (cos, sin) fp32 [F h w tokens, 64] (``rotary_tables``): every
+        [B, F, out_channels, h, w] fp16: patch unfold, ``forward_rows``, un-patchify (two torch permutes at the API edge)."""
+        B, Fr, C_, H, W = hidden_states.shape
+        p = self.config.patch_size
+        h, w = H // p, W // p
+        xh = hidden_states.to(device=self.device, dtype=torch.float16)
+        patches = xh.reshape(B, Fr, C_, h, p, w, p).permute(0, 1, 3, 5, 2, 4, 6).reshape(B * Fr * h * w, C_ * p * p).contiguous()
+        out_tok = self.forward_rows(patches, (Fr, h, w), fused_text, timestep, shard=shard, image_rotary_emb=image_rotary_emb)
+        out = out_tok.reshape(B, Fr, h, w, -1, p, p).permute(0, 1, 4, 2, 5, 3, 6).flatten(5, 6).flatten(3, 4)
+        return out.contiguous()
+
+    @torch.no_grad()
+    def forward_rows(self, patch_rows: torch.Tensor, grid, fused_text: torch.Tensor, timestep, shard=None,
+                     image_rotary_emb=None) -> torch.Tensor:
+        """the row-level core.  ``patch_rows`` fp16 [Bv * Tv, in_channels * p * p] (``ops.dit_patch_rows``; column (c, py, px)),
+        ``grid`` = (F, h, w) tokens, Tv = F h w; fused_text [B, L, 4096] fp16.  Bv divides B: batch entry b embeds the rows of
+        entry b % Bv, so ONE copy of the rows (Bv = 1) serves both CFG entries, as ``torch.cat([latents] * 2)`` did.  Returns
+        proj_out's token rows [B * Tv, out_channels * p * p] fp16 (before the un-patchify).
+        ``image_rotary_emb`` = (cos, sin) fp32 [F h w tokens, 64] (``rotary_tables``): every
         layer's per-head q / k norms and the rotation of their video rows are then ONE launch of ``lkgd_qk_norm_rope``; None =
         the two LayerNorm launches of the 2B path.  ``shard`` (lkgd_amd.dist_run.ShardInfo): this rank holds ONE batch entry (its CFG
         half) and the latent frames [f0, f0 + F) of the clip; everything is row-local except the attention, whose local
@@ -409,12 +411,19 @@ class CogVideoXTransformer3DModel(nn.Module):
         over the frame group every layer."""
         self.prepare()
         pk, cfg, dev = self._pk, self.config, self.device
-        B, Fr, C_, H, W = hidden_states.shape
+        B = fused_text.shape[0]
+        Fr, h, w = grid
         if shard is not None and B != 1:
             raise LkgdHipError("frame sharding of the DiT supports one batch entry per rank")
-        p, D = cfg.patch_size, self.inner_dim
-        h, w = H // p, W // p
+        D = self.inner_dim
         Tt, Tv = fused_text.shape[1], Fr * h * w
+        Kp = pk.w_pe.shape[1]
+        if patch_rows.dim() != 2 or patch_rows.dtype != torch.float16 or patch_rows.device != dev or patch_rows.shape[1] != Kp \
+                or patch_rows.shape[0] % Tv or patch_rows.shape[0] == 0 or B % (patch_rows.shape[0] // Tv) \
+                or patch_rows.stride(1) != 1:
+            raise LkgdHipError(f"forward_rows: patch_rows must be GPU fp16 [Bv * {Tv}, {Kp}] with Bv a divisor of the batch {B}, got "
+                               f"{tuple(patch_rows.shape)} {patch_rows.dtype}")
+        Bv = patch_rows.shape[0] // Tv
         L = Tt + Tv
         heads = cfg.num_attention_heads
         rotary = cfg.use_rotary_positional_embeddings
@@ -451,8 +460,6 @@ class CogVideoXTransformer3DModel(nn.Module):
         # patch embedding into the joint buffer: text rows, then video rows (+ position table in the epilogue)
         X = torch.empty(B * L, D, dtype=torch.float16, device=dev)
         txt = fused_text.to(device=dev, dtype=torch.float16).reshape(B * Tt, -1).contiguous()
-        xh = hidden_states.to(device=dev, dtype=torch.float16)
-        patches = xh.reshape(B, Fr, C_, h, p, w, p).permute(0, 1, 3, 5, 2, 4, 6).reshape(B, Tv, C_ * p * p).contiguous()
         pos_txt = None
         if not rotary:
             pos = self._pos_table(F_all, h, w)[v0:v0 + Tv]
@@ -468,7 +475,8 @@ class CogVideoXTransformer3DModel(nn.Module):
         rb_v = dict(rowbias=pos, rowmap=(1, 1, 1, 1 << 30)) if pos is not None else {}
         for b in range(B):
             ops.gemm(txt[b * Tt:(b + 1) * Tt], pk.w_tx, X[b * L:b * L + Tt], M=Tt, N=D, K=txt.shape[1], bias=pk.b_tx, **rb_t)
-            ops.gemm(patches[b], pk.w_pe, X[b * L + Tt:(b + 1) * L], M=Tv, N=D, K=C_ * p * p, bias=pk.b_pe, **rb_v)
+            ops.gemm(patch_rows[(b % Bv) * Tv:(b % Bv + 1) * Tv], pk.w_pe, X[b * L + Tt:(b + 1) * L], M=Tv, N=D, K=Kp, bias=pk.b_pe,
+                     **rb_v)
         T = B * L
         eps = cfg.norm_eps
 
@@ -507,7 +515,7 @@ class CogVideoXTransformer3DModel(nn.Module):
             ops.gelu_tanh_(hdn)
             ops.gemm(hdn, bp.f2[0], o, M=T, N=D, K=4 * D, bias=bp.f2[1])
             X = ops.gated_add(o, gates[i, 1].reshape(2 * B, D), X, L, Tt)
-        # norm_final on the video stream, norm_out (adaLN), proj_out, un-patchify
+        # norm_final on the video stream, norm_out (adaLN), proj_out
         po = pk.w_po.shape[0]
         out_tok = torch.empty(B, Tv, po, dtype=torch.float16, device=dev)
         for b in range(B):
@@ -517,8 +525,7 @@ class CogVideoXTransformer3DModel(nn.Module):
             bb = (pk.out_b * (1 + fin[b, 1]) + fin[b, 0]).contiguous()
             y = ops.layernorm(y, gg, bb, eps)
             ops.gemm(y, pk.w_po, out_tok[b], M=Tv, N=po, K=D, bias=pk.b_po)
-        out = out_tok.reshape(B, Fr, h, w, -1, p, p).permute(0, 1, 4, 2, 5, 3, 6).flatten(5, 6).flatten(3, 4)
-        return out.contiguous()
+        return out_tok.view(B * Tv, po)
 
     @torch.no_grad()
     def forward(self, hidden_states, encoder_hidden_states, timestep, domain_features, flow_features, timestep_cond=None,
@@ -586,29 +593,31 @@ def denoise(transformer: CogVideoXTransformer3DModel, scheduler: CogVideoXDDIMSc
             use_dynamic_cfg: bool = True, callback=None, image_rotary_emb=None) -> torch.Tensor:
     """the loop of pipeline_cogvideox_image2video.py:829-885 (the rotary tables are built once per clip when the config asks for
     them and none are given, :819-823).  latents / image_latents [B, F, C, h, w]; prompt_embeds
-    [2B, L, 4096] (negative first) when guidance_scale > 1.  The latents stay fp32 between steps (``noise_pred.float()`` :863,
-    the reference casts them back to the prompt dtype :881 - reproduced)."""
+    [2B, L, 4096] (negative first) when guidance_scale > 1.  The update runs in fp32 (``noise_pred.float()`` :863) and the
+    latents are cast back to the prompt dtype, fp16, after every step (:881 - reproduced).  Per step: ``lkgd_dit_patch_rows`` ->
+    ``forward_rows`` -> ``lkgd_dit_cfg_ddim_step`` (include/lkgd_hip_dit_loop.h); ``scheduler`` supplies ``coefficients(t)``."""
     dev = transformer.device
     scheduler.set_timesteps(num_inference_steps)
     cfg = guidance_scale > 1.0
     text = transformer.fused_text(prompt_embeds, domain_features, flow_features)          # step-invariant: once per clip
-    latents = latents.to(device=dev, dtype=torch.float16)
-    img = image_latents.to(device=dev, dtype=torch.float16)
-    img2 = torch.cat([img] * 2) if cfg else img
+    # the loop's own copy: the step kernel updates it in place
+    latents = latents.to(device=dev, dtype=torch.float16).clone(memory_format=torch.contiguous_format)
+    img = image_latents.to(device=dev, dtype=torch.float16).contiguous()
     tc = transformer.config
+    p = tc.patch_size
+    grid = (latents.shape[1], latents.shape[3] // p, latents.shape[4] // p)
     if tc.use_rotary_positional_embeddings:
         if image_rotary_emb is None:
-            image_rotary_emb = rotary_tables(tc, latents.shape[1], latents.shape[3] // tc.patch_size, latents.shape[4] // tc.patch_size)
+            image_rotary_emb = rotary_tables(tc, *grid)
         image_rotary_emb = tuple(t.to(device=dev, dtype=torch.float32).contiguous() for t in image_rotary_emb)
+    rows = None
     for i, t in enumerate(scheduler.timesteps.tolist()):
-        x = torch.cat([latents] * 2) if cfg else latents
-        x = torch.cat([x, img2], dim=2)
-        noise = transformer.forward_tokens(x, text, float(t), image_rotary_emb=image_rotary_emb).float()
+        # torch.cat([latents] * 2), the channel concat and the patch unfold: ONE set of rows, embedded for every CFG entry
+        rows = ops.dit_patch_rows(latents, img, p, out=rows)
+        noise_rows = transformer.forward_rows(rows, grid, text, float(t), image_rotary_emb=image_rotary_emb)
         g = dynamic_guidance(guidance_scale, num_inference_steps, t) if use_dynamic_cfg else guidance_scale
-        if cfg:
-            u, c = noise.chunk(2)
-            noise = u + g * (c - u)
-        latents = scheduler.step(noise, t, latents.float())[0].to(torch.float16)
+        # noise_pred.float(), the CFG combine, scheduler.step and the cast back: one launch, in place
+        ops.dit_cfg_ddim_step(noise_rows, latents, p, 2 if cfg else 1, g, *scheduler.coefficients(int(t)))
         if callback is not None:
-            callback(i, t, latents)
+            callback(i, t, latents.clone())         # a tensor of the callback's own, as the out-of-place loop handed out
     return latents

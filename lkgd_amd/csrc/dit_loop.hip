@@ -1,0 +1,137 @@
+// Loop glue of the CogVideoX DiT sampling loop (include/lkgd_hip_dit_loop.h; pipeline_cogvideox_image2video.py:829-885): the
+// patch rows of the embedding GEMM straight from the latents and the image latents, and CFG combine + DDIM update straight from
+// proj_out's token rows into the latents.  Both HBM/latency-bound.  A token row holds p x p = 4 pixels of every channel, channel
+// major: one thread moves one 16-byte piece of a row = 2 channels x (py, px).  Lanes run along x, so the px pairs of neighbouring
+// patches are one contiguous run of a latent plane's line; the grid rule is prepare_input_kernel's (elementwise.hip).
+#include <type_traits>
+
+#include "common.h"
+#include "../../include/lkgd_hip_dit_loop.h"
+
+static unsigned dit_grid_for(long long work_items, int per_block) {
+  long long g = (work_items + per_block - 1) / per_block;
+  if (g > 256 * 16) g = 256 * 16;
+  if (g < 1) g = 1;
+  return (unsigned)g;
+}
+
+// piece i -> (x, q, y, bf): x fastest, then the piece q of the row, then the patch line y, then b * F + f
+struct dit_piece { int x, q, y; long long bf; };
+__device__ __forceinline__ dit_piece dit_piece_of(long long i, int w, int h, int pieces) {
+  dit_piece d;
+  d.x = (int)(i % w);
+  const long long t1 = i / w;
+  d.q = (int)(t1 % pieces);
+  const long long t2 = t1 / pieces;
+  d.y = (int)(t2 % h);
+  d.bf = t2 / h;
+  return d;
+}
+
+template <typename T>
+__device__ __forceinline__ void dit_gather(const T* __restrict__ planes, int H, int W, int y, int x, half8_t& o) {
+#pragma unroll
+  for (int cc = 0; cc < 2; ++cc)
+#pragma unroll
+    for (int py = 0; py < 2; ++py) {
+      const T* src = planes + ((long long)cc * H + 2 * y + py) * W + 2 * x;
+      o[cc * 4 + py * 2] = (half_t)src[0];
+      o[cc * 4 + py * 2 + 1] = (half_t)src[1];
+    }
+}
+
+// ---- torch.cat([latents.half(), image_latents], 2) -> patch rows [B F h w, (c, py, px)]; C2 = channels of a row (C or 2 C)
+template <typename LT>
+__global__ __launch_bounds__(256) void dit_patch_rows_kernel(const LT* __restrict__ latents, const half_t* __restrict__ image_latents,
+                                                             int C, int C2, int H, int W, long long total,
+                                                             half_t* __restrict__ out, int ldp) {
+  const int h = H / 2, w = W / 2, pieces = C2 / 2;
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
+    const dit_piece d = dit_piece_of(i, w, h, pieces);
+    const int c0 = 2 * d.q;               // C is even: a piece never straddles the two tensors
+    half8_t o;
+    if (c0 < C) dit_gather(latents + (d.bf * C + c0) * H * W, H, W, d.y, d.x, o);
+    else dit_gather(image_latents + (d.bf * C + (c0 - C)) * H * W, H, W, d.y, d.x, o);
+    *(half8_t*)(out + ((d.bf * h + d.y) * w + d.x) * ldp + d.q * 8) = o;
+  }
+}
+
+// ---- one element of the step: the reference's fp32 statements, each operation rounded (ATen runs them as separate kernels)
+struct ddim_t { float g, a, b, sa, sb; };
+__device__ __forceinline__ float ddim_advance(const ddim_t& k, int cfg, float u, float c, float x) {
+#pragma clang fp contract(off)
+  float n = u;
+  if (cfg == 2) {
+    const float diff = c - u;
+    const float gd = k.g * diff;
+    n = u + gd;
+  }
+  const float sx = k.sa * x;
+  const float sn = k.sb * n;
+  const float x0 = sx - sn;
+  const float ax = k.a * x;
+  const float bx = k.b * x0;
+  return ax + bx;
+}
+
+template <typename LT>
+__global__ __launch_bounds__(256) void dit_cfg_ddim_kernel(const half_t* __restrict__ noise, int ldn, LT* __restrict__ latents,
+                                                           int C, int H, int W, int cfg, long long cond_rows, ddim_t k,
+                                                           long long total) {
+  const int h = H / 2, w = W / 2, pieces = C / 2;
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
+    const dit_piece d = dit_piece_of(i, w, h, pieces);
+    const long long row = (d.bf * h + d.y) * w + d.x;
+    const half8_t u = *(const half8_t*)(noise + row * ldn + d.q * 8);
+    half8_t c = u;
+    if (cfg == 2) c = *(const half8_t*)(noise + (row + cond_rows) * ldn + d.q * 8);
+    LT* planes = latents + (d.bf * C + 2 * d.q) * H * W;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      LT* px = planes + ((long long)(e >> 2) * H + 2 * d.y + ((e >> 1) & 1)) * W + 2 * d.x + (e & 1);
+      *px = (LT)ddim_advance(k, cfg, (float)u[e], (float)c[e], (float)*px);
+    }
+  }
+}
+
+static int dit_shape_ok(int32_t B, int32_t F, int32_t C, int32_t H, int32_t W, int32_t p, int32_t width, int32_t ld) {
+  if (B <= 0 || F <= 0 || C <= 0 || H <= 0 || W <= 0 || p != 2) return 0;
+  if (H % p || W % p || (C * p * p) % 8) return 0;
+  return ld >= width && ld % 8 == 0;
+}
+template <typename Launch>
+static int dit_launch_typed(int32_t is_f32, Launch&& launch) {
+  if (is_f32) launch((float*)nullptr);
+  else launch((half_t*)nullptr);
+  return hipGetLastError() == hipSuccess ? LKGD_OK : LKGD_E_LAUNCH;
+}
+
+extern "C" int lkgd_dit_patch_rows(const void* latents, int32_t latents_is_f32, const void* image_latents, int32_t B, int32_t F,
+                                   int32_t C, int32_t H, int32_t W, int32_t p, void* rows_out, int32_t ldp, lkgd_stream_t stream) {
+  if (!latents || !rows_out) return LKGD_E_NULL;
+  const long long C2 = image_latents ? 2ll * C : C;
+  if (C2 * 4 > 0x7fffffffll || !dit_shape_ok(B, F, C, H, W, p, (int32_t)(C2 * 4), ldp)) return LKGD_E_SHAPE;
+  if (!aligned16(rows_out)) return LKGD_E_ALIGN;
+  const long long total = (long long)B * F * (H / 2) * (W / 2) * (C2 / 2);
+  return dit_launch_typed(latents_is_f32, [&](auto* tag) {
+    using LT = std::remove_pointer_t<decltype(tag)>;
+    hipLaunchKernelGGL(dit_patch_rows_kernel<LT>, dim3(dit_grid_for(total, 256)), dim3(256), 0, (hipStream_t)stream,
+                       (const LT*)latents, (const half_t*)image_latents, C, (int)C2, H, W, total, (half_t*)rows_out, ldp);
+  });
+}
+
+extern "C" int lkgd_dit_cfg_ddim_step(const void* noise_rows, int32_t ldn, void* latents, int32_t latents_is_f32, int32_t B,
+                                      int32_t F, int32_t C, int32_t H, int32_t W, int32_t p, int32_t cfg, float guidance, float a,
+                                      float b, float sqrt_alpha, float sqrt_beta, lkgd_stream_t stream) {
+  if (!noise_rows || !latents) return LKGD_E_NULL;
+  if ((long long)C * 4 > 0x7fffffffll || !dit_shape_ok(B, F, C, H, W, p, C * 4, ldn) || (cfg != 1 && cfg != 2)) return LKGD_E_SHAPE;
+  if (!aligned16(noise_rows)) return LKGD_E_ALIGN;
+  const long long rows = (long long)B * F * (H / 2) * (W / 2);
+  const long long total = rows * (C / 2);
+  const ddim_t k = {guidance, a, b, sqrt_alpha, sqrt_beta};
+  return dit_launch_typed(latents_is_f32, [&](auto* tag) {
+    using LT = std::remove_pointer_t<decltype(tag)>;
+    hipLaunchKernelGGL(dit_cfg_ddim_kernel<LT>, dim3(dit_grid_for(total, 256)), dim3(256), 0, (hipStream_t)stream,
+                       (const half_t*)noise_rows, ldn, (LT*)latents, C, H, W, cfg, rows, k, total);
+  });
+}

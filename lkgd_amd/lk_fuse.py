@@ -85,3 +85,64 @@ def lk_fuse_cached(unet, e, d, f) -> torch.Tensor:
     out = lk_fuse(unet, e, d, f)
     unet._lk_cache = (tuple((t, t._version) for t in ins), out)
     return out
+
+
+# ---- the DiT form: the fuse of the CogVideoX text tokens (include/lkgd_hip_dit_loop.h, lkgd_amd/csrc/lk_fuse.hip) ----------------------
+LK_TOKENS_SHAPES = [(256, 16), (256, 4), (256, 4), (256,), (1024, 512), (512,), (129,), (129,), (512, 256), (256,), (512, 256), (256,),
+                    (5,), (5,), (1024, 512), (512,), (512, 4096), (4096,)]
+
+
+def pack_lk_tokens(transformer):
+    """the 18 fp32 operands of lkgd_lk_fuse_tokens in the order of ``pack_lk`` with the DiT's shapes (16-tap lconv from 4096
+    channels, fuse_sf 1024 -> 512 -> 4096), matrices as (in, out) row-major; built once per weight version (kept on the model's
+    pack)"""
+    dev = transformer.device
+
+    def f32(t):
+        return t.detach().to(device=dev, dtype=torch.float32).contiguous()
+    m = transformer
+    sf = m.quaternion_lora_fuse_sf
+    l0m, l0p = m.quaternion_lora_fuse_fft_mag0, m.quaternion_lora_fuse_fft_pha0
+    ws = [f32(m.quaternion_lora_lconv.weight.reshape(256, 16)), f32(m.quaternion_lora_dconv.weight.reshape(256, 4)),
+          f32(m.quaternion_lora_fconv.weight.reshape(256, 4)), f32(m.quaternion_lora_texts.reshape(256)),
+          f32(hamilton(m.quaternion_lora_fuse)), f32(m.quaternion_lora_fuse.bias),
+          f32(m.quaternion_lora_texts_fft_mag.reshape(129)), f32(m.quaternion_lora_texts_fft_pha.reshape(129)),
+          f32(hamilton(m.quaternion_lora_fuse_fft_mag)), f32(m.quaternion_lora_fuse_fft_mag.bias),
+          f32(hamilton(m.quaternion_lora_fuse_fft_pha)), f32(m.quaternion_lora_fuse_fft_pha.bias),
+          f32(torch.cat([l0m.weight.reshape(4), l0m.bias.reshape(1)])), f32(torch.cat([l0p.weight.reshape(4), l0p.bias.reshape(1)])),
+          f32(sf[0].weight.T), f32(sf[0].bias), f32(sf[2].weight.T), f32(sf[2].bias)]
+    for w, shp in zip(ws, LK_TOKENS_SHAPES):
+        if tuple(w.shape) != shp:
+            raise LkgdHipError(f"latent-knowledge fuse of the text tokens: parameter of shape {tuple(w.shape)}, expected {shp}")
+    ptrs = (C.c_void_p * 18)(*[w.data_ptr() for w in ws])
+    return ws, ptrs
+
+
+@torch.no_grad()
+def lk_fuse_tokens(pack, encoder_hidden_states, domain_features, flow_features, out=None) -> torch.Tensor:
+    """one launch of lkgd_lk_fuse_tokens: ``encoder_hidden_states`` [B, L, 4096], ``domain_features`` / ``flow_features``
+    [1 or B, 1, 1000] -> fp16 [B, L, 4096].  ``pack`` = ``pack_lk_tokens(model)``; everything lives on the pack's device."""
+    ws, ptrs = pack
+    dev = ws[0].device
+    if dev.type != "cuda":
+        raise LkgdHipError("the latent-knowledge fuse runs on the GPU (lkgd_amd has no CPU path)")
+    e = encoder_hidden_states.to(device=dev, dtype=torch.float32)
+    d = domain_features.to(device=dev, dtype=torch.float32).contiguous()
+    f = flow_features.to(device=dev, dtype=torch.float32).contiguous()
+    if e.dim() != 3 or e.shape[2] != 4096 or e.shape[0] < 1 or e.shape[1] < 1:
+        raise LkgdHipError(f"latent-knowledge fuse: encoder_hidden_states must be [batch, tokens, 4096], got {tuple(e.shape)}")
+    if e.stride(2) != 1 or e.stride(0) != e.shape[1] * e.stride(1) or e.stride(1) % 4 or e.data_ptr() % 16:
+        e = e.contiguous()
+    B, L, Bd = e.shape[0], e.shape[1], d.shape[0]
+    if d.dim() != 3 or tuple(d.shape[1:]) != (1, 1000) or tuple(f.shape) != tuple(d.shape):
+        raise LkgdHipError("latent-knowledge fuse: domain / flow features must be [1 or batch, 1, 1000]")
+    if Bd != B and Bd != 1:
+        raise LkgdHipError(f"latent-knowledge fuse: {Bd} feature rows for a batch of {B} (1 or {B})")
+    if out is None:
+        out = torch.empty(B, L, 4096, dtype=torch.float16, device=dev)
+    elif out.dtype != torch.float16 or out.device != dev or tuple(out.shape) != (B, L, 4096) or out.stride(2) != 1 \
+            or out.stride(0) != L * out.stride(1):
+        raise LkgdHipError(f"latent-knowledge fuse: out must be a GPU fp16 [{B}, {L}, 4096] tensor with one row stride")
+    check(_lib.lib().lkgd_lk_fuse_tokens(e.data_ptr(), e.stride(1), d.data_ptr(), f.data_ptr(), B, L, Bd, ptrs, out.data_ptr(),
+                                         out.stride(1), torch.cuda.current_stream(dev).cuda_stream), "lkgd_lk_fuse_tokens")
+    return out

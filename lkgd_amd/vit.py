@@ -2,7 +2,7 @@
 
 The reference builds two ``timm`` ``vit_base_patch16_384()`` models [EXT] and turns a clip into the latent-knowledge inputs of
 the UNet: /root/reference/train_models/train_svd_lora.py:1408-1433 (construction; weights = the ``encoder.*`` keys of a
-checkpoint) and :1455-1466 (``F.interpolate(size=[384, 384], mode="bilinear")`` -> logits [N, 1000] -> mean over the clip's
+checkpoint) and :1455-1466 (a bilinear resize to 384 x 384 -> logits [N, 1000] -> mean over the clip's
 frames -> ``domain_features`` / ``flow_features`` [B, 1, 1000]); the inference wiring is
 CogVideo-main/finetune/models/cogvideox_i2v/pipeline_cogvideox_image2video.py:794-799.  Parameter names are timm's, so those
 checkpoints load (``load_encoder_checkpoint``).  oracle/vit.py is the fp32 restatement the tests compare with (PARITY UNPINNED:

@@ -140,6 +140,15 @@ DIT_LOOP_SYMBOLS = {
                                       _vp]),
 }
 
+#: every symbol include/lkgd_hip_dit_tpatch.h declares (the loop glue for the temporal patches of the CogVideoX 1.5 models), bound on
+#: the same library object; tests/test_cogvideox15_cpu.py pins header, table and library to one another,
+#: tests/test_cogvideox15_gpu.py the footprint cases
+DIT_TPATCH_SYMBOLS = {
+    "lkgd_dit_patch_rows_t": (_i32, [_vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _vp]),
+    "lkgd_dit_cfg_ddim_step_t": (_i32, [_vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _f32, _f32, _f32,
+                                        _f32, _vp]),
+}
+
 #: include/lkgd_hip_debug.h: A/B and test knobs, per host thread; bound on the same library object, not part of the product interface
 DEBUG_SYMBOLS = {
     "lkgd_debug_set_wide_tile_n": (None, [_i32]),
@@ -174,7 +183,7 @@ def lib() -> C.CDLL:
             l = C.CDLL(LIB_PATH)
         except OSError as e:
             raise LkgdHipError(f"cannot load {LIB_PATH}: {e}") from e
-        for table in (SYMBOLS, WINDOW_SYMBOLS, DIT_SYMBOLS, DIT_LOOP_SYMBOLS, DEBUG_SYMBOLS):
+        for table in (SYMBOLS, WINDOW_SYMBOLS, DIT_SYMBOLS, DIT_LOOP_SYMBOLS, DIT_TPATCH_SYMBOLS, DEBUG_SYMBOLS):
             for name, (res, args) in table.items():
                 fn = getattr(l, name)       # AttributeError here = header / library mismatch
                 fn.restype, fn.argtypes = res, args

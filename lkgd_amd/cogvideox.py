@@ -31,7 +31,12 @@ MI355X design - the UNet's kernels, one joint token buffer:
   of latents | image latents ONCE for both CFG entries (no duplicated batch, no channel concat), ``forward_rows`` runs the DiT on
   them, ``lkgd_dit_cfg_ddim_step`` takes proj_out's token rows through the CFG combine and the DDIM update into the latents in
   place.  ``forward_tokens`` / ``forward`` keep the [B, F, C, H, W] interface: their patch unfold / un-patchify are torch permutes
-  (data movement at the API edge).
+  (data movement at the API edge);
+* the 1.5 models (``patch_size_t = 2``, rotary, no learned table, with or without ``ofs_embed_dim``): a token
+  spans two latent frames, so the patch embedding is a Linear over C p_t p p columns and the grid is (F / p_t, h, w); the loop's
+  glue is the ``_t`` pair of include/lkgd_hip_dit_tpatch.h; the ``ofs`` embedding (timestep-embedding kernel + two small GEMMs,
+  step-invariant: once per clip) is added to the time embedding before the modulation GEMM; ``rotary_tables`` restates the
+  pipeline's ``grid_type="slice"`` branch; ``pad_for_temporal_patches`` / ``drop_temporal_padding`` restate its frame padding.
 """
 from __future__ import annotations
 
@@ -54,7 +59,8 @@ from .unet import QuaternionLinearAutograd, TimestepEmbedding
 @dataclass
 class DiTConfig:
     """constructor keywords of CogVideoXTransformer3DModel (cogvideox_transformer_3d.py:224-255) used by the 2B and the 5B
-    1.0 models (5B-I2V: 48 heads, 42 layers, in_channels 32, rotary embeddings + a learned position table)"""
+    1.0 models (5B-I2V: 48 heads, 42 layers, in_channels 32, rotary embeddings + a learned position table) and by the 1.5
+    models (``patch_size_t`` 2, ``patch_bias`` False, rotary embeddings without a learned table; I2V: ``ofs_embed_dim`` 512)"""
     num_attention_heads: int = 30
     attention_head_dim: int = 64
     in_channels: int = 16
@@ -74,6 +80,27 @@ class DiTConfig:
     attention_bias: bool = True
     use_rotary_positional_embeddings: bool = False
     use_learned_positional_embeddings: bool = False
+    patch_size_t: Optional[int] = None
+    ofs_embed_dim: Optional[int] = None
+    patch_bias: bool = True
+
+
+def check_temporal_config(patch_size_t, ofs_embed_dim, rotary: bool, learned: bool, where: str) -> None:
+    """the one released combination of the 1.5 keys is built: ``patch_size_t == 2`` with rotary embeddings and no learned table,
+    with or without ``ofs_embed_dim``; every other use of either key raises, naming the key"""
+    if ofs_embed_dim and not patch_size_t:
+        raise LkgdHipError(f"{where}: ofs_embed_dim={ofs_embed_dim!r} without patch_size_t; the ofs embedding is built for the "
+                           "1.5 image-to-video architecture only (patch_size_t 2)")
+    if not patch_size_t:
+        return
+    if patch_size_t != 2:
+        raise LkgdHipError(f"{where}: patch_size_t={patch_size_t!r}; the temporal-patch kernels are built for patch_size_t 2")
+    if learned:
+        raise LkgdHipError(f"{where}: patch_size_t={patch_size_t!r} together with use_learned_positional_embeddings; the 1.5 "
+                           "models have no learned position table, the combination is not built")
+    if not rotary:
+        raise LkgdHipError(f"{where}: patch_size_t={patch_size_t!r} without use_rotary_positional_embeddings; the 1.5 models "
+                           "are rotary, a sin-cos table over temporal patches is not built")
 
 
 def _f32(p):
@@ -123,11 +150,13 @@ def rotary_tables(config, frames: int, h: int, w: int):
     TOKEN grid (latent frames, latent size // patch_size).  PARITY UNPINNED: restates diffusers' [EXT]
     ``get_resize_crop_region_for_grid`` and ``get_3d_rotary_pos_embed`` (linspace grid over the crop region of the configured
     sample grid, theta 10 000): dim/4 temporal channels, then 3 dim/8 for the height and 3 dim/8 for the width (16 + 24 + 24 of
-    64), each frequency repeated for the pair (2i, 2i+1) it rotates.  Tested by its properties only."""
-    if getattr(config, "patch_size_t", None) is not None:
-        raise LkgdHipError("rotary_tables: patch_size_t (the CogVideoX 1.5 models) is not implemented")
+    64), each frequency repeated for the pair (2i, 2i+1) it rotates.  Tested by its properties only.
+    With ``config.patch_size_t`` (the 1.5 models) it is the pipeline's ``grid_type="slice"`` branch (:572-584) instead; ``frames`` is
+    then the token grid's (latent frames + p_t - 1) // p_t, as the pipeline passes it (``_rotary_tables_slice``)."""
     d = config.attention_head_dim
     p = config.patch_size
+    if getattr(config, "patch_size_t", None):
+        return _rotary_tables_slice(d, frames, h, w, config.sample_height // p, config.sample_width // p)
     (top, left), (bottom, right) = rope_crop_region(h, w, config.sample_width // p, config.sample_height // p)
     gh = torch.linspace(top, bottom * (h - 1) / h, h, dtype=torch.float32)
     gw = torch.linspace(left, right * (w - 1) / w, w, dtype=torch.float32)
@@ -138,6 +167,55 @@ def rotary_tables(config, frames: int, h: int, w: int):
         out.append(torch.cat([ct[:, None, None, :].expand(frames, h, w, dt), ch[None, :, None, :].expand(frames, h, w, ds),
                               cw[None, None, :, :].expand(frames, h, w, ds)], dim=-1).reshape(frames * h * w, d).contiguous())
     return out[0], out[1]
+
+
+def _rotary_tables_slice(d: int, frames: int, h: int, w: int, max_h: int, max_w: int):
+    """PARITY UNPINNED: restates diffusers' [EXT] ``get_3d_rotary_pos_embed(grid_type="slice", max_size=(max_h, max_w))``: the
+    1-D tables of the integer positions 0 .. max - 1 of the configured sample grid, of which the first h (w) rows are taken - no
+    crop region, no linspace; positions 0 .. frames - 1 in time.  The same 16 + 24 + 24 channel split and pair repetition."""
+    if h > max_h or w > max_w:
+        raise LkgdHipError(f"rotary_tables: a {h} x {w} token grid exceeds the {max_h} x {max_w} (sample_height // patch_size, "
+                           "sample_width // patch_size) the 1.5 tables are sliced from")
+    dt, ds = d // 4, d // 8 * 3
+    gt = torch.arange(frames, dtype=torch.float32)
+    gh, gw = torch.arange(max_h, dtype=torch.float32), torch.arange(max_w, dtype=torch.float32)
+    out = []
+    for ct, ch, cw in zip(_rope_1d(dt, gt), _rope_1d(ds, gh), _rope_1d(ds, gw)):
+        ch, cw = ch[:h], cw[:w]
+        out.append(torch.cat([ct[:, None, None, :].expand(frames, h, w, dt), ch[None, :, None, :].expand(frames, h, w, ds),
+                              cw[None, None, :, :].expand(frames, h, w, ds)], dim=-1).reshape(frames * h * w, d).contiguous())
+    return out[0], out[1]
+
+
+def pad_for_temporal_patches(latents, image_latents, p_t: Optional[int]):
+    """``prepare_latents`` of pipeline_cogvideox_image2video.py for ``patch_size_t`` -> (latents shape or tensor, image_latents)
+    with a frame count the temporal patch divides.  ``latents`` as a SHAPE [B, F, C, h, w] (the noise is drawn afterwards) gets
+    :383-384's ``F + F % p_t``, arithmetic as written; ``image_latents`` [B, F, C, h, w] gets :416-418: its first ``F % p_t`` frames
+    once more at the FRONT.  A latents TENSOR is padded by the rule of the image latents (the pipeline takes given latents as
+    they are, already padded).  ``p_t`` None: both returned as they are."""
+    if p_t is None:
+        return latents, image_latents
+    if torch.is_tensor(latents):
+        latents = torch.cat([latents[:, : latents.size(1) % p_t, ...], latents], dim=1)
+    else:
+        shape = tuple(latents)
+        latents = shape[:1] + (shape[1] + shape[1] % p_t,) + shape[2:]
+    if image_latents is not None:
+        first_frame = image_latents[:, : image_latents.size(1) % p_t, ...]
+        image_latents = torch.cat([first_frame, image_latents], dim=1)
+    return latents, image_latents
+
+
+def temporal_padding_frames(latent_frames: int, p_t: Optional[int]) -> int:
+    """``additional_frames`` of :781-786: how many latent frames the pipeline adds so that ``p_t`` divides the count"""
+    if p_t is not None and latent_frames % p_t != 0:
+        return p_t - latent_frames % p_t
+    return 0
+
+
+def drop_temporal_padding(latents: torch.Tensor, additional_frames: int) -> torch.Tensor:
+    """:907 - the padding frames leave at the front before the VAE decodes"""
+    return latents[:, additional_frames:]
 
 
 # ------------------------------------------------------------------------------------------------ parameter holders
@@ -204,7 +282,11 @@ class CogVideoXBlock(nn.Module):
 class CogVideoXPatchEmbed(nn.Module):
     def __init__(self, cfg: DiTConfig, dim: int):
         super().__init__()
-        self.proj = nn.Conv2d(cfg.in_channels, dim, kernel_size=(cfg.patch_size, cfg.patch_size), stride=cfg.patch_size)
+        if cfg.patch_size_t is None:
+            self.proj = nn.Conv2d(cfg.in_channels, dim, kernel_size=(cfg.patch_size, cfg.patch_size), stride=cfg.patch_size,
+                                  bias=cfg.patch_bias)
+        else:       # [EXT diffusers CogVideoXPatchEmbed, 1.5]: a Linear over a patch's (c, pt, py, px) columns
+            self.proj = nn.Linear(cfg.in_channels * cfg.patch_size * cfg.patch_size * cfg.patch_size_t, dim, bias=cfg.patch_bias)
         self.text_proj = nn.Linear(cfg.text_embed_dim, dim)
         if cfg.use_learned_positional_embeddings:
             # [EXT diffusers CogVideoXPatchEmbed]: a persistent buffer over the JOINT sequence (text rows included), present in
@@ -227,25 +309,33 @@ class CogVideoXTransformer3DModel(nn.Module):
     def __init__(self, config: Optional[DiTConfig] = None, **kw):
         super().__init__()
         cfg = config if config is not None else DiTConfig(**kw)
-        self.config = SimpleNamespace(**cfg.__dict__, patch_size_t=None, ofs_embed_dim=None)
+        self.config = SimpleNamespace(**cfg.__dict__)
         if not cfg.use_rotary_positional_embeddings and cfg.use_learned_positional_embeddings:
             raise ValueError(                                                                   # cogvideox_transformer_3d.py:258-263
                 "There are no CogVideoX checkpoints available with disable rotary embeddings and learned positional "
                 "embeddings. If you're using a custom model and/or believe this should be supported, please open an "
                 "issue at https://github.com/huggingface/diffusers/issues.")
+        check_temporal_config(cfg.patch_size_t, cfg.ofs_embed_dim, cfg.use_rotary_positional_embeddings,
+                              cfg.use_learned_positional_embeddings, "CogVideoXTransformer3DModel")
+        if cfg.ofs_embed_dim and cfg.ofs_embed_dim != cfg.time_embed_dim:
+            raise LkgdHipError(f"CogVideoXTransformer3DModel: ofs_embed_dim={cfg.ofs_embed_dim} is added to the time embedding "
+                               f"and has to equal time_embed_dim={cfg.time_embed_dim}")
         d = cfg.num_attention_heads * cfg.attention_head_dim
-        if d % 64 or (cfg.in_channels * cfg.patch_size ** 2) % 64 or cfg.time_embed_dim % 64 or cfg.text_embed_dim % 64 \
-                or d > 3072 or (cfg.patch_size ** 2 * cfg.out_channels) % 8:
+        pt = cfg.patch_size_t or 1
+        if d % 64 or (cfg.in_channels * cfg.patch_size ** 2 * pt) % 64 or cfg.time_embed_dim % 64 or cfg.text_embed_dim % 64 \
+                or d > 3072 or (cfg.patch_size ** 2 * pt * cfg.out_channels) % 8:
             raise LkgdHipError("DiT on the HIP path: dims multiples of 64 (K granularity), inner dim <= 3072")
         self.inner_dim = d
         self.patch_embed = CogVideoXPatchEmbed(cfg, d)
         self.time_embedding = TimestepEmbedding(d, cfg.time_embed_dim)
+        # cogvideox_transformer_3d.py:290-296: the sinusoid of ``ofs`` has ofs_embed_dim channels, the MLP keeps that width
+        self.ofs_embedding = TimestepEmbedding(cfg.ofs_embed_dim, cfg.ofs_embed_dim) if cfg.ofs_embed_dim else None
         self.transformer_blocks = nn.ModuleList([
             CogVideoXBlock(d, cfg.num_attention_heads, cfg.attention_head_dim, cfg.time_embed_dim, cfg.attention_bias,
                            cfg.norm_eps) for _ in range(cfg.num_layers)])
         self.norm_final = nn.LayerNorm(d, cfg.norm_eps)
         self.norm_out = AdaLayerNorm(cfg.time_embed_dim, 2 * d, cfg.norm_eps)
-        self.proj_out = nn.Linear(d, cfg.patch_size * cfg.patch_size * cfg.out_channels)
+        self.proj_out = nn.Linear(d, cfg.patch_size * cfg.patch_size * pt * cfg.out_channels)              # :326-333
         self.init_quaternion_modules()
         self._pk = None
         self._pos = {}
@@ -292,10 +382,9 @@ class CogVideoXTransformer3DModel(nn.Module):
                         variant: Optional[str] = None, **_ignored):
         from .loading import build_from_pretrained, load_config, load_state_dict
         raw = load_config(pretrained_model_name_or_path, subfolder)
-        for key in ("patch_size_t", "ofs_embed_dim"):
-            if raw.get(key):        # the 1.5 variants (temporal patches, ofs embedding) are not built
-                raise LkgdHipError(f"CogVideoXTransformer3DModel.from_pretrained: config has {key}={raw[key]!r}; only the "
-                                   "1.0 architectures (2B, 5B: 2-D patches, no ofs embedding) are implemented")
+        # before any weight is read: of the 1.5 keys only the released combination is built
+        check_temporal_config(raw.get("patch_size_t"), raw.get("ofs_embed_dim"), bool(raw.get("use_rotary_positional_embeddings")),
+                              bool(raw.get("use_learned_positional_embeddings")), "CogVideoXTransformer3DModel.from_pretrained")
         # stock checkpoints have no quaternion_lora_* modules: those may be missing; anything else missing or unexpected
         # (a truncated shard, renamed parameters) would leave meta-initialised garbage behind a non-strict load
         sd_keys = set(load_state_dict(pretrained_model_name_or_path, subfolder, variant).keys())
@@ -323,6 +412,8 @@ class CogVideoXTransformer3DModel(nn.Module):
         for b in self.transformer_blocks:
             b.pack()
         self.time_embedding.pack()
+        if self.ofs_embedding is not None:
+            self.ofs_embedding.pack()
         pk = SimpleNamespace()
         # every block's two modulation linears as ONE [blocks * 2 * 6D, Te] GEMM per step (+ norm_out's [2D, Te])
         mods = [m for b in self.transformer_blocks for m in (b.norm1.linear, b.norm2.linear)] + [self.norm_out.linear]
@@ -335,7 +426,8 @@ class CogVideoXTransformer3DModel(nn.Module):
         pk.fin = (_f32(self.norm_final.weight), _f32(self.norm_final.bias))
         pk.out_g, pk.out_b = _f32(self.norm_out.norm.weight), _f32(self.norm_out.norm.bias)
         pe = self.patch_embed
-        pk.w_pe, pk.b_pe = pack_linear(pe.proj.weight.detach()), _f32(pe.proj.bias)          # [D, C*p*p], k = (c, ky, kx)
+        # [D, C*p*p], k = (c, ky, kx); temporal patches: [D, C*p_t*p*p], k = (c, pt, ky, kx) - both the order of the weight itself
+        pk.w_pe, pk.b_pe = pack_linear(pe.proj.weight.detach()), (_f32(pe.proj.bias) if pe.proj.bias is not None else None)
         pk.w_tx, pk.b_tx = pack_linear(pe.text_proj.weight), _f32(pe.text_proj.bias)
         pk.w_po, pk.b_po = pack_linear(self.proj_out.weight), _f32(self.proj_out.bias)
         pk.learned = pe.pos_embedding[0].detach().to(torch.float16).contiguous() if self.config.use_learned_positional_embeddings else None
@@ -384,21 +476,49 @@ class CogVideoXTransformer3DModel(nn.Module):
     # ---- the per-step forward ------------------------------------------------------------------------------------
     @torch.no_grad()
     def forward_tokens(self, hidden_states: torch.Tensor, fused_text: torch.Tensor, timestep, shard=None,
-                       image_rotary_emb=None) -> torch.Tensor:
+                       image_rotary_emb=None, ofs=None) -> torch.Tensor:
         """hidden_states [B, F, C, h, w]; fused_text [B, L, 4096] fp16 (``fused_text`` of the prompt embeddings) ->
-        [B, F, out_channels, h, w] fp16: patch unfold, ``forward_rows``, un-patchify (two torch permutes at the API edge)."""
+        [B, F, out_channels, h, w] fp16: patch unfold, ``forward_rows``, un-patchify (two torch permutes at the API edge).
+        ``ofs``: a scalar or a [1] / [B] tensor, exactly when the model has an ``ofs_embedding``."""
         B, Fr, C_, H, W = hidden_states.shape
-        p = self.config.patch_size
+        p, pt = self.config.patch_size, self.config.patch_size_t
         h, w = H // p, W // p
+        if (self.ofs_embedding is None) != (ofs is None):
+            raise LkgdHipError("ofs is given exactly when the model has an ofs_embedding (config ofs_embed_dim)")
+        if pt is not None and Fr % pt:
+            raise LkgdHipError(f"patch_size_t {pt} does not divide the {Fr} latent frames: pad_for_temporal_patches first")
+        ofs_emb = self.embed_ofs(ofs, B) if ofs is not None else None
         xh = hidden_states.to(device=self.device, dtype=torch.float16)
-        patches = xh.reshape(B, Fr, C_, h, p, w, p).permute(0, 1, 3, 5, 2, 4, 6).reshape(B * Fr * h * w, C_ * p * p).contiguous()
-        out_tok = self.forward_rows(patches, (Fr, h, w), fused_text, timestep, shard=shard, image_rotary_emb=image_rotary_emb)
-        out = out_tok.reshape(B, Fr, h, w, -1, p, p).permute(0, 1, 4, 2, 5, 3, 6).flatten(5, 6).flatten(3, 4)
+        if pt is None:
+            patches = xh.reshape(B, Fr, C_, h, p, w, p).permute(0, 1, 3, 5, 2, 4, 6).reshape(B * Fr * h * w, C_ * p * p).contiguous()
+            out_tok = self.forward_rows(patches, (Fr, h, w), fused_text, timestep, shard=shard, image_rotary_emb=image_rotary_emb)
+            out = out_tok.reshape(B, Fr, h, w, -1, p, p).permute(0, 1, 4, 2, 5, 3, 6).flatten(5, 6).flatten(3, 4)
+            return out.contiguous()
+        # [EXT diffusers CogVideoXPatchEmbed, 1.5] (column (c, pt, py, px)), and cogvideox_transformer_3d.py:626-630
+        patches = xh.permute(0, 1, 3, 4, 2).reshape(B, Fr // pt, pt, h, p, w, p, C_).permute(0, 1, 3, 5, 7, 2, 4, 6) \
+            .flatten(4, 7).flatten(1, 3).reshape(B * (Fr // pt) * h * w, C_ * pt * p * p).contiguous()
+        out_tok = self.forward_rows(patches, (Fr // pt, h, w), fused_text, timestep, shard=shard, image_rotary_emb=image_rotary_emb,
+                                    ofs_emb=ofs_emb)
+        out = out_tok.reshape(B, Fr // pt, h, w, -1, pt, p, p).permute(0, 1, 5, 4, 2, 6, 3, 7).flatten(6, 7).flatten(4, 5).flatten(1, 2)
         return out.contiguous()
 
     @torch.no_grad()
+    def embed_ofs(self, ofs, batch: int) -> torch.Tensor:
+        """cogvideox_transformer_3d.py:513-516: ``ofs`` (a scalar or a [1] / [batch] tensor) -> ofs_embedding(ofs_proj(ofs)) fp16
+        [batch, ofs_embed_dim]; the sinusoid leaves the timestep-embedding kernel in fp16 (the cast of :515), the MLP is the two
+        small GEMMs of the time embedding.  Step-invariant: ``denoise`` calls it once per clip."""
+        if self.ofs_embedding is None:
+            raise LkgdHipError("ofs: this model has no ofs_embedding (config ofs_embed_dim)")
+        self.prepare()
+        o = ofs if torch.is_tensor(ofs) else torch.tensor([float(ofs)])
+        o = o.to(device=self.device, dtype=torch.float32).reshape(-1)
+        if o.numel() not in (1, batch):
+            raise LkgdHipError(f"ofs must be a scalar or have 1 or {batch} entries, got {o.numel()}")
+        return self.ofs_embedding.run(ops.timestep_embedding(o.expand(batch).contiguous(), self.config.ofs_embed_dim))
+
+    @torch.no_grad()
     def forward_rows(self, patch_rows: torch.Tensor, grid, fused_text: torch.Tensor, timestep, shard=None,
-                     image_rotary_emb=None) -> torch.Tensor:
+                     image_rotary_emb=None, ofs_emb=None) -> torch.Tensor:
         """the row-level core.  ``patch_rows`` fp16 [Bv * Tv, in_channels * p * p] (``ops.dit_patch_rows``; column (c, py, px)),
         ``grid`` = (F, h, w) tokens, Tv = F h w; fused_text [B, L, 4096] fp16.  Bv divides B: batch entry b embeds the rows of
         entry b % Bv, so ONE copy of the rows (Bv = 1) serves both CFG entries, as ``torch.cat([latents] * 2)`` did.  Returns
@@ -408,11 +528,19 @@ class CogVideoXTransformer3DModel(nn.Module):
         the two LayerNorm launches of the 2B path.  ``shard`` (lkgd_amd.dist_run.ShardInfo): this rank holds ONE batch entry (its CFG
         half) and the latent frames [f0, f0 + F) of the clip; everything is row-local except the attention, whose local
         queries (the replicated text rows + the rank's video rows) attend to the keys / values of ALL frames, all-gathered
-        over the frame group every layer."""
+        over the frame group every layer.
+        A ``patch_size_t`` model: ``patch_rows`` [Bv * Tv, in_channels * p_t * p * p] (``ops.dit_patch_rows(p_t=)``; column
+        (c, pt, py, px)), ``grid`` = (F / p_t, h, w), the result [B * Tv, out_channels * p_t * p * p]; ``ofs_emb`` fp16
+        [B, time_embed_dim] (``embed_ofs``) exactly when the model has an ``ofs_embedding``: added to the time embedding in fp16
+        (:517) before the modulation GEMM."""
         self.prepare()
         pk, cfg, dev = self._pk, self.config, self.device
         B = fused_text.shape[0]
         Fr, h, w = grid
+        if shard is not None and cfg.patch_size_t is not None:
+            raise LkgdHipError("frame sharding of a patch_size_t (CogVideoX 1.5) model is not built")
+        if (self.ofs_embedding is None) != (ofs_emb is None):
+            raise LkgdHipError("ofs_emb (embed_ofs) is given exactly when the model has an ofs_embedding (config ofs_embed_dim)")
         if shard is not None and B != 1:
             raise LkgdHipError("frame sharding of the DiT supports one batch entry per rank")
         D = self.inner_dim
@@ -445,6 +573,11 @@ class CogVideoXTransformer3DModel(nn.Module):
         t = timestep if torch.is_tensor(timestep) else torch.tensor([timestep])
         t = t.to(device=dev, dtype=torch.float32).reshape(-1).expand(B).contiguous()
         emb = self.time_embedding.run(ops.timestep_embedding(t, D))
+        if ofs_emb is not None:
+            if ofs_emb.dtype != torch.float16 or tuple(ofs_emb.shape) != tuple(emb.shape) or not ofs_emb.is_contiguous():
+                raise LkgdHipError(f"ofs_emb must be contiguous fp16 {tuple(emb.shape)} (embed_ofs), got {tuple(ofs_emb.shape)} "
+                                   f"{ofs_emb.dtype}")
+            emb = ops.add(emb, ofs_emb)
         semb = ops.silu(emb)
         mod = torch.empty(B, pk.w_mod.shape[0], dtype=torch.float16, device=dev)
         ops.gemm(semb, pk.w_mod, mod, M=B, N=pk.w_mod.shape[0], K=pk.w_mod.shape[1], bias=pk.b_mod)
@@ -531,10 +664,15 @@ class CogVideoXTransformer3DModel(nn.Module):
     def forward(self, hidden_states, encoder_hidden_states, timestep, domain_features, flow_features, timestep_cond=None,
                 ofs=None, image_rotary_emb=None, attention_kwargs=None, return_dict: bool = True):
         """cogvideox_transformer_3d.py:473-486 - ``domain_features`` / ``flow_features`` are positional"""
-        if ofs is not None or timestep_cond is not None:
-            raise LkgdHipError("ofs belongs to the CogVideoX 1.5 models and timestep_cond to none of the released ones: not built")
+        if timestep_cond is not None:
+            raise LkgdHipError("timestep_cond belongs to none of the released CogVideoX models: not built")
+        if ofs is not None and self.ofs_embedding is None:
+            raise LkgdHipError("ofs belongs to the CogVideoX 1.5 image-to-video models: this model has no ofs_embedding "
+                               "(config ofs_embed_dim)")
+        if ofs is None and self.ofs_embedding is not None:
+            raise LkgdHipError("this model has an ofs_embedding (config ofs_embed_dim): forward needs ofs (the pipeline passes 2.0)")
         text = self.fused_text(encoder_hidden_states, domain_features, flow_features)
-        out = self.forward_tokens(hidden_states, text, timestep, image_rotary_emb=image_rotary_emb)
+        out = self.forward_tokens(hidden_states, text, timestep, image_rotary_emb=image_rotary_emb, ofs=ofs)
         if not return_dict:
             return (out,)
         return Transformer2DModelOutput(sample=out)
@@ -590,22 +728,35 @@ def dynamic_guidance(guidance_scale: float, num_inference_steps: int, t: int) ->
 @torch.no_grad()
 def denoise(transformer: CogVideoXTransformer3DModel, scheduler: CogVideoXDDIMScheduler, latents, image_latents, prompt_embeds,
             domain_features, flow_features, num_inference_steps: int = 50, guidance_scale: float = 6.0,
-            use_dynamic_cfg: bool = True, callback=None, image_rotary_emb=None) -> torch.Tensor:
+            use_dynamic_cfg: bool = True, callback=None, image_rotary_emb=None, ofs=None) -> torch.Tensor:
     """the loop of pipeline_cogvideox_image2video.py:829-885 (the rotary tables are built once per clip when the config asks for
     them and none are given, :819-823).  latents / image_latents [B, F, C, h, w]; prompt_embeds
     [2B, L, 4096] (negative first) when guidance_scale > 1.  The update runs in fp32 (``noise_pred.float()`` :863) and the
     latents are cast back to the prompt dtype, fp16, after every step (:881 - reproduced).  Per step: ``lkgd_dit_patch_rows`` ->
-    ``forward_rows`` -> ``lkgd_dit_cfg_ddim_step`` (include/lkgd_hip_dit_loop.h); ``scheduler`` supplies ``coefficients(t)``."""
+    ``forward_rows`` -> ``lkgd_dit_cfg_ddim_step`` (include/lkgd_hip_dit_loop.h); ``scheduler`` supplies ``coefficients(t)``.
+    A ``patch_size_t`` model takes tensors prepared by ``pad_for_temporal_patches`` (F % p_t == 0, or it raises), runs the ``_t``
+    glue pair (include/lkgd_hip_dit_tpatch.h) on the (F / p_t, h, w) grid, and embeds ``ofs`` (default 2.0 when the config has
+    ``ofs_embed_dim``, :826) once per clip."""
     dev = transformer.device
+    if transformer.config.patch_size_t is not None and latents.shape[1] % transformer.config.patch_size_t:
+        raise LkgdHipError(f"denoise: patch_size_t {transformer.config.patch_size_t} does not divide the {latents.shape[1]} latent "
+                           "frames: pad_for_temporal_patches first")
+    if ofs is not None and transformer.ofs_embedding is None:
+        raise LkgdHipError("denoise: ofs given, but the model has no ofs_embedding (config ofs_embed_dim)")
     scheduler.set_timesteps(num_inference_steps)
     cfg = guidance_scale > 1.0
     text = transformer.fused_text(prompt_embeds, domain_features, flow_features)          # step-invariant: once per clip
     # the loop's own copy: the step kernel updates it in place
     latents = latents.to(device=dev, dtype=torch.float16).clone(memory_format=torch.contiguous_format)
-    img = image_latents.to(device=dev, dtype=torch.float16).contiguous()
+    # text-to-video (no image latents): the rows hold the latents' channels alone
+    img = image_latents.to(device=dev, dtype=torch.float16).contiguous() if image_latents is not None else None
     tc = transformer.config
-    p = tc.patch_size
-    grid = (latents.shape[1], latents.shape[3] // p, latents.shape[4] // p)
+    p, pt = tc.patch_size, tc.patch_size_t
+    grid = (latents.shape[1] // (pt or 1), latents.shape[3] // p, latents.shape[4] // p)
+    extra = {}
+    if transformer.ofs_embedding is not None:         # step-invariant: once per clip
+        extra["ofs_emb"] = transformer.embed_ofs(2.0 if ofs is None else ofs, text.shape[0])
+    glue = {} if pt is None else {"p_t": pt}
     if tc.use_rotary_positional_embeddings:
         if image_rotary_emb is None:
             image_rotary_emb = rotary_tables(tc, *grid)
@@ -613,11 +764,11 @@ def denoise(transformer: CogVideoXTransformer3DModel, scheduler: CogVideoXDDIMSc
     rows = None
     for i, t in enumerate(scheduler.timesteps.tolist()):
         # torch.cat([latents] * 2), the channel concat and the patch unfold: ONE set of rows, embedded for every CFG entry
-        rows = ops.dit_patch_rows(latents, img, p, out=rows)
-        noise_rows = transformer.forward_rows(rows, grid, text, float(t), image_rotary_emb=image_rotary_emb)
+        rows = ops.dit_patch_rows(latents, img, p, out=rows, **glue)
+        noise_rows = transformer.forward_rows(rows, grid, text, float(t), image_rotary_emb=image_rotary_emb, **extra)
         g = dynamic_guidance(guidance_scale, num_inference_steps, t) if use_dynamic_cfg else guidance_scale
         # noise_pred.float(), the CFG combine, scheduler.step and the cast back: one launch, in place
-        ops.dit_cfg_ddim_step(noise_rows, latents, p, 2 if cfg else 1, g, *scheduler.coefficients(int(t)))
+        ops.dit_cfg_ddim_step(noise_rows, latents, p, 2 if cfg else 1, g, *scheduler.coefficients(int(t)), **glue)
         if callback is not None:
             callback(i, t, latents.clone())         # a tensor of the callback's own, as the out-of-place loop handed out
     return latents

@@ -3,10 +3,13 @@
 // proj_out's token rows into the latents.  Both HBM/latency-bound.  A token row holds p x p = 4 pixels of every channel, channel
 // major: one thread moves one 16-byte piece of a row = 2 channels x (py, px).  Lanes run along x, so the px pairs of neighbouring
 // patches are one contiguous run of a latent plane's line; the grid rule is prepare_input_kernel's (elementwise.hip).
+// The temporal-patch pair (include/lkgd_hip_dit_tpatch.h, CogVideoX 1.5: p_t = 2) is the same two kernels instantiated with T3: a
+// piece is then ONE channel x (pt, py, px), its four 2-element runs two frames x two lines apart instead of two channels x two lines.
 #include <type_traits>
 
 #include "common.h"
 #include "../../include/lkgd_hip_dit_loop.h"
+#include "../../include/lkgd_hip_dit_tpatch.h"
 
 static unsigned dit_grid_for(long long work_items, int per_block) {
   long long g = (work_items + per_block - 1) / per_block;
@@ -28,30 +31,43 @@ __device__ __forceinline__ dit_piece dit_piece_of(long long i, int w, int h, int
   return d;
 }
 
+// where a piece's 2 x 2 runs of (px, px + 1) start in [.., C, H, W] planes, and the stride between its two outer runs.  2-D patches
+// (T3 = false): piece q = the channels 2q, 2q + 1 of frame bf, runs (cc, py).  Temporal patches (T3 = true, p_t = 2): piece q = channel
+// q of the frames 2 bf, 2 bf + 1, runs (pt, py) - column ((c p_t + pt) p + py) p + px of a row
+template <bool T3>
+__device__ __forceinline__ long long dit_piece_planes(long long bf, int c, int C, long long HW, long long& outer) {
+  outer = T3 ? C * HW : HW;
+  return ((T3 ? 2 * bf : bf) * C + c) * HW;
+}
+
 template <typename T>
-__device__ __forceinline__ void dit_gather(const T* __restrict__ planes, int H, int W, int y, int x, half8_t& o) {
+__device__ __forceinline__ void dit_gather(const T* __restrict__ src0, long long outer, int W, half8_t& o) {
 #pragma unroll
-  for (int cc = 0; cc < 2; ++cc)
+  for (int a = 0; a < 2; ++a)
 #pragma unroll
     for (int py = 0; py < 2; ++py) {
-      const T* src = planes + ((long long)cc * H + 2 * y + py) * W + 2 * x;
-      o[cc * 4 + py * 2] = (half_t)src[0];
-      o[cc * 4 + py * 2 + 1] = (half_t)src[1];
+      const T* src = src0 + a * outer + (long long)py * W;
+      o[a * 4 + py * 2] = (half_t)src[0];
+      o[a * 4 + py * 2 + 1] = (half_t)src[1];
     }
 }
 
-// ---- torch.cat([latents.half(), image_latents], 2) -> patch rows [B F h w, (c, py, px)]; C2 = channels of a row (C or 2 C)
-template <typename LT>
+// ---- torch.cat([latents.half(), image_latents], 2) -> patch rows [B F h w, (c, py, px)] (T3: [B F/2 h w, (c, pt, py, px)], bf = b F/2 +
+// ft); C2 = channels of a row (C or 2 C)
+template <typename LT, bool T3>
 __global__ __launch_bounds__(256) void dit_patch_rows_kernel(const LT* __restrict__ latents, const half_t* __restrict__ image_latents,
                                                              int C, int C2, int H, int W, long long total,
                                                              half_t* __restrict__ out, int ldp) {
-  const int h = H / 2, w = W / 2, pieces = C2 / 2;
+  const int h = H / 2, w = W / 2, pieces = T3 ? C2 : C2 / 2;
+  const long long HW = (long long)H * W;
   for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
     const dit_piece d = dit_piece_of(i, w, h, pieces);
-    const int c0 = 2 * d.q;               // C is even: a piece never straddles the two tensors
+    const int c0 = T3 ? d.q : 2 * d.q;    // 2-D: C is even, a piece never straddles the two tensors
+    const long long at = (long long)2 * d.y * W + 2 * d.x;
+    long long outer;
     half8_t o;
-    if (c0 < C) dit_gather(latents + (d.bf * C + c0) * H * W, H, W, d.y, d.x, o);
-    else dit_gather(image_latents + (d.bf * C + (c0 - C)) * H * W, H, W, d.y, d.x, o);
+    if (c0 < C) dit_gather(latents + dit_piece_planes<T3>(d.bf, c0, C, HW, outer) + at, outer, W, o);
+    else dit_gather(image_latents + dit_piece_planes<T3>(d.bf, c0 - C, C, HW, outer) + at, outer, W, o);
     *(half8_t*)(out + ((d.bf * h + d.y) * w + d.x) * ldp + d.q * 8) = o;
   }
 }
@@ -74,21 +90,23 @@ __device__ __forceinline__ float ddim_advance(const ddim_t& k, int cfg, float u,
   return ax + bx;
 }
 
-template <typename LT>
+template <typename LT, bool T3>
 __global__ __launch_bounds__(256) void dit_cfg_ddim_kernel(const half_t* __restrict__ noise, int ldn, LT* __restrict__ latents,
                                                            int C, int H, int W, int cfg, long long cond_rows, ddim_t k,
                                                            long long total) {
-  const int h = H / 2, w = W / 2, pieces = C / 2;
+  const int h = H / 2, w = W / 2, pieces = T3 ? C : C / 2;
+  const long long HW = (long long)H * W;
   for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
     const dit_piece d = dit_piece_of(i, w, h, pieces);
     const long long row = (d.bf * h + d.y) * w + d.x;
     const half8_t u = *(const half8_t*)(noise + row * ldn + d.q * 8);
     half8_t c = u;
     if (cfg == 2) c = *(const half8_t*)(noise + (row + cond_rows) * ldn + d.q * 8);
-    LT* planes = latents + (d.bf * C + 2 * d.q) * H * W;
+    long long outer;
+    LT* at = latents + dit_piece_planes<T3>(d.bf, T3 ? d.q : 2 * d.q, C, HW, outer) + (long long)2 * d.y * W + 2 * d.x;
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
-      LT* px = planes + ((long long)(e >> 2) * H + 2 * d.y + ((e >> 1) & 1)) * W + 2 * d.x + (e & 1);
+      LT* px = at + (e >> 2) * outer + (long long)((e >> 1) & 1) * W + (e & 1);
       *px = (LT)ddim_advance(k, cfg, (float)u[e], (float)c[e], (float)*px);
     }
   }
@@ -115,7 +133,7 @@ extern "C" int lkgd_dit_patch_rows(const void* latents, int32_t latents_is_f32, 
   const long long total = (long long)B * F * (H / 2) * (W / 2) * (C2 / 2);
   return dit_launch_typed(latents_is_f32, [&](auto* tag) {
     using LT = std::remove_pointer_t<decltype(tag)>;
-    hipLaunchKernelGGL(dit_patch_rows_kernel<LT>, dim3(dit_grid_for(total, 256)), dim3(256), 0, (hipStream_t)stream,
+    hipLaunchKernelGGL((dit_patch_rows_kernel<LT, false>), dim3(dit_grid_for(total, 256)), dim3(256), 0, (hipStream_t)stream,
                        (const LT*)latents, (const half_t*)image_latents, C, (int)C2, H, W, total, (half_t*)rows_out, ldp);
   });
 }
@@ -131,7 +149,44 @@ extern "C" int lkgd_dit_cfg_ddim_step(const void* noise_rows, int32_t ldn, void*
   const ddim_t k = {guidance, a, b, sqrt_alpha, sqrt_beta};
   return dit_launch_typed(latents_is_f32, [&](auto* tag) {
     using LT = std::remove_pointer_t<decltype(tag)>;
-    hipLaunchKernelGGL(dit_cfg_ddim_kernel<LT>, dim3(dit_grid_for(total, 256)), dim3(256), 0, (hipStream_t)stream,
+    hipLaunchKernelGGL((dit_cfg_ddim_kernel<LT, false>), dim3(dit_grid_for(total, 256)), dim3(256), 0, (hipStream_t)stream,
+                       (const half_t*)noise_rows, ldn, (LT*)latents, C, H, W, cfg, rows, k, total);
+  });
+}
+
+// ---- temporal patches (include/lkgd_hip_dit_tpatch.h): a row spans p_t = 2 latent frames, a 16-byte piece is one channel's (pt, py, px)
+static int dit_shape_ok_t(int32_t B, int32_t F, int32_t C, int32_t H, int32_t W, int32_t p, int32_t p_t, long long width, int32_t ld) {
+  if (p_t != 2 || F <= 0 || F % p_t || width > 0x7fffffffll) return 0;
+  return dit_shape_ok(B, F, C, H, W, p, (int32_t)width, ld);
+}
+
+extern "C" int lkgd_dit_patch_rows_t(const void* latents, int32_t latents_is_f32, const void* image_latents, int32_t B, int32_t F,
+                                     int32_t C, int32_t H, int32_t W, int32_t p, int32_t p_t, void* rows_out, int32_t ldp,
+                                     lkgd_stream_t stream) {
+  if (!latents || !rows_out) return LKGD_E_NULL;
+  const long long C2 = image_latents ? 2ll * C : C;
+  if (!dit_shape_ok_t(B, F, C, H, W, p, p_t, C2 * 8, ldp)) return LKGD_E_SHAPE;
+  if (!aligned16(rows_out)) return LKGD_E_ALIGN;
+  const long long total = (long long)B * (F / 2) * (H / 2) * (W / 2) * C2;
+  return dit_launch_typed(latents_is_f32, [&](auto* tag) {
+    using LT = std::remove_pointer_t<decltype(tag)>;
+    hipLaunchKernelGGL((dit_patch_rows_kernel<LT, true>), dim3(dit_grid_for(total, 256)), dim3(256), 0, (hipStream_t)stream,
+                       (const LT*)latents, (const half_t*)image_latents, C, (int)C2, H, W, total, (half_t*)rows_out, ldp);
+  });
+}
+
+extern "C" int lkgd_dit_cfg_ddim_step_t(const void* noise_rows, int32_t ldn, void* latents, int32_t latents_is_f32, int32_t B,
+                                        int32_t F, int32_t C, int32_t H, int32_t W, int32_t p, int32_t p_t, int32_t cfg,
+                                        float guidance, float a, float b, float sqrt_alpha, float sqrt_beta, lkgd_stream_t stream) {
+  if (!noise_rows || !latents) return LKGD_E_NULL;
+  if (!dit_shape_ok_t(B, F, C, H, W, p, p_t, 8ll * C, ldn) || (cfg != 1 && cfg != 2)) return LKGD_E_SHAPE;
+  if (!aligned16(noise_rows)) return LKGD_E_ALIGN;
+  const long long rows = (long long)B * (F / 2) * (H / 2) * (W / 2);
+  const long long total = rows * C;
+  const ddim_t k = {guidance, a, b, sqrt_alpha, sqrt_beta};
+  return dit_launch_typed(latents_is_f32, [&](auto* tag) {
+    using LT = std::remove_pointer_t<decltype(tag)>;
+    hipLaunchKernelGGL((dit_cfg_ddim_kernel<LT, true>), dim3(dit_grid_for(total, 256)), dim3(256), 0, (hipStream_t)stream,
                        (const half_t*)noise_rows, ldn, (LT*)latents, C, H, W, cfg, rows, k, total);
   });
 }

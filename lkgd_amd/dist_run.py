@@ -287,6 +287,9 @@ class DistDiTDenoiser:
     are recomputed by tensor ops every step."""
 
     def __init__(self, transformer, scheduler, world: int, rank: int, latent_frames: int, cfg: bool = True):
+        if getattr(transformer.config, "patch_size_t", None) is not None:
+            raise LkgdHipError("DistDiTDenoiser: a patch_size_t (CogVideoX 1.5) model is not sharded - a token spans two latent "
+                               "frames, the frame split is not built; run lkgd_amd.cogvideox.denoise on one GPU")
         if not dist.is_initialized():
             raise LkgdHipError("torch.distributed is not initialised")
         self.transformer, self.scheduler = transformer, scheduler

@@ -803,7 +803,7 @@ def gated_add(x: torch.Tensor, gate: torch.Tensor, res: torch.Tensor, rows_per_b
     return out
 
 
-def _dit_latents(latents: torch.Tensor, p: int):
+def _dit_latents(latents: torch.Tensor, p: int, p_t: Optional[int] = None):
     _req_latents(latents)
     if latents.dim() != 5:
         raise _lib.LkgdHipError(f"latents must be [B, F, C, H, W], got {tuple(latents.shape)}")
@@ -811,41 +811,60 @@ def _dit_latents(latents: torch.Tensor, p: int):
     if p != 2 or H % p or W % p or (C_ * p * p) % 8:
         raise _lib.LkgdHipError(f"DiT loop glue: patch_size 2, even H and W, C * 4 a multiple of 8; got p = {p}, latents "
                                 f"{tuple(latents.shape)}")
+    if p_t is not None and (p_t != 2 or F % p_t):
+        raise _lib.LkgdHipError(f"DiT loop glue with temporal patches: patch_size_t 2 and a frame count it divides (pad_for_temporal_"
+                                f"patches); got patch_size_t = {p_t}, latents {tuple(latents.shape)}")
     return B, F, C_, H, W
 
 
 def dit_patch_rows(latents: torch.Tensor, image_latents: Optional[torch.Tensor], p: int = 2,
-                   out: Optional[torch.Tensor] = None) -> torch.Tensor:
+                   out: Optional[torch.Tensor] = None, p_t: Optional[int] = None) -> torch.Tensor:
     """[B,F,C,H,W] latents (fp16 / fp32) + fp16 image latents of the same shape (or None) -> the patch-embedding GEMM's rows
     [B*F*(H/p)*(W/p), 2C*p*p] (C*p*p without image latents), column (c*p + py)*p + px (lkgd_dit_patch_rows): one copy for
-    every CFG entry.  ``out``: an fp16 [rows, >= width] matrix or column window (row stride a multiple of 8)."""
-    B, F, C_, H, W = _dit_latents(latents, p)
+    every CFG entry.  ``out``: an fp16 [rows, >= width] matrix or column window (row stride a multiple of 8).
+    ``p_t`` (the CogVideoX 1.5 models): rows [B*(F/p_t)*(H/p)*(W/p), 2C*p_t*p*p], column ((c*p_t + pt)*p + py)*p + px
+    (lkgd_dit_patch_rows_t, include/lkgd_hip_dit_tpatch.h)."""
+    B, F, C_, H, W = _dit_latents(latents, p, p_t)
     if image_latents is not None:
         _req(image_latents, torch.float16, "image_latents")
         if tuple(image_latents.shape) != tuple(latents.shape) or not image_latents.is_contiguous():
             raise _lib.LkgdHipError(f"image_latents must be contiguous {tuple(latents.shape)}, got {tuple(image_latents.shape)}")
     rows, width = B * F * (H // p) * (W // p), (1 if image_latents is None else 2) * C_ * p * p
+    if p_t is not None:
+        rows, width = rows // p_t, width * p_t
     if out is None:
         out = torch.empty(rows, width, dtype=torch.float16, device=latents.device)
     else:
         _req(out, torch.float16, "out")
         if out.dim() != 2 or tuple(out.shape) != (rows, width) or out.stride(1) != 1:
             raise _lib.LkgdHipError(f"out must be an fp16 [{rows}, {width}] matrix, got {tuple(out.shape)}")
+    if p_t is not None:
+        check(_L().lkgd_dit_patch_rows_t(latents.data_ptr(), int(latents.dtype == torch.float32), _ptr(image_latents), B, F, C_, H, W,
+                                         p, p_t, out.data_ptr(), _ld(out), _stream()), "lkgd_dit_patch_rows_t")
+        return out
     check(_L().lkgd_dit_patch_rows(latents.data_ptr(), int(latents.dtype == torch.float32), _ptr(image_latents), B, F, C_, H, W, p,
                                    out.data_ptr(), _ld(out), _stream()), "lkgd_dit_patch_rows")
     return out
 
 
 def dit_cfg_ddim_step(noise_rows: torch.Tensor, latents: torch.Tensor, p: int, cfg: int, guidance: float, a: float, b: float,
-                      sqrt_alpha: float, sqrt_beta: float) -> torch.Tensor:
+                      sqrt_alpha: float, sqrt_beta: float, p_t: Optional[int] = None) -> torch.Tensor:
     """in-place CFG combine + DDIM update of ``latents`` [B,F,C,H,W] from proj_out's token rows [cfg*B*Tv, C*p*p] (unconditional
-    entries first; lkgd_dit_cfg_ddim_step); the scalars are ``dynamic_guidance`` / ``CogVideoXDDIMScheduler.coefficients``"""
-    B, F, C_, H, W = _dit_latents(latents, p)
+    entries first; lkgd_dit_cfg_ddim_step); the scalars are ``dynamic_guidance`` / ``CogVideoXDDIMScheduler.coefficients``.
+    ``p_t``: rows [cfg*B*Tv/p_t, C*p_t*p*p] of a temporal-patch model (lkgd_dit_cfg_ddim_step_t)"""
+    B, F, C_, H, W = _dit_latents(latents, p, p_t)
     _req(noise_rows, torch.float16, "noise_rows")
-    rows = cfg * B * F * (H // p) * (W // p)
-    if cfg not in (1, 2) or noise_rows.dim() != 2 or tuple(noise_rows.shape) != (rows, C_ * p * p) or noise_rows.stride(1) != 1:
-        raise _lib.LkgdHipError(f"noise_rows must be an fp16 [{rows}, {C_ * p * p}] matrix (cfg 1 or 2), got "
+    rows, width = cfg * B * F * (H // p) * (W // p), C_ * p * p
+    if p_t is not None:
+        rows, width = rows // p_t, width * p_t
+    if cfg not in (1, 2) or noise_rows.dim() != 2 or tuple(noise_rows.shape) != (rows, width) or noise_rows.stride(1) != 1:
+        raise _lib.LkgdHipError(f"noise_rows must be an fp16 [{rows}, {width}] matrix (cfg 1 or 2), got "
                                 f"{tuple(noise_rows.shape)}, cfg = {cfg}")
+    if p_t is not None:
+        check(_L().lkgd_dit_cfg_ddim_step_t(noise_rows.data_ptr(), _ld(noise_rows), latents.data_ptr(),
+                                            int(latents.dtype == torch.float32), B, F, C_, H, W, p, p_t, cfg, guidance, a, b, sqrt_alpha,
+                                            sqrt_beta, _stream()), "lkgd_dit_cfg_ddim_step_t")
+        return latents
     check(_L().lkgd_dit_cfg_ddim_step(noise_rows.data_ptr(), _ld(noise_rows), latents.data_ptr(), int(latents.dtype == torch.float32),
                                       B, F, C_, H, W, p, cfg, guidance, a, b, sqrt_alpha, sqrt_beta, _stream()),
           "lkgd_dit_cfg_ddim_step")

@@ -8,6 +8,12 @@
         * the per-step glue at the 2B-I2V and 5B-I2V geometries (13 x 60 x 90 latents, C = 16; both have 32 input channels, so
           the glue is the same work - the line says so instead of timing it twice): lkgd_dit_patch_rows +
           lkgd_dit_cfg_ddim_step against cat / cat / permute-copy, permute-copy / float / chunk / CFG / DDIM / half.
+    python tools/cogvideox_fuse_bench.py --v15 [--rounds 20] [--warmup 3]   one JSON line: the per-step glue of the 1.5 I2V loop
+                                                                         (include/lkgd_hip_dit_tpatch.h) at its geometry, 22 latent
+                                                                         frames x 96 x 170, C = 16 (+ 16 image channels), p_t = 2:
+                                                                         lkgd_dit_patch_rows_t + lkgd_dit_cfg_ddim_step_t against
+                                                                         cat / cat / permute-copy / permute-copy / float / CFG / DDIM /
+                                                                         half, alternating in one process; checks both bit for bit first
     python tools/cogvideox_fuse_bench.py --kernel-only N                 N launches of the fuse and of the two glue kernels and
                                                                          nothing else: the run to put under a kernel trace
                                                                          (rocprofv3 --kernel-trace --stats -- python tools/...)
@@ -109,12 +115,75 @@ def _aten_glue(lat, img2, noise_rows, g, coef, p=2):
     return patches, (a * s + b * x0).to(torch.float16)
 
 
+def _aten_glue_t(lat, img2, noise_rows, g, coef, p=2, pt=2):
+    """the per-step glue of a patch_size_t model without the kernels: CFG duplicate, channel concat, the 3-D patch unfold; the 3-D
+    un-patchify (cogvideox_transformer_3d.py:626-630), .float(), CFG, DDIM, .half()"""
+    B, F_, C_, H, W = lat.shape
+    h, w = H // p, W // p
+    x = torch.cat([lat] * 2)
+    x = torch.cat([x, img2], dim=2)
+    patches = x.permute(0, 1, 3, 4, 2).reshape(2 * B, F_ // pt, pt, h, p, w, p, 2 * C_).permute(0, 1, 3, 5, 7, 2, 4, 6) \
+        .flatten(4, 7).flatten(1, 3).contiguous()
+    noise = noise_rows.reshape(2 * B, F_ // pt, h, w, -1, pt, p, p).permute(0, 1, 5, 4, 2, 6, 3, 7).flatten(6, 7).flatten(4, 5) \
+        .flatten(1, 2).contiguous().float()
+    u, c = noise.chunk(2)
+    noise = u + g * (c - u)
+    a, b, sa, sb = coef
+    s = lat.float()
+    x0 = sa * s - sb * noise
+    return patches, (a * s + b * x0).to(torch.float16)
+
+
+def main_v15(args):
+    from lkgd_amd import cogvideox as pc
+    from lkgd_amd import ops
+    dev = torch.device("cuda", 0)
+    torch.cuda.set_device(dev)
+    F_, H, W, C_ = 22, 96, 170, 16
+    g = torch.Generator().manual_seed(1)
+    lat = torch.randn(1, F_, C_, H, W, generator=g).half().to(dev)
+    img = (0.5 * torch.randn(1, F_, C_, H, W, generator=g)).half().to(dev)
+    noise_rows = torch.randn(2 * (F_ // 2) * (H // 2) * (W // 2), C_ * 8, generator=g).half().to(dev)
+    img2 = torch.cat([img] * 2)
+    sched = pc.CogVideoXDDIMScheduler()
+    sched.set_timesteps(50)
+    t = sched.timesteps.tolist()[10]
+    gd, coef = pc.dynamic_guidance(6.0, 50, t), sched.coefficients(t)
+    rows = ops.dit_patch_rows(lat, img, p_t=2)
+    work = lat.clone()
+    ref_rows, ref_lat = _aten_glue_t(lat, img2, noise_rows, gd, coef)
+    ops.dit_cfg_ddim_step(noise_rows, work, 2, 2, gd, *coef, p_t=2)
+    # one copy of the rows serves both CFG entries: the ATen form holds them twice
+    same = bool(torch.equal(rows, ref_rows[0]) and torch.equal(rows, ref_rows[1]) and torch.equal(work, ref_lat))
+
+    def hip_glue():
+        ops.dit_patch_rows(lat, img, out=rows, p_t=2)
+        ops.dit_cfg_ddim_step(noise_rows, work, 2, 2, gd, *coef, p_t=2)
+    g_hip, g_aten = [], []
+    for i in range(args.warmup + args.rounds):
+        c = _timed(hip_glue)
+        d = _timed(lambda: _aten_glue_t(lat, img2, noise_rows, gd, coef))
+        if i >= args.warmup:
+            g_hip.append(c); g_aten.append(d)
+    med = statistics.median
+    print(json.dumps({"tool": "cogvideox_fuse_bench --v15", "rounds": args.rounds, "warmup": args.warmup,
+                      "step_glue_t": {"geometry": "22 x 96 x 170 latents, C = 16 (+ 16 image channels), p_t = 2: the 1.5 I2V loop",
+                                      "bitwise_equal_to_aten": same,
+                                      "two_launches_us_median": round(med(g_hip), 1), "aten_sequence_us_median": round(med(g_aten), 1),
+                                      "two_launches_us_min": round(min(g_hip), 1), "aten_sequence_us_min": round(min(g_aten), 1),
+                                      "not_slower": med(g_hip) <= med(g_aten)},
+                      "valid": args.rounds >= 20 and same}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=20, help="alternations of the two forms (>= 20 for a reported median)")
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--kernel-only", type=int, default=0, metavar="N")
+    ap.add_argument("--v15", action="store_true", help="the _t glue pair at the 1.5 I2V geometry instead")
     args = ap.parse_args()
+    if args.v15:
+        return main_v15(args)
     from lkgd_amd import cogvideox as pc
     from lkgd_amd import ops
     dev = torch.device("cuda", 0)

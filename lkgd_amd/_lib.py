@@ -149,6 +149,16 @@ DIT_TPATCH_SYMBOLS = {
                                         _f32, _vp]),
 }
 
+#: every symbol include/lkgd_hip_fp8.h declares (the FP8 e4m3 form of a DiT block's six linears: three dynamic per-row quantisers and
+#: the GEMM on the block-scaled matrix instruction), bound on the same library object; tests/test_fp8_cpu.py pins header, table and
+#: library to one another, tests/test_fp8_gpu.py the footprint cases
+FP8_SYMBOLS = {
+    "lkgd_quant_rows_fp8": (_i32, [_vp, _i32, _vp, _i32, _vp, _i64, _i32, _vp]),
+    "lkgd_gelu_tanh_quant_fp8": (_i32, [_vp, _i32, _vp, _i32, _vp, _i64, _i32, _vp]),
+    "lkgd_layernorm_quant_fp8": (_i32, [_vp, _i32, _i64, _i32, _vp, _vp, _f32, _vp, _i32, _vp, _vp]),
+    "lkgd_gemm_fp8": (_i32, [_vp, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp]),
+}
+
 #: include/lkgd_hip_debug.h: A/B and test knobs, per host thread; bound on the same library object, not part of the product interface
 DEBUG_SYMBOLS = {
     "lkgd_debug_set_wide_tile_n": (None, [_i32]),
@@ -183,7 +193,7 @@ def lib() -> C.CDLL:
             l = C.CDLL(LIB_PATH)
         except OSError as e:
             raise LkgdHipError(f"cannot load {LIB_PATH}: {e}") from e
-        for table in (SYMBOLS, WINDOW_SYMBOLS, DIT_SYMBOLS, DIT_LOOP_SYMBOLS, DIT_TPATCH_SYMBOLS, DEBUG_SYMBOLS):
+        for table in (SYMBOLS, WINDOW_SYMBOLS, DIT_SYMBOLS, DIT_LOOP_SYMBOLS, DIT_TPATCH_SYMBOLS, FP8_SYMBOLS, DEBUG_SYMBOLS):
             for name, (res, args) in table.items():
                 fn = getattr(l, name)       # AttributeError here = header / library mismatch
                 fn.restype, fn.argtypes = res, args

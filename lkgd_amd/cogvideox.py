@@ -36,7 +36,12 @@ MI355X design - the UNet's kernels, one joint token buffer:
   spans two latent frames, so the patch embedding is a Linear over C p_t p p columns and the grid is (F / p_t, h, w); the loop's
   glue is the ``_t`` pair of include/lkgd_hip_dit_tpatch.h; the ``ofs`` embedding (timestep-embedding kernel + two small GEMMs,
   step-invariant: once per clip) is added to the time embedding before the modulation GEMM; ``rotary_tables`` restates the
-  pipeline's ``grid_type="slice"`` branch; ``pad_for_temporal_patches`` / ``drop_temporal_padding`` restate its frame padding.
+  pipeline's ``grid_type="slice"`` branch; ``pad_for_temporal_patches`` / ``drop_temporal_padding`` restate its frame padding;
+* the opt-in FP8 mode (``lkgd_amd.fp8.quantize_to_float8`` or LKGD_DIT_FP8=1; DESIGN.md section 14, include/lkgd_hip_fp8.h): the six
+  linears of every block run on ``lkgd_gemm_fp8`` over e4m3 weights (one scale per output channel, quantised when the model packs)
+  and e4m3 activations (one scale per token row, quantised by the kernel that produces them: ``lkgd_layernorm_quant_fp8`` for the
+  two modulated norms, ``lkgd_quant_rows_fp8`` for the attention output, ``lkgd_gelu_tanh_quant_fp8`` for the feed-forward's hidden
+  rows).  Residual stream, norms, q/k norm + rope, attention, gates and every other linear stay as they are.
 """
 from __future__ import annotations
 
@@ -49,6 +54,7 @@ import numpy as np
 import torch
 import torch.nn as nn
 
+from . import fp8 as fp8_mode
 from . import ops
 from ._lib import LkgdHipError
 from .lk_fuse import lk_fuse_tokens, pack_lk_tokens
@@ -269,11 +275,15 @@ class CogVideoXBlock(nn.Module):
         self.norm2 = CogVideoXLayerNormZero(time_embed_dim, dim, eps)
         self.ff = FeedForward(dim)
 
-    def pack(self):
+    def pack(self, fp8: bool = False):
+        """``fp8``: the six linears pack as (e4m3 bytes [N, K], fp32 scale [N], bias) and their fp16 copies are not made"""
         a, f = self.attn1, self.ff
 
         def lin(m):
-            return pack_linear(m.weight), (_f32(m.bias) if m.bias is not None else None)
+            bias = _f32(m.bias) if m.bias is not None else None
+            if fp8:
+                return fp8_mode.quantize_weight(m.weight) + (bias,)
+            return pack_linear(m.weight), bias
         self._pk = SimpleNamespace(q=lin(a.to_q), k=lin(a.to_k), v=lin(a.to_v), o=lin(a.to_out[0]),
                                    nq=(_f32(a.norm_q.weight), _f32(a.norm_q.bias)), nk=(_f32(a.norm_k.weight), _f32(a.norm_k.bias)),
                                    f1=lin(f.net[0].proj), f2=lin(f.net[2]))
@@ -337,6 +347,8 @@ class CogVideoXTransformer3DModel(nn.Module):
         self.norm_out = AdaLayerNorm(cfg.time_embed_dim, 2 * d, cfg.norm_eps)
         self.proj_out = nn.Linear(d, cfg.patch_size * cfg.patch_size * pt * cfg.out_channels)              # :326-333
         self.init_quaternion_modules()
+        #: None, or "fp8" after ``lkgd_amd.fp8.quantize_to_float8`` (the block linears then pack and run as e4m3)
+        self.quantization = None
         self._pk = None
         self._pos = {}
 
@@ -407,14 +419,18 @@ class CogVideoXTransformer3DModel(nn.Module):
     def prepare(self):
         if self._pk is not None:
             return
+        fp8 = fp8_mode.active(self)
+        if fp8 and self.inner_dim % 128:
+            raise LkgdHipError(f"the FP8 mode (quantize_to_float8 / LKGD_DIT_FP8) tiles N and K by 128: inner dim {self.inner_dim} is "
+                               "not a multiple")
         if self.device.type != "cuda":
             raise LkgdHipError("lkgd_amd DiT runs on MI355X only: move the module to cuda first")
         for b in self.transformer_blocks:
-            b.pack()
+            b.pack(fp8)
         self.time_embedding.pack()
         if self.ofs_embedding is not None:
             self.ofs_embedding.pack()
-        pk = SimpleNamespace()
+        pk = SimpleNamespace(fp8=fp8)
         # every block's two modulation linears as ONE [blocks * 2 * 6D, Te] GEMM per step (+ norm_out's [2D, Te])
         mods = [m for b in self.transformer_blocks for m in (b.norm1.linear, b.norm2.linear)] + [self.norm_out.linear]
         pk.w_mod = torch.cat([pack_linear(m.weight) for m in mods], dim=0).contiguous()
@@ -533,6 +549,8 @@ class CogVideoXTransformer3DModel(nn.Module):
         (c, pt, py, px)), ``grid`` = (F / p_t, h, w), the result [B * Tv, out_channels * p_t * p * p]; ``ofs_emb`` fp16
         [B, time_embed_dim] (``embed_ofs``) exactly when the model has an ``ofs_embedding``: added to the time embedding in fp16
         (:517) before the modulation GEMM."""
+        if shard is not None and fp8_mode.active(self):
+            raise LkgdHipError("frame sharding together with the FP8 mode (quantize_to_float8 / LKGD_DIT_FP8) is not built")
         self.prepare()
         pk, cfg, dev = self._pk, self.config, self.device
         B = fused_text.shape[0]
@@ -620,12 +638,26 @@ class CogVideoXTransformer3DModel(nn.Module):
                 ops.layernorm(X[r0:r0 + Tt], eff_g[b, i, which, 0], eff_b[b, i, which, 0], eps, out=n[r0:r0 + Tt])
                 ops.layernorm(X[r0 + Tt:r0 + L], eff_g[b, i, which, 1], eff_b[b, i, which, 1], eps, out=n[r0 + Tt:r0 + L])
             return n
+
+        def modnorm_fp8(i, which):
+            """``modnorm`` straight into e4m3 rows [T, D] + one scale per row: what the next GEMMs take"""
+            nq = torch.empty(T, D, dtype=torch.uint8, device=dev)
+            ns = torch.empty(T, dtype=torch.float32, device=dev)
+            for b in range(B):
+                for r0, r1, st in ((b * L, b * L + Tt, 0), (b * L + Tt, (b + 1) * L, 1)):
+                    ops.layernorm_quant_fp8(X[r0:r1], eff_g[b, i, which, st], eff_b[b, i, which, st], eps, q=nq[r0:r1], scale=ns[r0:r1])
+            return nq, ns
+        fp8 = pk.fp8
         for i, blkm in enumerate(self.transformer_blocks):
             bp = blkm._pk
-            n = modnorm(i, 0)
+            n = modnorm_fp8(i, 0) if fp8 else modnorm(i, 0)
             q, k, v = (torch.empty(T, D, dtype=torch.float16, device=dev) for _ in range(3))
-            for dst, (wgt, bias) in ((q, bp.q), (k, bp.k), (v, bp.v)):
-                ops.gemm(n, wgt, dst, M=T, N=D, K=D, bias=bias)
+            if fp8:     # one quantised activation feeds the three projections
+                for dst, (wq, ws, bias) in ((q, bp.q), (k, bp.k), (v, bp.v)):
+                    ops.gemm_fp8(*n, wq, ws, bias, out=dst)
+            else:
+                for dst, (wgt, bias) in ((q, bp.q), (k, bp.k), (v, bp.v)):
+                    ops.gemm(n, wgt, dst, M=T, N=D, K=D, bias=bias)
             if rope is not None:    # per-head qk norm + rotation of the video rows, q and k in one launch
                 ops.qk_norm_rope(q, k, heads, bp.nq, bp.nk, 1e-6, rope, L, Tt)
             else:
@@ -640,6 +672,14 @@ class CogVideoXTransformer3DModel(nn.Module):
                     full[Tt:].copy_(shard.gather(loc[Tt:]))
                 ops.attn_spatial(q, KV[0], KV[1], a, 1, Tt + Tv_all, heads, Sq=L)
             o = torch.empty(T, D, dtype=torch.float16, device=dev)
+            if fp8:
+                ops.gemm_fp8(*ops.quant_rows_fp8(a), *bp.o, out=o)
+                X = ops.gated_add(o, gates[i, 0].reshape(2 * B, D), X, L, Tt)
+                hdn = torch.empty(T, 4 * D, dtype=torch.float16, device=dev)
+                ops.gemm_fp8(*modnorm_fp8(i, 1), *bp.f1, out=hdn)
+                ops.gemm_fp8(*ops.gelu_tanh_quant_fp8(hdn), *bp.f2, out=o)      # GELU and Q in one pass over the hidden rows
+                X = ops.gated_add(o, gates[i, 1].reshape(2 * B, D), X, L, Tt)
+                continue
             ops.gemm(a, bp.o[0], o, M=T, N=D, K=D, bias=bp.o[1])
             X = ops.gated_add(o, gates[i, 0].reshape(2 * B, D), X, L, Tt)
             n = modnorm(i, 1)

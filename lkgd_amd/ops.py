@@ -953,3 +953,80 @@ def resize_bicubic_ac(x: torch.Tensor, ho: int, wo: int) -> torch.Tensor:
     check(_L().lkgd_resize_bicubic_ac(x.data_ptr(), b * c, h, w, out.data_ptr(), ho, wo, _stream()),
           "lkgd_resize_bicubic_ac")
     return out
+
+
+# ---- FP8 (e4m3fn) block linears of the DiT: include/lkgd_hip_fp8.h ----------------------------------------------------------------
+def _fp8_rows(x: torch.Tensor, q: Optional[torch.Tensor], scale: Optional[torch.Tensor], what: str):
+    """(q, scale) of a quantiser call on fp16 ``x`` [T, K]: uint8 [T, K] (row stride a multiple of 16) and fp32 [T], allocated
+    when not given"""
+    _req(x, torch.float16, "x")
+    if x.dim() != 2 or x.stride(1) != 1:
+        raise _lib.LkgdHipError(f"{what}: x must be [T, K] with contiguous channels, got {tuple(x.shape)}")
+    T, K = x.shape
+    if q is None:
+        q = torch.empty(T, K, dtype=torch.uint8, device=x.device)
+    if scale is None:
+        scale = torch.empty(T, dtype=torch.float32, device=x.device)
+    _req(q, torch.uint8, "q"); _req(scale, torch.float32, "scale")
+    if q.dim() != 2 or tuple(q.shape) != (T, K) or q.stride(1) != 1 or tuple(scale.shape) != (T,) or not scale.is_contiguous():
+        raise _lib.LkgdHipError(f"{what}: q must be uint8 [{T}, {K}] and scale contiguous fp32 [{T}], got {tuple(q.shape)} / "
+                                f"{tuple(scale.shape)}")
+    return q, scale
+
+
+def quant_rows_fp8(x: torch.Tensor, q: Optional[torch.Tensor] = None, scale: Optional[torch.Tensor] = None):
+    """fp16 [T, K] -> (e4m3fn bytes uint8 [T, K], fp32 scale [T]): the per-row statement Q of include/lkgd_hip_fp8.h, one launch"""
+    q, scale = _fp8_rows(x, q, scale, "quant_rows_fp8")
+    check(_L().lkgd_quant_rows_fp8(x.data_ptr(), _ld(x), q.data_ptr(), _ld(q), scale.data_ptr(), x.shape[0], x.shape[1], _stream()),
+          "lkgd_quant_rows_fp8")
+    return q, scale
+
+
+def gelu_tanh_quant_fp8(x: torch.Tensor, q: Optional[torch.Tensor] = None, scale: Optional[torch.Tensor] = None):
+    """``quant_rows_fp8(gelu_tanh(x))`` exactly, in one launch and without the fp16 round trip (x is left as it is)"""
+    q, scale = _fp8_rows(x, q, scale, "gelu_tanh_quant_fp8")
+    check(_L().lkgd_gelu_tanh_quant_fp8(x.data_ptr(), _ld(x), q.data_ptr(), _ld(q), scale.data_ptr(), x.shape[0], x.shape[1],
+                                        _stream()), "lkgd_gelu_tanh_quant_fp8")
+    return q, scale
+
+
+def layernorm_quant_fp8(x: torch.Tensor, gamma: Optional[torch.Tensor], beta: Optional[torch.Tensor], eps: float,
+                        q: Optional[torch.Tensor] = None, scale: Optional[torch.Tensor] = None):
+    """``quant_rows_fp8(layernorm(x, gamma, beta, eps))`` exactly, in one launch; gamma / beta fp32 [C] or both None"""
+    q, scale = _fp8_rows(x, q, scale, "layernorm_quant_fp8")
+    if (gamma is None) != (beta is None):
+        raise _lib.LkgdHipError("layernorm_quant_fp8: gamma and beta are given together or not at all")
+    for name, t in (("gamma", gamma), ("beta", beta)):
+        if t is not None:
+            _req(t, torch.float32, name)
+            if tuple(t.shape) != (x.shape[1],) or not t.is_contiguous():
+                raise _lib.LkgdHipError(f"layernorm_quant_fp8: {name} must be a contiguous fp32 [{x.shape[1]}] vector")
+    check(_L().lkgd_layernorm_quant_fp8(x.data_ptr(), _ld(x), x.shape[0], x.shape[1], _ptr(gamma), _ptr(beta), eps, q.data_ptr(),
+                                        _ld(q), scale.data_ptr(), _stream()), "lkgd_layernorm_quant_fp8")
+    return q, scale
+
+
+def gemm_fp8(a: torch.Tensor, a_scale: torch.Tensor, w: torch.Tensor, w_scale: torch.Tensor, bias: Optional[torch.Tensor],
+             out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out[m, n] = fp16((sum_k a[m, k] w[n, k]) a_scale[m] w_scale[n] + bias[n]): a uint8 [M, K] and w uint8 [N, K] hold e4m3fn
+    bytes (K contiguous), the scales and the bias are fp32; N and K multiples of 128 (lkgd_gemm_fp8)"""
+    _req(a, torch.uint8, "a"); _req(w, torch.uint8, "w"); _req(a_scale, torch.float32, "a_scale"); _req(w_scale, torch.float32, "w_scale")
+    if a.dim() != 2 or w.dim() != 2 or a.shape[1] != w.shape[1] or a.stride(1) != 1 or w.stride(1) != 1:
+        raise _lib.LkgdHipError(f"gemm_fp8: a [M, K] and w [N, K] must share K and be K-contiguous, got {tuple(a.shape)} / "
+                                f"{tuple(w.shape)}")
+    (M, K), N = a.shape, w.shape[0]
+    if tuple(a_scale.shape) != (M,) or tuple(w_scale.shape) != (N,) or not a_scale.is_contiguous() or not w_scale.is_contiguous():
+        raise _lib.LkgdHipError(f"gemm_fp8: a_scale must be contiguous fp32 [{M}] and w_scale [{N}]")
+    if bias is not None:
+        _req(bias, torch.float32, "bias")
+        if tuple(bias.shape) != (N,) or not bias.is_contiguous():
+            raise _lib.LkgdHipError(f"gemm_fp8: bias must be a contiguous fp32 [{N}] vector")
+    if out is None:
+        out = torch.empty(M, N, dtype=torch.float16, device=a.device)
+    _req(out, torch.float16, "out")
+    if out.dim() != 2 or tuple(out.shape) != (M, N) or out.stride(1) != 1:
+        raise _lib.LkgdHipError(f"gemm_fp8: out must be fp16 [{M}, {N}], got {tuple(out.shape)}")
+    # a member of the GEMM family for the live roofline and the replay plan: the same events and FLOP accounting as ``gemm``
+    _gemm_family("lkgd_gemm_fp8", (a.data_ptr(), _ld(a), a_scale.data_ptr(), w.data_ptr(), _ld(w), w_scale.data_ptr(), _ptr(bias),
+                                   out.data_ptr(), _ld(out), M, N, K), 2.0 * M * N * K)
+    return out

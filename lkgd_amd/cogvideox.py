@@ -150,6 +150,18 @@ def rope_crop_region(grid_h: int, grid_w: int, base_w: int, base_h: int):
     return (top, left), (top + rh, left + rw)
 
 
+def _rope_3d(d: int, gt, gh, gw, frames: int, h: int, w: int):
+    """the 1-D tables of the positions gt / gh / gw (the first h / w rows of the height / width tables) expanded over the
+    (frames, h, w) grid -> (cos, sin) [frames * h * w, d]"""
+    dt, ds = d // 4, d // 8 * 3
+    out = []
+    for ct, ch, cw in zip(_rope_1d(dt, gt), _rope_1d(ds, gh), _rope_1d(ds, gw)):
+        ch, cw = ch[:h], cw[:w]
+        out.append(torch.cat([ct[:, None, None, :].expand(frames, h, w, dt), ch[None, :, None, :].expand(frames, h, w, ds),
+                              cw[None, None, :, :].expand(frames, h, w, ds)], dim=-1).reshape(frames * h * w, d).contiguous())
+    return out[0], out[1]
+
+
 def rotary_tables(config, frames: int, h: int, w: int):
     """the pipeline's ``_prepare_rotary_positional_embeddings`` for ``patch_size_t is None``
     (pipeline_cogvideox_image2video.py:544-571) -> (cos, sin) fp32 [frames * h * w, attention_head_dim]; frames / h / w are the
@@ -157,40 +169,22 @@ def rotary_tables(config, frames: int, h: int, w: int):
     ``get_resize_crop_region_for_grid`` and ``get_3d_rotary_pos_embed`` (linspace grid over the crop region of the configured
     sample grid, theta 10 000): dim/4 temporal channels, then 3 dim/8 for the height and 3 dim/8 for the width (16 + 24 + 24 of
     64), each frequency repeated for the pair (2i, 2i+1) it rotates.  Tested by its properties only.
-    With ``config.patch_size_t`` (the 1.5 models) it is the pipeline's ``grid_type="slice"`` branch (:572-584) instead; ``frames`` is
-    then the token grid's (latent frames + p_t - 1) // p_t, as the pipeline passes it (``_rotary_tables_slice``)."""
-    d = config.attention_head_dim
-    p = config.patch_size
+    With ``config.patch_size_t`` (the 1.5 models) it is the pipeline's ``grid_type="slice"`` branch (:572-584) instead ([EXT]
+    ``get_3d_rotary_pos_embed(grid_type="slice", max_size=(max_h, max_w))``): the integer positions 0 .. max - 1 of the configured
+    sample grid, the first h (w) rows of their tables - no crop region, no linspace; ``frames`` is then the token grid's
+    (latent frames + p_t - 1) // p_t, as the pipeline passes it."""
+    d, p = config.attention_head_dim, config.patch_size
+    max_h, max_w = config.sample_height // p, config.sample_width // p
     if getattr(config, "patch_size_t", None):
-        return _rotary_tables_slice(d, frames, h, w, config.sample_height // p, config.sample_width // p)
-    (top, left), (bottom, right) = rope_crop_region(h, w, config.sample_width // p, config.sample_height // p)
-    gh = torch.linspace(top, bottom * (h - 1) / h, h, dtype=torch.float32)
-    gw = torch.linspace(left, right * (w - 1) / w, w, dtype=torch.float32)
-    gt = torch.arange(frames, dtype=torch.float32)
-    dt, ds = d // 4, d // 8 * 3
-    out = []
-    for ct, ch, cw in zip(_rope_1d(dt, gt), _rope_1d(ds, gh), _rope_1d(ds, gw)):
-        out.append(torch.cat([ct[:, None, None, :].expand(frames, h, w, dt), ch[None, :, None, :].expand(frames, h, w, ds),
-                              cw[None, None, :, :].expand(frames, h, w, ds)], dim=-1).reshape(frames * h * w, d).contiguous())
-    return out[0], out[1]
-
-
-def _rotary_tables_slice(d: int, frames: int, h: int, w: int, max_h: int, max_w: int):
-    """PARITY UNPINNED: restates diffusers' [EXT] ``get_3d_rotary_pos_embed(grid_type="slice", max_size=(max_h, max_w))``: the
-    1-D tables of the integer positions 0 .. max - 1 of the configured sample grid, of which the first h (w) rows are taken - no
-    crop region, no linspace; positions 0 .. frames - 1 in time.  The same 16 + 24 + 24 channel split and pair repetition."""
-    if h > max_h or w > max_w:
-        raise LkgdHipError(f"rotary_tables: a {h} x {w} token grid exceeds the {max_h} x {max_w} (sample_height // patch_size, "
-                           "sample_width // patch_size) the 1.5 tables are sliced from")
-    dt, ds = d // 4, d // 8 * 3
-    gt = torch.arange(frames, dtype=torch.float32)
-    gh, gw = torch.arange(max_h, dtype=torch.float32), torch.arange(max_w, dtype=torch.float32)
-    out = []
-    for ct, ch, cw in zip(_rope_1d(dt, gt), _rope_1d(ds, gh), _rope_1d(ds, gw)):
-        ch, cw = ch[:h], cw[:w]
-        out.append(torch.cat([ct[:, None, None, :].expand(frames, h, w, dt), ch[None, :, None, :].expand(frames, h, w, ds),
-                              cw[None, None, :, :].expand(frames, h, w, ds)], dim=-1).reshape(frames * h * w, d).contiguous())
-    return out[0], out[1]
+        if h > max_h or w > max_w:
+            raise LkgdHipError(f"rotary_tables: a {h} x {w} token grid exceeds the {max_h} x {max_w} (sample_height // patch_size, "
+                               "sample_width // patch_size) the 1.5 tables are sliced from")
+        gh, gw = torch.arange(max_h, dtype=torch.float32), torch.arange(max_w, dtype=torch.float32)
+    else:
+        (top, left), (bottom, right) = rope_crop_region(h, w, max_w, max_h)
+        gh = torch.linspace(top, bottom * (h - 1) / h, h, dtype=torch.float32)
+        gw = torch.linspace(left, right * (w - 1) / w, w, dtype=torch.float32)
+    return _rope_3d(d, torch.arange(frames, dtype=torch.float32), gh, gw, frames, h, w)
 
 
 def pad_for_temporal_patches(latents, image_latents, p_t: Optional[int]):
@@ -287,6 +281,62 @@ class CogVideoXBlock(nn.Module):
         self._pk = SimpleNamespace(q=lin(a.to_q), k=lin(a.to_k), v=lin(a.to_v), o=lin(a.to_out[0]),
                                    nq=(_f32(a.norm_q.weight), _f32(a.norm_q.bias)), nk=(_f32(a.norm_k.weight), _f32(a.norm_k.bias)),
                                    f1=lin(f.net[0].proj), f2=lin(f.net[2]))
+
+    def run(self, st, X, eff_g, eff_b, gates):
+        """the joint rows X [B * L, D] -> the new X.  ``st``: ``forward_rows``' sizes, rotary tables, shard and row format; eff_g /
+        eff_b [B, norm (1, 2), stream, D] and gates [norm, B, stream, D]: this block's modulation"""
+        bp, rows, B, L, Tt, heads = self._pk, st.rows, st.B, st.L, st.Tt, st.heads
+        T, D = X.shape
+
+        def modnorm(which):     # norm(x) * (1 + scale) + shift of both streams -> the operand of the next linears
+            n = rows.empty(T, D, X.device)
+            for b in range(B):
+                for r0, r1, s in ((b * L, b * L + Tt, 0), (b * L + Tt, (b + 1) * L, 1)):
+                    rows.norm(X[r0:r1], eff_g[b, which, s], eff_b[b, which, s], st.eps, [t[r0:r1] for t in n])
+            return n
+
+        def empty(width=D):
+            return torch.empty(T, width, dtype=torch.float16, device=X.device)
+        n = modnorm(0)
+        q, k, v = empty(), empty(), empty()
+        for dst, lin in ((q, bp.q), (k, bp.k), (v, bp.v)):      # one operand feeds the three
+            rows.linear(n, lin, dst)
+        if st.rope is not None:    # per-head qk norm + rotation of the video rows, q and k in one launch
+            ops.qk_norm_rope(q, k, heads, bp.nq, bp.nk, 1e-6, st.rope, L, Tt)
+        else:
+            ops.layernorm(q.view(T * heads, 64), bp.nq[0], bp.nq[1], 1e-6, out=q.view(T * heads, 64))     # per-head qk norm
+            ops.layernorm(k.view(T * heads, 64), bp.nk[0], bp.nk[1], 1e-6, out=k.view(T * heads, 64))
+        a = empty()
+        if st.shard is None:
+            ops.attn_spatial(q, k, v, a, B, L, heads)
+        else:                   # keys / values of every frame of this CFG half: text rows (replicated) + gathered video rows
+            for full, loc in zip(st.KV, (k, v)):
+                full[:Tt].copy_(loc[:Tt])
+                full[Tt:].copy_(st.shard.gather(loc[Tt:]))
+            ops.attn_spatial(q, st.KV[0], st.KV[1], a, 1, st.KV[0].shape[0], heads, Sq=L)
+        o = empty()
+        rows.linear(rows.of(a), bp.o, o)
+        X = ops.gated_add(o, gates[0].reshape(2 * B, D), X, L, Tt)
+        hdn = empty(4 * D)
+        rows.linear(modnorm(1), bp.f1, hdn)
+        rows.linear(rows.gelu(hdn), bp.f2, o)
+        return ops.gated_add(o, gates[1].reshape(2 * B, D), X, L, Tt)
+
+
+# the five places where the fp16 and the FP8 block differ.  A block linear's operand is a tuple: (fp16 rows,) for ``ops.gemm`` over
+# (w, bias), or (e4m3 bytes, a scale per row) from the kernel that produces the rows, for ``ops.gemm_fp8`` over (bytes, scale, bias)
+_FP16_ROWS = SimpleNamespace(
+    empty=lambda T, D, dev: (torch.empty(T, D, dtype=torch.float16, device=dev),),
+    norm=lambda x, gamma, beta, eps, out: ops.layernorm(x, gamma, beta, eps, out=out[0]),
+    linear=lambda n, lin, out: ops.gemm(n[0], lin[0], out, M=out.shape[0], N=out.shape[1], K=n[0].shape[1], bias=lin[1]),
+    of=lambda a: (a,),
+    gelu=lambda hdn: (ops.gelu_tanh_(hdn),))
+_FP8_ROWS = SimpleNamespace(
+    empty=lambda T, D, dev: (torch.empty(T, D, dtype=torch.uint8, device=dev), torch.empty(T, dtype=torch.float32, device=dev)),
+    norm=lambda x, gamma, beta, eps, out: ops.layernorm_quant_fp8(x, gamma, beta, eps, q=out[0], scale=out[1]),
+    linear=lambda n, lin, out: ops.gemm_fp8(*n, *lin, out=out),
+    of=ops.quant_rows_fp8,
+    gelu=ops.gelu_tanh_quant_fp8)       # GELU and Q in one pass over the hidden rows
 
 
 class CogVideoXPatchEmbed(nn.Module):
@@ -497,24 +547,20 @@ class CogVideoXTransformer3DModel(nn.Module):
         [B, F, out_channels, h, w] fp16: patch unfold, ``forward_rows``, un-patchify (two torch permutes at the API edge).
         ``ofs``: a scalar or a [1] / [B] tensor, exactly when the model has an ``ofs_embedding``."""
         B, Fr, C_, H, W = hidden_states.shape
-        p, pt = self.config.patch_size, self.config.patch_size_t
+        p, pt = self.config.patch_size, self.config.patch_size_t or 1
         h, w = H // p, W // p
         if (self.ofs_embedding is None) != (ofs is None):
             raise LkgdHipError("ofs is given exactly when the model has an ofs_embedding (config ofs_embed_dim)")
-        if pt is not None and Fr % pt:
+        if Fr % pt:
             raise LkgdHipError(f"patch_size_t {pt} does not divide the {Fr} latent frames: pad_for_temporal_patches first")
-        ofs_emb = self.embed_ofs(ofs, B) if ofs is not None else None
+        extra = dict(ofs_emb=self.embed_ofs(ofs, B)) if ofs is not None else {}
         xh = hidden_states.to(device=self.device, dtype=torch.float16)
-        if pt is None:
-            patches = xh.reshape(B, Fr, C_, h, p, w, p).permute(0, 1, 3, 5, 2, 4, 6).reshape(B * Fr * h * w, C_ * p * p).contiguous()
-            out_tok = self.forward_rows(patches, (Fr, h, w), fused_text, timestep, shard=shard, image_rotary_emb=image_rotary_emb)
-            out = out_tok.reshape(B, Fr, h, w, -1, p, p).permute(0, 1, 4, 2, 5, 3, 6).flatten(5, 6).flatten(3, 4)
-            return out.contiguous()
-        # [EXT diffusers CogVideoXPatchEmbed, 1.5] (column (c, pt, py, px)), and cogvideox_transformer_3d.py:626-630
+        # [EXT diffusers CogVideoXPatchEmbed, 1.5] (column (c, pt, py, px)), and cogvideox_transformer_3d.py:626-630; with pt = 1
+        # bit for bit the 2-D unfold (column (c, py, px)) and un-patchify of :624-625
         patches = xh.permute(0, 1, 3, 4, 2).reshape(B, Fr // pt, pt, h, p, w, p, C_).permute(0, 1, 3, 5, 7, 2, 4, 6) \
             .flatten(4, 7).flatten(1, 3).reshape(B * (Fr // pt) * h * w, C_ * pt * p * p).contiguous()
         out_tok = self.forward_rows(patches, (Fr // pt, h, w), fused_text, timestep, shard=shard, image_rotary_emb=image_rotary_emb,
-                                    ofs_emb=ofs_emb)
+                                    **extra)
         out = out_tok.reshape(B, Fr // pt, h, w, -1, pt, p, p).permute(0, 1, 5, 4, 2, 6, 3, 7).flatten(6, 7).flatten(4, 5).flatten(1, 2)
         return out.contiguous()
 
@@ -539,16 +585,23 @@ class CogVideoXTransformer3DModel(nn.Module):
         ``grid`` = (F, h, w) tokens, Tv = F h w; fused_text [B, L, 4096] fp16.  Bv divides B: batch entry b embeds the rows of
         entry b % Bv, so ONE copy of the rows (Bv = 1) serves both CFG entries, as ``torch.cat([latents] * 2)`` did.  Returns
         proj_out's token rows [B * Tv, out_channels * p * p] fp16 (before the un-patchify).
-        ``image_rotary_emb`` = (cos, sin) fp32 [F h w tokens, 64] (``rotary_tables``): every
-        layer's per-head q / k norms and the rotation of their video rows are then ONE launch of ``lkgd_qk_norm_rope``; None =
-        the two LayerNorm launches of the 2B path.  ``shard`` (lkgd_amd.dist_run.ShardInfo): this rank holds ONE batch entry (its CFG
-        half) and the latent frames [f0, f0 + F) of the clip; everything is row-local except the attention, whose local
-        queries (the replicated text rows + the rank's video rows) attend to the keys / values of ALL frames, all-gathered
-        over the frame group every layer.
+        ``image_rotary_emb`` = (cos, sin) fp32 [F h w tokens, 64] (``rotary_tables``) exactly when the model is rotary.
+        ``shard`` (lkgd_amd.dist_run.ShardInfo): this rank holds ONE batch entry (its CFG half) and the latent frames [f0, f0 + F)
+        of the clip; everything is row-local except the attention, whose local queries (the replicated text rows + the rank's video
+        rows) attend to the keys / values of ALL frames, all-gathered over the frame group every layer (``CogVideoXBlock.run``).
         A ``patch_size_t`` model: ``patch_rows`` [Bv * Tv, in_channels * p_t * p * p] (``ops.dit_patch_rows(p_t=)``; column
         (c, pt, py, px)), ``grid`` = (F / p_t, h, w), the result [B * Tv, out_channels * p_t * p * p]; ``ofs_emb`` fp16
         [B, time_embed_dim] (``embed_ofs``) exactly when the model has an ``ofs_embedding``: added to the time embedding in fp16
         (:517) before the modulation GEMM."""
+        st = self._check_rows(patch_rows, grid, fused_text, shard, image_rotary_emb, ofs_emb)
+        eff_g, eff_b, gates, fin = self._modulation(timestep, st.B, ofs_emb)
+        X = self._embed_rows(st, patch_rows, fused_text)
+        for i, block in enumerate(self.transformer_blocks):
+            X = block.run(st, X, eff_g[:, i], eff_b[:, i], gates[i])
+        return self._head(st, X, fin)
+
+    def _check_rows(self, patch_rows, grid, fused_text, shard, image_rotary_emb, ofs_emb):
+        """``forward_rows``' argument checks -> the call's sizes, shard window, rotary tables and row format"""
         if shard is not None and fp8_mode.active(self):
             raise LkgdHipError("frame sharding together with the FP8 mode (quantize_to_float8 / LKGD_DIT_FP8) is not built")
         self.prepare()
@@ -561,7 +614,6 @@ class CogVideoXTransformer3DModel(nn.Module):
             raise LkgdHipError("ofs_emb (embed_ofs) is given exactly when the model has an ofs_embedding (config ofs_embed_dim)")
         if shard is not None and B != 1:
             raise LkgdHipError("frame sharding of the DiT supports one batch entry per rank")
-        D = self.inner_dim
         Tt, Tv = fused_text.shape[1], Fr * h * w
         Kp = pk.w_pe.shape[1]
         if patch_rows.dim() != 2 or patch_rows.dtype != torch.float16 or patch_rows.device != dev or patch_rows.shape[1] != Kp \
@@ -569,9 +621,6 @@ class CogVideoXTransformer3DModel(nn.Module):
                 or patch_rows.stride(1) != 1:
             raise LkgdHipError(f"forward_rows: patch_rows must be GPU fp16 [Bv * {Tv}, {Kp}] with Bv a divisor of the batch {B}, got "
                                f"{tuple(patch_rows.shape)} {patch_rows.dtype}")
-        Bv = patch_rows.shape[0] // Tv
-        L = Tt + Tv
-        heads = cfg.num_attention_heads
         rotary = cfg.use_rotary_positional_embeddings
         if rotary != (image_rotary_emb is not None):
             raise LkgdHipError("image_rotary_emb is given exactly when the model has use_rotary_positional_embeddings "
@@ -587,7 +636,14 @@ class CogVideoXTransformer3DModel(nn.Module):
                 raise LkgdHipError(f"image_rotary_emb: (cos, sin) must each be [{F_all * h * w}, 64], got "
                                    f"{[tuple(t.shape) for t in rope]}")
             rope = tuple(t[v0:v0 + Tv].contiguous() for t in rope)
-        # time embedding -> all modulation vectors of the step (one GEMM)
+        KV = [] if shard is None else [torch.empty(Tt + F_all * h * w, self.inner_dim, dtype=torch.float16, device=dev) for _ in range(2)]
+        return SimpleNamespace(B=B, Bv=patch_rows.shape[0] // Tv, Tt=Tt, Tv=Tv, L=Tt + Tv, grid=(F_all, h, w), v0=v0, rope=rope, KV=KV,
+                               shard=shard, heads=cfg.num_attention_heads, eps=cfg.norm_eps, rows=_FP8_ROWS if pk.fp8 else _FP16_ROWS)
+
+    def _modulation(self, timestep, B: int, ofs_emb):
+        """time embedding (+ ``ofs_emb``) -> the step's modulation (one GEMM), fp32: the effective affine of norm(x) * (1 + scale) +
+        shift, eff_g / eff_b [B, nb, 2, stream (0 text, 1 video), D]; gates [nb, 2, B, stream, D]; norm_out's (shift, scale) [B, 2, D]"""
+        pk, dev, D = self._pk, self.device, self.inner_dim
         t = timestep if torch.is_tensor(timestep) else torch.tensor([timestep])
         t = t.to(device=dev, dtype=torch.float32).reshape(-1).expand(B).contiguous()
         emb = self.time_embedding.run(ops.timestep_embedding(t, D))
@@ -603,101 +659,42 @@ class CogVideoXTransformer3DModel(nn.Module):
         nb = pk.nb
         blk = mod[:, :nb * 12 * D].reshape(B, nb, 2, 6, D)            # (shift, scale, gate, enc_shift, enc_scale, enc_gate)
         g, be = pk.ln_g[None], pk.ln_b[None]                          # [1, nb, 2, D]
-        # effective affine of norm(x) * (1 + scale) + shift, [B, nb, 2, stream (0 text, 1 video), D]
         eff_g = torch.stack([g * (1 + blk[:, :, :, 4]), g * (1 + blk[:, :, :, 1])], dim=3).contiguous()
         eff_b = torch.stack([be * (1 + blk[:, :, :, 4]) + blk[:, :, :, 3], be * (1 + blk[:, :, :, 1]) + blk[:, :, :, 0]], dim=3).contiguous()
-        gates = torch.stack([blk[:, :, :, 5], blk[:, :, :, 2]], dim=3).permute(1, 2, 0, 3, 4).contiguous()   # [nb, 2, B, stream, D]
-        fin = mod[:, nb * 12 * D:].reshape(B, 2, D)                   # norm_out: (shift, scale)
-        # patch embedding into the joint buffer: text rows, then video rows (+ position table in the epilogue)
+        gates = torch.stack([blk[:, :, :, 5], blk[:, :, :, 2]], dim=3).permute(1, 2, 0, 3, 4).contiguous()
+        return eff_g, eff_b, gates, mod[:, nb * 12 * D:].reshape(B, 2, D)
+
+    def _embed_rows(self, st, patch_rows, fused_text):
+        """the two embedding GEMMs into the joint buffer [B * L, D]: text rows, then video rows (+ position table in the epilogue)"""
+        pk, cfg, dev, D = self._pk, self.config, self.device, self.inner_dim
+        B, Bv, Tt, Tv, L, v0 = st.B, st.Bv, st.Tt, st.Tv, st.L, st.v0
         X = torch.empty(B * L, D, dtype=torch.float16, device=dev)
         txt = fused_text.to(device=dev, dtype=torch.float16).reshape(B * Tt, -1).contiguous()
-        pos_txt = None
-        if not rotary:
-            pos = self._pos_table(F_all, h, w)[v0:v0 + Tv]
+        pos_txt = pos = None
+        if not cfg.use_rotary_positional_embeddings:
+            pos = self._pos_table(*st.grid)[v0:v0 + Tv]
         elif cfg.use_learned_positional_embeddings:     # the learned joint table covers the text rows as well
-            tab = self._learned_table(Tt, F_all, h, w)
+            tab = self._learned_table(Tt, *st.grid)
             pos_txt, pos = tab[:Tt], tab[Tt + v0:Tt + v0 + Tv]
-        else:
-            pos = None
-        if shard is not None:
-            Tv_all = F_all * h * w
-            KV = [torch.empty(Tt + Tv_all, D, dtype=torch.float16, device=dev) for _ in range(2)]
-        rb_t = dict(rowbias=pos_txt, rowmap=(1, 1, 1, 1 << 30)) if pos_txt is not None else {}
-        rb_v = dict(rowbias=pos, rowmap=(1, 1, 1, 1 << 30)) if pos is not None else {}
+        rb_t, rb_v = (dict(rowbias=t, rowmap=(1, 1, 1, 1 << 30)) if t is not None else {} for t in (pos_txt, pos))
         for b in range(B):
             ops.gemm(txt[b * Tt:(b + 1) * Tt], pk.w_tx, X[b * L:b * L + Tt], M=Tt, N=D, K=txt.shape[1], bias=pk.b_tx, **rb_t)
-            ops.gemm(patch_rows[(b % Bv) * Tv:(b % Bv + 1) * Tv], pk.w_pe, X[b * L + Tt:(b + 1) * L], M=Tv, N=D, K=Kp, bias=pk.b_pe,
-                     **rb_v)
-        T = B * L
-        eps = cfg.norm_eps
+            ops.gemm(patch_rows[(b % Bv) * Tv:(b % Bv + 1) * Tv], pk.w_pe, X[b * L + Tt:(b + 1) * L], M=Tv, N=D, K=pk.w_pe.shape[1],
+                     bias=pk.b_pe, **rb_v)
+        return X
 
-        def modnorm(i, which):
-            n = torch.empty_like(X)
-            for b in range(B):
-                r0 = b * L
-                ops.layernorm(X[r0:r0 + Tt], eff_g[b, i, which, 0], eff_b[b, i, which, 0], eps, out=n[r0:r0 + Tt])
-                ops.layernorm(X[r0 + Tt:r0 + L], eff_g[b, i, which, 1], eff_b[b, i, which, 1], eps, out=n[r0 + Tt:r0 + L])
-            return n
-
-        def modnorm_fp8(i, which):
-            """``modnorm`` straight into e4m3 rows [T, D] + one scale per row: what the next GEMMs take"""
-            nq = torch.empty(T, D, dtype=torch.uint8, device=dev)
-            ns = torch.empty(T, dtype=torch.float32, device=dev)
-            for b in range(B):
-                for r0, r1, st in ((b * L, b * L + Tt, 0), (b * L + Tt, (b + 1) * L, 1)):
-                    ops.layernorm_quant_fp8(X[r0:r1], eff_g[b, i, which, st], eff_b[b, i, which, st], eps, q=nq[r0:r1], scale=ns[r0:r1])
-            return nq, ns
-        fp8 = pk.fp8
-        for i, blkm in enumerate(self.transformer_blocks):
-            bp = blkm._pk
-            n = modnorm_fp8(i, 0) if fp8 else modnorm(i, 0)
-            q, k, v = (torch.empty(T, D, dtype=torch.float16, device=dev) for _ in range(3))
-            if fp8:     # one quantised activation feeds the three projections
-                for dst, (wq, ws, bias) in ((q, bp.q), (k, bp.k), (v, bp.v)):
-                    ops.gemm_fp8(*n, wq, ws, bias, out=dst)
-            else:
-                for dst, (wgt, bias) in ((q, bp.q), (k, bp.k), (v, bp.v)):
-                    ops.gemm(n, wgt, dst, M=T, N=D, K=D, bias=bias)
-            if rope is not None:    # per-head qk norm + rotation of the video rows, q and k in one launch
-                ops.qk_norm_rope(q, k, heads, bp.nq, bp.nk, 1e-6, rope, L, Tt)
-            else:
-                ops.layernorm(q.view(T * heads, 64), bp.nq[0], bp.nq[1], 1e-6, out=q.view(T * heads, 64))     # per-head qk norm
-                ops.layernorm(k.view(T * heads, 64), bp.nk[0], bp.nk[1], 1e-6, out=k.view(T * heads, 64))
-            a = torch.empty(T, D, dtype=torch.float16, device=dev)
-            if shard is None:
-                ops.attn_spatial(q, k, v, a, B, L, heads)
-            else:                   # keys / values of every frame of this CFG half: text rows (replicated) + gathered video rows
-                for full, loc in zip(KV, (k, v)):
-                    full[:Tt].copy_(loc[:Tt])
-                    full[Tt:].copy_(shard.gather(loc[Tt:]))
-                ops.attn_spatial(q, KV[0], KV[1], a, 1, Tt + Tv_all, heads, Sq=L)
-            o = torch.empty(T, D, dtype=torch.float16, device=dev)
-            if fp8:
-                ops.gemm_fp8(*ops.quant_rows_fp8(a), *bp.o, out=o)
-                X = ops.gated_add(o, gates[i, 0].reshape(2 * B, D), X, L, Tt)
-                hdn = torch.empty(T, 4 * D, dtype=torch.float16, device=dev)
-                ops.gemm_fp8(*modnorm_fp8(i, 1), *bp.f1, out=hdn)
-                ops.gemm_fp8(*ops.gelu_tanh_quant_fp8(hdn), *bp.f2, out=o)      # GELU and Q in one pass over the hidden rows
-                X = ops.gated_add(o, gates[i, 1].reshape(2 * B, D), X, L, Tt)
-                continue
-            ops.gemm(a, bp.o[0], o, M=T, N=D, K=D, bias=bp.o[1])
-            X = ops.gated_add(o, gates[i, 0].reshape(2 * B, D), X, L, Tt)
-            n = modnorm(i, 1)
-            hdn = torch.empty(T, 4 * D, dtype=torch.float16, device=dev)
-            ops.gemm(n, bp.f1[0], hdn, M=T, N=4 * D, K=D, bias=bp.f1[1])
-            ops.gelu_tanh_(hdn)
-            ops.gemm(hdn, bp.f2[0], o, M=T, N=D, K=4 * D, bias=bp.f2[1])
-            X = ops.gated_add(o, gates[i, 1].reshape(2 * B, D), X, L, Tt)
-        # norm_final on the video stream, norm_out (adaLN), proj_out
+    def _head(self, st, X, fin):
+        """norm_final on the video stream, norm_out (adaLN), proj_out -> [B * Tv, out_channels * p * p]"""
+        pk, B, L, Tt, Tv = self._pk, st.B, st.L, st.Tt, st.Tv
         po = pk.w_po.shape[0]
-        out_tok = torch.empty(B, Tv, po, dtype=torch.float16, device=dev)
+        out_tok = torch.empty(B, Tv, po, dtype=torch.float16, device=X.device)
         for b in range(B):
             vid = X[b * L + Tt:(b + 1) * L]
-            y = ops.layernorm(vid, pk.fin[0], pk.fin[1], eps)
+            y = ops.layernorm(vid, pk.fin[0], pk.fin[1], st.eps)
             gg = (pk.out_g * (1 + fin[b, 1])).contiguous()
             bb = (pk.out_b * (1 + fin[b, 1]) + fin[b, 0]).contiguous()
-            y = ops.layernorm(y, gg, bb, eps)
-            ops.gemm(y, pk.w_po, out_tok[b], M=Tv, N=po, K=D, bias=pk.b_po)
+            y = ops.layernorm(y, gg, bb, st.eps)
+            ops.gemm(y, pk.w_po, out_tok[b], M=Tv, N=po, K=self.inner_dim, bias=pk.b_po)
         return out_tok.view(B * Tv, po)
 
     @torch.no_grad()

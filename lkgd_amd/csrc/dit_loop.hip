@@ -112,7 +112,11 @@ __global__ __launch_bounds__(256) void dit_cfg_ddim_kernel(const half_t* __restr
   }
 }
 
-static int dit_shape_ok(int32_t B, int32_t F, int32_t C, int32_t H, int32_t W, int32_t p, int32_t width, int32_t ld) {
+// T3: the temporal-patch pair (include/lkgd_hip_dit_tpatch.h): a row spans p_t = 2 latent frames, a 16-byte piece is one channel's
+// (pt, py, px).  ``width`` = the elements of a row, refused before anything narrows it to int32
+template <bool T3>
+static int dit_shape_ok(int32_t B, int32_t F, int32_t C, int32_t H, int32_t W, int32_t p, int32_t p_t, long long width, int32_t ld) {
+  if (width > 0x7fffffffll || (T3 && (p_t != 2 || F <= 0 || F % p_t))) return 0;
   if (B <= 0 || F <= 0 || C <= 0 || H <= 0 || W <= 0 || p != 2) return 0;
   if (H % p || W % p || (C * p * p) % 8) return 0;
   return ld >= width && ld % 8 == 0;
@@ -124,69 +128,59 @@ static int dit_launch_typed(int32_t is_f32, Launch&& launch) {
   return hipGetLastError() == hipSuccess ? LKGD_OK : LKGD_E_LAUNCH;
 }
 
-extern "C" int lkgd_dit_patch_rows(const void* latents, int32_t latents_is_f32, const void* image_latents, int32_t B, int32_t F,
-                                   int32_t C, int32_t H, int32_t W, int32_t p, void* rows_out, int32_t ldp, lkgd_stream_t stream) {
+template <bool T3>
+static int dit_patch_rows_host(const void* latents, int32_t latents_is_f32, const void* image_latents, int32_t B, int32_t F, int32_t C,
+                               int32_t H, int32_t W, int32_t p, int32_t p_t, void* rows_out, int32_t ldp, lkgd_stream_t stream) {
   if (!latents || !rows_out) return LKGD_E_NULL;
   const long long C2 = image_latents ? 2ll * C : C;
-  if (C2 * 4 > 0x7fffffffll || !dit_shape_ok(B, F, C, H, W, p, (int32_t)(C2 * 4), ldp)) return LKGD_E_SHAPE;
+  if (!dit_shape_ok<T3>(B, F, C, H, W, p, p_t, C2 * (T3 ? 8 : 4), ldp)) return LKGD_E_SHAPE;
   if (!aligned16(rows_out)) return LKGD_E_ALIGN;
-  const long long total = (long long)B * F * (H / 2) * (W / 2) * (C2 / 2);
+  const long long total = (long long)B * (T3 ? F / 2 : F) * (H / 2) * (W / 2) * (T3 ? C2 : C2 / 2);
   return dit_launch_typed(latents_is_f32, [&](auto* tag) {
     using LT = std::remove_pointer_t<decltype(tag)>;
-    hipLaunchKernelGGL((dit_patch_rows_kernel<LT, false>), dim3(dit_grid_for(total, 256)), dim3(256), 0, (hipStream_t)stream,
+    hipLaunchKernelGGL((dit_patch_rows_kernel<LT, T3>), dim3(dit_grid_for(total, 256)), dim3(256), 0, (hipStream_t)stream,
                        (const LT*)latents, (const half_t*)image_latents, C, (int)C2, H, W, total, (half_t*)rows_out, ldp);
   });
+}
+
+template <bool T3>
+static int dit_cfg_ddim_host(const void* noise_rows, int32_t ldn, void* latents, int32_t latents_is_f32, int32_t B, int32_t F,
+                             int32_t C, int32_t H, int32_t W, int32_t p, int32_t p_t, int32_t cfg, float guidance, float a, float b,
+                             float sqrt_alpha, float sqrt_beta, lkgd_stream_t stream) {
+  if (!noise_rows || !latents) return LKGD_E_NULL;
+  if (!dit_shape_ok<T3>(B, F, C, H, W, p, p_t, (T3 ? 8ll : 4ll) * C, ldn) || (cfg != 1 && cfg != 2)) return LKGD_E_SHAPE;
+  if (!aligned16(noise_rows)) return LKGD_E_ALIGN;
+  const long long rows = (long long)B * (T3 ? F / 2 : F) * (H / 2) * (W / 2);
+  const long long total = rows * (T3 ? C : C / 2);
+  const ddim_t k = {guidance, a, b, sqrt_alpha, sqrt_beta};
+  return dit_launch_typed(latents_is_f32, [&](auto* tag) {
+    using LT = std::remove_pointer_t<decltype(tag)>;
+    hipLaunchKernelGGL((dit_cfg_ddim_kernel<LT, T3>), dim3(dit_grid_for(total, 256)), dim3(256), 0, (hipStream_t)stream,
+                       (const half_t*)noise_rows, ldn, (LT*)latents, C, H, W, cfg, rows, k, total);
+  });
+}
+
+extern "C" int lkgd_dit_patch_rows(const void* latents, int32_t latents_is_f32, const void* image_latents, int32_t B, int32_t F,
+                                   int32_t C, int32_t H, int32_t W, int32_t p, void* rows_out, int32_t ldp, lkgd_stream_t stream) {
+  return dit_patch_rows_host<false>(latents, latents_is_f32, image_latents, B, F, C, H, W, p, 0, rows_out, ldp, stream);
 }
 
 extern "C" int lkgd_dit_cfg_ddim_step(const void* noise_rows, int32_t ldn, void* latents, int32_t latents_is_f32, int32_t B,
                                       int32_t F, int32_t C, int32_t H, int32_t W, int32_t p, int32_t cfg, float guidance, float a,
                                       float b, float sqrt_alpha, float sqrt_beta, lkgd_stream_t stream) {
-  if (!noise_rows || !latents) return LKGD_E_NULL;
-  if ((long long)C * 4 > 0x7fffffffll || !dit_shape_ok(B, F, C, H, W, p, C * 4, ldn) || (cfg != 1 && cfg != 2)) return LKGD_E_SHAPE;
-  if (!aligned16(noise_rows)) return LKGD_E_ALIGN;
-  const long long rows = (long long)B * F * (H / 2) * (W / 2);
-  const long long total = rows * (C / 2);
-  const ddim_t k = {guidance, a, b, sqrt_alpha, sqrt_beta};
-  return dit_launch_typed(latents_is_f32, [&](auto* tag) {
-    using LT = std::remove_pointer_t<decltype(tag)>;
-    hipLaunchKernelGGL((dit_cfg_ddim_kernel<LT, false>), dim3(dit_grid_for(total, 256)), dim3(256), 0, (hipStream_t)stream,
-                       (const half_t*)noise_rows, ldn, (LT*)latents, C, H, W, cfg, rows, k, total);
-  });
-}
-
-// ---- temporal patches (include/lkgd_hip_dit_tpatch.h): a row spans p_t = 2 latent frames, a 16-byte piece is one channel's (pt, py, px)
-static int dit_shape_ok_t(int32_t B, int32_t F, int32_t C, int32_t H, int32_t W, int32_t p, int32_t p_t, long long width, int32_t ld) {
-  if (p_t != 2 || F <= 0 || F % p_t || width > 0x7fffffffll) return 0;
-  return dit_shape_ok(B, F, C, H, W, p, (int32_t)width, ld);
+  return dit_cfg_ddim_host<false>(noise_rows, ldn, latents, latents_is_f32, B, F, C, H, W, p, 0, cfg, guidance, a, b, sqrt_alpha,
+                                  sqrt_beta, stream);
 }
 
 extern "C" int lkgd_dit_patch_rows_t(const void* latents, int32_t latents_is_f32, const void* image_latents, int32_t B, int32_t F,
                                      int32_t C, int32_t H, int32_t W, int32_t p, int32_t p_t, void* rows_out, int32_t ldp,
                                      lkgd_stream_t stream) {
-  if (!latents || !rows_out) return LKGD_E_NULL;
-  const long long C2 = image_latents ? 2ll * C : C;
-  if (!dit_shape_ok_t(B, F, C, H, W, p, p_t, C2 * 8, ldp)) return LKGD_E_SHAPE;
-  if (!aligned16(rows_out)) return LKGD_E_ALIGN;
-  const long long total = (long long)B * (F / 2) * (H / 2) * (W / 2) * C2;
-  return dit_launch_typed(latents_is_f32, [&](auto* tag) {
-    using LT = std::remove_pointer_t<decltype(tag)>;
-    hipLaunchKernelGGL((dit_patch_rows_kernel<LT, true>), dim3(dit_grid_for(total, 256)), dim3(256), 0, (hipStream_t)stream,
-                       (const LT*)latents, (const half_t*)image_latents, C, (int)C2, H, W, total, (half_t*)rows_out, ldp);
-  });
+  return dit_patch_rows_host<true>(latents, latents_is_f32, image_latents, B, F, C, H, W, p, p_t, rows_out, ldp, stream);
 }
 
 extern "C" int lkgd_dit_cfg_ddim_step_t(const void* noise_rows, int32_t ldn, void* latents, int32_t latents_is_f32, int32_t B,
                                         int32_t F, int32_t C, int32_t H, int32_t W, int32_t p, int32_t p_t, int32_t cfg,
                                         float guidance, float a, float b, float sqrt_alpha, float sqrt_beta, lkgd_stream_t stream) {
-  if (!noise_rows || !latents) return LKGD_E_NULL;
-  if (!dit_shape_ok_t(B, F, C, H, W, p, p_t, 8ll * C, ldn) || (cfg != 1 && cfg != 2)) return LKGD_E_SHAPE;
-  if (!aligned16(noise_rows)) return LKGD_E_ALIGN;
-  const long long rows = (long long)B * (F / 2) * (H / 2) * (W / 2);
-  const long long total = rows * C;
-  const ddim_t k = {guidance, a, b, sqrt_alpha, sqrt_beta};
-  return dit_launch_typed(latents_is_f32, [&](auto* tag) {
-    using LT = std::remove_pointer_t<decltype(tag)>;
-    hipLaunchKernelGGL((dit_cfg_ddim_kernel<LT, true>), dim3(dit_grid_for(total, 256)), dim3(256), 0, (hipStream_t)stream,
-                       (const half_t*)noise_rows, ldn, (LT*)latents, C, H, W, cfg, rows, k, total);
-  });
+  return dit_cfg_ddim_host<true>(noise_rows, ldn, latents, latents_is_f32, B, F, C, H, W, p, p_t, cfg, guidance, a, b, sqrt_alpha,
+                                 sqrt_beta, stream);
 }

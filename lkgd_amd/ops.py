@@ -838,12 +838,9 @@ def dit_patch_rows(latents: torch.Tensor, image_latents: Optional[torch.Tensor],
         _req(out, torch.float16, "out")
         if out.dim() != 2 or tuple(out.shape) != (rows, width) or out.stride(1) != 1:
             raise _lib.LkgdHipError(f"out must be an fp16 [{rows}, {width}] matrix, got {tuple(out.shape)}")
-    if p_t is not None:
-        check(_L().lkgd_dit_patch_rows_t(latents.data_ptr(), int(latents.dtype == torch.float32), _ptr(image_latents), B, F, C_, H, W,
-                                         p, p_t, out.data_ptr(), _ld(out), _stream()), "lkgd_dit_patch_rows_t")
-        return out
-    check(_L().lkgd_dit_patch_rows(latents.data_ptr(), int(latents.dtype == torch.float32), _ptr(image_latents), B, F, C_, H, W, p,
-                                   out.data_ptr(), _ld(out), _stream()), "lkgd_dit_patch_rows")
+    name, pt = ("lkgd_dit_patch_rows", ()) if p_t is None else ("lkgd_dit_patch_rows_t", (p_t,))
+    check(getattr(_L(), name)(latents.data_ptr(), int(latents.dtype == torch.float32), _ptr(image_latents), B, F, C_, H, W, p, *pt,
+                              out.data_ptr(), _ld(out), _stream()), name)
     return out
 
 
@@ -860,14 +857,9 @@ def dit_cfg_ddim_step(noise_rows: torch.Tensor, latents: torch.Tensor, p: int, c
     if cfg not in (1, 2) or noise_rows.dim() != 2 or tuple(noise_rows.shape) != (rows, width) or noise_rows.stride(1) != 1:
         raise _lib.LkgdHipError(f"noise_rows must be an fp16 [{rows}, {width}] matrix (cfg 1 or 2), got "
                                 f"{tuple(noise_rows.shape)}, cfg = {cfg}")
-    if p_t is not None:
-        check(_L().lkgd_dit_cfg_ddim_step_t(noise_rows.data_ptr(), _ld(noise_rows), latents.data_ptr(),
-                                            int(latents.dtype == torch.float32), B, F, C_, H, W, p, p_t, cfg, guidance, a, b, sqrt_alpha,
-                                            sqrt_beta, _stream()), "lkgd_dit_cfg_ddim_step_t")
-        return latents
-    check(_L().lkgd_dit_cfg_ddim_step(noise_rows.data_ptr(), _ld(noise_rows), latents.data_ptr(), int(latents.dtype == torch.float32),
-                                      B, F, C_, H, W, p, cfg, guidance, a, b, sqrt_alpha, sqrt_beta, _stream()),
-          "lkgd_dit_cfg_ddim_step")
+    name, pt = ("lkgd_dit_cfg_ddim_step", ()) if p_t is None else ("lkgd_dit_cfg_ddim_step_t", (p_t,))
+    check(getattr(_L(), name)(noise_rows.data_ptr(), _ld(noise_rows), latents.data_ptr(), int(latents.dtype == torch.float32),
+                              B, F, C_, H, W, p, *pt, cfg, guidance, a, b, sqrt_alpha, sqrt_beta, _stream()), name)
     return latents
 
 

@@ -8,39 +8,7 @@ import pytest
 import torch
 from safetensors.torch import load_file
 
-DEV = "cuda:0"
-DIT_SEED = 191
-
-
-def _rel(a, b):
-    a, b = a.float().cpu(), b.float().cpu()
-    return ((a - b).norm() / b.norm()).item()
-
-
-def _inputs(cfg, seed=DIT_SEED + 1, batch=2):
-    g = torch.Generator().manual_seed(seed)
-    f = (cfg.sample_frames - 1) // cfg.temporal_compression_ratio + 1
-    return dict(hidden=torch.randn(batch, f, cfg.in_channels, cfg.sample_height, cfg.sample_width, generator=g).half().float(),
-                text=torch.randn(batch, cfg.max_text_seq_length, cfg.text_embed_dim, generator=g).half().float(),
-                t=torch.tensor([721] * batch), domain=torch.randn(1, 1, 1000, generator=g),
-                flow=torch.randn(1, 1, 1000, generator=g))
-
-
-def _oracle(cfg):
-    from oracle import cogvideox as oc
-    o = oc.init_weights_(oc.CogVideoXTransformer3DModel(cfg), DIT_SEED)
-    with torch.no_grad():
-        for p in o.parameters():
-            p.copy_(p.half().float())
-    return o
-
-
-def _hip(o, cfg):
-    from lkgd_amd import cogvideox as pc
-    m = pc.CogVideoXTransformer3DModel(pc.DiTConfig(**cfg.__dict__))
-    missing, unexpected = m.load_state_dict(o.state_dict(), strict=False)
-    assert not missing and not unexpected, (missing, unexpected)
-    return m
+from cogvideox_support import DEV, dit_inputs as _inputs, hip_twin as _hip, loop_inputs, rel as _rel, tiny_oracle
 
 
 @pytest.fixture(scope="module")
@@ -50,7 +18,7 @@ def golden(golden_dir):
 
 def test_oracle_dit_vs_reference_golden(golden):
     from oracle import cogvideox as oc
-    o = _oracle(oc.TINY_DIT)
+    o = tiny_oracle()
     ck = float(sum(p.detach().double().abs().sum() for p in o.parameters()))
     assert abs(ck - golden["checksum"].item()) <= 1e-9 * ck
     i = _inputs(oc.TINY_DIT)
@@ -118,7 +86,7 @@ def test_dit_kernels_vs_torch():
 @pytest.mark.gpu
 def test_hip_dit_forward_vs_reference_golden(golden):
     from oracle import cogvideox as oc
-    m = _hip(_oracle(oc.TINY_DIT), oc.TINY_DIT).half().to(DEV)
+    m = _hip(tiny_oracle(), dev=DEV)
     i = _inputs(oc.TINY_DIT)
     fused = m.fused_text(i["text"].to(DEV), i["domain"].to(DEV), i["flow"].to(DEV))
     assert _rel(fused, golden["fused_text"]) < 2e-3
@@ -133,15 +101,9 @@ def test_hip_dit_loop_vs_oracle():
     """pipeline_cogvideox_image2video.py:829-885: 4 DDIM steps with dynamic CFG, tiny DiT, against the oracle's loop"""
     from lkgd_amd import cogvideox as pc
     from oracle import cogvideox as oc
-    cfg = oc.TINY_DIT
-    o = _oracle(cfg)
-    m = _hip(o, cfg).half().to(DEV)
-    g = torch.Generator().manual_seed(5)
-    f = 3
-    lat = torch.randn(1, f, 16, cfg.sample_height, cfg.sample_width, generator=g)
-    img = (0.5 * torch.randn(1, f, 16, cfg.sample_height, cfg.sample_width, generator=g)).half().float()
-    pe = torch.randn(2, cfg.max_text_seq_length, cfg.text_embed_dim, generator=g).half().float()
-    dom, flow = torch.randn(1, 1, 1000, generator=g), torch.randn(1, 1, 1000, generator=g)
+    o = tiny_oracle()
+    m = _hip(o, dev=DEV)
+    lat, img, pe, dom, flow = loop_inputs()
     ref_steps, got_steps = [], []
     ref = oc.denoise(o, oc.CogVideoXDDIMScheduler(), lat.half().float(), img, pe, dom, flow, 4, 6.0, True,
                      callback=lambda i, t, l: ref_steps.append(l.clone()))
@@ -158,8 +120,8 @@ def test_hip_dit_real_width_vs_oracle():
     with 2 layers on a small video (5 latent frames of 16 x 24 -> 480 video tokens), against the oracle"""
     from oracle import cogvideox as oc
     cfg = oc.DiTConfig(in_channels=32, num_layers=2, sample_width=24, sample_height=16, sample_frames=17)
-    o = _oracle(cfg)
-    m = _hip(o, cfg).half().to(DEV)
+    o = tiny_oracle(cfg=cfg)
+    m = _hip(o, cfg, DEV)
     i = _inputs(cfg, seed=7)
     with torch.no_grad():
         ref = o(i["hidden"], i["text"], i["t"], i["domain"], i["flow"])[0]

@@ -3,7 +3,6 @@ its refusals; the 1.5 configurations (I2V with ``ofs_embed_dim``, T2V without) w
 round trip; every refused combination of the 1.5 keys; the slice rotary tables by their properties; the frame padding against the
 pipeline's statements; the fp32 twin (tests/cogvideox15_oracle.py) against tests/golden/cogvideox15.safetensors = the reference's
 own in-tree forward (make_goldens_cogvideox15.py)."""
-import ctypes as C
 import json
 import os
 import re
@@ -14,9 +13,8 @@ from safetensors import safe_open
 from safetensors.torch import load_file
 
 import cogvideox15_oracle as vo
+from cogvideox_support import DIT_SEED, REPO, Host, declared as _declared, dit_inputs as _inputs, hip_twin, rel as _rel
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-DIT_SEED = 191                                                        # make_goldens.py
 NAMES = {"lkgd_dit_patch_rows_t", "lkgd_dit_cfg_ddim_step_t"}
 OK, NULL, SHAPE, ALIGN = 0, -1, -2, -3
 
@@ -25,25 +23,6 @@ KW_15_I2V = dict(num_attention_heads=48, attention_head_dim=64, in_channels=32, 
                  temporal_compression_ratio=4, max_text_seq_length=224, norm_eps=1e-5, attention_bias=True,
                  use_rotary_positional_embeddings=True, use_learned_positional_embeddings=False, patch_size_t=2, ofs_embed_dim=512,
                  patch_bias=False)
-
-
-def _rel(a, b):
-    a, b = a.float().cpu(), b.float().cpu()
-    return ((a - b).norm() / b.norm()).item()
-
-
-def _inputs(cfg, seed=DIT_SEED + 1, batch=2):
-    """make_goldens.py::dit_inputs"""
-    g = torch.Generator().manual_seed(seed)
-    f = (cfg.sample_frames - 1) // cfg.temporal_compression_ratio + 1
-    return dict(hidden=torch.randn(batch, f, cfg.in_channels, cfg.sample_height, cfg.sample_width, generator=g).half().float(),
-                text=torch.randn(batch, cfg.max_text_seq_length, cfg.text_embed_dim, generator=g).half().float(),
-                t=torch.tensor([721] * batch), domain=torch.randn(1, 1, 1000, generator=g),
-                flow=torch.randn(1, 1, 1000, generator=g))
-
-
-def _declared(header):
-    return set(re.findall(r"\b(lkgd_[a-z0-9_]+)\s*\(", open(os.path.join(REPO, "include", header)).read()))
 
 
 # ------------------------------------------------------------------------------------------------------------ the C interface
@@ -73,9 +52,8 @@ def test_dit_tpatch_refusals():
     """the errors of lkgd_dit_patch_rows / lkgd_dit_cfg_ddim_step, plus LKGD_E_SHAPE unless p_t == 2 and F % p_t == 0; host memory
     stands in for device pointers: a refused call never launches, so nothing dereferences them"""
     from lkgd_amd import _lib
-    lib = _lib.lib()
-    buf = C.create_string_buffer(4096 + 64)
-    hp = (C.addressof(buf) + 63) & ~63
+    lib, h = _lib.lib(), Host()
+    hp = h.p
 
     def patch(**kw):
         a = dict(lat=hp, f32=0, img=hp, B=1, F=4, C=16, H=8, W=12, p=2, p_t=2, out=hp, ld=256)
@@ -136,13 +114,8 @@ def test_15_i2v_config_constructs_with_the_twins_names():
 
 
 def _tiny(ofs=True):
-    from lkgd_amd import cogvideox as pc
     cfg = vo.TINY_V15_DIT if ofs else vo.V15DiTConfig(**{**vo.TINY_V15_DIT.__dict__, "ofs_embed_dim": None})
-    o = vo.seeded_model(cfg, DIT_SEED)
-    m = pc.CogVideoXTransformer3DModel(pc.DiTConfig(**cfg.__dict__))
-    missing, unexpected = m.load_state_dict(o.state_dict(), strict=False)
-    assert not missing and not unexpected, (missing, unexpected)
-    return m
+    return hip_twin(vo.seeded_model(cfg, DIT_SEED), cfg)
 
 
 @pytest.mark.parametrize("ofs", [True, False])

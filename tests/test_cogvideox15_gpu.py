@@ -10,12 +10,12 @@ import torch
 from safetensors.torch import load_file
 
 import cogvideox15_oracle as vo
+from cogvideox_support import DEV, DIT_SEED, P, aten_denoise, aten_step, dit_inputs as _inputs, glue_data, hip_twin, loop_inputs, patchify, \
+    rel as _rel, unpatchify
 from footprint import run_case
 
 gpu = pytest.mark.gpu
-DEV = "cuda:0"
-DIT_SEED = 191                                                        # make_goldens.py
-P, PT = 2, 2
+PT = 2
 
 #: every name in lkgd_amd._lib.DIT_TPATCH_SYMBOLS -> its footprint tests in this module (the rule REGISTRY keeps for _lib.SYMBOLS
 #: in tests/test_footprint_gpu.py)
@@ -27,21 +27,6 @@ FOOTPRINT = {
 #: (B, F, C, H, W): the smallest shapes where a frame-in-patch (F = 2: one temporal patch, 4: two), channel (C = 2, 16), batch or
 #: x / y (4 x 4 against 4 x 6: w = 2 against 3, odd) transposition shows
 GLUE_SHAPES = [(B, F, C_, H, W) for B in (1, 2) for F in (2, 4) for C_ in (2, 16) for H, W in ((4, 4), (4, 6))]
-
-
-def _rel(a, b):
-    a, b = a.float().cpu(), b.float().cpu()
-    return ((a - b).norm() / b.norm()).item()
-
-
-def _inputs(cfg, seed=DIT_SEED + 1, batch=2):
-    """make_goldens.py::dit_inputs"""
-    g = torch.Generator().manual_seed(seed)
-    f = (cfg.sample_frames - 1) // cfg.temporal_compression_ratio + 1
-    return dict(hidden=torch.randn(batch, f, cfg.in_channels, cfg.sample_height, cfg.sample_width, generator=g).half().float(),
-                text=torch.randn(batch, cfg.max_text_seq_length, cfg.text_embed_dim, generator=g).half().float(),
-                t=torch.tensor([721] * batch), domain=torch.randn(1, 1, 1000, generator=g),
-                flow=torch.randn(1, 1, 1000, generator=g))
 
 
 @pytest.fixture(scope="module")
@@ -56,9 +41,7 @@ def tiny(tmp_path_factory):
     from lkgd_amd import cogvideox as pc
     cfg = vo.TINY_V15_DIT
     o = vo.seeded_model(cfg, DIT_SEED)
-    m = pc.CogVideoXTransformer3DModel(pc.DiTConfig(**cfg.__dict__))
-    missing, unexpected = m.load_state_dict(o.state_dict(), strict=False)
-    assert not missing and not unexpected, (missing, unexpected)
+    m = hip_twin(o, cfg)
     d = str(tmp_path_factory.mktemp("cogvideox15") / "transformer")
     m.save_pretrained(d)
     r = pc.CogVideoXTransformer3DModel.from_pretrained(d, torch_dtype=torch.float16)
@@ -67,60 +50,25 @@ def tiny(tmp_path_factory):
 
 
 # ------------------------------------------------------------------------------------------------------------- the glue
-def _patchify_t(x):
-    """the reshape of the 1.5 patch embedding ([EXT] diffusers CogVideoXPatchEmbed; column (c, pt, py, px))"""
-    B, F, C_, H, W = x.shape
-    r = x.permute(0, 1, 3, 4, 2).reshape(B, F // PT, PT, H // P, P, W // P, P, C_).permute(0, 1, 3, 5, 7, 2, 4, 6).flatten(4, 7).flatten(1, 3)
-    return r.reshape(-1, C_ * PT * P * P).contiguous()
-
-
-def _unpatchify_t(rows, B, F, H, W):
-    """cogvideox_transformer_3d.py:626-630"""
-    out = rows.reshape(B, (F + PT - 1) // PT, H // P, W // P, -1, PT, P, P)
-    return out.permute(0, 1, 5, 4, 2, 6, 3, 7).flatten(6, 7).flatten(4, 5).flatten(1, 2).contiguous()
-
-
-def _glue_data(shape, seed):
-    g = torch.Generator().manual_seed(seed)
-    B, F, C_, H, W = shape
-    lat = torch.randn(B, F, C_, H, W, generator=g)
-    img = (0.5 * torch.randn(B, F, C_, H, W, generator=g)).half()
-    noise = (2 * torch.randn(2 * B * (F // PT) * (H // P) * (W // P), C_ * PT * P * P, generator=g)).half()
-    return lat, img, noise
-
-
-def _aten_step(noise_rows, lat, cfg, g, coef):
-    """the loop body the step kernel replaces, on the tensors' device: the un-patchify, .float(), the CFG statements,
-    CogVideoXDDIMScheduler.step, the cast back"""
-    B, F, C_, H, W = lat.shape
-    noise = _unpatchify_t(noise_rows, cfg * B, F, H, W).float()
-    if cfg == 2:
-        u, c = noise.chunk(2)
-        noise = u + g * (c - u)
-    a, b, sa, sb = coef
-    sample = lat.float()
-    x0 = sa * sample - sb * noise
-    return (a * sample + b * x0).to(lat.dtype)
-
-
 def test_the_two_torch_statements_are_inverse():
     """the available cross-check of the unpinned column order: the in-tree un-patchify undoes the restated patch reshape"""
     x = torch.randn(2, 4, 6, 4, 6)
-    assert torch.equal(_unpatchify_t(_patchify_t(x), 2, 4, 4, 6), x)
+    assert torch.equal(unpatchify(patchify(x, PT), 2, 4, 4, 6, PT), x)
     # column ((c * p_t + pt) * p + py) * p + px of row (b, ft, y, x)
-    r = _patchify_t(x).reshape(2, 2, 2, 3, 6, 2, 2, 2)
+    r = patchify(x, PT).reshape(2, 2, 2, 3, 6, 2, 2, 2)
     assert r[1, 1, 0, 2, 4, 1, 0, 1] == x[1, 1 * 2 + 1, 4, 0 * 2 + 0, 2 * 2 + 1]
+    assert torch.equal(patchify(x, p_t=1), patchify(x))          # one frame per patch is the 2-D statement, bit for bit
 
 
 @gpu
 @pytest.mark.parametrize("shape", GLUE_SHAPES)
 def test_dit_patch_rows_t_bitwise(shape):
     from lkgd_amd import ops
-    lat32, img, _ = (t.to(DEV) for t in _glue_data(shape, 3))
+    lat32, img, _ = (t.to(DEV) for t in glue_data(shape, 3, PT))
     for lat in (lat32, lat32.half()):
         for im in (img, None):
             x = lat.half() if im is None else torch.cat([lat.half(), im], 2)
-            ref = _patchify_t(x)
+            ref = patchify(x, PT)
             got = ops.dit_patch_rows(lat, im, p_t=PT)
             assert got.dtype == torch.float16 and got.shape == ref.shape and torch.equal(got, ref), (shape, lat.dtype, im is None)
             buf = torch.full((ref.shape[0], ref.shape[1] + 24), float("nan"), dtype=torch.float16, device=DEV)   # ldp wider than the row
@@ -133,7 +81,7 @@ def test_dit_patch_rows_t_bitwise(shape):
 def test_dit_cfg_ddim_step_t_bitwise(shape):
     from lkgd_amd import cogvideox as pc
     from lkgd_amd import ops
-    lat32, _, noise = (t.to(DEV) for t in _glue_data(shape, 4))
+    lat32, _, noise = (t.to(DEV) for t in glue_data(shape, 4, PT))
     sched = pc.CogVideoXDDIMScheduler()
     sched.set_timesteps(4)
     rows = noise.shape[0] // 2
@@ -142,7 +90,7 @@ def test_dit_cfg_ddim_step_t_bitwise(shape):
         for lat0 in (lat32, lat32.half()):
             for cfg in (1, 2):
                 n = noise[:cfg * rows].contiguous()
-                ref = _aten_step(n, lat0, cfg, g, coef)
+                ref = aten_step(n, lat0, cfg, g, coef, PT)
                 wide = torch.full((cfg * rows, n.shape[1] + 8), float("nan"), dtype=torch.float16, device=DEV)      # ldn wider than the row
                 wide[:, :n.shape[1]] = n
                 for src in (n, wide[:, :n.shape[1]]):
@@ -160,7 +108,7 @@ def test_dit_tpatch_refusals():
     lib = _lib_()
     NULL, SHAPE, ALIGN = -1, -2, -3
     shape = (1, 4, 16, 8, 12)
-    lat, img, noise = (t.to(DEV) for t in _glue_data(shape, 5))
+    lat, img, noise = (t.to(DEV) for t in glue_data(shape, 5, PT))
     lat = lat.half()
     rows = torch.full((48, 256), 7.0, dtype=torch.float16, device=DEV)
     lat0, rows0 = lat.clone(), rows.clone()
@@ -216,7 +164,7 @@ def test_dit_patch_rows_t_footprint(shape, f32, with_img):
     from test_footprint_gpu import _lib_, _ok, _st, flat_in
     lib = _lib_()
     B, F, C_, H, W_ = shape
-    lat, img, _ = _glue_data(shape, 11)
+    lat, img, _ = glue_data(shape, 11, PT)
     lat = lat if f32 else lat.half()
     rows, width = B * (F // PT) * (H // P) * (W_ // P), (2 if with_img else 1) * C_ * PT * P * P
 
@@ -230,7 +178,7 @@ def test_dit_patch_rows_t_footprint(shape, f32, with_img):
 
     def refs():
         x = torch.cat([lat.half(), img], 2) if with_img else lat.half()
-        return {"rows": _patchify_t(x).to(DEV)}
+        return {"rows": patchify(x, PT).to(DEV)}
 
     def close(got, ref, what):
         assert torch.equal(got, ref), what
@@ -245,7 +193,7 @@ def test_dit_cfg_ddim_step_t_footprint(shape, f32, cfg):
     from lkgd_amd import cogvideox as pc
     lib = _lib_()
     B, F, C_, H, W_ = shape
-    lat, _, noise = _glue_data(shape, 12)
+    lat, _, noise = glue_data(shape, 12, PT)
     lat = lat if f32 else lat.half()
     noise = noise[:cfg * noise.shape[0] // 2].contiguous()
     sched = pc.CogVideoXDDIMScheduler()
@@ -261,7 +209,7 @@ def test_dit_cfg_ddim_step_t_footprint(shape, f32, cfg):
         return {"latents": lv}
 
     def refs():
-        return {"latents": _aten_step(noise.to(DEV), lat.to(DEV), cfg, g, coef).reshape(1, -1)}
+        return {"latents": aten_step(noise.to(DEV), lat.to(DEV), cfg, g, coef, PT).reshape(1, -1)}
 
     def close(got, ref, what):
         assert torch.equal(got, ref), (what, (got.float() - ref.float()).abs().max().item())
@@ -269,37 +217,6 @@ def test_dit_cfg_ddim_step_t_footprint(shape, f32, cfg):
 
 
 # ------------------------------------------------------------------------------------------------------------------ the loop
-def _loop_inputs(seed=5, f=4, cfg=True):
-    c = vo.TINY_V15_DIT
-    g = torch.Generator().manual_seed(seed)
-    lat = torch.randn(1, f, 16, c.sample_height, c.sample_width, generator=g)
-    img = (0.5 * torch.randn(1, f, 16, c.sample_height, c.sample_width, generator=g)).half().float()
-    pe = torch.randn(2 if cfg else 1, c.max_text_seq_length, c.text_embed_dim, generator=g).half().float()
-    return lat, img, pe, torch.randn(1, 1, 1000, generator=g), torch.randn(1, 1, 1000, generator=g)
-
-
-def _aten_denoise(pc, m, sched, latents, image_latents, prompt_embeds, dom, flow, steps, guidance_scale, rope, ofs, callback):
-    """the loop of pipeline_cogvideox_image2video.py:829-885 without the glue kernels: ``forward_tokens`` on the CFG-duplicated,
-    channel-concatenated batch + the ATen statements"""
-    sched.set_timesteps(steps)
-    cfg = guidance_scale > 1.0
-    text = m.fused_text(prompt_embeds, dom, flow)
-    latents = latents.to(torch.float16)
-    img = image_latents.to(torch.float16)
-    img2 = torch.cat([img] * 2) if cfg else img
-    for i, t in enumerate(sched.timesteps.tolist()):
-        x = torch.cat([latents] * 2) if cfg else latents
-        x = torch.cat([x, img2], dim=2)
-        noise = m.forward_tokens(x, text, float(t), image_rotary_emb=rope, ofs=ofs).float()
-        g = pc.dynamic_guidance(guidance_scale, steps, t)
-        if cfg:
-            u, c = noise.chunk(2)
-            noise = u + g * (c - u)
-        latents = sched.step(noise, t, latents.float())[0].to(torch.float16)
-        callback(i, t, latents)
-    return latents
-
-
 @gpu
 @pytest.mark.parametrize("guidance_scale", [6.0, 1.0])
 def test_denoise_equals_the_aten_loop_bitwise(tiny, guidance_scale):
@@ -311,12 +228,12 @@ def test_denoise_equals_the_aten_loop_bitwise(tiny, guidance_scale):
     from lkgd_amd import cogvideox as pc
     _, m = tiny
     cfg = vo.TINY_V15_DIT
-    lat, img, pe, dom, flow = _loop_inputs(cfg=guidance_scale > 1.0)
+    lat, img, pe, dom, flow = loop_inputs(cfg, f=4, cfg=guidance_scale > 1.0)
     dv = [t.to(DEV) for t in (lat.half(), img, pe, dom, flow)]
     lat_in = dv[0].clone()
     rope = pc.rotary_tables(m.config, 4 // PT, cfg.sample_height // P, cfg.sample_width // P)
     old_steps, new_steps = [], []
-    old = _aten_denoise(pc, m, pc.CogVideoXDDIMScheduler(), *dv, 3, guidance_scale, rope, 2.0, lambda i, t, l: old_steps.append(l))
+    old = aten_denoise(pc, m, pc.CogVideoXDDIMScheduler(), *dv, 3, guidance_scale, lambda i, t, l: old_steps.append(l), rope, 2.0)
     new = pc.denoise(m, pc.CogVideoXDDIMScheduler(), *dv, 3, guidance_scale, True, callback=lambda i, t, l: new_steps.append(l))
     assert torch.equal(dv[0], lat_in)                                # the caller's latents are not the loop's in-place operand
     assert len(new_steps) == len(old_steps) == 3 and new.dtype == torch.float16 and new.shape == lat.shape
@@ -335,7 +252,7 @@ def test_denoise_refuses_an_odd_frame_count_and_pads(tiny):
     from lkgd_amd import cogvideox as pc
     from lkgd_amd._lib import LkgdHipError
     _, m = tiny
-    lat, img, pe, dom, flow = (t.to(DEV) for t in _loop_inputs(seed=6, f=3))
+    lat, img, pe, dom, flow = (t.to(DEV) for t in loop_inputs(vo.TINY_V15_DIT, seed=6, f=3))
     with pytest.raises(LkgdHipError, match="patch_size_t"):
         pc.denoise(m, pc.CogVideoXDDIMScheduler(), lat.half(), img, pe, dom, flow, 2)
     add = pc.temporal_padding_frames(3, m.config.patch_size_t)
@@ -380,10 +297,7 @@ def test_hip_15_t2v_forward_vs_twin():
     from lkgd_amd import cogvideox as pc
     cfg = vo.V15DiTConfig(**{**vo.TINY_V15_DIT.__dict__, "ofs_embed_dim": None})
     o = vo.seeded_model(cfg, DIT_SEED + 3)
-    m = pc.CogVideoXTransformer3DModel(pc.DiTConfig(**cfg.__dict__))
-    missing, unexpected = m.load_state_dict(o.state_dict(), strict=False)
-    assert not missing and not unexpected
-    m = m.half().to(DEV)
+    m = hip_twin(o, cfg, DEV)
     i = _inputs(cfg, seed=9)
     rope = vo.rotary_tables(cfg, 4, 4, 6)
     with torch.no_grad():

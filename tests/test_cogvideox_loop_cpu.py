@@ -10,13 +10,10 @@ import re
 import pytest
 import torch
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from cogvideox_support import REPO, Host as _Host, declared as _declared, tiny_cpu_model
+
 NAMES = {"lkgd_lk_fuse_tokens", "lkgd_dit_patch_rows", "lkgd_dit_cfg_ddim_step"}
 OK, NULL, SHAPE, ALIGN = 0, -1, -2, -3
-
-
-def _declared(header):
-    return set(re.findall(r"\b(lkgd_[a-z0-9_]+)\s*\(", open(os.path.join(REPO, "include", header)).read()))
 
 
 def test_dit_loop_symbols_agree_three_ways():
@@ -37,17 +34,6 @@ def test_dit_loop_symbols_agree_three_ways():
         decl = re.search(r"^int %s\s*\(([^;]*)\);" % s, hdr, re.M | re.S).group(1)
         assert len(re.sub(r"/\*.*?\*/", "", decl).split(",")) == len(args), s
     assert [len(_lib.DIT_LOOP_SYMBOLS[s][1]) for s in sorted(NAMES)] == [17, 12, 11]
-
-
-class _Host:
-    """host memory standing in for device pointers: a refused call never launches, so nothing dereferences them (only the
-    array `w` is read on the host)"""
-
-    def __init__(self):
-        self.buf = C.create_string_buffer(4096 + 64)
-        base = C.addressof(self.buf)
-        self.p = (base + 63) & ~63           # 64-byte aligned
-        self.w = (C.c_void_p * 18)(*[self.p] * 18)
 
 
 def test_lk_fuse_tokens_refusals():
@@ -100,19 +86,9 @@ def test_dit_glue_refusals():
     assert patch(out=h.p + 8) == ALIGN and step(noise=h.p + 2) == ALIGN
 
 
-def _tiny_cpu_model():
-    from lkgd_amd import cogvideox as pc
-    from oracle import cogvideox as oc
-    o = oc.init_weights_(oc.CogVideoXTransformer3DModel(oc.TINY_DIT), 4242)
-    m = pc.CogVideoXTransformer3DModel(pc.DiTConfig(**oc.TINY_DIT.__dict__))
-    missing, unexpected = m.load_state_dict(o.state_dict(), strict=False)
-    assert not missing and not unexpected
-    return m
-
-
 def test_pack_lk_tokens_shapes_and_hamilton():
     from lkgd_amd import lk_fuse
-    m = _tiny_cpu_model()
+    m = tiny_cpu_model(4242)
     ws, ptrs = lk_fuse.pack_lk_tokens(m)
     assert [tuple(w.shape) for w in ws] == lk_fuse.LK_TOKENS_SHAPES == [
         (256, 16), (256, 4), (256, 4), (256,), (1024, 512), (512,), (129,), (129,), (512, 256), (256,), (512, 256), (256,), (5,), (5,),
@@ -140,7 +116,7 @@ def test_pack_lk_tokens_shapes_and_hamilton():
 
 def test_fused_text_on_a_cpu_model_raises():
     from lkgd_amd._lib import LkgdHipError
-    m = _tiny_cpu_model()
+    m = tiny_cpu_model(4242)
     with pytest.raises(LkgdHipError, match="no CPU path"):
         m.fused_text(torch.zeros(1, 4, 4096), torch.zeros(1, 1, 1000), torch.zeros(1, 1, 1000))
 

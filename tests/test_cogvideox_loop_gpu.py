@@ -9,12 +9,13 @@ import pytest
 import torch
 from safetensors.torch import load_file
 
+from cogvideox_support import (DEV, DIT_SEED, aten_denoise, aten_step as _aten_step, dit_inputs as _pin_inputs, glue_data as _glue_data,
+                               hip_twin, loop_inputs as _loop_inputs, patchify as _patchify, rel as _rel, tiny_oracle as _oracle,
+                               unpatchify as _unpatchify)
 from footprint import run_case
 
 gpu = pytest.mark.gpu
-DEV = "cuda:0"
 LK_SEED = 4242                       # weights of the fuse tests
-DIT_SEED = 191                       # make_goldens.py: weights of tests/golden/cogvideox.safetensors
 
 #: every name in lkgd_amd._lib.DIT_LOOP_SYMBOLS -> its footprint tests in this module (the rule REGISTRY keeps for _lib.SYMBOLS in
 #: tests/test_footprint_gpu.py)
@@ -28,41 +29,18 @@ FUSE_CASES = [(2, 1, 1), (2, 5, 2), (2, 16, 1), (3, 7, 3)]        # (B, L, Bd): 
 GLUE_SHAPES = [(1, 3, 16, 8, 12), (2, 2, 16, 6, 10), (1, 1, 4, 2, 4)]   # (B, F, C, H, W); the second has an odd w = 5
 
 
-def _rel(a, b):
-    a, b = a.float().cpu(), b.float().cpu()
-    return ((a - b).norm() / b.norm()).item()
-
-
-def _oracle(seed):
-    from oracle import cogvideox as oc
-    o = oc.init_weights_(oc.CogVideoXTransformer3DModel(oc.TINY_DIT), seed)
-    with torch.no_grad():
-        for p in o.parameters():
-            p.copy_(p.half().float())
-    return o
-
-
-def _hip(o, dev=DEV):
-    from lkgd_amd import cogvideox as pc
-    from oracle import cogvideox as oc
-    m = pc.CogVideoXTransformer3DModel(pc.DiTConfig(**oc.TINY_DIT.__dict__))
-    missing, unexpected = m.load_state_dict(o.state_dict(), strict=False)
-    assert not missing and not unexpected, (missing, unexpected)
-    return m.half().to(dev)
-
-
 @pytest.fixture(scope="module")
 def lk():
     """(oracle, HIP model) with the fuse tests' weights; neither is modified by a test"""
     o = _oracle(LK_SEED)
-    return o, _hip(o)
+    return o, hip_twin(o, dev=DEV)
 
 
 @pytest.fixture(scope="module")
 def pinned():
     """(oracle, HIP model) with the weights of the reference fixture"""
     o = _oracle(DIT_SEED)
-    return o, _hip(o)
+    return o, hip_twin(o, dev=DEV)
 
 
 def _fuse_inputs(seed):
@@ -136,16 +114,6 @@ def test_lk_fuse_tokens_rows_are_independent(lk):
     assert torch.equal(outw[:, :, :4096], full) and bool(torch.isnan(outw[:, :, 4096:]).all())
 
 
-def _pin_inputs(cfg, seed=DIT_SEED + 1, batch=2):
-    """make_goldens.py::dit_inputs"""
-    g = torch.Generator().manual_seed(seed)
-    f = (cfg.sample_frames - 1) // cfg.temporal_compression_ratio + 1
-    return dict(hidden=torch.randn(batch, f, cfg.in_channels, cfg.sample_height, cfg.sample_width, generator=g).half().float(),
-                text=torch.randn(batch, cfg.max_text_seq_length, cfg.text_embed_dim, generator=g).half().float(),
-                t=torch.tensor([721] * batch), domain=torch.randn(1, 1, 1000, generator=g),
-                flow=torch.randn(1, 1, 1000, generator=g))
-
-
 def _no_aten_fuse(monkeypatch):
     def refuse(*a, **k):
         raise AssertionError("the DiT path called rocFFT / ATen interpolation")
@@ -174,41 +142,6 @@ def test_fused_text_vs_reference_pin_without_aten(pinned, golden_dir, monkeypatc
 
 
 # -------------------------------------------------------------------------------------------------------------- the glue
-def _patchify(x, p=2):
-    """the statement of forward_tokens"""
-    B, F, C_, H, W = x.shape
-    h, w = H // p, W // p
-    return x.reshape(B, F, C_, h, p, w, p).permute(0, 1, 3, 5, 2, 4, 6).reshape(B * F * h * w, C_ * p * p).contiguous()
-
-
-def _unpatchify(rows, B, F, H, W, p=2):
-    h, w = H // p, W // p
-    return rows.reshape(B, F, h, w, -1, p, p).permute(0, 1, 4, 2, 5, 3, 6).flatten(5, 6).flatten(3, 4).contiguous()
-
-
-def _glue_data(shape, seed):
-    g = torch.Generator().manual_seed(seed)
-    B, F, C_, H, W = shape
-    lat = torch.randn(B, F, C_, H, W, generator=g)
-    img = (0.5 * torch.randn(B, F, C_, H, W, generator=g)).half()
-    noise = (2 * torch.randn(2 * B * F * (H // 2) * (W // 2), C_ * 4, generator=g)).half()
-    return lat, img, noise
-
-
-def _aten_step(noise_rows, lat, cfg, g, coef):
-    """denoise:606-611 of the loop before the kernels, on the tensors' device: .float(), the CFG statements,
-    CogVideoXDDIMScheduler.step, the cast back"""
-    B, F, C_, H, W = lat.shape
-    noise = _unpatchify(noise_rows, cfg * B, F, H, W).float()
-    if cfg == 2:
-        u, c = noise.chunk(2)
-        noise = u + g * (c - u)
-    a, b, sa, sb = coef
-    sample = lat.float()
-    x0 = sa * sample - sb * noise
-    return (a * sample + b * x0).to(lat.dtype)
-
-
 @gpu
 @pytest.mark.parametrize("shape", GLUE_SHAPES)
 def test_dit_patch_rows_bitwise(shape):
@@ -248,37 +181,6 @@ def test_dit_cfg_ddim_step_bitwise(shape):
                     assert torch.equal(lat, ref), (shape, t, lat0.dtype, cfg, (lat.float() - ref.float()).abs().max().item())
 
 
-def _loop_inputs(seed=5, f=3, cfg=True):
-    from oracle import cogvideox as oc
-    c = oc.TINY_DIT
-    g = torch.Generator().manual_seed(seed)
-    lat = torch.randn(1, f, 16, c.sample_height, c.sample_width, generator=g)
-    img = (0.5 * torch.randn(1, f, 16, c.sample_height, c.sample_width, generator=g)).half().float()
-    pe = torch.randn(2 if cfg else 1, c.max_text_seq_length, c.text_embed_dim, generator=g).half().float()
-    return lat, img, pe, torch.randn(1, 1, 1000, generator=g), torch.randn(1, 1, 1000, generator=g)
-
-
-def _old_denoise(pc, m, sched, latents, image_latents, prompt_embeds, dom, flow, steps, guidance_scale, callback):
-    """``denoise`` before the glue kernels: forward_tokens on the CFG-duplicated, channel-concatenated batch + ATen glue"""
-    sched.set_timesteps(steps)
-    cfg = guidance_scale > 1.0
-    text = m.fused_text(prompt_embeds, dom, flow)
-    latents = latents.to(torch.float16)
-    img = image_latents.to(torch.float16)
-    img2 = torch.cat([img] * 2) if cfg else img
-    for i, t in enumerate(sched.timesteps.tolist()):
-        x = torch.cat([latents] * 2) if cfg else latents
-        x = torch.cat([x, img2], dim=2)
-        noise = m.forward_tokens(x, text, float(t)).float()
-        g = pc.dynamic_guidance(guidance_scale, steps, t)
-        if cfg:
-            u, c = noise.chunk(2)
-            noise = u + g * (c - u)
-        latents = sched.step(noise, t, latents.float())[0].to(torch.float16)
-        callback(i, t, latents)
-    return latents
-
-
 @gpu
 @pytest.mark.parametrize("guidance_scale", [6.0, 1.0])
 def test_denoise_equals_the_aten_loop_bitwise(lk, guidance_scale):
@@ -291,7 +193,7 @@ def test_denoise_equals_the_aten_loop_bitwise(lk, guidance_scale):
     dv = [t.to(DEV) for t in (lat.half(), img, pe, dom, flow)]
     lat_in = dv[0].clone()
     old_steps, new_steps = [], []
-    old = _old_denoise(pc, m, pc.CogVideoXDDIMScheduler(), *dv, 4, guidance_scale, lambda i, t, l: old_steps.append(l))
+    old = aten_denoise(pc, m, pc.CogVideoXDDIMScheduler(), *dv, 4, guidance_scale, lambda i, t, l: old_steps.append(l))
     new = pc.denoise(m, pc.CogVideoXDDIMScheduler(), *dv, 4, guidance_scale, True, callback=lambda i, t, l: new_steps.append(l))
     assert torch.equal(dv[0], lat_in)                                # the caller's latents are not the loop's in-place operand
     assert len(new_steps) == len(old_steps) == 4 and new.dtype == torch.float16
@@ -344,7 +246,7 @@ def test_lk_fuse_tokens_footprint(B, L, Bd):
     from lkgd_amd import lk_fuse
     lib = _lib_()
     o = _oracle(LK_SEED)
-    ws_cpu, _ = lk_fuse.pack_lk_tokens(_hip(o, "cpu").float())
+    ws_cpu, _ = lk_fuse.pack_lk_tokens(hip_twin(o, dev="cpu").float())
     g = torch.Generator().manual_seed(100 * B + L)
     e = torch.randn(B, L, 4096, generator=g).half().float()
     d, f = 3 * torch.randn(Bd, 1, 1000, generator=g), 3 * torch.randn(Bd, 1, 1000, generator=g)

@@ -12,24 +12,7 @@ import torch
 from safetensors.torch import load_file
 
 import cogvideox_rope_oracle as ro
-
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-DIT_SEED = 191                                                        # make_goldens.py
-
-
-def _rel(a, b):
-    a, b = a.float().cpu(), b.float().cpu()
-    return ((a - b).norm() / b.norm()).item()
-
-
-def _inputs(cfg, seed=DIT_SEED + 1, batch=2):
-    """make_goldens.py::dit_inputs"""
-    g = torch.Generator().manual_seed(seed)
-    f = (cfg.sample_frames - 1) // cfg.temporal_compression_ratio + 1
-    return dict(hidden=torch.randn(batch, f, cfg.in_channels, cfg.sample_height, cfg.sample_width, generator=g).half().float(),
-                text=torch.randn(batch, cfg.max_text_seq_length, cfg.text_embed_dim, generator=g).half().float(),
-                t=torch.tensor([721] * batch), domain=torch.randn(1, 1, 1000, generator=g),
-                flow=torch.randn(1, 1, 1000, generator=g))
+from cogvideox_support import DIT_SEED, REPO, declared as _declared, dit_inputs as _inputs, hip_twin, rel as _rel
 
 
 @pytest.fixture(scope="module")
@@ -42,12 +25,12 @@ def test_dit_symbols_agree_three_ways():
     the built library with the table's signature, and declared with as many parameters as the table binds"""
     from lkgd_amd import _lib
     hdr = open(os.path.join(REPO, "include", "lkgd_hip_dit.h")).read()
-    declared = set(re.findall(r"\b(lkgd_[a-z0-9_]+)\s*\(", hdr))
+    declared = _declared("lkgd_hip_dit.h")
     assert declared == set(_lib.DIT_SYMBOLS) == {"lkgd_qk_norm_rope"}, declared ^ set(_lib.DIT_SYMBOLS)
     for other in (_lib.SYMBOLS, _lib.WINDOW_SYMBOLS, _lib.DEBUG_SYMBOLS):
         assert not declared & set(other)
     for h in ("lkgd_hip.h", "lkgd_hip_window.h", "lkgd_hip_debug.h"):
-        assert not declared & set(re.findall(r"\b(lkgd_[a-z0-9_]+)\s*\(", open(os.path.join(REPO, "include", h)).read())), h
+        assert not declared & _declared(h), h
     lib = _lib.lib()
     for s, (res, args) in _lib.DIT_SYMBOLS.items():
         fn = getattr(lib, s)
@@ -184,13 +167,8 @@ def test_config_refusals():
 
 
 def _tiny_rotary(learned=True):
-    from lkgd_amd import cogvideox as pc
     cfg = ro.RopeDiTConfig(**{**ro.TINY_ROPE_DIT.__dict__, "use_learned_positional_embeddings": learned})
-    o = ro.seeded_model(cfg, DIT_SEED)
-    m = pc.CogVideoXTransformer3DModel(pc.DiTConfig(**cfg.__dict__))
-    missing, unexpected = m.load_state_dict(o.state_dict(), strict=False)
-    assert not missing and not unexpected, (missing, unexpected)
-    return m
+    return hip_twin(ro.seeded_model(cfg, DIT_SEED), cfg)
 
 
 @pytest.mark.parametrize("learned", [True, False])

@@ -12,40 +12,16 @@ import torch.nn.functional as F
 from safetensors.torch import load_file
 
 import cogvideox_rope_oracle as ro
+from cogvideox_support import DEV, DIT_SEED, dit_inputs as _inputs, hip_twin, loop_inputs, rel as _rel
 from footprint import run_case
 
 gpu = pytest.mark.gpu
-DEV = "cuda:0"
-DIT_SEED = 191                                                        # make_goldens.py
 
 #: every name in lkgd_amd._lib.DIT_SYMBOLS -> its footprint tests in this module (the rule REGISTRY keeps for _lib.SYMBOLS in
 #: tests/test_footprint_gpu.py)
 FOOTPRINT = {
     "lkgd_qk_norm_rope": ["test_qk_norm_rope_footprint"],
 }
-
-
-def _rel(a, b):
-    a, b = a.float().cpu(), b.float().cpu()
-    return ((a - b).norm() / b.norm()).item()
-
-
-def _inputs(cfg, seed=DIT_SEED + 1, batch=2):
-    """make_goldens.py::dit_inputs"""
-    g = torch.Generator().manual_seed(seed)
-    f = (cfg.sample_frames - 1) // cfg.temporal_compression_ratio + 1
-    return dict(hidden=torch.randn(batch, f, cfg.in_channels, cfg.sample_height, cfg.sample_width, generator=g).half().float(),
-                text=torch.randn(batch, cfg.max_text_seq_length, cfg.text_embed_dim, generator=g).half().float(),
-                t=torch.tensor([721] * batch), domain=torch.randn(1, 1, 1000, generator=g),
-                flow=torch.randn(1, 1, 1000, generator=g))
-
-
-def _hip(o, cfg):
-    from lkgd_amd import cogvideox as pc
-    m = pc.CogVideoXTransformer3DModel(pc.DiTConfig(**cfg.__dict__))
-    missing, unexpected = m.load_state_dict(o.state_dict(), strict=False)
-    assert not missing and not unexpected, (missing, unexpected)
-    return m.half().to(DEV)
 
 
 @pytest.fixture(scope="module")
@@ -57,7 +33,7 @@ def golden(golden_dir):
 def tiny():
     """(twin, HIP model) of the fixture's tiny rotary DiT; neither is modified by a test"""
     o = ro.seeded_model(ro.TINY_ROPE_DIT, DIT_SEED)
-    return o, _hip(o, ro.TINY_ROPE_DIT)
+    return o, hip_twin(o, ro.TINY_ROPE_DIT, DEV)
 
 
 # --------------------------------------------------------------------------------------------------------------- the kernel
@@ -288,7 +264,7 @@ def test_hip_rotary_dit_real_width_vs_twin():
     from lkgd_amd import cogvideox as pc
     cfg = ro.RopeDiTConfig(num_attention_heads=48, in_channels=32, num_layers=2, sample_width=24, sample_height=16, sample_frames=17)
     o = ro.seeded_model(cfg, DIT_SEED)
-    m = _hip(o, cfg)
+    m = hip_twin(o, cfg, DEV)
     i = _inputs(cfg, seed=7)
     cos, sin = pc.rotary_tables(m.config, 5, 8, 12)
     with torch.no_grad():
@@ -308,13 +284,8 @@ def test_hip_rotary_dit_loop_vs_twin(tiny):
     from oracle import cogvideox as oc
     cfg = ro.TINY_ROPE_DIT
     o, m = tiny
-    g = torch.Generator().manual_seed(5)
-    f = 3
-    lat = torch.randn(1, f, 16, cfg.sample_height, cfg.sample_width, generator=g)
-    img = (0.5 * torch.randn(1, f, 16, cfg.sample_height, cfg.sample_width, generator=g)).half().float()
-    pe = torch.randn(2, cfg.max_text_seq_length, cfg.text_embed_dim, generator=g).half().float()
-    dom, flow = torch.randn(1, 1, 1000, generator=g), torch.randn(1, 1, 1000, generator=g)
-    rope = ro.rotary_tables(cfg, f, cfg.sample_height // 2, cfg.sample_width // 2)
+    lat, img, pe, dom, flow = loop_inputs(cfg)
+    rope = ro.rotary_tables(cfg, 3, cfg.sample_height // 2, cfg.sample_width // 2)
     ref_steps, got_steps = [], []
     ref = oc.denoise(lambda *a: o(*a, image_rotary_emb=rope), oc.CogVideoXDDIMScheduler(), lat.half().float(), img, pe, dom, flow, 4,
                      6.0, True, callback=lambda i, t, l: ref_steps.append(l.clone()))
@@ -341,7 +312,7 @@ def _worker_rope_dit(rank, world, port, q):
         from lkgd_amd import cogvideox as pc
         from lkgd_amd.dist_run import DistDiTDenoiser
         dev = torch.device("cuda", 0)
-        m = _hip(ro.seeded_model(ro.TINY_ROPE_DIT, 4), ro.TINY_ROPE_DIT)
+        m = hip_twin(ro.seeded_model(ro.TINY_ROPE_DIT, 4), ro.TINY_ROPE_DIT, DEV)
         g = torch.Generator().manual_seed(79)
         lat = torch.randn(1, 3, 16, 8, 12, generator=g).half()
         img = (0.5 * torch.randn(1, 3, 16, 8, 12, generator=g)).half()

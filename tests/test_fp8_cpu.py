@@ -2,7 +2,6 @@
 bad arguments with the documented codes before any launch; ``quantize_weight`` against the independent restatement of
 tests/fp8_oracle.py; ``quantize_to_float8`` / ``dequantize`` state, the refusals and LKGD_DIT_FP8; the fake-quant twin against its fp32
 original at ``TINY_DIT`` (the distance ``e_q`` the GPU rule is built on)."""
-import ctypes as C
 import os
 import re
 
@@ -10,15 +9,12 @@ import pytest
 import torch
 
 import fp8_oracle as fo
+from cogvideox_support import REPO, Host as _Host, declared as _declared, dit_inputs as _inputs, tiny_cpu_model as _tiny_cpu_model, \
+    tiny_oracle as _oracle
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = {"lkgd_quant_rows_fp8", "lkgd_gelu_tanh_quant_fp8", "lkgd_layernorm_quant_fp8", "lkgd_gemm_fp8"}
 OK, NULL, SHAPE, ALIGN = 0, -1, -2, -3
 DIT_SEED = 191                                                      # make_goldens.py
-
-
-def _declared(header):
-    return set(re.findall(r"\b(lkgd_[a-z0-9_]+)\s*\(", open(os.path.join(REPO, "include", header)).read()))
 
 
 def test_fp8_symbols_agree_three_ways():
@@ -39,14 +35,6 @@ def test_fp8_symbols_agree_three_ways():
         decl = re.search(r"^int %s\s*\(([^;]*)\);" % s, hdr, re.M | re.S).group(1)
         assert len(re.sub(r"/\*.*?\*/", "", decl).split(",")) == len(args), s
     assert [len(_lib.FP8_SYMBOLS[s][1]) for s in sorted(NAMES)] == [8, 13, 11, 8]
-
-
-class _Host:
-    """host memory standing in for device pointers: a refused call never launches, so nothing dereferences them"""
-
-    def __init__(self):
-        self.buf = C.create_string_buffer(4096 + 64)
-        self.p = (C.addressof(self.buf) + 63) & ~63
 
 
 def test_fp8_entry_points_refuse_before_launching():
@@ -138,12 +126,6 @@ def test_quantize_weight_is_the_statement(K):
 
 
 # ------------------------------------------------------------------------------------------------------- the mode's state
-def _tiny_cpu_model(**over):
-    from lkgd_amd import cogvideox as pc
-    from oracle import cogvideox as oc
-    return pc.CogVideoXTransformer3DModel(pc.DiTConfig(**{**oc.TINY_DIT.__dict__, **over}))
-
-
 def test_quantize_to_float8_state_and_refusals(monkeypatch):
     from lkgd_amd import cogvideox as pc
     from lkgd_amd import fp8
@@ -219,25 +201,6 @@ def test_sharding_together_with_the_mode_raises(monkeypatch):
 
 
 # ------------------------------------------------------------------------------------------------------- the twin and e_q
-def _oracle(seed):
-    from oracle import cogvideox as oc
-    o = oc.init_weights_(oc.CogVideoXTransformer3DModel(oc.TINY_DIT), seed)
-    with torch.no_grad():
-        for p in o.parameters():
-            p.copy_(p.half().float())
-    return o
-
-
-def _inputs(cfg, seed, batch=2):
-    """make_goldens.py::dit_inputs"""
-    g = torch.Generator().manual_seed(seed)
-    f = (cfg.sample_frames - 1) // cfg.temporal_compression_ratio + 1
-    return dict(hidden=torch.randn(batch, f, cfg.in_channels, cfg.sample_height, cfg.sample_width, generator=g).half().float(),
-                text=torch.randn(batch, cfg.max_text_seq_length, cfg.text_embed_dim, generator=g).half().float(),
-                t=torch.tensor([721] * batch), domain=torch.randn(1, 1, 1000, generator=g),
-                flow=torch.randn(1, 1, 1000, generator=g))
-
-
 @pytest.mark.parametrize("seed", [191, 7, 23])
 def test_twin_is_a_measurable_distance_from_its_original(seed):
     """e_q = d(twin, fp32 original) on the weights of seed and the inputs of seed + 1: at least 5e-3, so the GPU rule

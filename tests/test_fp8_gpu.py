@@ -8,10 +8,10 @@ import torch
 
 import footprint
 import fp8_oracle as fo
+from cogvideox_support import DEV, dit_inputs as _inputs, hip_twin, loop_inputs as _loop_inputs, tiny_oracle as _oracle
 from footprint import run_case
 
 gpu = pytest.mark.gpu
-DEV = "cuda:0"
 NAN_BYTE = 0x7F
 
 #: every name in lkgd_amd._lib.FP8_SYMBOLS -> its footprint tests in this module
@@ -367,31 +367,8 @@ def test_gemm_fp8_footprint(fp8_windows, M):
 
 
 # ---------------------------------------------------------------------------------------------------------- the DiT forward
-def _oracle(seed):
-    from oracle import cogvideox as oc
-    o = oc.init_weights_(oc.CogVideoXTransformer3DModel(oc.TINY_DIT), seed)
-    with torch.no_grad():
-        for p in o.parameters():
-            p.copy_(p.half().float())
-    return o
-
-
 def _hip(o, cfg):
-    from lkgd_amd import cogvideox as pc
-    m = pc.CogVideoXTransformer3DModel(pc.DiTConfig(**cfg.__dict__))
-    missing, unexpected = m.load_state_dict(o.state_dict(), strict=False)
-    assert not missing and not unexpected, (missing, unexpected)
-    return m.half().to(DEV)
-
-
-def _inputs(cfg, seed, batch=2):
-    """make_goldens.py::dit_inputs"""
-    g = torch.Generator().manual_seed(seed)
-    f = (cfg.sample_frames - 1) // cfg.temporal_compression_ratio + 1
-    return dict(hidden=torch.randn(batch, f, cfg.in_channels, cfg.sample_height, cfg.sample_width, generator=g).half().float(),
-                text=torch.randn(batch, cfg.max_text_seq_length, cfg.text_embed_dim, generator=g).half().float(),
-                t=torch.tensor([721] * batch), domain=torch.randn(1, 1, 1000, generator=g),
-                flow=torch.randn(1, 1, 1000, generator=g))
+    return hip_twin(o, cfg, DEV)
 
 
 def _forward_rule(what, run_oracle, run_hip, o, m16, m8):
@@ -451,16 +428,6 @@ def test_fp8_forward_of_the_tiny_15_model_against_its_twin():
         return m(*(i[k].to(DEV) for k in ("hidden", "text", "t", "domain", "flow")), ofs=2.0,
                  image_rotary_emb=pc.rotary_tables(m.config, 2, 4, 6), return_dict=False)[0]
     _forward_rule("TINY_V15_DIT", run_oracle, run_hip, o, m16, m8)
-
-
-def _loop_inputs(seed=5, f=3):
-    from oracle import cogvideox as oc
-    c = oc.TINY_DIT
-    g = torch.Generator().manual_seed(seed)
-    lat = torch.randn(1, f, 16, c.sample_height, c.sample_width, generator=g)
-    img = (0.5 * torch.randn(1, f, 16, c.sample_height, c.sample_width, generator=g)).half().float()
-    pe = torch.randn(2, c.max_text_seq_length, c.text_embed_dim, generator=g).half().float()
-    return lat, img, pe, torch.randn(1, 1, 1000, generator=g), torch.randn(1, 1, 1000, generator=g)
 
 
 @gpu

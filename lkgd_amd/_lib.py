@@ -149,6 +149,16 @@ DIT_TPATCH_SYMBOLS = {
                                         _f32, _vp]),
 }
 
+#: every symbol include/lkgd_hip_dit_dpm.h declares (CFG combine + DPM-Solver++ step of the CogVideoX loop, 2-D and temporal patches),
+#: bound on the same library object; tests/test_cogvideox_dpm_cpu.py pins header, table and library to one another,
+#: tests/test_cogvideox_dpm_gpu.py the footprint cases
+DIT_DPM_SYMBOLS = {
+    "lkgd_dit_cfg_dpm_step": (_i32, [_vp, _i32, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _f32, _f32,
+                                     _f32, _f32, _f32, _f32, _f32, _vp]),
+    "lkgd_dit_cfg_dpm_step_t": (_i32, [_vp, _i32, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _f32,
+                                       _f32, _f32, _f32, _f32, _f32, _f32, _vp]),
+}
+
 #: every symbol include/lkgd_hip_fp8.h declares (the FP8 e4m3 form of a DiT block's six linears: three dynamic per-row quantisers and
 #: the GEMM on the block-scaled matrix instruction), bound on the same library object; tests/test_fp8_cpu.py pins header, table and
 #: library to one another, tests/test_fp8_gpu.py the footprint cases
@@ -193,7 +203,8 @@ def lib() -> C.CDLL:
             l = C.CDLL(LIB_PATH)
         except OSError as e:
             raise LkgdHipError(f"cannot load {LIB_PATH}: {e}") from e
-        for table in (SYMBOLS, WINDOW_SYMBOLS, DIT_SYMBOLS, DIT_LOOP_SYMBOLS, DIT_TPATCH_SYMBOLS, FP8_SYMBOLS, DEBUG_SYMBOLS):
+        for table in (SYMBOLS, WINDOW_SYMBOLS, DIT_SYMBOLS, DIT_LOOP_SYMBOLS, DIT_TPATCH_SYMBOLS, DIT_DPM_SYMBOLS, FP8_SYMBOLS,
+                      DEBUG_SYMBOLS):
             for name, (res, args) in table.items():
                 fn = getattr(l, name)       # AttributeError here = header / library mismatch
                 fn.restype, fn.argtypes = res, args

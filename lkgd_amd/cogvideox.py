@@ -32,6 +32,10 @@ MI355X design - the UNet's kernels, one joint token buffer:
   them, ``lkgd_dit_cfg_ddim_step`` takes proj_out's token rows through the CFG combine and the DDIM update into the latents in
   place.  ``forward_tokens`` / ``forward`` keep the [B, F, C, H, W] interface: their patch unfold / un-patchify are torch permutes
   (data movement at the API edge);
+* the loop's other scheduler branch (``CogVideoXDPMScheduler``: DPM-Solver++ SDE 2M, what the reference installs for the 5B models;
+  DESIGN.md section 15): the same two launches per step with ``lkgd_dit_cfg_dpm_step`` (include/lkgd_hip_dit_dpm.h) as the second -
+  CFG combine, x0, the first- or second-order update with the step's noise, the fp32 ``old_pred_original_sample`` state and the
+  cast back, 2-D and temporal patches;
 * the 1.5 models (``patch_size_t = 2``, rotary, no learned table, with or without ``ofs_embed_dim``): a token
   spans two latent frames, so the patch embedding is a Linear over C p_t p p columns and the grid is (F / p_t, h, w); the loop's
   glue is the ``_t`` pair of include/lkgd_hip_dit_tpatch.h; the ``ofs`` embedding (timestep-embedding kernel + two small GEMMs,
@@ -46,6 +50,7 @@ MI355X design - the UNet's kernels, one joint token buffer:
 from __future__ import annotations
 
 import math
+from collections import namedtuple
 from dataclasses import dataclass
 from types import SimpleNamespace
 from typing import Optional
@@ -716,10 +721,10 @@ class CogVideoXTransformer3DModel(nn.Module):
 
 
 # ------------------------------------------------------------------------------------------------ scheduler + loop
-class CogVideoXDDIMScheduler:
-    """[EXT diffusers scheduling_ddim_cogvideox.py] with CogVideoX-2B's scheduler_config.json (scaled-linear betas
-    0.00085..0.012, snr_shift_scale 3.0, zero-terminal-SNR rescale, trailing spacing, v-prediction, set_alpha_to_one); host
-    tables in fp64, the update itself runs on the device"""
+class _CogVideoXSchedule:
+    """what the two CogVideoX schedulers share, [EXT diffusers scheduling_ddim_cogvideox.py / scheduling_dpm_cogvideox.py] with
+    CogVideoX's scheduler_config.json (scaled-linear betas 0.00085..0.012, snr_shift_scale 3.0 for the 2B and 1.0 for the 5B models,
+    zero-terminal-SNR rescale, trailing spacing, v-prediction, set_alpha_to_one): the host tables in fp64 and the timesteps"""
     order = 1
     init_noise_sigma = 1.0
 
@@ -732,7 +737,7 @@ class CogVideoXDDIMScheduler:
         self.alphas_cumprod = ((s - sT) * (s0 / (s0 - sT))) ** 2
         self.final_alpha_cumprod = torch.tensor(1.0, dtype=torch.float64)
         self.config = SimpleNamespace(num_train_timesteps=num_train_timesteps, prediction_type="v_prediction",
-                                      timestep_spacing="trailing", snr_shift_scale=snr_shift_scale)
+                                      timestep_spacing="trailing", snr_shift_scale=snr_shift_scale, _class_name=type(self).__name__)
         self.timesteps = None
 
     def set_timesteps(self, num_inference_steps: int, device=None):
@@ -743,10 +748,18 @@ class CogVideoXDDIMScheduler:
     def scale_model_input(self, sample, timestep=None):
         return sample
 
-    def coefficients(self, t: int):
+    def _alpha_pair(self, t: int):
+        """(alphas_cumprod[t], alphas_cumprod of the step's target, the target's timestep), fp64 0-dim tensors"""
         prev_t = t - self.config.num_train_timesteps // self.num_inference_steps
-        at = self.alphas_cumprod[t]
-        ap = self.alphas_cumprod[prev_t] if prev_t >= 0 else self.final_alpha_cumprod
+        return self.alphas_cumprod[t], (self.alphas_cumprod[prev_t] if prev_t >= 0 else self.final_alpha_cumprod), prev_t
+
+
+class CogVideoXDDIMScheduler(_CogVideoXSchedule):
+    """[EXT diffusers scheduling_ddim_cogvideox.py] (the reference's cli_demo.py recommends it for CogVideoX-2B); host tables in
+    fp64, the update itself runs on the device"""
+
+    def coefficients(self, t: int):
+        at, ap, _ = self._alpha_pair(t)
         a = ((1 - ap) / (1 - at)) ** 0.5
         b = ap ** 0.5 - at ** 0.5 * a
         return float(a), float(b), float(at ** 0.5), float((1 - at) ** 0.5)
@@ -757,15 +770,105 @@ class CogVideoXDDIMScheduler:
         return (a * sample + b * x0,)
 
 
+#: ``CogVideoXDPMScheduler.coefficients``: x0 = sqrt_alpha x - sqrt_beta n; order 1: x' = m1 x - m2 x0 + mn eps; order 2: the same
+#: with m3 x0 - m4 x0_old in the place of x0
+DPMCoefficients = namedtuple("DPMCoefficients", "sqrt_alpha sqrt_beta m1 m2 m3 m4 mn order")
+
+
+class CogVideoXDPMScheduler(_CogVideoXSchedule):
+    """[EXT diffusers scheduling_dpm_cogvideox.py], PARITY UNPINNED: DPM-Solver++ (SDE, 2M) on the tables of
+    the DDIM class - the scheduler the reference's pipeline keeps ``old_pred_original_sample`` for
+    (pipeline_cogvideox_image2video.py:832-883) and its cli_demo.py installs for CogVideoX-5B / 5B-I2V.  ``coefficients`` in fp64 on
+    the host; ``step`` is the out-of-place ATen form, ``denoise`` runs the same statements as one launch (``ops.dit_cfg_dpm_step``)"""
+
+    def coefficients(self, t: int, t_back: Optional[int] = None) -> DPMCoefficients:
+        """``t_back``: the previous timestep of the loop, None on its first step.  At t = 999 alphas_cumprod is 0 (zero terminal SNR):
+        lam = -inf, h = +inf, and the multipliers are their finite limits (m1 = 0, m2 = -sqrt(ap)); on the step after it r = inf gives
+        m3 = 1, m4 = 0; a last step onto final_alpha_cumprod = 1 has lam_next = +inf and (m1, m2, mn) = (0, -1, 0) - all of it by
+        IEEE arithmetic on fp64 0-dim tensors, as written"""
+        at, ap, prev_t = self._alpha_pair(int(t))
+        lam = torch.log((at / (1 - at)) ** 0.5)
+        lam_next = torch.log((ap / (1 - ap)) ** 0.5)
+        h = lam_next - lam
+        m1 = ((1 - ap) / (1 - at)) ** 0.5 * torch.exp(-h)
+        m2 = torch.expm1(-2 * h) * ap ** 0.5
+        mn = (1 - ap) ** 0.5 * (1 - torch.exp(-2 * h)) ** 0.5
+        m3, m4, order = 1.0, 0.0, 1
+        if t_back is not None and prev_t >= 0:
+            ab = self.alphas_cumprod[int(t_back)]
+            r = (lam - torch.log((ab / (1 - ab)) ** 0.5)) / h
+            m3, m4, order = 1 + 1 / (2 * r), 1 / (2 * r), 2
+        return DPMCoefficients(float(at ** 0.5), float((1 - at) ** 0.5), float(m1), float(m2), float(m3), float(m4), float(mn), order)
+
+    def step(self, model_output, old_pred_original_sample, timestep, timestep_back, sample, eta: float = 0.0, generator=None,
+             return_dict: bool = False):
+        """the reference's argument order -> (prev_sample, pred_original_sample), both fp32 (the pipeline casts the first back).
+        The noise is ``randn`` of the sample's shape in the sample's dtype from ``generator`` (a generator of another device draws
+        on that device and the tensor is moved; lkgd_amd/scheduler.py); a second-order step draws twice and uses the second draw"""
+        if eta != 0.0:
+            raise LkgdHipError(f"CogVideoXDPMScheduler.step: eta={eta!r} is not built (eta 0.0 only)")
+        if return_dict:
+            raise LkgdHipError("CogVideoXDPMScheduler.step: return_dict=True is not built (the pipeline passes False)")
+        second = old_pred_original_sample is not None and timestep_back is not None
+        k = self.coefficients(int(timestep), int(timestep_back) if second else None)
+        eps = dpm_noise(sample.shape, sample.dtype, sample.device, generator, k.order)
+        x = sample.float()
+        x0 = k.sqrt_alpha * x - k.sqrt_beta * model_output.float()
+        d = x0 if k.order == 1 else k.m3 * x0 - k.m4 * old_pred_original_sample.float()
+        prev = k.m1 * x - k.m2 * d
+        if k.mn != 0.0:
+            prev = prev + k.mn * eps.float()
+        return prev, x0
+
+
+def dpm_noise(shape, dtype, device, generator, order: int) -> torch.Tensor:
+    """the draws of one DPM step: ``order`` calls of randn, the last one kept ([EXT] scheduling_dpm_cogvideox.py: a second-order step
+    draws twice and uses the second draw - with a caller's generator the discarded draw is observable in its state)"""
+    gdev = generator.device if generator is not None else device
+    for _ in range(order):
+        eps = torch.randn(tuple(shape), generator=generator, device=gdev, dtype=dtype)
+    return eps.to(device)
+
+
+_SCHEDULERS = {c.__name__: c for c in (CogVideoXDDIMScheduler, CogVideoXDPMScheduler)}
+
+
+def scheduler_from_config(path_or_dict):
+    """a checkpoint directory (its ``scheduler/scheduler_config.json``, read as lkgd_amd/loading.py reads the other configs) or that
+    file's contents as a dict -> the scheduler its ``_class_name`` names.  Every value that is not the one implemented raises,
+    naming the key"""
+    raw, where = path_or_dict, "scheduler_from_config"
+    if not isinstance(raw, dict):
+        from .loading import load_config
+        raw = load_config(str(path_or_dict), "scheduler", name="scheduler_config.json")
+        where = f"scheduler_from_config({str(path_or_dict)!r})"
+    name = raw.get("_class_name")
+    if name not in _SCHEDULERS:
+        raise LkgdHipError(f"{where}: _class_name={name!r}; built: {sorted(_SCHEDULERS)}")
+    built = dict(prediction_type="v_prediction", timestep_spacing="trailing", rescale_betas_zero_snr=True, set_alpha_to_one=True,
+                 beta_schedule="scaled_linear")
+    # a key the file leaves out has the constructor default of [EXT] diffusers' two CogVideoX schedulers - for three of the five not
+    # the value the released checkpoints set, so a config without them is refused like one that sets them otherwise
+    absent = dict(prediction_type="epsilon", timestep_spacing="leading", rescale_betas_zero_snr=False, set_alpha_to_one=True,
+                  beta_schedule="scaled_linear")
+    for key, want in built.items():
+        got = raw.get(key, absent[key])
+        if got != want:
+            raise LkgdHipError(f"{where}: {key}={got!r}{'' if key in raw else ' (the default of an absent key)'}; only "
+                               f"{key}={want!r} is built")
+    kw = {k: raw[k] for k in ("num_train_timesteps", "beta_start", "beta_end", "snr_shift_scale") if k in raw}
+    return _SCHEDULERS[name](**kw)
+
+
 def dynamic_guidance(guidance_scale: float, num_inference_steps: int, t: int) -> float:
     """pipeline_cogvideox_image2video.py:866-869"""
     return 1 + guidance_scale * ((1 - math.cos(math.pi * ((num_inference_steps - t) / num_inference_steps) ** 5.0)) / 2)
 
 
 @torch.no_grad()
-def denoise(transformer: CogVideoXTransformer3DModel, scheduler: CogVideoXDDIMScheduler, latents, image_latents, prompt_embeds,
+def denoise(transformer: CogVideoXTransformer3DModel, scheduler, latents, image_latents, prompt_embeds,
             domain_features, flow_features, num_inference_steps: int = 50, guidance_scale: float = 6.0,
-            use_dynamic_cfg: bool = True, callback=None, image_rotary_emb=None, ofs=None) -> torch.Tensor:
+            use_dynamic_cfg: bool = True, callback=None, image_rotary_emb=None, ofs=None, generator=None) -> torch.Tensor:
     """the loop of pipeline_cogvideox_image2video.py:829-885 (the rotary tables are built once per clip when the config asks for
     them and none are given, :819-823).  latents / image_latents [B, F, C, h, w]; prompt_embeds
     [2B, L, 4096] (negative first) when guidance_scale > 1.  The update runs in fp32 (``noise_pred.float()`` :863) and the
@@ -773,7 +876,15 @@ def denoise(transformer: CogVideoXTransformer3DModel, scheduler: CogVideoXDDIMSc
     ``forward_rows`` -> ``lkgd_dit_cfg_ddim_step`` (include/lkgd_hip_dit_loop.h); ``scheduler`` supplies ``coefficients(t)``.
     A ``patch_size_t`` model takes tensors prepared by ``pad_for_temporal_patches`` (F % p_t == 0, or it raises), runs the ``_t``
     glue pair (include/lkgd_hip_dit_tpatch.h) on the (F / p_t, h, w) grid, and embeds ``ofs`` (default 2.0 when the config has
-    ``ofs_embed_dim``, :826) once per clip."""
+    ``ofs_embed_dim``, :826) once per clip.
+    ``scheduler`` is a ``CogVideoXDDIMScheduler`` (the steps above) or a ``CogVideoXDPMScheduler`` (:874-883): the step is then
+    ``lkgd_dit_cfg_dpm_step`` (include/lkgd_hip_dit_dpm.h) on ``coefficients(t, previous t)``, with ``old_pred_original_sample`` kept
+    in one fp32 tensor per clip and the step's noise drawn from ``generator`` in the latents' dtype (``dpm_noise``: twice on a
+    second-order step).  Anything else raises: there is no step to fall back to."""
+    dpm = isinstance(scheduler, CogVideoXDPMScheduler)
+    if not dpm and not isinstance(scheduler, CogVideoXDDIMScheduler):
+        raise LkgdHipError(f"denoise: scheduler is a {type(scheduler).__module__}.{type(scheduler).__qualname__}; the loop's step is "
+                           "built for CogVideoXDDIMScheduler and CogVideoXDPMScheduler")
     dev = transformer.device
     if transformer.config.patch_size_t is not None and latents.shape[1] % transformer.config.patch_size_t:
         raise LkgdHipError(f"denoise: patch_size_t {transformer.config.patch_size_t} does not divide the {latents.shape[1]} latent "
@@ -799,13 +910,22 @@ def denoise(transformer: CogVideoXTransformer3DModel, scheduler: CogVideoXDDIMSc
             image_rotary_emb = rotary_tables(tc, *grid)
         image_rotary_emb = tuple(t.to(device=dev, dtype=torch.float32).contiguous() for t in image_rotary_emb)
     rows = None
+    # DPM: old_pred_original_sample, fp32; step i reads step i - 1's x0 (second order only) and leaves its own
+    x0_state = torch.empty(latents.shape, dtype=torch.float32, device=dev) if dpm else None
+    t_back = None
     for i, t in enumerate(scheduler.timesteps.tolist()):
         # torch.cat([latents] * 2), the channel concat and the patch unfold: ONE set of rows, embedded for every CFG entry
         rows = ops.dit_patch_rows(latents, img, p, out=rows, **glue)
         noise_rows = transformer.forward_rows(rows, grid, text, float(t), image_rotary_emb=image_rotary_emb, **extra)
         g = dynamic_guidance(guidance_scale, num_inference_steps, t) if use_dynamic_cfg else guidance_scale
         # noise_pred.float(), the CFG combine, scheduler.step and the cast back: one launch, in place
-        ops.dit_cfg_ddim_step(noise_rows, latents, p, 2 if cfg else 1, g, *scheduler.coefficients(int(t)), **glue)
+        if dpm:
+            k = scheduler.coefficients(int(t), t_back)
+            eps = dpm_noise(latents.shape, latents.dtype, dev, generator, k.order)
+            ops.dit_cfg_dpm_step(noise_rows, latents, x0_state, eps, p, 2 if cfg else 1, k.order, g, k, **glue)
+            t_back = int(t)
+        else:
+            ops.dit_cfg_ddim_step(noise_rows, latents, p, 2 if cfg else 1, g, *scheduler.coefficients(int(t)), **glue)
         if callback is not None:
             callback(i, t, latents.clone())         # a tensor of the callback's own, as the out-of-place loop handed out
     return latents

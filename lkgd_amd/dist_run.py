@@ -290,6 +290,11 @@ class DistDiTDenoiser:
         if getattr(transformer.config, "patch_size_t", None) is not None:
             raise LkgdHipError("DistDiTDenoiser: a patch_size_t (CogVideoX 1.5) model is not sharded - a token spans two latent "
                                "frames, the frame split is not built; run lkgd_amd.cogvideox.denoise on one GPU")
+        from .cogvideox import CogVideoXDPMScheduler
+        if isinstance(scheduler, CogVideoXDPMScheduler):
+            raise LkgdHipError("DistDiTDenoiser: the replicated stochastic step of CogVideoXDPMScheduler needs identical noise on "
+                               "every rank; sharded DPM sampling is not built - sharded sampling needs CogVideoXDDIMScheduler "
+                               "(lkgd_amd.cogvideox.denoise runs the DPM scheduler on one GPU)")
         if not dist.is_initialized():
             raise LkgdHipError("torch.distributed is not initialised")
         self.transformer, self.scheduler = transformer, scheduler

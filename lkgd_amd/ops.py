@@ -863,6 +863,41 @@ def dit_cfg_ddim_step(noise_rows: torch.Tensor, latents: torch.Tensor, p: int, c
     return latents
 
 
+def dit_cfg_dpm_step(noise_rows: torch.Tensor, latents: torch.Tensor, x0_state: torch.Tensor, eps: Optional[torch.Tensor], p: int,
+                     cfg: int, order: int, g: float, coef, p_t: Optional[int] = None) -> torch.Tensor:
+    """in-place CFG combine + DPM-Solver++ update of ``latents`` [B,F,C,H,W] from proj_out's token rows, as ``dit_cfg_ddim_step`` takes
+    them (lkgd_dit_cfg_dpm_step / _t with ``p_t``, include/lkgd_hip_dit_dpm.h).  ``x0_state`` fp32, the latents' shape: read when
+    ``order`` is 2 (the previous step's x0), always rewritten with this step's.  ``eps``: the step's noise in the latents' shape and
+    dtype; None only when ``coef.mn`` is 0.  ``coef`` = ``CogVideoXDPMScheduler.coefficients(t, t_back)`` (its own ``order`` field is
+    not read: the caller passes ``order``)"""
+    B, F, C_, H, W = _dit_latents(latents, p, p_t)
+    _req(noise_rows, torch.float16, "noise_rows")
+    _req(x0_state, torch.float32, "x0_state")
+    rows, width = cfg * B * F * (H // p) * (W // p), C_ * p * p
+    if p_t is not None:
+        rows, width = rows // p_t, width * p_t
+    if cfg not in (1, 2) or noise_rows.dim() != 2 or tuple(noise_rows.shape) != (rows, width) or noise_rows.stride(1) != 1:
+        raise _lib.LkgdHipError(f"noise_rows must be an fp16 [{rows}, {width}] matrix (cfg 1 or 2), got "
+                                f"{tuple(noise_rows.shape)}, cfg = {cfg}")
+    if order not in (1, 2):
+        raise _lib.LkgdHipError(f"dit_cfg_dpm_step: order must be 1 or 2, got {order!r}")
+    if tuple(x0_state.shape) != tuple(latents.shape) or not x0_state.is_contiguous():
+        raise _lib.LkgdHipError(f"x0_state must be contiguous fp32 {tuple(latents.shape)}, got {tuple(x0_state.shape)}")
+    mn = float(coef.mn)
+    if eps is None:
+        if mn != 0.0:
+            raise _lib.LkgdHipError(f"dit_cfg_dpm_step: the step has a noise term (mn = {mn}) and needs eps")
+    else:
+        _req(eps, latents.dtype, "eps")
+        if tuple(eps.shape) != tuple(latents.shape) or not eps.is_contiguous():
+            raise _lib.LkgdHipError(f"eps must be contiguous {tuple(latents.shape)} in the latents' dtype, got {tuple(eps.shape)}")
+    name, pt = ("lkgd_dit_cfg_dpm_step", ()) if p_t is None else ("lkgd_dit_cfg_dpm_step_t", (p_t,))
+    check(getattr(_L(), name)(noise_rows.data_ptr(), _ld(noise_rows), latents.data_ptr(), int(latents.dtype == torch.float32),
+                              x0_state.data_ptr(), _ptr(eps), B, F, C_, H, W, p, *pt, cfg, order, g, float(coef.sqrt_alpha),
+                              float(coef.sqrt_beta), float(coef.m1), float(coef.m2), float(coef.m3), float(coef.m4), mn, _stream()), name)
+    return latents
+
+
 def qk_norm_rope(q: torch.Tensor, k: torch.Tensor, heads: int, nq, nk, eps: float, rope, rows_per_batch: int,
                  split: int) -> None:
     """per-head LayerNorm of q and k, then the rotary embedding of their video rows, in place and in one launch

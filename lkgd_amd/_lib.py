@@ -169,6 +169,17 @@ FP8_SYMBOLS = {
     "lkgd_gemm_fp8": (_i32, [_vp, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp]),
 }
 
+#: every symbol include/lkgd_hip_t5.h declares (the operators of the T5 text encoder in front of the CogVideoX loop: embedding rows, RMS
+#: norm, dense attention with a relative-position bias, gated tanh-GELU, fp32 residual add), bound on the same library object;
+#: tests/test_t5_cpu.py pins header, table and library to one another, tests/test_t5_gpu.py the footprint cases
+T5_SYMBOLS = {
+    "lkgd_t5_embed_rows": (_i32, [_vp, _vp, _i32, _i32, _i32, _vp, _i32, _i64, _vp]),
+    "lkgd_t5_rmsnorm": (_i32, [_vp, _i32, _i64, _i32, _vp, _f32, _vp, _i32, _vp]),
+    "lkgd_attn_dense_relbias": (_i32, [_vp, _i32, _vp, _i32, _vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _f32, _vp]),
+    "lkgd_t5_gated_gelu": (_i32, [_vp, _i32, _i64, _i32, _vp, _i32, _vp]),
+    "lkgd_t5_residual_add": (_i32, [_vp, _i32, _vp, _i32, _i64, _i32, _f32, _vp]),
+}
+
 #: include/lkgd_hip_debug.h: A/B and test knobs, per host thread; bound on the same library object, not part of the product interface
 DEBUG_SYMBOLS = {
     "lkgd_debug_set_wide_tile_n": (None, [_i32]),
@@ -204,7 +215,7 @@ def lib() -> C.CDLL:
         except OSError as e:
             raise LkgdHipError(f"cannot load {LIB_PATH}: {e}") from e
         for table in (SYMBOLS, WINDOW_SYMBOLS, DIT_SYMBOLS, DIT_LOOP_SYMBOLS, DIT_TPATCH_SYMBOLS, DIT_DPM_SYMBOLS, FP8_SYMBOLS,
-                      DEBUG_SYMBOLS):
+                      T5_SYMBOLS, DEBUG_SYMBOLS):
             for name, (res, args) in table.items():
                 fn = getattr(l, name)       # AttributeError here = header / library mismatch
                 fn.restype, fn.argtypes = res, args

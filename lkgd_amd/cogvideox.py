@@ -46,6 +46,8 @@ MI355X design - the UNet's kernels, one joint token buffer:
   and e4m3 activations (one scale per token row, quantised by the kernel that produces them: ``lkgd_layernorm_quant_fp8`` for the
   two modulated norms, ``lkgd_quant_rows_fp8`` for the attention output, ``lkgd_gelu_tanh_quant_fp8`` for the feed-forward's hidden
   rows).  Residual stream, norms, q/k norm + rope, attention, gates and every other linear stay as they are.
+* ``encode_prompt``: the pipeline's method in front of the loop, with the T5 text encoder of ``lkgd_amd/t5.py``
+  (include/lkgd_hip_t5.h) and the caller's tokenizer as arguments; its embeddings are what ``denoise`` takes.
 """
 from __future__ import annotations
 
@@ -929,3 +931,70 @@ def denoise(transformer: CogVideoXTransformer3DModel, scheduler, latents, image_
         if callback is not None:
             callback(i, t, latents.clone())         # a tensor of the callback's own, as the out-of-place loop handed out
     return latents
+
+
+# ---- the prompt in front of the loop ------------------------------------------------------------------------------------------------
+def _get_t5_prompt_embeds(text_encoder, tokenizer, prompt, num_videos_per_prompt: int = 1, max_sequence_length: int = 226,
+                          device=None, dtype=None) -> torch.Tensor:
+    """pipeline_cogvideox_image2video.py:230-270 with ``self.text_encoder`` / ``self.tokenizer`` as arguments.  ``prompt``: a string,
+    a list of strings, or the token ids themselves as an int64 [B, S] tensor (no tokenizer needed).  The tokenizer is called as the
+    reference calls it; its second, untruncated call only feeds a warning about cut-off text and is not made."""
+    device = device or text_encoder.device
+    dtype = dtype or text_encoder.dtype
+    if isinstance(prompt, torch.Tensor):
+        if prompt.dim() != 2 or prompt.dtype != torch.int64:
+            raise ValueError(f"a prompt given as token ids must be an int64 [B, S] tensor, got {prompt.dtype} {tuple(prompt.shape)}")
+        text_input_ids, batch_size = prompt, prompt.shape[0]
+    else:
+        prompt = [prompt] if isinstance(prompt, str) else prompt
+        batch_size = len(prompt)
+        if tokenizer is None:
+            raise LkgdHipError("encode_prompt: a text prompt needs a tokenizer (the T5 sentencepiece vocabulary is the caller's: "
+                               "transformers' T5Tokenizer of the checkpoint's tokenizer/ directory); token ids need none")
+        text_inputs = tokenizer(prompt, padding="max_length", max_length=max_sequence_length, truncation=True,
+                                add_special_tokens=True, return_tensors="pt")
+        text_input_ids = text_inputs.input_ids
+    prompt_embeds = text_encoder(text_input_ids.to(device))[0]
+    prompt_embeds = prompt_embeds.to(dtype=dtype, device=device)
+    # duplicate text embeddings for each generation per prompt (:265-268)
+    _, seq_len, _ = prompt_embeds.shape
+    prompt_embeds = prompt_embeds.repeat(1, num_videos_per_prompt, 1)
+    return prompt_embeds.view(batch_size * num_videos_per_prompt, seq_len, -1)
+
+
+def encode_prompt(text_encoder, tokenizer, prompt, negative_prompt=None, do_classifier_free_guidance: bool = True,
+                  num_videos_per_prompt: int = 1, prompt_embeds: Optional[torch.Tensor] = None,
+                  negative_prompt_embeds: Optional[torch.Tensor] = None, max_sequence_length: int = 226, device=None, dtype=None):
+    """the reference's ``encode_prompt`` (pipeline_cogvideox_image2video.py:273-352): same parameters, defaults and errors, with
+    ``text_encoder`` (``lkgd_amd.t5.T5EncoderModel``) and ``tokenizer`` in place of ``self``.  Returns ``(prompt_embeds,
+    negative_prompt_embeds)``, each [B * num_videos_per_prompt, max_sequence_length, d_model] in the encoder's dtype (the second None
+    without guidance).  For :func:`denoise` under guidance the pipeline concatenates them negative first (:772):
+    ``torch.cat([negative_prompt_embeds, prompt_embeds])``.  Prompts may also be int64 id tensors [B, S]."""
+    device = device or text_encoder.device
+    prompt = [prompt] if isinstance(prompt, str) else prompt
+    if prompt is not None:
+        batch_size = len(prompt)
+    else:
+        batch_size = prompt_embeds.shape[0]
+
+    if prompt_embeds is None:
+        prompt_embeds = _get_t5_prompt_embeds(text_encoder, tokenizer, prompt, num_videos_per_prompt, max_sequence_length, device, dtype)
+
+    if do_classifier_free_guidance and negative_prompt_embeds is None:
+        if not isinstance(negative_prompt, torch.Tensor):
+            negative_prompt = negative_prompt or ""
+        negative_prompt = batch_size * [negative_prompt] if isinstance(negative_prompt, str) else negative_prompt
+        ids = isinstance(prompt, torch.Tensor) or isinstance(negative_prompt, torch.Tensor)      # id tensors mix with the "" default
+
+        if prompt is not None and not ids and type(prompt) is not type(negative_prompt):
+            raise TypeError(f"`negative_prompt` should be the same type to `prompt`, but got {type(negative_prompt)} !="
+                            f" {type(prompt)}.")
+        elif batch_size != len(negative_prompt):
+            raise ValueError(f"`negative_prompt`: {negative_prompt} has batch size {len(negative_prompt)}, but `prompt`:"
+                             f" {prompt} has batch size {batch_size}. Please make sure that passed `negative_prompt` matches"
+                             " the batch size of `prompt`.")
+
+        negative_prompt_embeds = _get_t5_prompt_embeds(text_encoder, tokenizer, negative_prompt, num_videos_per_prompt,
+                                                       max_sequence_length, device, dtype)
+
+    return prompt_embeds, negative_prompt_embeds

@@ -1057,3 +1057,81 @@ def gemm_fp8(a: torch.Tensor, a_scale: torch.Tensor, w: torch.Tensor, w_scale: t
     _gemm_family("lkgd_gemm_fp8", (a.data_ptr(), _ld(a), a_scale.data_ptr(), w.data_ptr(), _ld(w), w_scale.data_ptr(), _ptr(bias),
                                    out.data_ptr(), _ld(out), M, N, K), 2.0 * M * N * K)
     return out
+
+
+# ---- the T5 text encoder's operators: include/lkgd_hip_t5.h -----------------------------------------------------------------------
+def _t5_rows(t: torch.Tensor, dtype, name: str, like: Optional[torch.Tensor] = None, width: Optional[int] = None) -> None:
+    """a [T, C] matrix with contiguous channels; with ``like`` / ``width``: of that row count and width"""
+    _req(t, dtype, name)
+    if t.dim() != 2 or t.stride(1) != 1:
+        raise _lib.LkgdHipError(f"{name} must be [T, C] with contiguous channels, got {tuple(t.shape)} strides {tuple(t.stride())}")
+    if like is not None and (t.shape[0] != like.shape[0] or t.shape[1] != (like.shape[1] if width is None else width)):
+        raise _lib.LkgdHipError(f"{name} must be [{like.shape[0]}, {like.shape[1] if width is None else width}], got {tuple(t.shape)}")
+
+
+def t5_embed_rows(ids: torch.Tensor, table: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out[t, :] = float(table[ids[t], :]): int64 ids [T], fp16 table [V, D] -> fp32 [T, D] (lkgd_t5_embed_rows).  The ids are the
+    caller's to validate (a host check costs a sync); the kernel clamps them into the table"""
+    _req(ids, torch.int64, "ids"); _t5_rows(table, torch.float16, "table")
+    if ids.dim() != 1 or not ids.is_contiguous():
+        raise _lib.LkgdHipError(f"ids must be a contiguous int64 [T] vector, got {tuple(ids.shape)}")
+    if out is None:
+        out = torch.empty(ids.shape[0], table.shape[1], dtype=torch.float32, device=table.device)
+    _t5_rows(out, torch.float32, "out")
+    if tuple(out.shape) != (ids.shape[0], table.shape[1]):
+        raise _lib.LkgdHipError(f"out must be [{ids.shape[0]}, {table.shape[1]}], got {tuple(out.shape)}")
+    check(_L().lkgd_t5_embed_rows(ids.data_ptr(), table.data_ptr(), _ld(table), table.shape[0], table.shape[1], out.data_ptr(), _ld(out),
+                                  ids.shape[0], _stream()), "lkgd_t5_embed_rows")
+    return out
+
+
+def t5_rmsnorm(x: torch.Tensor, weight: torch.Tensor, eps: float, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """T5LayerNorm: fp32 [T, C] rows -> fp16(weight * (x * rsqrt(mean(x^2) + eps))), C <= 4096 (lkgd_t5_rmsnorm)"""
+    _t5_rows(x, torch.float32, "x"); _req(weight, torch.float32, "weight")
+    if tuple(weight.shape) != (x.shape[1],) or not weight.is_contiguous():
+        raise _lib.LkgdHipError(f"weight must be a contiguous fp32 [{x.shape[1]}] vector")
+    if out is None:
+        out = torch.empty(x.shape, dtype=torch.float16, device=x.device)
+    _t5_rows(out, torch.float16, "out", like=x)
+    check(_L().lkgd_t5_rmsnorm(x.data_ptr(), _ld(x), x.shape[0], x.shape[1], weight.data_ptr(), eps, out.data_ptr(), _ld(out), _stream()),
+          "lkgd_t5_rmsnorm")
+    return out
+
+
+def attn_dense_relbias(q, k, v, out, nbatch: int, S: int, heads: int, head_dim: int, relbias: torch.Tensor,
+                       scale: Optional[float] = None):
+    """:func:`attn_dense` with ``relbias[h, j - i + S - 1]`` added to the scaled score of query i and key j before the softmax;
+    relbias fp32 [heads, 2S - 1] (lkgd_attn_dense_relbias).  ``scale`` None = head_dim ** -0.5; T5 passes 1.0"""
+    _req(q, torch.float16, "q"); _req(k, torch.float16, "k"); _req(v, torch.float16, "v"); _req(out, torch.float16, "out")
+    _req(relbias, torch.float32, "relbias")
+    if tuple(relbias.shape) != (heads, 2 * S - 1) or not relbias.is_contiguous():
+        raise _lib.LkgdHipError(f"relbias must be a contiguous fp32 [{heads}, {2 * S - 1}] table, got {tuple(relbias.shape)}")
+    for name, t in (("q", q), ("k", k), ("v", v), ("out", out)):
+        if t.dim() != 2 or t.shape[0] != nbatch * S or t.shape[1] != heads * head_dim:
+            raise _lib.LkgdHipError(f"{name} must be [{nbatch * S}, {heads * head_dim}], got {tuple(t.shape)}")
+    if scale is None:
+        scale = head_dim ** -0.5
+    check(_L().lkgd_attn_dense_relbias(q.data_ptr(), _ld(q), k.data_ptr(), _ld(k), v.data_ptr(), _ld(v), out.data_ptr(), _ld(out),
+                                       nbatch, S, heads, head_dim, relbias.data_ptr(), scale, _stream()), "lkgd_attn_dense_relbias")
+    return out
+
+
+def t5_gated_gelu(h: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """fp16 [T, 2F] -> fp16 [T, F]: gelu_tanh(h[:, :F]) * h[:, F:], fp32 arithmetic, one rounding (lkgd_t5_gated_gelu)"""
+    _t5_rows(h, torch.float16, "h")
+    if h.shape[1] % 2:
+        raise _lib.LkgdHipError(f"h must hold the two halves side by side, got width {h.shape[1]}")
+    F_ = h.shape[1] // 2
+    if out is None:
+        out = torch.empty(h.shape[0], F_, dtype=torch.float16, device=h.device)
+    _t5_rows(out, torch.float16, "out", like=h, width=F_)
+    check(_L().lkgd_t5_gated_gelu(h.data_ptr(), _ld(h), h.shape[0], F_, out.data_ptr(), _ld(out), _stream()), "lkgd_t5_gated_gelu")
+    return out
+
+
+def t5_residual_add_(x: torch.Tensor, y: torch.Tensor, s: float = 1.0) -> torch.Tensor:
+    """x += s * float(y) in place: x fp32 [T, C] (the encoder's residual stream), y fp16 [T, C] (lkgd_t5_residual_add)"""
+    _t5_rows(x, torch.float32, "x"); _t5_rows(y, torch.float16, "y", like=x)
+    check(_L().lkgd_t5_residual_add(x.data_ptr(), _ld(x), y.data_ptr(), _ld(y), x.shape[0], x.shape[1], s, _stream()),
+          "lkgd_t5_residual_add")
+    return x

@@ -9,7 +9,8 @@ the real forward against it, and tests/test_gemm_oracle_cpu.py holds IT against 
 ``bufs`` maps a0 / a1 / w / bias / rowbias / res1 / res2 / ln_colsum to 2-D (1-D: bias, ln_colsum) tensors of any dtype and
 device whose row stride is the descriptor's leading dimension (row r of the buffer = elements [r*ld, r*ld + ld) behind the
 pointer); absent or None = the NULL pointer.  Only the rows a result needs are gathered and converted to fp64, so the buffers may
-stay on the device."""
+stay on the device.  W is converted ``COL_BLOCK`` output columns at a time, so the fp64 copy of a weight never exceeds
+COL_BLOCK * K * 8 bytes whatever N is, and ``cols`` restricts a result to the named output columns."""
 import math
 from types import SimpleNamespace
 
@@ -36,12 +37,20 @@ def desc(**fields):
     return SimpleNamespace(**f)
 
 
-def _gather(buf, rows, valid=None):
-    """rows `rows` (int64 [R]) of a 2-D buffer as fp64 on the CPU; rows where `valid` is False read as zeros"""
+#: output columns whose weights are held in fp64 at one time (gemm_rows)
+COL_BLOCK = 8192
+
+
+def _gather(buf, rows, valid=None, cols=None):
+    """rows `rows` (int64 [R]) of a 2-D buffer as fp64 on the CPU; rows where `valid` is False read as zeros; `cols` (int64):
+    those columns only, selected before the conversion"""
     rows = torch.as_tensor(rows, dtype=torch.int64)
     if valid is not None:
         rows = torch.where(valid, rows, torch.zeros_like(rows))
-    x = buf.index_select(0, rows.to(buf.device)).to("cpu", torch.float64)
+    x = buf.index_select(0, rows.to(buf.device))
+    if cols is not None:
+        x = x.index_select(1, cols.to(buf.device))
+    x = x.to("cpu", torch.float64)
     if valid is not None:
         x = x * valid.to(torch.float64)[:, None]
     return x
@@ -104,38 +113,61 @@ def gelu_erf(x):
     return 0.5 * x * (1.0 + torch.erf(x / math.sqrt(2.0)))
 
 
-def gemm_rows(d, bufs, rows):
+def _vector(buf, N, cols):
+    v = buf[:N] if cols is None else buf.index_select(0, cols.to(buf.device))
+    return v.to("cpu", torch.float64)[None, :]
+
+
+def gemm_rows(d, bufs, rows, cols=None, block=None):
     """rows `rows` of out in fp64: ([R, N] or, GEGLU, [R, N / 2],  S [R, N] = sum_k |A(m,k) * W[n,k]| or None for GEGLU).
-    With the LayerNorm fold S is the magnitude that enters the rounded sum: rstd * (sum_k |A W| + |mean * ln_colsum|)."""
+    With the LayerNorm fold S is the magnitude that enters the rounded sum: rstd * (sum_k |A W| + |mean * ln_colsum|).
+    ``cols`` (int64 [Q], not with GEGLU): output columns `cols` only, [R, Q] - the same numbers the full result has there.
+    ``block``: output columns per fp64 piece of W (default COL_BLOCK); every element is one dot product over K whatever the
+    block, so the block size moves a result by fp64 summation order at most."""
     m = torch.as_tensor(rows, dtype=torch.int64)
     N, K = int(d.N), int(d.K)
+    block = int(block or COL_BLOCK)
     get = lambda k: bufs.get(k)                                                      # noqa: E731
+    if cols is not None:
+        cols = torch.as_tensor(cols, dtype=torch.int64)
+        assert not int(d.geglu), "cols: GEGLU pairs columns, select on the result instead"
+        assert cols.numel() and int(cols.min()) >= 0 and int(cols.max()) < N
+    Q = N if cols is None else cols.numel()
     A = a_rows(d, bufs, m)
-    W = bufs["w"][:N, :K].to("cpu", torch.float64)
-    acc = A @ W.T
-    S = A.abs() @ W.abs().T
+    Aabs = A.abs()
+    W = bufs["w"]
+    acc = torch.empty(m.numel(), Q, dtype=torch.float64)
+    S = torch.empty(m.numel(), Q, dtype=torch.float64)
+    for c0 in range(0, Q, block):
+        c1 = min(Q, c0 + block)
+        Wb = W[c0:c1, :K] if cols is None else W.index_select(0, cols[c0:c1].to(W.device))[:, :K]
+        Wb = Wb.to("cpu", torch.float64)
+        acc[:, c0:c1] = A @ Wb.T
+        S[:, c0:c1] = Aabs @ Wb.abs().T
+        del Wb
     if get("ln_colsum") is not None:
         # LayerNorm of the A rows (no affine: folded into W / bias) applied after the product
         assert int(d.mode) == A_PLAIN and not int(d.geglu)
         mean = A.mean(dim=1, keepdim=True)
         rstd = 1.0 / torch.sqrt(((A - mean) ** 2).mean(dim=1, keepdim=True) + float(d.ln_eps))
-        cs = bufs["ln_colsum"][:N].to("cpu", torch.float64)[None, :]
+        cs = _vector(bufs["ln_colsum"], N, cols)
         acc = rstd * (acc - mean * cs)
         S = rstd * (S + (mean * cs).abs())
     v = acc
     if get("bias") is not None:
-        v = v + bufs["bias"][:N].to("cpu", torch.float64)[None, :]
+        v = v + _vector(bufs["bias"], N, cols)
     if int(d.geglu):
         h = int(d.geglu)
         assert h in (32, 80) and N % (2 * h) == 0
         assert get("rowbias") is None and get("res1") is None and get("res2") is None and float(d.s_acc) == 1.0
         v = v.reshape(m.numel(), N // (2 * h), 2, h)                 # packed rows: h hidden | their h gates
         return (v[:, :, 0] * gelu_erf(v[:, :, 1])).reshape(m.numel(), N // 2), None
+    sel = (lambda x: x[:, :N]) if cols is None else (lambda x: x)                    # noqa: E731
     if get("rowbias") is not None:
-        v = v + _gather(bufs["rowbias"], rowmap_index(d, m))[:, :N]
+        v = v + sel(_gather(bufs["rowbias"], rowmap_index(d, m), cols=cols))
     v = float(d.s_acc) * v
     if get("res1") is not None:
-        v = v + float(d.r1) * _gather(bufs["res1"], m)[:, :N]
+        v = v + float(d.r1) * sel(_gather(bufs["res1"], m, cols=cols))
     if get("res2") is not None:
-        v = v + float(d.r2) * _gather(bufs["res2"], m)[:, :N]
+        v = v + float(d.r2) * sel(_gather(bufs["res2"], m, cols=cols))
     return v, S

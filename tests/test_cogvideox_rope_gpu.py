@@ -111,6 +111,43 @@ def _dev(t):
     return [x.to(DEV) for x in t] if isinstance(t, list) else t.to(DEV)
 
 
+#: qk_norm_rope_kernel runs at most 4096 workgroups of 4 tokens (one per wave): the smallest token count at which a workgroup runs
+#: its loop body three times, plus a ragged rest
+QK_LOOP_TOKENS = 3 * 4096 * 4 + 5              # 49 157
+
+
+@gpu
+def test_qk_norm_rope_three_loop_iterations():
+    """one batch entry of 49 157 tokens with 226 text rows: the 32-bit ``tok % rows_per_batch`` and the table row ``r - split`` are
+    used far from zero, and every workgroup walks its loop three or four times.  The statement of test_qk_norm_rope_bitwise:
+    with tables == the composition, norm only == lkgd_layernorm, bit for bit.  Row r of q and k is scaled by 0.05 + r % 97 and
+    the table rows all differ, so a token, a table row or a statistic taken from another loop iteration cannot pass"""
+    from lkgd_amd import ops
+    heads, rpb, split, eps = 2, QK_LOOP_TOKENS, 226, 1e-6
+    g = torch.Generator().manual_seed(49157)
+    amp = (0.05 + (torch.arange(rpb) % 97).float())[:, None]
+    q = ((torch.randn(rpb, heads * 64, generator=g) + 0.3) * amp).half().to(DEV)
+    k = ((torch.randn(rpb, heads * 64, generator=g) * 3 - 1) * amp).half().to(DEV)
+    gq, bq, gk, bk = (_dev(t) for t in [1 + 0.3 * torch.randn(64, generator=g), 0.3 * torch.randn(64, generator=g),
+                                        1 + 0.3 * torch.randn(64, generator=g), 0.3 * torch.randn(64, generator=g)])
+    ang = torch.rand(rpb - split, 64, generator=g) * 6.283
+    cos, sin = ang.cos().float().to(DEV), ang.sin().float().to(DEV)
+    for tables in (None, (cos, sin)):
+        (qb, qw), (kb, kw) = _window(q), _window(k, extra=24, col0=16)
+        ops.qk_norm_rope(qw, kw, heads, (gq, bq), (gk, bk), eps, tables, rpb, split)
+        c, s = tables if tables is not None else (None, None)
+        rq, rk = _composed(q, heads, gq, bq, eps, c, s, rpb, split), _composed(k, heads, gk, bk, eps, c, s, rpb, split)
+        for name, got, ref in (("q", qw, rq), ("k", kw, rk)):
+            bad = torch.nonzero((got != ref).any(dim=1)).flatten()
+            assert bad.numel() == 0, (tables is not None, name, bad.numel(), bad[:8].tolist(), (got.float() - ref.float()).abs().max().item())
+        for buf, w in ((qb, qw), (kb, kw)):                                # nothing outside the live columns was written
+            assert int(torch.isnan(buf).sum()) == buf.numel() - w.numel()
+        if tables is not None:                                              # the rotation acts, and only on video rows
+            nq = _composed(q, heads, gq, bq, eps, None, None, rpb, split)
+            assert torch.equal(qw[:split], nq[:split]) and not torch.equal(qw[split:], nq[split:])
+            assert bool((qw[split:] != nq[split:]).any(dim=1).all())        # on every one of them
+
+
 def test_footprint_registry_covers_every_dit_symbol():
     from lkgd_amd import _lib
     assert set(FOOTPRINT) == set(_lib.DIT_SYMBOLS)

@@ -107,6 +107,99 @@ def test_gelu_tanh_quant_fp8_equals_gelu_then_quant(K):
     assert s[2].item() == 1.0 and s[3].item() == 1.0
 
 
+# ------------------------------------------------------------------------------------------- rows beyond the grid caps
+# quant_rows_kernel runs at most 8192 workgroups of one row each and uses its two LDS slots in turn from one loop iteration to the
+# next; layernorm_quant_kernel runs at most 4096 workgroups of 4 rows each (one row per wave at these widths).  The smallest row
+# counts at which a workgroup runs its loop body three times - both slots, and the first one a second time - plus a ragged rest:
+QUANT_LOOP_ROWS = 3 * 8192 * 1 + 5             # 24 581
+LN_LOOP_ROWS = 3 * 4096 * 4 + 5                # 49 157
+
+
+def _scaled_rows(T, K, seed, shift=0.0):
+    """fp16 [T, K]: row r is N(shift, 1) x (0.05 + r % 97), so every row has its own maximum and scale - a value or scale left
+    over from another loop iteration of the same workgroup (rows r +- 8192 / 16384) cannot pass; rows 8192, 16384 and T - 1 are
+    zero rows between them"""
+    g = torch.Generator().manual_seed(seed)
+    x = (torch.randn(T, K, generator=g) + shift) * (0.05 + (torch.arange(T) % 97).float())[:, None]
+    x[[8192, 16384, T - 1]] = 0.0
+    return x.half()
+
+
+@gpu
+def test_quant_rows_fp8_three_loop_iterations():
+    from lkgd_amd import ops
+    T, K = QUANT_LOOP_ROWS, 128
+    x = _scaled_rows(T, K, 11)
+    ref_q, ref_s = fo.q_rows(x)
+    # the rows a workgroup sees one after the other (8192 apart) have different scales: a stale one shows
+    assert (ref_s[:-8192] != ref_s[8192:]).float().mean() > 0.99 and bool((ref_s[[8192, 16384, T - 1]] == 1.0).all())
+    q, s = ops.quant_rows_fp8(x.to(DEV))
+    _same_q(q, s, ref_q, ref_s, "quant_rows_fp8 past the grid cap")
+
+
+@gpu
+def test_gelu_tanh_quant_fp8_three_loop_iterations():
+    """against fo.q_rows of the fp16 values ``ops.gelu_tanh_`` stores (test_gelu_tanh_quant_fp8_footprint's reference)"""
+    from lkgd_amd import ops
+    T, K = QUANT_LOOP_ROWS, 128
+    x = (_scaled_rows(T, K, 12).float() * 0.1).half().to(DEV)            # |x| up to about 40: both tails of the activation
+    ref_q, ref_s = fo.q_rows(ops.gelu_tanh_(x.clone()).cpu())
+    # the rows a workgroup sees one after the other (8192 apart) have different scales: a stale one shows
+    assert (ref_s[:-8192] != ref_s[8192:]).float().mean() > 0.99 and bool((ref_s[[8192, 16384, T - 1]] == 1.0).all())
+    q, s = ops.gelu_tanh_quant_fp8(x)
+    _same_q(q, s, ref_q, ref_s, "gelu_tanh_quant_fp8 past the grid cap")
+
+
+@pytest.fixture(scope="module", params=[1920, 3072])
+def ln_loop_case(request):
+    """(C, x, gamma, beta, y): LN_LOOP_ROWS rows through the four- (C = 1920) and the six-vector (3072) LayerNorm, y = what
+    ``ops.layernorm`` stores; computed once, left unchanged"""
+    from lkgd_amd import ops
+    C = request.param
+    x = _scaled_rows(LN_LOOP_ROWS, C, C, shift=0.3).to(DEV)
+    g = torch.Generator().manual_seed(C + 1)
+    gamma, beta = (1 + 0.3 * torch.randn(C, generator=g)).to(DEV), (0.2 * torch.randn(C, generator=g)).to(DEV)
+    return C, x, gamma, beta, ops.layernorm(x, gamma, beta, 1e-5)
+
+
+@gpu
+def test_layernorm_quant_fp8_three_loop_iterations(ln_loop_case):
+    """bit for bit ``quant_rows_fp8(layernorm(x))``, and ``fo.q_rows`` of the stored norm.  A zero row normalises to beta: no
+    row of the quantiser's input is zero here, the zero rows of x give three EQUAL rows between differing neighbours"""
+    from lkgd_amd import ops
+    C, x, gamma, beta, y = ln_loop_case
+    T = LN_LOOP_ROWS
+    ref_q, ref_s = ops.quant_rows_fp8(y)
+    q, s = ops.layernorm_quant_fp8(x, gamma, beta, 1e-5)
+    assert torch.equal(s, ref_s), (C, int((s != ref_s).sum()))
+    assert torch.equal(q, ref_q), (C, int((q != ref_q).sum()))
+    assert torch.equal(q[8192], q[16384]) and torch.equal(q[8192], q[T - 1]) and not torch.equal(q[8192], q[8191])
+    # the table search of fo.q_rows on every 61st row (coprime with 97 and with both caps: every scale class, every loop
+    # iteration) and on the rows around the iteration edges; the two equalities above carry it to all rows
+    rows = torch.unique(torch.cat([torch.arange(0, T, 61), torch.tensor([8191, 8192, 16383, 16384, 16385, 32767, 32768, T - 2, T - 1])]))
+    _same_q(q[rows.to(DEV)], s[rows.to(DEV)], *fo.q_rows(y[rows.to(DEV)].cpu()), ("layernorm_quant_fp8 past the grid cap", C))
+    ref_q, ref_s = ops.quant_rows_fp8(ops.layernorm(x, None, None, 1e-5))          # no affine: the zero rows stay zero rows
+    q, s = ops.layernorm_quant_fp8(x, None, None, 1e-5)
+    assert torch.equal(s, ref_s) and torch.equal(q, ref_q), (C, int((q != ref_q).sum()))
+    assert bool((s[[8192, 16384, T - 1]] == 1.0).all()) and not bool(q[[8192, 16384, T - 1]].any())
+
+
+@gpu
+def test_layernorm_three_loop_iterations(ln_loop_case):
+    """``lkgd_layernorm`` itself past its cap of 4096 workgroups, against fp32 ``F.layer_norm`` on the CPU under the tolerance of
+    test_layernorm_rows_up_to_3072 (tests/test_cogvideox_rope_gpu.py: 8e-3 with the affine, 4e-3 without), row by row relative to
+    nothing: the bound is absolute on normalised values of unit size"""
+    import torch.nn.functional as F
+    from lkgd_amd import ops
+    C, x, gamma, beta, y = ln_loop_case
+    xf = x.float().cpu()
+    ea = (y.float().cpu() - F.layer_norm(xf, (C,), gamma.cpu(), beta.cpu(), 1e-5)).abs().amax(dim=1)
+    ep = (ops.layernorm(x, None, None, 1e-5).float().cpu() - F.layer_norm(xf, (C,), eps=1e-5)).abs().amax(dim=1)
+    print(f"\nLayerNorm {LN_LOOP_ROWS} x {C}: max abs error affine {ea.max():.2e} (row {int(ea.argmax())}), plain {ep.max():.2e} "
+          f"(row {int(ep.argmax())})")
+    assert ea.max() < 8e-3 and ep.max() < 4e-3
+
+
 # ------------------------------------------------------------------------------------------------------------- GEMM, exact
 def _bytes_of(v):
     """integers (|v| <= 16) -> their exact e4m3 bytes"""
@@ -161,6 +254,23 @@ def test_gemm_fp8_exact_on_integers(N, K):
         _exact(a, w)
         _exact(a, w, a_scale=2.0 ** ((torch.arange(M) % 5) - 2).float(), w_scale=2.0 ** ((torch.arange(N) % 3) - 1).float())
         _exact(a, w, bias=((torch.arange(N) % 7) - 3).float())
+
+
+@gpu
+@pytest.mark.parametrize("M,N,K", [(300, 7680, 1920), (300, 1920, 7680)])
+def test_gemm_fp8_exact_at_the_real_loop_depths(M, N, K):
+    """the smallest shapes with the block linears' real loop depths: 60 K-steps (K = 7680) and 60 tile columns (N = 7680), with an
+    M tail across a 128-row edge.  a in {-1, 0, 1}, w in {-2 .. 2}: a sum of 7680 such products has a standard deviation of
+    about 100, the largest |sum| of these seeds is 269 / 471 (computed on the CPU) - below 2048, so every sum is an fp16 value,
+    and power-of-two scales keep it one as long as the product stays within fp16's exponent range: a_scale in 2^-4 .. 2^0 (never
+    above one), w_scale in 2^-1 .. 2^1 give |ref| <= 904 and >= 2^-5.  ``_exact`` asserts the premise itself"""
+    g = torch.Generator().manual_seed(N + K)
+    a = torch.randint(-1, 2, (M, K), generator=g).float()
+    w = torch.randint(-2, 3, (N, K), generator=g).float()
+    assert (a.double() @ w.double().t()).abs().max() < 2048
+    _exact(*_one_hot(M, N, K))
+    _exact(a, w, a_scale=2.0 ** (-(torch.arange(M) % 5)).float(), w_scale=2.0 ** ((torch.arange(N) % 3) - 1).float())
+    _exact(a, w, bias=((torch.arange(N) % 7) - 3).float())           # (integers again: no scale beside a bias)
 
 
 # ------------------------------------------------------------------------------------------------- GEMM, random e4m3 data

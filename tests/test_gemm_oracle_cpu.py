@@ -163,3 +163,39 @@ def test_layernorm_fold():
     # and through gamma / beta themselves, up to the fp16 rounding of the folded weights
     ref2 = F.linear(F.layer_norm(x, (K,), gamma, beta, eps), w, b) + res
     assert (got - ref2).abs().max() < 2e-3 * ref2.abs().max()
+
+
+def test_column_blocks_and_cols_select_the_same_numbers():
+    """the bounded-memory evaluation: any block size gives the unblocked result (one dot product per element either way: fp64
+    summation order at most), and ``cols`` returns exactly those columns of it - every epilogue term included, in any order,
+    with repeats, across block edges"""
+    g = _g(7)
+    M, N, K = 19, 203, 128                                # 203 columns: no block size below divides it
+    a0 = _rn(g, M, 136)
+    w = pk.pack_linear(_rn(g, N, K) / K ** 0.5).double()
+    bias, res1, res2, rb = _rn(g, N), _rn(g, M, N + 5), _rn(g, M, N), _rn(g, 7, N + 3)
+    d = go.desc(M=M, N=N, K=K, lda0=136, ldrb=N + 3, rb_d1=3, rb_m1=1, rb_d2=1, rb_md=7, ldr1=N + 5, ldr2=N, ldc=N, s_acc=0.5,
+                r1=0.25, r2=-2.0)
+    bufs = dict(a0=a0, w=w, bias=bias, rowbias=rb, res1=res1, res2=res2)
+    rows = torch.tensor([18, 0, 7, 11])
+    full, S = go.gemm_rows(d, bufs, rows, block=N)        # one block: the unblocked evaluation
+    idx = (rows // 3) % 7
+    _agree(full, 0.5 * (F.linear(a0[rows, :K], w, bias) + rb[idx, :N]) + 0.25 * res1[rows, :N] - 2.0 * res2[rows], "unblocked")
+    assert go.COL_BLOCK >= N
+    for block in (None, 1, 7, 64, 202):
+        got, Sb = go.gemm_rows(d, bufs, rows, block=block)
+        _agree(got, full, f"block {block}")
+        _agree(Sb, S, f"S, block {block}")
+    cols = torch.tensor([202, 0, 64, 63, 7, 7, 201, 100])
+    for block in (None, 3):
+        got, Sc = go.gemm_rows(d, bufs, rows, cols=cols, block=block)
+        assert got.shape == Sc.shape == (4, 8)
+        _agree(got, full[:, cols], f"cols, block {block}")
+        _agree(Sc, S[:, cols], f"S of cols, block {block}")
+    # the LayerNorm fold's column sums follow the selection too
+    dl = go.desc(M=M, N=N, K=K, lda0=136, ldc=N, ln_eps=1e-5)
+    bl = dict(a0=a0, w=w, bias=bias, ln_colsum=w.sum(1))
+    fl, Sl = go.gemm_rows(dl, bl, rows, block=N)
+    gl, Sg = go.gemm_rows(dl, bl, rows, cols=cols, block=5)
+    _agree(gl, fl[:, cols], "fold cols")
+    _agree(Sg, Sl[:, cols], "fold S cols")

@@ -483,10 +483,8 @@ CENSUS_NOT_COVERED = {
                  "temporal-attention kernels or, with a residual, on the resident-weight program; no forward issues a LayerNorm-fold "
                  "descriptor at these geometries (tests/test_kernels_gpu.py::test_gemm_layernorm_fold and the forced `rowpanel` "
                  "variant cover the program)",
-    "form 256x256": "256-column tiles serve N = 256 / 512 / 768, the VAE decoder's widths: at the census' 96x128-pixel VAE geometry "
-                    "every such launch is a one-round problem, where the 192-row form is modelled cheaper "
-                    "(test_gemm_wide_256_column_tiles forces 256 rows)",
 }
+# (form 256x256 left this list with the row ladder of the DiT's block linears: ff1 of the 2B model selects it at 2048 and 4096 rows)
 
 
 def test_gemm_census_covers_every_program_and_tile_form():
@@ -624,3 +622,21 @@ def test_replayed_disabled_runs_the_forward_every_call():
         assert [f(None), f([]), f()] == [0, 1, 2]
         assert f.plan is None and ops.PLAN is None
     assert runs == [0, 1, 2] and f.plan is None
+
+
+def test_gemm_census_hand_written_rows_are_what_the_builders_build():
+    """the table's dit_mod_real_depth and dit_row_ladder rows are not recorded from a forward: they must equal what
+    tools/gemm_census.py builds through the product's descriptor builder today, and the ladder must still reach the plans it is
+    there for (tests/test_gemm_census_dit_gpu.py replays them)"""
+    from tools import gemm_census as gc
+    for fwd, descs in ((gc.MOD_FORWARD, gc.modulation_descs()), (gc.LADDER_FORWARD, gc.ladder_descs())):
+        want = sorted(gc.sig_key(gc.signature(d)) for d in descs)
+        have = sorted(gc.sig_key(e) for e in gc.load_table() if fwd in e["launches"])
+        assert want == have and len(set(want)) == len(want), fwd
+    plans = [e["plan"] for e in gc.load_table() if gc.LADDER_FORWARD in e["launches"]]
+    reached = {(p["program"], p["tile_m"], p["tile_n"], p["k_slices"] > 1) for p in plans}
+    assert {(7, 128, 128, True), (4, 256, 320, True), (4, 256, 256, False), (4, 192, 320, False), (1, 128, 128, False)} <= reached
+    # the real-depth modulation GEMM: two live rows in 192x320 tiles, the last tile column ragged at 42 layers x 3072
+    mod = {(e["fields"]["M"], e["fields"]["N"]): e["plan"] for e in gc.load_table() if gc.MOD_FORWARD in e["launches"]}
+    assert set(mod) == {(b, n) for b in (1, 2) for n in (695040, 1554432)} and 1554432 % 320 == 192
+    assert all((p["program"], p["tile_m"], p["tile_n"], p["k_slices"]) == (4, 192, 320, 1) for p in mod.values())

@@ -80,6 +80,14 @@ enum {
  *      LKGD_A_TCONV3    k = kt*Cin + c; token m = (b, f, s) reads frame f+kt-1 (zero outside [0,F)); Conv3d (3,1,1);
  *                       m = (b*Floc + fl)*HW + s is output frame f = f_off + fl, source row (b*F + f+kt-1)*HW + s
  *      LKGD_A_CONV3X3_C8 conv3x3 with Cin == 8 (conv_in): one 16-byte chunk per tap, K padded to 128
+ *      LKGD_A_CCONV3    causal Conv3d (3,3,3): K = 27*Cin, k = kt*9*Cin + (the LKGD_A_CONV3X3 order of the 3x3 taps); token
+ *                       m = (b, t, y, x) over B x Floc x Hout x Wout (Hout = Hin, Wout = Win, stride 1, ups 0, pad_off 0).  a0 holds,
+ *                       per batch entry, F = Floc + 2 frames of Hin x Win rows: two CONTEXT frames, then the chunk's Floc frames.
+ *                       Row m reads frame t + kt of those F at pixel (y+ky-1, x+kx-1), zero outside the image (pad 1 in height
+ *                       and width); there is no test in time - the caller puts the context in place (the chunk's first frame
+ *                       twice, or the last two frames of the previous chunk's buffer) and keeps the last two frames of this
+ *                       buffer as the next context.  All 27 taps accumulate in fp32 in one launch.  a1 unused (csplit = Cin).
+ *                       Program 4 only (M < 2^24, no GEGLU, K never sliced): LKGD_E_SHAPE otherwise
  *
  *    Replaces (reference call sites):
  *      F.linear      - attention to_q/k/v/to_out, GEGLU proj + FF out, proj_in/out, time_emb_proj
@@ -88,11 +96,13 @@ enum {
  *                      ResnetBlock2D conv1/conv2, Downsample2D, Upsample2D [EXT resnet.py]
  *      F.conv2d 1x1  - ResnetBlock2D.conv_shortcut [EXT]
  *      F.conv3d      - TemporalResnetBlock conv1/conv2 (3,1,1) [EXT resnet.py]
+ *      F.conv3d      - CogVideoXCausalConv3d (3,3,3) of AutoencoderKLCogVideoX [EXT diffusers autoencoder_kl_cogvideox.py,
+ *                      PARITY UNPINNED], reached from pipeline_cogvideox_image2video.py:430-435 (decode_latents)
  *      F.gelu, residual adds, AlphaBlender - fused epilogues [EXT attention.py GEGLU, resnet.py AlphaBlender]
  *    Contract: K % 64 == 0; for conv modes Cin % 64 == 0 and csplit % 64 == 0 (C8 mode: Cin == 8, K == 128);
  *              N % 4 == 0 (geglu = h: N % 4h == 0); all leading dimensions % 8 == 0; pointers 16-byte aligned.
  * ------------------------------------------------------------------------------------------------------------- */
-enum { LKGD_A_PLAIN = 0, LKGD_A_CONV3X3 = 1, LKGD_A_TCONV3 = 2, LKGD_A_CONV3X3_C8 = 3 };
+enum { LKGD_A_PLAIN = 0, LKGD_A_CONV3X3 = 1, LKGD_A_TCONV3 = 2, LKGD_A_CONV3X3_C8 = 3, LKGD_A_CCONV3 = 4 };
 
 typedef struct lkgd_gemm_desc {
   const void* a0;      /* fp16 */

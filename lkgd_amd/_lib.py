@@ -180,6 +180,14 @@ T5_SYMBOLS = {
     "lkgd_t5_residual_add": (_i32, [_vp, _i32, _vp, _i32, _i64, _i32, _f32, _vp]),
 }
 
+#: every symbol include/lkgd_hip_cogvae.h declares (the latent-modulated norm of the CogVideoX 3-D causal VAE decoder), bound on the same
+#: library object; tests/test_cogvideox_vae_cpu.py pins header, table and library to one another, tests/test_cogvideox_vae_gpu.py the
+#: footprint cases
+COGVAE_SYMBOLS = {
+    "lkgd_spatial_norm3d": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _i32, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _i32,
+                                   _i32, _vp]),
+}
+
 #: include/lkgd_hip_debug.h: A/B and test knobs, per host thread; bound on the same library object, not part of the product interface
 DEBUG_SYMBOLS = {
     "lkgd_debug_set_wide_tile_n": (None, [_i32]),
@@ -215,7 +223,7 @@ def lib() -> C.CDLL:
         except OSError as e:
             raise LkgdHipError(f"cannot load {LIB_PATH}: {e}") from e
         for table in (SYMBOLS, WINDOW_SYMBOLS, DIT_SYMBOLS, DIT_LOOP_SYMBOLS, DIT_TPATCH_SYMBOLS, DIT_DPM_SYMBOLS, FP8_SYMBOLS,
-                      T5_SYMBOLS, DEBUG_SYMBOLS):
+                      T5_SYMBOLS, COGVAE_SYMBOLS, DEBUG_SYMBOLS):
             for name, (res, args) in table.items():
                 fn = getattr(l, name)       # AttributeError here = header / library mismatch
                 fn.restype, fn.argtypes = res, args

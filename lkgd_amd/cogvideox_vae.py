@@ -1,0 +1,426 @@
+"""The decoder of the CogVideoX 3-D causal VAE (``AutoencoderKLCogVideoX``) on the MI355X path: denoised latents -> frames, the last
+boundary stage of the CogVideoX pipeline.
+
+Call sites in the reference: CogVideo-main/finetune/models/cogvideox_i2v/pipeline_cogvideox_image2video.py:430-435 (``decode_latents``:
+permute, ``1 / scaling_factor``, ``vae.decode(latents).sample``), called at :908; ``inference/cli_vae_demo.py`` (``model.decode``).
+The class itself is diffusers' ``autoencoder_kl_cogvideox.py`` - [EXT], PARITY UNPINNED: diffusers is not vendored and the reference
+tree only imports the class, so module tree, parameter names and arithmetic restate the published source
+(tests/cogvideox_vae_oracle.py carries the same restatement in fp32 torch).  A real ``vae/`` checkpoint loads with
+``from_pretrained`` / ``load_state_dict``: its ``encoder.*`` and ``quant_conv.*`` keys are accepted and DROPPED (the encoder is not
+built: ``encode`` raises); any other missing or unexpected key raises.
+
+MI355X design: channels-last fp16 token matrices [B*T*H*W, C], rows (b, t, y, x) -
+* every causal 3x3x3 convolution is ONE implicit-GEMM launch (``LKGD_A_CCONV3``: 27 taps, fp32 accumulation) over a buffer that
+  holds two context frames in front of the chunk's frames per batch entry: the chunk's first frame twice, or the conv cache = the
+  last two frames of the previous chunk's buffer.  The producer of the convolution's input - the spatial norm - writes straight
+  into that buffer behind the context frames;
+* ``CogVideoXSpatialNorm3D`` is ``lkgd_spatial_norm3d``: GroupNorm apply, modulation by conv_y(zq) / conv_b(zq) and SiLU in one
+  pass.  The two 1x1x1 convolutions commute with the nearest resize of zq, so they run once per chunk and norm on the LATENT grid
+  (one plain GEMM, K 16 -> 64 padded, N = 2C) and the kernel gathers their rows through a frame table and a shift;
+* ``CogVideoXUpsample3D``: the per-frame 3x3 convolution with the nearest 2x folded into its gather (``LKGD_A_CONV3X3``, ups = 1);
+  the doubling in time commutes with it - T frames are convolved once and each result placed twice (a strided device copy).
+Activations are fp16 with fp32 accumulation whatever dtype the parameters are kept in.  Chunks of two latent frames, as diffusers.
+"""
+from __future__ import annotations
+
+from dataclasses import dataclass
+from types import SimpleNamespace
+from typing import List, Optional, Tuple
+
+import torch
+import torch.nn as nn
+
+from . import ops
+from ._lib import LkgdHipError
+from .packing import pack_cconv3, pack_conv3x3, pack_linear
+from .vae import DecoderOutput, _f32, _new, _pad_cout
+
+
+@dataclass
+class CogVAEConfig:
+    """constructor keywords of AutoencoderKLCogVideoX [EXT] the decoder reads (CogVideoX ``vae/config.json``)"""
+    block_out_channels: Tuple[int, ...] = (128, 256, 256, 512)
+    latent_channels: int = 16
+    layers_per_block: int = 3
+    norm_eps: float = 1e-6
+    norm_num_groups: int = 32
+    temporal_compression_ratio: int = 4
+    scaling_factor: float = 1.15258426          # 2B; 0.7 for 5B
+    out_channels: int = 3
+    act_fn: str = "silu"
+    use_quant_conv: bool = False
+    use_post_quant_conv: bool = False
+    invert_scale_latents: bool = False
+
+
+def chunk_bounds(T: int) -> List[Tuple[int, int]]:
+    """the latent-frame ranges ``decode`` runs one after the other: chunks of two, the remainder in the first (13 -> 3|2|2|2|2|2)"""
+    n, rem = max(T // 2, 1), T % 2
+    return [(2 * i + (0 if i == 0 else rem), min(2 * (i + 1) + rem, T)) for i in range(n)]
+
+
+def spatial_norm_tmap(Tz: int, T: int) -> List[int]:
+    """latent frame of every one of f's T frames: nearest resize of Tz frames to T, the first frame apart when T is odd and above one
+    (CogVideoXSpatialNorm3D.forward)"""
+    if T > 1 and T % 2 == 1:
+        if Tz < 2:
+            raise LkgdHipError("spatial norm: an odd chunk of more than one frame needs at least two latent frames")
+        return [0] + [1 + (i * (Tz - 1)) // (T - 1) for i in range(T - 1)]
+    return [(t * Tz) // T for t in range(T)]
+
+
+def upsample_frame_map(T: int, compress_time: bool) -> List[int]:
+    """source frame of every output frame of CogVideoXUpsample3D: with ``compress_time`` frames are doubled - all of an even count,
+    all but the first of an odd count above one; a single frame stays single"""
+    if not compress_time or T == 1:
+        return list(range(T))
+    if T % 2 == 1:
+        return [0] + [1 + i // 2 for i in range(2 * (T - 1))]
+    return [i // 2 for i in range(2 * T)]
+
+
+class _Chunk:
+    """what the blocks of one chunk share: geometry, the padded latent rows and the per-(Tz, T) frame tables"""
+
+    def __init__(self, B, Tz, h, w, zq64):
+        self.B, self.Tz, self.h, self.w, self.zq64 = B, Tz, h, w, zq64
+        self.T, self.H, self.W, self.sh = Tz, h, w, 0
+        self._tmaps = {}
+
+    def tmap(self):
+        t = self._tmaps.get(self.T)
+        if t is None:
+            t = self._tmaps[self.T] = torch.tensor(spatial_norm_tmap(self.Tz, self.T), dtype=torch.int32).to(self.zq64.device)
+        return t
+
+
+def _prefixed(c: _Chunk, C_: int, dev) -> torch.Tensor:
+    """[B, T + 2, H*W, C]: two context frames, then the chunk's frames"""
+    return torch.empty(c.B, c.T + 2, c.H * c.W, C_, dtype=torch.float16, device=dev)
+
+
+# ------------------------------------------------------------------------------------------------ parameter holders
+class CogVideoXCausalConv3d(nn.Module):
+    """CogVideoXCausalConv3d(cin, cout, k) [EXT]: zero padding k//2 in height / width, k - 1 context frames in time"""
+
+    def __init__(self, cin: int, cout: int, k: int):
+        super().__init__()
+        self.cin, self.cout, self.k = cin, cout, k
+        self.conv = nn.Conv3d(cin, cout, k, padding=(0, k // 2, k // 2))
+        self._cache = None
+
+    def pack(self, pad_cin: int = 0, pad_cout: int = 0):
+        w, b = self.conv.weight.detach().float(), self.conv.bias.detach().float()
+        if pad_cin and w.shape[1] < pad_cin:
+            w = torch.nn.functional.pad(w, (0, 0, 0, 0, 0, 0, 0, pad_cin - w.shape[1]))
+        if pad_cout:
+            w, b = _pad_cout(w, b, pad_cout)
+        self._cin, self._n = w.shape[1], w.shape[0]
+        self._w, self._b = pack_cconv3(w), b.contiguous()
+
+    def run(self, P: torch.Tensor, c: _Chunk, res1=None, colstats: int = 0):
+        """``P`` = [B, T + 2, H*W, Cin] with the chunk's frames in place behind two free frames: puts the context there, keeps the
+        buffer's last two frames as the next chunk's context, convolves"""
+        if self._cache is None:
+            P[:, 0] = P[:, 2]
+            P[:, 1] = P[:, 2]
+        else:
+            P[:, :2] = self._cache
+        self._cache = P[:, -2:].clone()
+        M = c.B * c.T * c.H * c.W
+        out = _new(M, self._n, P.device)
+        ops.gemm(P.view(-1, self._cin), self._w, out, M=M, N=self._n, K=27 * self._cin, bias=self._b, mode=ops.A_CCONV3,
+                 Cin=self._cin, cconv=(c.T, c.H, c.W), res1=res1, colstats=colstats)
+        return out
+
+
+class CogVideoXSpatialNorm3D(nn.Module):
+    """CogVideoXSpatialNorm3D(C, zq_channels) [EXT]: norm_layer(f) * conv_y(zq') + conv_b(zq')"""
+
+    def __init__(self, c: int, zq: int, groups: int, eps: float):
+        super().__init__()
+        self.c, self.eps = c, eps
+        self.norm_layer = nn.GroupNorm(groups, c, eps=eps, affine=True)
+        self.conv_y = CogVideoXCausalConv3d(zq, c, 1)
+        self.conv_b = CogVideoXCausalConv3d(zq, c, 1)
+
+    def pack(self):
+        self._g, self._bt = _f32(self.norm_layer.weight), _f32(self.norm_layer.bias)
+        wy, wb = pack_linear(self.conv_y.conv.weight.detach()), pack_linear(self.conv_b.conv.weight.detach())
+        w = torch.cat([wy, wb])                                       # [2C, zq]: the 1x1x1 pair as one GEMM on the latent grid
+        self._wyb = torch.nn.functional.pad(w, (0, 64 - w.shape[1])).contiguous()
+        self._byb = torch.cat([_f32(self.conv_y.conv.bias), _f32(self.conv_b.conv.bias)]).contiguous()
+
+    def run(self, x: torch.Tensor, c: _Chunk, P: torch.Tensor, silu: bool = True):
+        """norm (+ SiLU) of the chunk's rows ``x`` into ``P`` [B, T + 2, H*W, C] behind its two context frames"""
+        Mz = c.B * c.Tz * c.h * c.w
+        yb = _new(Mz, 2 * self.c, x.device)
+        ops.gemm(c.zq64, self._wyb, yb, M=Mz, N=2 * self.c, K=64, bias=self._byb)
+        stats = ops.groupnorm_stats(x, None, c.B, c.T * c.H * c.W, self.eps)
+        hw = c.H * c.W
+        ops.spatial_norm3d(x, stats, self._g, self._bt, yb, c.tmap(), P.view(-1, self.c)[2 * hw:], c.B, c.T, c.H, c.W, c.Tz, c.sh,
+                           silu, out_batch_rows=(c.T + 2) * hw)
+        return P
+
+
+class CogVideoXResnetBlock3D(nn.Module):
+    def __init__(self, cin: int, cout: int, cfg: CogVAEConfig):
+        super().__init__()
+        self.cin, self.cout = cin, cout
+        self.norm1 = CogVideoXSpatialNorm3D(cin, cfg.latent_channels, cfg.norm_num_groups, cfg.norm_eps)
+        self.conv1 = CogVideoXCausalConv3d(cin, cout, 3)
+        self.norm2 = CogVideoXSpatialNorm3D(cout, cfg.latent_channels, cfg.norm_num_groups, cfg.norm_eps)
+        self.conv2 = CogVideoXCausalConv3d(cout, cout, 3)
+        self.conv_shortcut = nn.Conv3d(cin, cout, 1) if cin != cout else None
+
+    def pack(self):
+        self.norm1.pack(); self.norm2.pack(); self.conv1.pack(); self.conv2.pack()
+        if self.conv_shortcut is not None:
+            self._ws, self._bs = pack_linear(self.conv_shortcut.weight.detach()), _f32(self.conv_shortcut.bias)
+
+    def run(self, x: torch.Tensor, c: _Chunk):
+        """launches: [plain GEMM (conv_y | conv_b), GroupNorm statistics unless the producing GEMM left column sums, spatial norm,
+        causal conv] x 2, + the 1x1x1 shortcut GEMM where the channel count changes; the residual is conv2's epilogue"""
+        rows = c.T * c.H * c.W
+        h = self.conv1.run(self.norm1.run(x, c, _prefixed(c, self.cin, x.device)), c, colstats=rows)
+        P2 = self.norm2.run(h, c, _prefixed(c, self.cout, x.device))
+        del h
+        sc = x
+        if self.conv_shortcut is not None:
+            sc = _new(x.shape[0], self.cout, x.device)
+            ops.gemm(x, self._ws, sc, M=x.shape[0], N=self.cout, K=self.cin, bias=self._bs)
+        return self.conv2.run(P2, c, res1=sc, colstats=rows)
+
+
+class CogVideoXUpsample3D(nn.Module):
+    def __init__(self, c: int, compress_time: bool):
+        super().__init__()
+        self.c, self.compress_time = c, compress_time
+        self.conv = nn.Conv2d(c, c, 3, padding=1)
+
+    def pack(self):
+        self._w, self._b = pack_conv3x3(self.conv.weight.detach()), _f32(self.conv.bias)
+
+    def run(self, x: torch.Tensor, c: _Chunk):
+        """conv(dup(x)) = dup(conv(x)): the T frames are convolved once (nearest 2x in height / width inside the gather), then each
+        result frame is placed as often as the time doubling repeats it"""
+        N, Ho, Wo = c.B * c.T, 2 * c.H, 2 * c.W
+        fmap = upsample_frame_map(c.T, self.compress_time)
+        To = len(fmap)
+        out = _new(N * Ho * Wo, self.c, x.device)
+        ops.gemm(x, self._w, out, M=N * Ho * Wo, N=self.c, K=9 * self.c, bias=self._b, mode=ops.A_CONV3X3, Cin=self.c,
+                 conv=(Ho, Wo, c.H, c.W, 1, 1), colstats=(c.T * Ho * Wo if To == c.T else 0))
+        if To != c.T:
+            idx = torch.tensor(fmap, dtype=torch.int64).to(x.device)
+            out = out.view(c.B, c.T, Ho * Wo * self.c).index_select(1, idx).view(-1, self.c)      # the strided device copy
+        c.T, c.H, c.W, c.sh = To, Ho, Wo, c.sh + 1
+        return out
+
+
+class CogVideoXMidBlock3D(nn.Module):
+    def __init__(self, c: int, cfg: CogVAEConfig):
+        super().__init__()
+        self.resnets = nn.ModuleList([CogVideoXResnetBlock3D(c, c, cfg) for _ in range(2)])
+
+
+class CogVideoXUpBlock3D(nn.Module):
+    def __init__(self, cin, cout, layers, add_upsample, compress_time, cfg):
+        super().__init__()
+        self.resnets = nn.ModuleList([CogVideoXResnetBlock3D(cin if i == 0 else cout, cout, cfg) for i in range(layers)])
+        self.upsamplers = nn.ModuleList([CogVideoXUpsample3D(cout, compress_time)]) if add_upsample else None
+
+
+class CogVideoXDecoder3D(nn.Module):
+    def __init__(self, cfg: CogVAEConfig):
+        super().__init__()
+        r = list(reversed(cfg.block_out_channels))
+        self.conv_in = CogVideoXCausalConv3d(cfg.latent_channels, r[0], 3)
+        self.mid_block = CogVideoXMidBlock3D(r[0], cfg)
+        nt = cfg.temporal_compression_ratio.bit_length() - 1
+        self.up_blocks = nn.ModuleList()
+        c = r[0]
+        for i, co in enumerate(r):
+            self.up_blocks.append(CogVideoXUpBlock3D(c, co, cfg.layers_per_block + 1, i != len(r) - 1, i < nt, cfg))
+            c = co
+        self.norm_out = CogVideoXSpatialNorm3D(r[-1], cfg.latent_channels, cfg.norm_num_groups, cfg.norm_eps)
+        self.conv_act = nn.SiLU()
+        self.conv_out = CogVideoXCausalConv3d(r[-1], cfg.out_channels, 3)
+
+
+def _check_config(cfg: CogVAEConfig) -> None:
+    if cfg.use_post_quant_conv:
+        raise LkgdHipError("AutoencoderKLCogVideoX: use_post_quant_conv = True is not built (no CogVideoX checkpoint sets it)")
+    if cfg.norm_num_groups != 32:
+        raise LkgdHipError(f"AutoencoderKLCogVideoX: norm_num_groups = {cfg.norm_num_groups}: the norm kernels have 32 groups")
+    for ch in cfg.block_out_channels:
+        if ch % 64:
+            raise LkgdHipError(f"AutoencoderKLCogVideoX: block_out_channels entry {ch} is not a multiple of 64 "
+                               "(implicit-GEMM K granularity)")
+    if not 0 < cfg.latent_channels <= 64 or cfg.latent_channels % 8:
+        raise LkgdHipError(f"AutoencoderKLCogVideoX: latent_channels = {cfg.latent_channels}: a multiple of 8 up to 64")
+    if not 0 < cfg.out_channels <= 4:
+        raise LkgdHipError(f"AutoencoderKLCogVideoX: out_channels = {cfg.out_channels}: at most 4")
+    if cfg.act_fn != "silu":
+        raise LkgdHipError(f"AutoencoderKLCogVideoX: act_fn = {cfg.act_fn!r}: only 'silu' is built")
+    t = cfg.temporal_compression_ratio
+    if t < 1 or t & (t - 1) or (t.bit_length() - 1) >= len(cfg.block_out_channels):
+        raise LkgdHipError(f"AutoencoderKLCogVideoX: temporal_compression_ratio = {t}: a power of two below 2^len(block_out_channels)")
+
+
+class AutoencoderKLCogVideoX(nn.Module):
+    """decoder half of diffusers' AutoencoderKLCogVideoX [EXT], PARITY UNPINNED.  State-dict names are diffusers'
+    (``decoder.conv_in.conv.weight`` ...); ``encoder.*`` / ``quant_conv.*`` keys of a checkpoint are accepted and dropped, any other
+    missing or unexpected key raises."""
+
+    DROPPED_PREFIXES = ("encoder.", "quant_conv.")
+
+    def __init__(self, config: Optional[CogVAEConfig] = None, **kw):
+        super().__init__()
+        cfg = config if config is not None else CogVAEConfig(**kw)
+        cfg.block_out_channels = tuple(cfg.block_out_channels)
+        _check_config(cfg)
+        self.config = SimpleNamespace(**cfg.__dict__)
+        self.decoder = CogVideoXDecoder3D(cfg)
+        self._packed = False
+
+    # ---- reference API surface ---------------------------------------------------------------------------------
+    @property
+    def dtype(self):
+        return self.decoder.conv_in.conv.weight.dtype
+
+    @property
+    def device(self):
+        return self.decoder.conv_in.conv.weight.device
+
+    @classmethod
+    def from_pretrained(cls, pretrained_model_name_or_path: str, subfolder: Optional[str] = None, torch_dtype=None,
+                        variant: Optional[str] = None, **_ignored):
+        from .loading import build_from_pretrained
+        return build_from_pretrained(cls, CogVAEConfig, pretrained_model_name_or_path, subfolder, torch_dtype, variant)
+
+    def save_pretrained(self, save_directory: str, variant: Optional[str] = None, **_ignored):
+        from .loading import save_pretrained
+        save_pretrained(self, save_directory, dict(self.config.__dict__), type(self).__name__, variant)
+
+    def invalidate(self):
+        self._packed = False
+
+    def load_state_dict(self, state_dict, strict: bool = True, **k):
+        """``encoder.*`` and ``quant_conv.*`` keys are dropped; every other missing or unexpected key raises (whatever ``strict``)"""
+        sd = {n: v for n, v in state_dict.items() if not n.startswith(self.DROPPED_PREFIXES)}
+        r = super().load_state_dict(sd, strict=False, **k)
+        self._packed = False
+        if r.missing_keys or r.unexpected_keys:
+            raise RuntimeError(f"AutoencoderKLCogVideoX.load_state_dict: missing keys {list(r.missing_keys)[:5]}, "
+                               f"unexpected keys {list(r.unexpected_keys)[:5]}")
+        return r
+
+    def _apply(self, fn, *a, **k):
+        r = super()._apply(fn, *a, **k)
+        self._packed = False
+        return r
+
+    def encode(self, *a, **k):
+        raise LkgdHipError("AutoencoderKLCogVideoX.encode is not built: the encoder (plain-GroupNorm resnets, 3-D downsamplers) is "
+                           "not on the HIP path yet")
+
+    def enable_tiling(self, *a, **k):
+        raise LkgdHipError("AutoencoderKLCogVideoX.enable_tiling is not built: a whole chunk decodes at once")
+
+    def enable_slicing(self, *a, **k):
+        raise LkgdHipError("AutoencoderKLCogVideoX.enable_slicing is not built: the batch decodes at once")
+
+    # ---- packing -----------------------------------------------------------------------------------------------
+    @torch.no_grad()
+    def prepare(self):
+        if self._packed:
+            return
+        if self.device.type != "cuda":
+            raise LkgdHipError("lkgd_amd CogVideoX VAE runs on MI355X only: move the module to cuda first")
+        d = self.decoder
+        for m in self.modules():
+            if isinstance(m, (CogVideoXResnetBlock3D, CogVideoXUpsample3D)):
+                m.pack()
+        d.conv_in.pack(pad_cin=64)                  # the latent rows are padded to 64 channels with zeros
+        d.norm_out.pack()
+        d.conv_out.pack(pad_cout=4)                 # GEMM output granularity
+        self._packed = True
+
+    def _convs(self):
+        return [m for m in self.modules() if isinstance(m, CogVideoXCausalConv3d)]
+
+    # ---- decode ------------------------------------------------------------------------------------------------
+    def _decode_chunk(self, zc: torch.Tensor, out: torch.Tensor, t_out: int) -> int:
+        """one chunk of latent frames ``zc`` [B, Tz, h, w, 16] (fp16) through the decoder; its frames go to out[:, :, t_out:]"""
+        d, dev = self.decoder, zc.device
+        B, Tz, h, w, lc = zc.shape
+        P0 = torch.zeros(B, Tz + 2, h * w, 64, dtype=torch.float16, device=dev)
+        P0[:, 2:, :, :lc] = zc.reshape(B, Tz, h * w, lc)
+        zq64 = P0[:, 2:].reshape(B * Tz * h * w, 64).contiguous()
+        c = _Chunk(B, Tz, h, w, zq64)
+        x = d.conv_in.run(P0, c, colstats=Tz * h * w)
+        del P0
+        for r in d.mid_block.resnets:
+            x = r.run(x, c)
+        for blk in d.up_blocks:
+            for r in blk.resnets:
+                x = r.run(x, c)
+            if blk.upsamplers is not None:
+                x = blk.upsamplers[0].run(x, c)
+        c0 = self.config.block_out_channels[0]
+        P = d.norm_out.run(x, c, _prefixed(c, c0, dev))
+        del x
+        rgb = d.conv_out.run(P, c)                                              # [B*T*H*W, 4]
+        oc = self.config.out_channels
+        frames = ops.tokens_to_nchw(rgb, B * c.T, oc, c.H, c.W)                 # [B*T, 3, H, W]
+        out[:, :, t_out:t_out + c.T] = frames.view(B, c.T, oc, c.H, c.W).permute(0, 2, 1, 3, 4)
+        return c.T
+
+    @torch.no_grad()
+    def decode(self, z: torch.Tensor, return_dict: bool = True):
+        """[B, 16, T, h, w] -> sample [B, 3, T', 8h, 8w] in z's dtype (T' = 1 + 4 (T - 1) for odd T, 4 T for even T): chunks of two
+        latent frames, the conv caches carried from chunk to chunk"""
+        self.prepare()
+        lc = self.config.latent_channels
+        if z.dim() != 5 or z.shape[1] != lc:
+            raise ValueError(f"expected [B, {lc}, T, h, w]")
+        B, _, T, h, w = z.shape
+        dev = self.device
+        zh = z.to(device=dev, dtype=torch.float16).permute(0, 2, 3, 4, 1).contiguous()           # [B, T, h, w, 16]
+        bounds = chunk_bounds(T)
+        nt = self.config.temporal_compression_ratio.bit_length() - 1
+        up = 2 ** (len(self.config.block_out_channels) - 1)
+
+        def frames_of(n):
+            for _ in range(nt):
+                n = len(upsample_frame_map(n, True))
+            return n
+
+        Tout = sum(frames_of(b - a) for a, b in bounds)
+        out_dtype = z.dtype if z.dtype in (torch.float16, torch.float32) else torch.float32
+        out = torch.empty(B, self.config.out_channels, Tout, up * h, up * w, dtype=torch.float16, device=dev)
+        convs = self._convs()
+        for m in convs:
+            m._cache = None
+        t_out = 0
+        try:
+            for a, b in bounds:
+                t_out += self._decode_chunk(zh[:, a:b], out, t_out)      # (a chunk's activations are gone when it returns)
+        finally:
+            for m in convs:
+                m._cache = None
+        out = out.to(out_dtype)
+        if not return_dict:
+            return (out,)
+        return DecoderOutput(sample=out)
+
+    def forward(self, z):
+        return self.decode(z)
+
+
+def decode_latents(vae: AutoencoderKLCogVideoX, latents: torch.Tensor) -> torch.Tensor:
+    """``CogVideoXImageToVideoPipeline.decode_latents`` (pipeline_cogvideox_image2video.py:430-435): [B, T, 16, h, w] latents ->
+    [B, 3, T', 8h, 8w] frames"""
+    latents = latents.permute(0, 2, 1, 3, 4)
+    latents = 1 / vae.config.scaling_factor * latents
+    return vae.decode(latents).sample

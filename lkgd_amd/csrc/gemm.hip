@@ -452,6 +452,15 @@ static int check_desc(const lkgd_gemm_desc* d) {
       if (d->Cin != 8 || d->K != 128 || d->lda0 != 8 || d->stride != 1 || d->ups != 0 || d->pad_off != 0) return LKGD_E_SHAPE;
       if (d->Hout != d->Hin || d->Wout != d->Win || d->M % (d->Hout * d->Wout)) return LKGD_E_SHAPE;
       break;
+    case LKGD_A_CCONV3:
+      if (d->Cin <= 0 || d->Cin % BK || d->K != 27 * d->Cin || d->csplit != d->Cin) return LKGD_E_SHAPE;
+      if (d->Hout <= 0 || d->Wout <= 0 || d->Hout != d->Hin || d->Wout != d->Win) return LKGD_E_SHAPE;
+      if (d->stride != 1 || d->ups != 0 || d->pad_off != 0) return LKGD_E_SHAPE;
+      if (d->Floc <= 0 || d->F != d->Floc + 2 || d->f_off != 0) return LKGD_E_SHAPE;   // two context frames, then the chunk
+      if (d->M % (d->Floc * d->Hout * d->Wout)) return LKGD_E_SHAPE;
+      if ((long long)(d->M / d->Floc) * d->F >= (1LL << 31)) return LKGD_E_SHAPE;      // 32-bit source row index
+      if (d->geglu) return LKGD_E_SHAPE;
+      break;
     default:
       return LKGD_E_MODE;
   }
@@ -586,6 +595,13 @@ static int gemm_pick(const lkgd_gemm_desc* d, int cus, int* wide_ks_out) {   // 
   const bool n320 = d->N % wide_n == 0 || (long long)((d->N + 319) / 320) * 320 * 4 <= (long long)d->N * 5;
   int pick = 0;   // 1 = 128x128, 2 = 256x128 ring, 3 = stream, 4 = wide (256x320), 5 = rowpanel
   int wide_ks = 1;
+  if (d->mode == LKGD_A_CCONV3) {
+    // the causal 3x3x3 gather exists in the 256x320 program only (its kernels are instantiated per mode; the runtime-mode gathers of
+    // the other programs do not know it), unsliced: whatever variant a knob forces
+    if (!wide_ok || d->ln_colsum) return LKGD_E_SHAPE;
+    *wide_ks_out = 1;
+    return 4;
+  }
   if (d->geglu == 80) {
     if (!wide_ok) return LKGD_E_SHAPE;
     // 80-wide GEGLU interleave: the 256x320 kernel, or - at K <= 320 from 32k rows - the resident-weight kernel (a slab = one
@@ -644,6 +660,7 @@ static int gemm_pick(const lkgd_gemm_desc* d, int cus, int* wide_ks_out) {   // 
 // wide_split() for a forced 256x320 variant follows the same slicing rule as the automatic one
 static int gemm_wide_slices(const lkgd_gemm_desc* d, int cus, int pick, int wide_ks) {
   if (pick != 4) return 1;
+  if (d->mode == LKGD_A_CCONV3) return 1;
   if (gemm_variant_override == 4) {
     const int wide_n = lkgd_gemm_wide_tile_n(d->N);
     const long long tiles_wide = (long long)((d->M + 255) / 256) * ((d->N + wide_n - 1) / wide_n);
@@ -661,11 +678,14 @@ static int gemm_wide_slices(const lkgd_gemm_desc* d, int cus, int pick, int wide
 // On the full forward every large shape keeps 256x320 (1008 tiles = 4 rounds against 1344 = 6 x 0.83); the smaller forms are
 // for the levels of a sharded rank, where 256-row tiles leave CUs idle.
 static void gemm_wide_form(const lkgd_gemm_desc* d, int cus, int slices, int* wn_out, int* wm_out) {
-  const int wn0 = lkgd_gemm_wide_tile_n(d->N);
+  const int fn = lkgd_debug_wide_tile_n_forced(), fm = lkgd_debug_wide_tile_m_forced();
+  int wn0 = lkgd_gemm_wide_tile_n(d->N);
+  // the causal 3x3x3 convolutions run on this program whatever N is: up to 256 channels (the CogVideoX VAE decoder's 128 at its
+  // 480 x 720 level, where most of its FLOP are) one 256-column tile idles fewer columns than one 320-column tile
+  if (d->mode == LKGD_A_CCONV3 && d->N <= 256 && !fn) wn0 = 256;
   *wn_out = wn0;
   *wm_out = 256;
   if (slices != 1) return;
-  const int fn = lkgd_debug_wide_tile_n_forced(), fm = lkgd_debug_wide_tile_m_forced();
   if (fn || fm) {                                  // A/B knobs: no rule
     if (fm) *wm_out = fm;
     return;

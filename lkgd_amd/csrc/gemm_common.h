@@ -191,6 +191,7 @@ __device__ __forceinline__ void lean_rcps(const lkgd_gemm_desc& p, float& rcp0, 
   rcp0 = 1.f; rcp1 = 1.f;
   if (MODE == LKGD_A_CONV3X3) { rcp0 = 1.0f / (float)(p.Hout * p.Wout); rcp1 = 1.0f / (float)p.Wout; }
   if (MODE == LKGD_A_TCONV3) { rcp0 = 1.0f / (float)p.HW; rcp1 = 1.0f / (float)p.Floc; }
+  if (MODE == LKGD_A_CCONV3) { rcp0 = 1.0f / (float)(p.Hout * p.Wout); rcp1 = 1.0f / (float)p.Wout; }
 }
 
 template <int MODE>
@@ -209,6 +210,15 @@ __device__ __forceinline__ RowD lean_row(const lkgd_gemm_desc& p, int m, float r
       const int b = fast_div(bf, p.Floc, rcp1);
       r.yx = bf - b * p.Floc + p.f_off;                      // global frame
       r.base = b * p.F * p.HW + (m - bf * p.HW);             // + f*HW added per tap
+    } else if (MODE == LKGD_A_CCONV3) {
+      // row (b, t, y, x) of B x Floc x H x W; the source holds F = Floc + 2 frames per batch entry (two context frames first), so
+      // temporal tap kt of output frame t is source frame t + kt: always inside the buffer, no test in time
+      const int hw = p.Hout * p.Wout;
+      const int bt = fast_div(m, hw, rcp0), rem = m - bt * hw;
+      const int y = fast_div(rem, p.Wout, rcp1), x = rem - y * p.Wout;
+      const int b = bt / p.Floc;                             // (an integer division per tile row: Floc is 1..9, b a few units)
+      r.base = (bt + 2 * b) * hw;                            // (b * F + t) * H * W;  + kt * H * W added per tap
+      r.yx = ((y - 1) & 0xffff) | ((x - 1) << 16);
     } else {
       r.base = m;
     }
@@ -266,6 +276,32 @@ __device__ __forceinline__ void lean_segment(const lkgd_gemm_desc& p, LeanGather
       const bool ok = st.rd[i].base >= 0 && (unsigned)vy < (unsigned)Hv && (unsigned)vx < (unsigned)Wv;
       const unsigned row = (unsigned)(st.rd[i].base + (vy >> p.ups) * p.Win + (vx >> p.ups));
       st.aptr[i] = ok ? src + (unsigned long long)row * ld : zero;
+      st.zmask |= (ok ? 0u : 1u) << i;
+    }
+  } else if (MODE == LKGD_A_CCONV3) {
+    // K = 27 Cin, k = kt * 9 Cin + (the LKGD_A_CONV3X3 order): conv_k_decode of the K-tile index gives ky9 = 3 kt + ky in st.ky, and
+    // the 3x3 odometer (kx, chunk, ky9) runs over nine kernel rows; the outer kt shifts the row base by one frame (Hin * Win rows)
+    if (k0 != 0 && k0 == st.seg_end) {
+      if (++st.kx == 3) {
+        st.kx = 0;
+        st.cc += BK;
+        if (st.cc == p.Cin) { st.cc = 0; ++st.ky; }
+      }
+    } else {
+      conv_k_decode(k0, p.Cin, st.ky, st.kx, st.cc);       // wave-uniform (scalar) divisions
+    }
+    const int kt = st.ky >= 6 ? 2 : (st.ky >= 3 ? 1 : 0);
+    const int ky = st.ky - 3 * kt, kx = st.kx;
+    st.seg_k0 = k0;                                        // one K-tile per segment
+    st.seg_end = k0 + BK;
+    const half_t* src = (const half_t*)p.a0 + st.cc + schunk * 8;
+    const int fshift = kt * p.Hin * p.Win;
+#pragma unroll
+    for (int i = 0; i < NR; ++i) {
+      const int vy = (int)(short)(st.rd[i].yx & 0xffff) + ky, vx = (st.rd[i].yx >> 16) + kx;
+      const bool ok = st.rd[i].base >= 0 && (unsigned)vy < (unsigned)p.Hin && (unsigned)vx < (unsigned)p.Win;
+      const unsigned row = (unsigned)(st.rd[i].base + fshift + vy * p.Win + vx);
+      st.aptr[i] = ok ? src + (unsigned long long)row * (unsigned)p.lda0 : zero;
       st.zmask |= (ok ? 0u : 1u) << i;
     }
   } else {   // LKGD_A_TCONV3

@@ -622,7 +622,8 @@ extern "C" int lkgd_gemm_wide_launch(const lkgd_gemm_desc* d, hipStream_t stream
   LKGD_DEVICE_ONCE_BEGIN
     if (!wide_set_lds<LKGD_A_PLAIN>((const void*)lkgd_gemm_wide_split_kernel<LKGD_A_PLAIN>) ||
         !wide_set_lds<LKGD_A_CONV3X3>((const void*)lkgd_gemm_wide_split_kernel<LKGD_A_CONV3X3>) ||
-        !wide_set_lds<LKGD_A_TCONV3>((const void*)lkgd_gemm_wide_split_kernel<LKGD_A_TCONV3>))
+        !wide_set_lds<LKGD_A_TCONV3>((const void*)lkgd_gemm_wide_split_kernel<LKGD_A_TCONV3>) ||
+        !wide_set_lds<LKGD_A_CCONV3>((const void*)lkgd_gemm_wide_kernel<LKGD_A_CCONV3, false, 10, 4>))   // (never sliced: no split kernel)
       return LKGD_E_LAUNCH;
   LKGD_DEVICE_ONCE_END
   if ((wn != 256 && wn != WBN) || (wm != 192 && wm != WBM)) return LKGD_E_SHAPE;
@@ -648,6 +649,10 @@ extern "C" int lkgd_gemm_wide_launch(const lkgd_gemm_desc* d, hipStream_t stream
   if (d->mode == LKGD_A_PLAIN) WIDE_LAUNCH(LKGD_A_PLAIN)
   else if (d->mode == LKGD_A_CONV3X3) WIDE_LAUNCH(LKGD_A_CONV3X3)
   else if (d->mode == LKGD_A_TCONV3) WIDE_LAUNCH(LKGD_A_TCONV3)
+  else if (d->mode == LKGD_A_CCONV3) {
+    if (ksplit > 1) return LKGD_E_SHAPE;                 // the causal 3x3x3 gather runs unsliced
+    wide_go<LKGD_A_CCONV3>(d, stream, grid, tiles_m, tiles_n, lds_out, wn, wm);
+  }
 #undef WIDE_LAUNCH
   else
     return LKGD_E_MODE;

@@ -12,7 +12,7 @@ import torch
 from . import _lib
 from ._lib import GemmDesc, check
 
-A_PLAIN, A_CONV3X3, A_TCONV3, A_CONV3X3_C8 = 0, 1, 2, 3
+A_PLAIN, A_CONV3X3, A_TCONV3, A_CONV3X3_C8, A_CCONV3 = 0, 1, 2, 3, 4
 
 _zeros = {}
 
@@ -143,7 +143,7 @@ _FAKE_PTR = 1 << 12     # gemm_plan off the device: a non-NULL, 16-byte aligned 
 
 def _gemm_desc(a0, w, out, *, M, N, K, bias=None, a1=None, csplit=None, mode=A_PLAIN, Cin=0, conv=None, tconv=None,
                rowbias=None, rowmap=None, res1=None, r1=1.0, res2=None, r2=1.0, s_acc=1.0, geglu=0, colstats=0, ln=None,
-               plan_cus=None):
+               cconv=None, plan_cus=None):
     """the lkgd_gemm_desc of a :func:`gemm` call.  ``plan_cus`` None: for launching (device tensors, the workspace and the column
     sum buffer are allocated); an int: for :func:`gemm_plan` - the same fields and pointer classes, nothing allocated."""
     launch = plan_cus is None
@@ -168,6 +168,11 @@ def _gemm_desc(a0, w, out, *, M, N, K, bias=None, a1=None, csplit=None, mode=A_P
     if tconv is not None:      # (F, HW) or (F, HW, Floc, f_off) under frame sharding
         d.F, d.HW = tconv[0], tconv[1]
         d.Floc, d.f_off = (tconv[2], tconv[3]) if len(tconv) == 4 else (tconv[0], 0)
+    if cconv is not None:      # (Floc, H, W): A_CCONV3 - a0 holds Floc + 2 frames per batch entry, two context frames first
+        d.Floc, d.F, d.f_off = cconv[0], cconv[0] + 2, 0
+        d.Hout = d.Hin = cconv[1]
+        d.Wout = d.Win = cconv[2]
+        d.stride, d.ups, d.pad_off, d.HW = 1, 0, 0, cconv[1] * cconv[2]
     if rowbias is not None:
         req(rowbias, torch.float16, "rowbias")
         d.rowbias, d.ldrb = rowbias.data_ptr(), _ld(rowbias)
@@ -216,15 +221,17 @@ def gemm(a0: torch.Tensor, w: torch.Tensor, out: torch.Tensor, *, M: int, N: int
          tconv: Optional[Tuple[int, int]] = None, rowbias: Optional[torch.Tensor] = None,
          rowmap: Optional[RowMap] = None, res1: Optional[torch.Tensor] = None, r1: float = 1.0,
          res2: Optional[torch.Tensor] = None, r2: float = 1.0, s_acc: float = 1.0, geglu: int = 0,
-         colstats: int = 0, ln: Optional[Tuple[torch.Tensor, float]] = None) -> torch.Tensor:
+         colstats: int = 0, ln: Optional[Tuple[torch.Tensor, float]] = None,
+         cconv: Optional[Tuple[int, int, int]] = None) -> torch.Tensor:
     """out = epilogue(A(.) @ w.T) - see include/lkgd_hip.h section 1.  ``conv`` = (Hout, Wout, Hin, Win, stride, ups);
-    ``tconv`` = (F, HW).  ``colstats`` = rows per GroupNorm sample (0 = off): ``out`` feeds a GroupNorm next - where the
+    ``tconv`` = (F, HW); ``cconv`` = (Floc, H, W) of A_CCONV3 (``a0`` = the [B * (Floc + 2) * H * W, Cin] context-prefixed rows).
+    ``colstats`` = rows per GroupNorm sample (0 = off): ``out`` feeds a GroupNorm next - where the
     tile program that will run supports it and its row blocks tile the samples, the GEMM leaves the per-(row block, channel
     pair) sums of its rounded outputs and ``out`` carries them (``out._lkgd_colstats``) to :func:`groupnorm_stats`, which
     then skips its read pass over the tensor."""
     d = _gemm_desc(a0, w, out, M=M, N=N, K=K, bias=bias, a1=a1, csplit=csplit, mode=mode, Cin=Cin, conv=conv, tconv=tconv,
                    rowbias=rowbias, rowmap=rowmap, res1=res1, r1=r1, res2=res2, r2=r2, s_acc=s_acc, geglu=geglu,
-                   colstats=colstats, ln=ln)
+                   colstats=colstats, ln=ln, cconv=cconv)
     _gemm_family("lkgd_gemm_f16", (C.byref(d),), 2.0 * M * N * (72 if mode == A_CONV3X3_C8 else K))
     return out
 
@@ -378,6 +385,28 @@ def groupnorm_silu(x0, x1, nsamples, rows_per_sample, gamma, beta, eps, silu=Tru
     check(L.lkgd_groupnorm_silu(x0.data_ptr(), c0, _ld(x0), _ptr(x1), c1, _ld(x1) if x1 is not None else 0, nsamples,
                                 rows_per_sample, eps, partial.data_ptr(), stats.data_ptr(), gamma.data_ptr(), beta.data_ptr(),
                                 1 if silu else 0, out.data_ptr(), _ld(out), _stream()), "lkgd_groupnorm_silu")
+    return out
+
+
+def spatial_norm3d(f: torch.Tensor, stats: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, yb: torch.Tensor,
+                   tmap: torch.Tensor, out: torch.Tensor, B: int, T: int, H: int, W: int, Tz: int, sh: int, silu: bool,
+                   out_batch_rows: Optional[int] = None) -> torch.Tensor:
+    """CogVideoXSpatialNorm3D (+ SiLU) in one pass (include/lkgd_hip_cogvae.h): ``f`` [B*T*H*W, C] rows, ``stats`` [B, 32, 2] from
+    :func:`groupnorm_stats` over T*H*W rows per sample, ``yb`` [B*Tz*(H>>sh)*(W>>sh), 2C] = conv_y | conv_b on the latent grid,
+    ``tmap`` int32 [T].  ``out`` = the first output row (a [rows, C] view: of a compact matrix, or of a context-prefixed buffer
+    behind its two context frames with ``out_batch_rows`` = (T + 2)*H*W)."""
+    _req(f, torch.float16, "f"); _req(yb, torch.float16, "yb"); _req(out, torch.float16, "out")
+    _req(stats, torch.float32, "stats"); _req(gamma, torch.float32, "gamma"); _req(beta, torch.float32, "beta")
+    _req(tmap, torch.int32, "tmap")
+    C_ = f.shape[1]
+    if tmap.numel() != T or not tmap.is_contiguous() or not stats.is_contiguous() or stats.numel() != B * 64:
+        raise _lib.LkgdHipError("spatial_norm3d: tmap must be int32 [T], stats fp32 [B, 32, 2]")
+    if f.shape[0] != B * T * H * W or yb.shape[1] != 2 * C_ or yb.shape[0] != B * Tz * (H >> sh) * (W >> sh) or out.shape[1] != C_:
+        raise _lib.LkgdHipError("spatial_norm3d: f / yb / out shapes do not match (B, T, H, W, Tz, sh)")
+    obr = T * H * W if out_batch_rows is None else int(out_batch_rows)
+    check(_L().lkgd_spatial_norm3d(f.data_ptr(), _ld(f), stats.data_ptr(), gamma.data_ptr(), beta.data_ptr(), yb.data_ptr(), _ld(yb),
+                                   tmap.data_ptr(), out.data_ptr(), _ld(out), obr, B, T, H, W, C_, Tz, sh, 1 if silu else 0, _stream()),
+          "lkgd_spatial_norm3d")
     return out
 
 

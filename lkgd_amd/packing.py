@@ -37,6 +37,14 @@ def pack_tconv3(w: torch.Tensor) -> torch.Tensor:
     return w[:, :, :, 0, 0].permute(0, 2, 1).reshape(co, 3 * ci).to(torch.float16).contiguous()
 
 
+def pack_cconv3(w: torch.Tensor) -> torch.Tensor:
+    """causal Conv3d weight [Cout, Cin, 3, 3, 3] -> fp16 [Cout, 27*Cin], k = kt*9*Cin + (the :func:`pack_conv3x3` order of tap
+    kt's [Cout, Cin, 3, 3] slice): LKGD_A_CCONV3 (include/lkgd_hip.h section 1).  Cin must be a multiple of 64."""
+    co, ci = w.shape[:2]
+    assert tuple(w.shape[2:]) == (3, 3, 3) and ci % 64 == 0, "causal 3x3x3 implicit GEMM needs Cin % 64 == 0"
+    return torch.cat([pack_conv3x3(w[:, :, kt]) for kt in range(3)], dim=1).contiguous()
+
+
 def pack_tfront(wqkv: torch.Tensor, heads: int) -> torch.Tensor:
     """fused projection [3C, C] (rows q | k | v, head-major) -> the MFMA-fragment stream of lkgd_tattn_front:
     [head][q,k,v][fragment i of 16 rows][K-step ks of 32][lane = 16*lq + row][8 halfs at k = 32 ks + 8 lq]"""

@@ -188,6 +188,16 @@ COGVAE_SYMBOLS = {
                                    _i32, _vp]),
 }
 
+#: every symbol include/lkgd_hip_cogvae_enc.h declares (the encoder of the CogVideoX 3-D causal VAE: conv_in's tap rows over the pixel
+#: channels, the downsamplers' temporal average pool, the posterior of conv_out's moment rows), bound on the same library object;
+#: tests/test_cogvideox_vae_encoder_cpu.py pins header, table and library to one another, tests/test_cogvideox_vae_encoder_gpu.py the
+#: footprint cases
+COGVAE_ENC_SYMBOLS = {
+    "lkgd_cogvae_pixel_taps": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
+    "lkgd_cogvae_time_pool": (_i32, [_vp, _i32, _vp, _i32, _i32, _i32, _i64, _i32, _vp]),
+    "lkgd_cogvae_posterior": (_i32, [_vp, _i32, _vp, _vp, _vp, _f32, _i32, _i32, _i32, _i32, _i32, _vp]),
+}
+
 #: include/lkgd_hip_debug.h: A/B and test knobs, per host thread; bound on the same library object, not part of the product interface
 DEBUG_SYMBOLS = {
     "lkgd_debug_set_wide_tile_n": (None, [_i32]),
@@ -223,7 +233,7 @@ def lib() -> C.CDLL:
         except OSError as e:
             raise LkgdHipError(f"cannot load {LIB_PATH}: {e}") from e
         for table in (SYMBOLS, WINDOW_SYMBOLS, DIT_SYMBOLS, DIT_LOOP_SYMBOLS, DIT_TPATCH_SYMBOLS, DIT_DPM_SYMBOLS, FP8_SYMBOLS,
-                      T5_SYMBOLS, COGVAE_SYMBOLS, DEBUG_SYMBOLS):
+                      T5_SYMBOLS, COGVAE_SYMBOLS, COGVAE_ENC_SYMBOLS, DEBUG_SYMBOLS):
             for name, (res, args) in table.items():
                 fn = getattr(l, name)       # AttributeError here = header / library mismatch
                 fn.restype, fn.argtypes = res, args

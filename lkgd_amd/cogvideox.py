@@ -998,3 +998,75 @@ def encode_prompt(text_encoder, tokenizer, prompt, negative_prompt=None, do_clas
                                                        max_sequence_length, device, dtype)
 
     return prompt_embeds, negative_prompt_embeds
+
+
+# ---- the image in front of the loop -------------------------------------------------------------------------------------------------
+def retrieve_latents(encoder_output, generator=None, sample_mode: str = "sample"):
+    """pipeline_cogvideox_image2video.py:153-163"""
+    if hasattr(encoder_output, "latent_dist") and sample_mode == "sample":
+        return encoder_output.latent_dist.sample(generator)
+    elif hasattr(encoder_output, "latent_dist") and sample_mode == "argmax":
+        return encoder_output.latent_dist.mode()
+    elif hasattr(encoder_output, "latents"):
+        return encoder_output.latents
+    else:
+        raise AttributeError("Could not access latents of provided encoder_output")
+
+
+def _scaled_sample(encoder_output, generator, scale: float):
+    """``scale * retrieve_latents(encoder_output, generator)``; a posterior of lkgd_amd's VAE folds the scale into the launch that
+    samples (``lkgd_cogvae_posterior``)"""
+    from .cogvideox_vae import DiagonalGaussianDistribution
+    dist = getattr(encoder_output, "latent_dist", None)
+    if isinstance(dist, DiagonalGaussianDistribution):
+        return dist.sample(generator, scale=scale)
+    return scale * retrieve_latents(encoder_output, generator)
+
+
+@torch.no_grad()
+def prepare_latents(vae, scheduler, transformer_config, image: torch.Tensor, batch_size: int = 1, num_channels_latents: int = 16,
+                    num_frames: int = 13, height: int = 60, width: int = 90, dtype=None, device=None, generator=None, latents=None):
+    """the reference's ``prepare_latents`` (pipeline_cogvideox_image2video.py:354-427) with ``self.vae`` / ``self.scheduler`` /
+    ``self.transformer.config`` as arguments: every image [C, H, W] of ``image`` [B, C, H, W] is encoded on its own
+    (``vae.encode(img[None, :, None])``) and sampled with its generator, scaled by ``scaling_factor`` (its inverse under
+    ``invert_scale_latents``), followed by ``num_frames - 1`` zero latent frames and, under ``patch_size_t``, padded at the front
+    (``pad_for_temporal_patches``); the noise is drawn with the (padded) latent shape - or ``latents`` taken as given - and
+    multiplied by ``scheduler.init_noise_sigma``.  Returns ``(latents, image_latents)``, both [B, F, C, h, w]: what :func:`denoise`
+    takes."""
+    if isinstance(generator, list) and len(generator) != batch_size:
+        raise ValueError(f"You have passed a list of generators of length {len(generator)}, but requested an effective batch"
+                         f" size of {batch_size}. Make sure the batch size matches the length of the generators.")
+    vc = vae.config
+    scale_t, scale_s = vc.temporal_compression_ratio, 2 ** (len(vc.block_out_channels) - 1)
+    device = device if device is not None else vae.device
+    dtype = dtype if dtype is not None else vae.dtype
+    p_t = transformer_config.patch_size_t
+
+    num_frames = (num_frames - 1) // scale_t + 1
+    shape = (batch_size, num_frames, num_channels_latents, height // scale_s, width // scale_s)
+    shape, _ = pad_for_temporal_patches(shape, None, p_t)                               # :383-384
+
+    image = image.unsqueeze(2)                                                          # [B, C, F, H, W]
+    factor = vc.scaling_factor if not vc.invert_scale_latents else 1 / vc.scaling_factor          # :397-402
+    if isinstance(generator, list):
+        image_latents = [_scaled_sample(vae.encode(image[i].unsqueeze(0)), generator[i], factor) for i in range(batch_size)]
+    else:
+        image_latents = [_scaled_sample(vae.encode(img.unsqueeze(0)), generator, factor) for img in image]
+    image_latents = torch.cat(image_latents, dim=0).to(device=device, dtype=dtype).permute(0, 2, 1, 3, 4)      # [B, F, C, h, w]
+
+    padding_shape = (batch_size, num_frames - 1, num_channels_latents, height // scale_s, width // scale_s)
+    latent_padding = torch.zeros(padding_shape, device=device, dtype=dtype)
+    image_latents = torch.cat([image_latents, latent_padding], dim=1)
+    _, image_latents = pad_for_temporal_patches(shape, image_latents, p_t)              # :416-418 (the shape is padded already)
+
+    if latents is None:
+        if isinstance(generator, list):
+            gdev = generator[0].device
+            latents = torch.cat([torch.randn((1,) + shape[1:], generator=g, device=gdev, dtype=dtype) for g in generator]).to(device)
+        else:
+            gdev = generator.device if generator is not None else device
+            latents = torch.randn(shape, generator=generator, device=gdev, dtype=dtype).to(device)
+    else:
+        latents = latents.to(device)
+    latents = latents * scheduler.init_noise_sigma
+    return latents, image_latents

@@ -1,13 +1,15 @@
-"""The decoder of the CogVideoX 3-D causal VAE (``AutoencoderKLCogVideoX``) on the MI355X path: denoised latents -> frames, the last
-boundary stage of the CogVideoX pipeline.
+"""The CogVideoX 3-D causal VAE (``AutoencoderKLCogVideoX``) on the MI355X path: the decoder (denoised latents -> frames, the last
+boundary stage of the CogVideoX pipeline) and, built on request (``encoder=True``), the encoder (image or clip -> the posterior
+whose sample conditions every step of the image-to-video loop).
 
 Call sites in the reference: CogVideo-main/finetune/models/cogvideox_i2v/pipeline_cogvideox_image2video.py:430-435 (``decode_latents``:
 permute, ``1 / scaling_factor``, ``vae.decode(latents).sample``), called at :908; ``inference/cli_vae_demo.py`` (``model.decode``).
 The class itself is diffusers' ``autoencoder_kl_cogvideox.py`` - [EXT], PARITY UNPINNED: diffusers is not vendored and the reference
 tree only imports the class, so module tree, parameter names and arithmetic restate the published source
 (tests/cogvideox_vae_oracle.py carries the same restatement in fp32 torch).  A real ``vae/`` checkpoint loads with
-``from_pretrained`` / ``load_state_dict``: its ``encoder.*`` and ``quant_conv.*`` keys are accepted and DROPPED (the encoder is not
-built: ``encode`` raises); any other missing or unexpected key raises.
+``from_pretrained`` / ``load_state_dict``: its ``quant_conv.*`` keys are accepted and DROPPED, and so are its ``encoder.*`` keys when
+the module was constructed without its encoder (the default: ``encode`` then raises); with ``encoder=True`` the ``encoder.*`` keys
+load strictly.  Any other missing or unexpected key raises.
 
 MI355X design: channels-last fp16 token matrices [B*T*H*W, C], rows (b, t, y, x) -
 * every causal 3x3x3 convolution is ONE implicit-GEMM launch (``LKGD_A_CCONV3``: 27 taps, fp32 accumulation) over a buffer that
@@ -20,6 +22,16 @@ MI355X design: channels-last fp16 token matrices [B*T*H*W
 * ``CogVideoXUpsample3D``: the per-frame 3x3 convolution with the nearest 2x folded into its gather (``LKGD_A_CONV3X3``, ups = 1);
   the doubling in time commutes with it - T frames are convolved once and each result placed twice (a strided device copy).
 Activations are fp16 with fp32 accumulation whatever dtype the parameters are kept in.  Chunks of two latent frames, as diffusers.
+
+The encoder (call sites pipeline_cogvideox_image2video.py:386-393 ``prepare_latents`` and
+inference/cli_vae_demo.py:63) runs frame batches of eight, the remainder in the first, on the same token matrices -
+* ``conv_in`` (3 pixel channels) is ``lkgd_cogvae_pixel_taps`` + ONE plain GEMM with K = 128: the taps are gathered from the clip
+  itself, whose earlier frames are the conv cache, so neither a cache nor a context-prefixed buffer exists for it;
+* the resnets' plain GroupNorm + SiLU is ``lkgd_groupnorm_apply`` writing behind the two context frames of the buffer the causal
+  convolution reads (statistics over the batch's frames, from the producing GEMM's column sums where the tile form allows);
+* ``CogVideoXDownsample3D``: ``lkgd_cogvae_time_pool`` (where ``compress_time``) in front of the stride-2 ``LKGD_A_CONV3X3`` with
+  ``pad_off = 1`` (F.pad(0,1,0,1) + padding 0), one image per frame;
+* ``lkgd_cogvae_posterior`` turns ``conv_out``'s moment rows into the mean and the scaled sample, [B, 16, T, h, w].
 """
 from __future__ import annotations
 
@@ -35,10 +47,13 @@ from ._lib import LkgdHipError
 from .packing import pack_cconv3, pack_conv3x3, pack_linear
 from .vae import DecoderOutput, _f32, _new, _pad_cout
 
+#: frames per batch of ``encode`` (diffusers' num_sample_frames_batch_size)
+ENCODE_FRAME_BATCH = 8
+
 
 @dataclass
 class CogVAEConfig:
-    """constructor keywords of AutoencoderKLCogVideoX [EXT] the decoder reads (CogVideoX ``vae/config.json``)"""
+    """constructor keywords of AutoencoderKLCogVideoX [EXT] the decoder and the encoder read (CogVideoX ``vae/config.json``)"""
     block_out_channels: Tuple[int, ...] = (128, 256, 256, 512)
     latent_channels: int = 16
     layers_per_block: int = 3
@@ -47,6 +62,7 @@ class CogVAEConfig:
     temporal_compression_ratio: int = 4
     scaling_factor: float = 1.15258426          # 2B; 0.7 for 5B
     out_channels: int = 3
+    in_channels: int = 3
     act_fn: str = "silu"
     use_quant_conv: bool = False
     use_post_quant_conv: bool = False
@@ -77,6 +93,14 @@ def upsample_frame_map(T: int, compress_time: bool) -> List[int]:
     if T % 2 == 1:
         return [0] + [1 + i // 2 for i in range(2 * (T - 1))]
     return [i // 2 for i in range(2 * T)]
+
+
+def frame_batch_bounds(T: int) -> List[Tuple[int, int]]:
+    """the frame ranges ``encode`` runs one after the other: batches of eight, the remainder in the FIRST (49 -> 9|8|8|8|8|8); fewer
+    than eight frames are one batch (AutoencoderKLCogVideoX._encode)"""
+    fb = ENCODE_FRAME_BATCH
+    n, rem = max(T // fb, 1), T % fb
+    return [(fb * i + (0 if i == 0 else rem), min(fb * (i + 1) + rem, T)) for i in range(n)]
 
 
 class _Chunk:
@@ -247,6 +271,169 @@ class CogVideoXDecoder3D(nn.Module):
         self.conv_out = CogVideoXCausalConv3d(r[-1], cfg.out_channels, 3)
 
 
+# ------------------------------------------------------------------------------------------------ the encoder's holders
+def _gn_prefixed(x: torch.Tensor, c: _Chunk, norm: nn.GroupNorm, g: torch.Tensor, bt: torch.Tensor) -> torch.Tensor:
+    """plain GroupNorm + SiLU of the batch's rows ``x`` into a fresh [B, T + 2, H*W, C] buffer behind its two context frames: the
+    statistics span the batch's frames (from the producing GEMM's column sums where it left them), then one
+    ``lkgd_groupnorm_apply`` per batch entry - ``out`` behind that entry's context frames, ``stats`` offset to the entry"""
+    rows, C_ = c.T * c.H * c.W, x.shape[1]
+    stats = ops.groupnorm_stats(x, None, c.B, rows, norm.eps)
+    P = _prefixed(c, C_, x.device)
+    for b in range(c.B):
+        ops.groupnorm_apply(x[b * rows:(b + 1) * rows], None, 1, rows, stats[b], g, bt, True, P[b, 2:].view(rows, C_))
+    return P
+
+
+class CogVideoXEncoderResnetBlock3D(nn.Module):
+    """CogVideoXResnetBlock3D [EXT] without a spatial norm dimension: norm1 / norm2 are plain GroupNorms"""
+
+    def __init__(self, cin: int, cout: int, cfg: CogVAEConfig):
+        super().__init__()
+        self.cin, self.cout = cin, cout
+        self.norm1 = nn.GroupNorm(cfg.norm_num_groups, cin, eps=cfg.norm_eps)
+        self.conv1 = CogVideoXCausalConv3d(cin, cout, 3)
+        self.norm2 = nn.GroupNorm(cfg.norm_num_groups, cout, eps=cfg.norm_eps)
+        self.conv2 = CogVideoXCausalConv3d(cout, cout, 3)
+        self.conv_shortcut = nn.Conv3d(cin, cout, 1) if cin != cout else None
+
+    def pack(self):
+        self._g1, self._bt1, self._g2, self._bt2 = (_f32(p) for p in (self.norm1.weight, self.norm1.bias, self.norm2.weight,
+                                                                      self.norm2.bias))
+        self.conv1.pack(); self.conv2.pack()
+        if self.conv_shortcut is not None:
+            self._ws, self._bs = pack_linear(self.conv_shortcut.weight.detach()), _f32(self.conv_shortcut.bias)
+
+    def run(self, x: torch.Tensor, c: _Chunk):
+        """launches: [GroupNorm statistics unless the producing GEMM left column sums, GroupNorm apply per batch entry, causal conv]
+        x 2, + the 1x1x1 shortcut GEMM where the channel count changes; the residual is conv2's epilogue"""
+        rows = c.T * c.H * c.W
+        h = self.conv1.run(_gn_prefixed(x, c, self.norm1, self._g1, self._bt1), c, colstats=rows)
+        P2 = _gn_prefixed(h, c, self.norm2, self._g2, self._bt2)
+        del h
+        sc = x
+        if self.conv_shortcut is not None:
+            sc = _new(x.shape[0], self.cout, x.device)
+            ops.gemm(x, self._ws, sc, M=x.shape[0], N=self.cout, K=self.cin, bias=self._bs)
+        return self.conv2.run(P2, c, res1=sc, colstats=rows)
+
+
+class CogVideoXDownsample3D(nn.Module):
+    """CogVideoXDownsample3D(c, c, padding=0, compress_time) [EXT]: avg_pool1d(2, 2) along the frames (the first frame apart when the
+    count is odd), then F.pad(0,1,0,1) and a 3x3 stride-2 convolution per frame"""
+
+    def __init__(self, c: int, compress_time: bool):
+        super().__init__()
+        self.c, self.compress_time = c, compress_time
+        self.conv = nn.Conv2d(c, c, 3, stride=2, padding=0)
+
+    def pack(self):
+        self._w, self._b = pack_conv3x3(self.conv.weight.detach()), _f32(self.conv.bias)
+
+    def run(self, x: torch.Tensor, c: _Chunk):
+        """the pool runs first, as diffusers does: the convolution then has half the rows"""
+        if self.compress_time:
+            x = ops.cogvae_time_pool(x, c.B, c.T, c.H * c.W)
+            c.T = ops.pooled_frames(c.T)
+        Ho, Wo = (c.H - 2) // 2 + 1, (c.W - 2) // 2 + 1
+        M = c.B * c.T * Ho * Wo
+        out = _new(M, self.c, x.device)
+        ops.gemm(x, self._w, out, M=M, N=self.c, K=9 * self.c, bias=self._b, mode=ops.A_CONV3X3, Cin=self.c,
+                 conv=(Ho, Wo, c.H, c.W, 2, 0, 1), colstats=c.T * Ho * Wo)
+        c.H, c.W = Ho, Wo
+        return out
+
+
+class CogVideoXEncoderMidBlock3D(nn.Module):
+    def __init__(self, c: int, cfg: CogVAEConfig):
+        super().__init__()
+        self.resnets = nn.ModuleList([CogVideoXEncoderResnetBlock3D(c, c, cfg) for _ in range(2)])
+
+
+class CogVideoXDownBlock3D(nn.Module):
+    def __init__(self, cin, cout, layers, add_downsample, compress_time, cfg):
+        super().__init__()
+        self.resnets = nn.ModuleList([CogVideoXEncoderResnetBlock3D(cin if i == 0 else cout, cout, cfg) for i in range(layers)])
+        self.downsamplers = nn.ModuleList([CogVideoXDownsample3D(cout, compress_time)]) if add_downsample else None
+
+
+class CogVideoXEncoder3D(nn.Module):
+    def __init__(self, cfg: CogVAEConfig):
+        super().__init__()
+        ch = list(cfg.block_out_channels)
+        self.conv_in = CogVideoXCausalConv3d(cfg.in_channels, ch[0], 3)
+        nt = cfg.temporal_compression_ratio.bit_length() - 1
+        self.down_blocks = nn.ModuleList()
+        c = ch[0]
+        for i, co in enumerate(ch):
+            self.down_blocks.append(CogVideoXDownBlock3D(c, co, cfg.layers_per_block, i != len(ch) - 1, i < nt, cfg))
+            c = co
+        self.mid_block = CogVideoXEncoderMidBlock3D(ch[-1], cfg)
+        self.norm_out = nn.GroupNorm(cfg.norm_num_groups, ch[-1], eps=1e-6)
+        self.conv_act = nn.SiLU()
+        self.conv_out = CogVideoXCausalConv3d(ch[-1], 2 * cfg.latent_channels, 3)
+
+    def pack(self):
+        """conv_in's weight in the k order of ``lkgd_cogvae_pixel_taps`` - k = ((kt*3 + ky)*3 + kx)*Cin + c, zeros up to K = 128"""
+        w = self.conv_in.conv.weight.detach().float()                                  # [c0, Cin, 3, 3, 3]
+        wk = w.permute(0, 2, 3, 4, 1).reshape(w.shape[0], -1)
+        self._w_in = torch.nn.functional.pad(wk, (0, 128 - wk.shape[1])).to(torch.float16).contiguous()
+        self._b_in = _f32(self.conv_in.conv.bias)
+        self._g_out, self._bt_out = _f32(self.norm_out.weight), _f32(self.norm_out.bias)
+        self.conv_out.pack()
+
+
+class DiagonalGaussianDistribution:
+    """the posterior ``encode`` returns ([EXT] diffusers DiagonalGaussianDistribution) over the moment rows ``conv_out`` left:
+    ``mean`` [B, lc, T, h, w] and ``sample`` come from ``lkgd_cogvae_posterior``; ``logvar`` (clamped to [-30, 20]) and ``std`` are
+    accessors computed on first use.  Tensors are handed out in ``dtype`` (the parameters')."""
+
+    def __init__(self, moments: torch.Tensor, B: int, lc: int, T: int, h: int, w: int, dtype):
+        self._mom, self._geo, self._dtype = moments, (B, lc, T, h, w), dtype
+        self.mean = ops.cogvae_posterior(moments, B, lc, T, h, w)[0].to(dtype)
+        self._logvar = None
+
+    @property
+    def logvar(self) -> torch.Tensor:
+        if self._logvar is None:
+            B, lc, T, h, w = self._geo
+            lv = self._mom[:, lc:2 * lc].reshape(B, T, h, w, lc).permute(0, 4, 1, 2, 3)
+            self._logvar = torch.clamp(lv.float(), -30.0, 20.0).to(self._dtype).contiguous()
+        return self._logvar
+
+    @property
+    def std(self) -> torch.Tensor:
+        return torch.exp(0.5 * self.logvar.float()).to(self._dtype)
+
+    def mode(self) -> torch.Tensor:
+        return self.mean
+
+    def sample(self, generator=None, scale: float = 1.0) -> torch.Tensor:
+        """``scale * (mean + std * noise)`` in one launch; the noise is drawn as ``dpm_noise`` draws: on the generator's device, in
+        the parameters' dtype, with the shape of the mean.  ``scale`` (1.0: diffusers' ``sample``) folds a caller's scaling factor."""
+        dev = self._mom.device
+        gdev = generator.device if generator is not None else dev
+        noise = torch.randn(tuple(self.mean.shape), generator=generator, device=gdev, dtype=self._dtype)
+        noise = noise.to(device=dev, dtype=torch.float16).contiguous()
+        return ops.cogvae_posterior(self._mom, *self._geo, noise=noise, scale=scale)[1].to(self._dtype)
+
+
+class AutoencoderKLOutput:
+    """what ``encode`` returns: ``.latent_dist``, also as item 0 (inference/cli_vae_demo.py indexes it)"""
+
+    def __init__(self, latent_dist: DiagonalGaussianDistribution):
+        self.latent_dist = latent_dist
+
+    def __getitem__(self, i):
+        return (self.latent_dist,)[i]
+
+
+def _check_encoder_config(cfg: CogVAEConfig) -> None:
+    if not 0 < cfg.in_channels <= 4:
+        raise LkgdHipError(f"AutoencoderKLCogVideoX: in_channels = {cfg.in_channels}: the tap rows of conv_in hold at most 4")
+    if cfg.use_quant_conv:
+        raise LkgdHipError("AutoencoderKLCogVideoX: use_quant_conv = True is not built (no CogVideoX checkpoint sets it)")
+
+
 def _check_config(cfg: CogVAEConfig) -> None:
     if cfg.use_post_quant_conv:
         raise LkgdHipError("AutoencoderKLCogVideoX: use_post_quant_conv = True is not built (no CogVideoX checkpoint sets it)")
@@ -268,20 +455,31 @@ def _check_config(cfg: CogVAEConfig) -> None:
 
 
 class AutoencoderKLCogVideoX(nn.Module):
-    """decoder half of diffusers' AutoencoderKLCogVideoX [EXT], PARITY UNPINNED.  State-dict names are diffusers'
-    (``decoder.conv_in.conv.weight`` ...); ``encoder.*`` / ``quant_conv.*`` keys of a checkpoint are accepted and dropped, any other
-    missing or unexpected key raises."""
+    """diffusers' AutoencoderKLCogVideoX [EXT], PARITY UNPINNED: the decoder, and with ``encoder=True`` the encoder.  State-dict
+    names are diffusers' (``decoder.conv_in.conv.weight``, ``encoder.down_blocks.0.resnets.0.norm1.weight`` ...).  ``quant_conv.*``
+    keys of a checkpoint are accepted and dropped; so are ``encoder.*`` keys when the module has no encoder - with one they load
+    strictly.  Any other missing or unexpected key raises."""
 
     DROPPED_PREFIXES = ("encoder.", "quant_conv.")
 
-    def __init__(self, config: Optional[CogVAEConfig] = None, **kw):
+    def __init__(self, config: Optional[CogVAEConfig] = None, encoder: bool = False, **kw):
         super().__init__()
         cfg = config if config is not None else CogVAEConfig(**kw)
         cfg.block_out_channels = tuple(cfg.block_out_channels)
         _check_config(cfg)
         self.config = SimpleNamespace(**cfg.__dict__)
         self.decoder = CogVideoXDecoder3D(cfg)
+        if encoder:
+            _check_encoder_config(cfg)
+            self.encoder = CogVideoXEncoder3D(cfg)
         self._packed = False
+
+    @property
+    def has_encoder(self) -> bool:
+        return "encoder" in self._modules
+
+    def _dropped_prefixes(self):
+        return ("quant_conv.",) if self.has_encoder else self.DROPPED_PREFIXES
 
     # ---- reference API surface ---------------------------------------------------------------------------------
     @property
@@ -294,9 +492,16 @@ class AutoencoderKLCogVideoX(nn.Module):
 
     @classmethod
     def from_pretrained(cls, pretrained_model_name_or_path: str, subfolder: Optional[str] = None, torch_dtype=None,
-                        variant: Optional[str] = None, **_ignored):
+                        variant: Optional[str] = None, encoder: Optional[bool] = None, **_ignored):
+        """``encoder`` None: the encoder is built iff the checkpoint holds an ``encoder.`` key (a saved decoder-only module comes
+        back decoder-only); True / False: as the constructor"""
         from .loading import build_from_pretrained
-        return build_from_pretrained(cls, CogVAEConfig, pretrained_model_name_or_path, subfolder, torch_dtype, variant)
+
+        def ctor(sd):
+            return {"encoder": any(k.startswith("encoder.") for k in sd) if encoder is None else bool(encoder)}
+
+        return build_from_pretrained(cls, CogVAEConfig, pretrained_model_name_or_path, subfolder, torch_dtype, variant,
+                                     ctor_from_state=ctor)
 
     def save_pretrained(self, save_directory: str, variant: Optional[str] = None, **_ignored):
         from .loading import save_pretrained
@@ -306,8 +511,9 @@ class AutoencoderKLCogVideoX(nn.Module):
         self._packed = False
 
     def load_state_dict(self, state_dict, strict: bool = True, **k):
-        """``encoder.*`` and ``quant_conv.*`` keys are dropped; every other missing or unexpected key raises (whatever ``strict``)"""
-        sd = {n: v for n, v in state_dict.items() if not n.startswith(self.DROPPED_PREFIXES)}
+        """``quant_conv.*`` keys are dropped, ``encoder.*`` keys too when the module has no encoder; every other missing or unexpected
+        key raises (whatever ``strict``)"""
+        sd = {n: v for n, v in state_dict.items() if not n.startswith(self._dropped_prefixes())}
         r = super().load_state_dict(sd, strict=False, **k)
         self._packed = False
         if r.missing_keys or r.unexpected_keys:
@@ -320,15 +526,13 @@ class AutoencoderKLCogVideoX(nn.Module):
         self._packed = False
         return r
 
-    def encode(self, *a, **k):
-        raise LkgdHipError("AutoencoderKLCogVideoX.encode is not built: the encoder (plain-GroupNorm resnets, 3-D downsamplers) is "
-                           "not on the HIP path yet")
-
     def enable_tiling(self, *a, **k):
-        raise LkgdHipError("AutoencoderKLCogVideoX.enable_tiling is not built: a whole chunk decodes at once")
+        raise LkgdHipError("AutoencoderKLCogVideoX.enable_tiling is not built: a whole chunk decodes (a whole frame batch encodes) "
+                           "at once")
 
     def enable_slicing(self, *a, **k):
-        raise LkgdHipError("AutoencoderKLCogVideoX.enable_slicing is not built: the batch decodes at once")
+        raise LkgdHipError("AutoencoderKLCogVideoX.enable_slicing is not built: the batch decodes at once (encode runs its batch "
+                           "entries one after the other as it is)")
 
     # ---- packing -----------------------------------------------------------------------------------------------
     @torch.no_grad()
@@ -344,10 +548,88 @@ class AutoencoderKLCogVideoX(nn.Module):
         d.conv_in.pack(pad_cin=64)                  # the latent rows are padded to 64 channels with zeros
         d.norm_out.pack()
         d.conv_out.pack(pad_cout=4)                 # GEMM output granularity
+        if self.has_encoder:
+            for m in self.encoder.modules():
+                if isinstance(m, (CogVideoXEncoderResnetBlock3D, CogVideoXDownsample3D)):
+                    m.pack()
+            self.encoder.pack()
         self._packed = True
 
     def _convs(self):
         return [m for m in self.modules() if isinstance(m, CogVideoXCausalConv3d)]
+
+    # ---- encode ------------------------------------------------------------------------------------------------
+    def _encode_batch(self, xh: torch.Tensor, a: int, b: int, mom: torch.Tensor, t_out: int) -> int:
+        """frames [a, b) of the clip ``xh`` [B, Cin, T, H, W] (fp16) through the encoder; the moment rows of its latent frames go to
+        mom[:, t_out:]"""
+        e, dev = self.encoder, xh.device
+        B, _, _, H, W = xh.shape
+        c = _Chunk(B, b - a, H, W, None)
+        c0 = self.config.block_out_channels[0]
+        M = B * c.T * H * W
+        taps = ops.cogvae_pixel_taps(xh, a, b - a)           # the clip's own frames a - 2, a - 1 are conv_in's cache
+        x = _new(M, c0, dev)
+        ops.gemm(taps, e._w_in, x, M=M, N=c0, K=128, bias=e._b_in, colstats=c.T * H * W)
+        del taps
+        for blk in e.down_blocks:
+            for r in blk.resnets:
+                x = r.run(x, c)
+            if blk.downsamplers is not None:
+                x = blk.downsamplers[0].run(x, c)
+        for r in e.mid_block.resnets:
+            x = r.run(x, c)
+        P = _gn_prefixed(x, c, e.norm_out, e._g_out, e._bt_out)
+        del x
+        m = e.conv_out.run(P, c)                                                # [B*T'*h*w, 2 lc]
+        mom[:, t_out:t_out + c.T] = m.view(B, c.T, c.H * c.W, m.shape[1])
+        return c.T
+
+    @torch.no_grad()
+    def encode(self, x: torch.Tensor, return_dict: bool = True):
+        """[B, 3, T, H, W] in [-1, 1] -> an output with ``.latent_dist`` (also its item 0): the posterior over [B, 16, T', H/8, W/8],
+        T' = 1 + (T - 1)/4 for T = 4k + 1.  Frame batches of eight with the remainder in the first (49 -> 9|8|8|8|8|8), the conv caches
+        carried from batch to batch; GroupNorm statistics span one batch's frames.  The batch entries are encoded one after the
+        other (the I2V pipeline encodes one image at a time): an entry's result does not depend on its neighbours."""
+        if not self.has_encoder:
+            raise LkgdHipError("AutoencoderKLCogVideoX.encode: this module was built without its encoder - construct it with "
+                               "encoder=True (from_pretrained builds it when the checkpoint holds encoder.* keys, or with encoder=True)")
+        ic, lc = self.config.in_channels, self.config.latent_channels
+        if x.dim() != 5 or x.shape[1] != ic:
+            raise ValueError(f"expected [B, {ic}, T, H, W]")
+        B, _, T, H, W = x.shape
+        down = 2 ** (len(self.config.block_out_channels) - 1)
+        if H % down or W % down:
+            raise ValueError(f"height and width must be multiples of {down}, got {H} x {W}")
+        if x.dtype == torch.bfloat16 or self.dtype == torch.bfloat16:
+            raise LkgdHipError("AutoencoderKLCogVideoX.encode: bf16 is not built - activations are fp16 (keep the module in fp16 or fp32)")
+        self.prepare()
+        dev = self.device
+        xh = x.to(device=dev, dtype=torch.float16).contiguous()
+        bounds = frame_batch_bounds(T)
+        nt = self.config.temporal_compression_ratio.bit_length() - 1
+
+        def frames_of(n):
+            for _ in range(nt):
+                n = ops.pooled_frames(n)
+            return n
+
+        Tl, h, w = sum(frames_of(b - a) for a, b in bounds), H // down, W // down
+        mom = torch.empty(B, Tl, h * w, 2 * lc, dtype=torch.float16, device=dev)
+        convs = self._convs()
+        try:
+            for i in range(B):
+                for m in convs:
+                    m._cache = None
+                t_out = 0
+                for a, b in bounds:
+                    t_out += self._encode_batch(xh[i:i + 1], a, b, mom[i:i + 1], t_out)
+        finally:
+            for m in convs:
+                m._cache = None
+        dist = DiagonalGaussianDistribution(mom.view(-1, 2 * lc), B, lc, Tl, h, w, self.dtype)
+        if not return_dict:
+            return (dist,)
+        return AutoencoderKLOutput(dist)
 
     # ---- decode ------------------------------------------------------------------------------------------------
     def _decode_chunk(self, zc: torch.Tensor, out: torch.Tensor, t_out: int) -> int:

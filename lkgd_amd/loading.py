@@ -71,10 +71,11 @@ def save_pretrained(model: torch.nn.Module, path: str, config: Dict, class_name:
 
 
 def build_from_pretrained(cls, config_cls, path: str, subfolder: Optional[str] = None, torch_dtype=None,
-                          variant: Optional[str] = None, strict: bool = True, **extra_ctor):
+                          variant: Optional[str] = None, strict: bool = True, ctor_from_state=None, **extra_ctor):
     """shared body of the models' ``from_pretrained``: config keys the dataclass knows are used, the rest (diffusers
     bookkeeping such as ``_class_name`` / ``_diffusers_version``) ignored; parameters are created on the meta device and
-    filled from the checkpoint (no random init of 1.5 B parameters)"""
+    filled from the checkpoint (no random init of 1.5 B parameters).  ``ctor_from_state`` (optional): called with the checkpoint's
+    state dict, returns further constructor keywords - for a module whose tree depends on which keys the checkpoint holds."""
     raw = load_config(path, subfolder)
     known = {k: (tuple(v) if isinstance(v, list) else v) for k, v in raw.items()
              if k in config_cls.__dataclass_fields__}
@@ -82,6 +83,8 @@ def build_from_pretrained(cls, config_cls, path: str, subfolder: Optional[str] =
     extra = {k: (tuple(raw[k]) if isinstance(raw[k], list) else raw[k]) for k in extra_ctor if k in raw}
     extra_ctor = {**extra_ctor, **extra}
     sd = load_state_dict(path, subfolder, variant)
+    if ctor_from_state is not None:
+        extra_ctor = {**extra_ctor, **ctor_from_state(sd)}
     with torch.device("meta"):
         m = cls(cfg, **extra_ctor)
     m = m.to_empty(device="cpu")

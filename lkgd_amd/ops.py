@@ -1164,3 +1164,63 @@ def t5_residual_add_(x: torch.Tensor, y: torch.Tensor, s: float = 1.0) -> torch.
     check(_L().lkgd_t5_residual_add(x.data_ptr(), _ld(x), y.data_ptr(), _ld(y), x.shape[0], x.shape[1], s, _stream()),
           "lkgd_t5_residual_add")
     return x
+
+
+# ---- the encoder of the CogVideoX 3-D causal VAE (include/lkgd_hip_cogvae_enc.h) --------------------------------------------------------
+def pooled_frames(T: int) -> int:
+    """frames the temporal pool of CogVideoXDownsample3D leaves of T: T/2, or with the first frame apart 1 + (T - 1)/2 for odd T"""
+    return 1 + (T - 1) // 2 if T % 2 else T // 2
+
+
+def cogvae_pixel_taps(x: torch.Tensor, t0: int, Tc: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """the A operand of the encoder's conv_in (lkgd_cogvae_pixel_taps): ``x`` fp16 [B, Cin <= 4, T, H, W] contiguous -> fp16
+    [B*Tc*H*W, 128] rows of the 27*Cin causal taps of frames [t0, t0 + Tc), k = ((kt*3 + ky)*3 + kx)*Cin + c, zeros behind them"""
+    _req(x, torch.float16, "x")
+    if x.dim() != 5 or not x.is_contiguous():
+        raise _lib.LkgdHipError(f"x must be a contiguous [B, Cin, T, H, W] clip, got {tuple(x.shape)} strides {tuple(x.stride())}")
+    B, Cin, T, H, W = x.shape
+    rows = B * Tc * H * W
+    if out is None:
+        out = torch.empty(rows, 128, dtype=torch.float16, device=x.device)
+    _req(out, torch.float16, "out")
+    if out.dim() != 2 or tuple(out.shape) != (rows, 128):
+        raise _lib.LkgdHipError(f"out must be [{rows}, 128], got {tuple(out.shape)}")
+    check(_L().lkgd_cogvae_pixel_taps(x.data_ptr(), out.data_ptr(), _ld(out), B, Cin, T, H, W, int(t0), int(Tc), _stream()),
+          "lkgd_cogvae_pixel_taps")
+    return out
+
+
+def cogvae_time_pool(x: torch.Tensor, B: int, T: int, HW: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """the temporal average pool of CogVideoXDownsample3D (lkgd_cogvae_time_pool): fp16 rows [B*T*HW, C] -> [B*pooled_frames(T)*HW, C]"""
+    _req(x, torch.float16, "x")
+    if x.dim() != 2 or x.shape[0] != B * T * HW:
+        raise _lib.LkgdHipError(f"x must be [{B * T * HW}, C] rows, got {tuple(x.shape)}")
+    C_ = x.shape[1]
+    orows = B * pooled_frames(T) * HW
+    if out is None:
+        out = torch.empty(orows, C_, dtype=torch.float16, device=x.device)
+    _req(out, torch.float16, "out")
+    if out.dim() != 2 or tuple(out.shape) != (orows, C_):
+        raise _lib.LkgdHipError(f"out must be [{orows}, {C_}], got {tuple(out.shape)}")
+    check(_L().lkgd_cogvae_time_pool(x.data_ptr(), _ld(x), out.data_ptr(), _ld(out), B, T, HW, C_, _stream()), "lkgd_cogvae_time_pool")
+    return out
+
+
+def cogvae_posterior(mom: torch.Tensor, B: int, lc: int, T: int, h: int, w: int, noise: Optional[torch.Tensor] = None,
+                     scale: float = 1.0):
+    """the posterior of the encoder's moment rows (lkgd_cogvae_posterior): ``mom`` fp16 [B*T*h*w, >= 2*lc] -> ``mean`` fp16
+    [B, lc, T, h, w] and, with ``noise`` (same layout), ``sample`` = scale * (mean + exp(0.5 * clamp(logvar, -30, 20)) * noise);
+    returns (mean, sample or None)"""
+    _req(mom, torch.float16, "mom")
+    if mom.dim() != 2 or mom.shape[0] != B * T * h * w or mom.shape[1] < 2 * lc:
+        raise _lib.LkgdHipError(f"mom must be [{B * T * h * w}, >= {2 * lc}] rows, got {tuple(mom.shape)}")
+    mean = torch.empty(B, lc, T, h, w, dtype=torch.float16, device=mom.device)
+    sample = None
+    if noise is not None:
+        _req(noise, torch.float16, "noise")
+        if tuple(noise.shape) != tuple(mean.shape) or not noise.is_contiguous():
+            raise _lib.LkgdHipError(f"noise must be a contiguous {tuple(mean.shape)} tensor, got {tuple(noise.shape)}")
+        sample = torch.empty_like(mean)
+    check(_L().lkgd_cogvae_posterior(mom.data_ptr(), _ld(mom), _ptr(noise), mean.data_ptr(), _ptr(sample), float(scale), B, lc, T, h, w,
+                                     _stream()), "lkgd_cogvae_posterior")
+    return mean, sample

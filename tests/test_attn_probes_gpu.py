@@ -7,7 +7,11 @@ The bounds are derived in attn_probes.py (two fp16 roundings of 2^-11 - the prob
 reject a dropped / doubled key, exchanged value rows, unmasked duplicate keys, an inverted kv map, exchanged temporal pairs and
 a wrong cross-attention context is shown without a GPU in test_attn_probes_cpu.py.  Outputs are pre-filled with NaN, the K / V
 of a batch entry that no query selects are NaN, and the debug knobs are reset in `finally`.  Every case prints the worst
-err / bound it saw (`PROBE ...`, visible with -s)."""
+err / bound it saw (`PROBE ...`, visible with -s).
+
+The fused temporal kernels (ops.tattn_block, ops.tattn_front) take x and packed weights, not q / k / v: attn_probes.FusedProbe
+builds both forms on rows and signed-selection weights that keep every intermediate exact, with the bounds derived in that module's
+docstring.  ops.attn_dense_relbias runs the two probes under a zero table, and an offset and a weighted probe of the table itself."""
 import pytest
 import torch
 
@@ -152,3 +156,99 @@ def test_attn_dense(nb, S, heads, hd):
         out = torch.full((nb * S, heads * hd), NAN, dtype=torch.float16, device=DEV)
         ops.attn_dense(q, k, v, out, nb, S, heads, hd)
         _report("attn_dense", "-", f"nb={nb},S={S},heads={heads},hd={hd}", kind, p.check(out.cpu(), f"attn_dense S={S} head_dim {hd}"))
+
+
+# ================================================================================================== fused temporal blocks
+def _pitched(t, ld, fill=0.0):
+    """t's rows in a [T, ld] device buffer (row pitch ld > width): the view of its first columns, and the buffer"""
+    buf = torch.full((t.shape[0], ld), fill, dtype=torch.float16, device=DEV)
+    buf[:, :t.shape[1]] = t.to(DEV)
+    return buf[:, :t.shape[1]], buf
+
+
+def _fused_case(B, HW, F):
+    return f"B={B},HW={HW},F={F}"
+
+
+def _run_tattn_block(p, ldx=None, ldo=None):
+    from lkgd_amd import ops
+    from lkgd_amd.packing import pack_tblock
+    ws = pack_tblock(p.wqkv.float(), p.bqkv.float(), p.wo.float()).to(DEV)
+    x = _pitched(p.x, ldx)[0] if ldx else p.x.to(DEV)
+    out, buf = _pitched(torch.full((p.T, 320), NAN, dtype=torch.float16), ldo or 320, NAN)
+    kw = {}
+    if p.table is not None:
+        kw = dict(rowbias=p.table.half().to(DEV), rowmap=p.rowmap)
+    ops.tattn_block(x, ws, p.bo.float().to(DEV), out, p.B, p.F, p.HW, **kw)
+    assert torch.isnan(buf[:, 320:]).all(), "columns beyond the row were written"
+    return out.cpu()
+
+
+@pytest.mark.parametrize("F", ap.FUSED_F)
+def test_tattn_block(F):
+    """lkgd_tattn_block_c320 on exact inputs (attn_probes.FusedProbe): 14 -> 16 frame-slot padding (F = 13, 14, 15 against 16), a
+    single pixel, a ragged / full / one-past-full panel, odd HW with B > 1 (a wave's pixel pair on a batch border), the (b_hi, b_lo)
+    bias k-step, the per-head value and out-projection chunk order, the rebuilt residual at four row amplitudes; x and out with a
+    row pitch of their own in one case each"""
+    for B, HW in ap.TBLOCK_BHW:
+        for kind in ap.fused_kinds(F):
+            p = ap.fused_probe(kind, B, HW, F)
+            ldx = 328 if (B, HW, F) == ap.TBLOCK_LDX else None
+            ldo = 336 if (B, HW, F) == ap.TBLOCK_LDO else None
+            out = _run_tattn_block(p, ldx, ldo)
+            _report("tattn_block", f"ldx={ldx or 320},ldo={ldo or 320}", _fused_case(B, HW, F), kind,
+                    p.check_block(out, f"tattn_block {_fused_case(B, HW, F)}"))
+
+
+def test_tattn_block_row_bias():
+    """the row-bias table (entries in multiples of 1/4) behind the row map of test_tblock_row_bias_and_sharp_scores"""
+    B, HW, F = ap.TBLOCK_ROWBIAS
+    for kind in ("uniform", "identity"):
+        p = ap.fused_probe(kind, B, HW, F, True)
+        _report("tattn_block", "rowbias", _fused_case(B, HW, F), kind, p.check_block(_run_tattn_block(p), f"tattn_block row bias {_fused_case(B, HW, F)}"))
+
+
+def test_tattn_block_more_panels_than_cus():
+    """515 panels, the last one ragged: the grid-stride panel loop, its token-row prefetch and the weight chunks issued across panel
+    borders"""
+    B, HW, F = ap.TBLOCK_MANY
+    assert (B * HW + 7) // 8 > torch.cuda.get_device_properties(0).multi_processor_count and (B * HW) % 8
+    for kind in ("uniform", "identity"):
+        p = ap.fused_probe(kind, B, HW, F)
+        _report("tattn_block", "panels>CUs", _fused_case(B, HW, F), kind, p.check_block(_run_tattn_block(p), f"tattn_block {_fused_case(B, HW, F)}"))
+
+
+@pytest.mark.parametrize("F", ap.FUSED_F)
+def test_tattn_front(F):
+    """lkgd_tattn_front (the A/B fallback and the sharded path) on the same inputs: its own padding mask, softmax and fp32 bias"""
+    from lkgd_amd import ops
+    from lkgd_amd.packing import pack_tfront
+    for B, HW in ap.TFRONT_BHW:
+        for kind in ap.fused_kinds(F):
+            p = ap.fused_probe(kind, B, HW, F)
+            ldx = 328 if (B, HW, F) == ap.TFRONT_LDX else None
+            ldo = 336 if (B, HW, F) == ap.TFRONT_LDO else None
+            x = _pitched(p.x, ldx)[0] if ldx else p.x.to(DEV)
+            out, buf = _pitched(torch.full((p.T, 320), NAN, dtype=torch.float16), ldo or 320, NAN)
+            ops.tattn_front(x, pack_tfront(p.wqkv.half().to(DEV), 5), p.bqkv.float().to(DEV), out, B, F, HW, 5)
+            assert torch.isnan(buf[:, 320:]).all(), "columns beyond the row were written"
+            _report("tattn_front", f"ldx={ldx or 320},ldo={ldo or 320}", _fused_case(B, HW, F), kind,
+                    p.check_front(out.cpu(), f"tattn_front {_fused_case(B, HW, F)}"))
+
+
+# ================================================================================================== attn_dense_relbias
+@pytest.mark.parametrize("nb,S,heads,hd", ap.RELBIAS_SHAPES)
+def test_attn_dense_relbias(nb, S, heads, hd):
+    """the RELBIAS instantiation: both plain probes under an all-zero table at scale 1.0 (T5's) and hd^-0.5; one-entry tables that
+    shift every row by d = 0, +-1, +-(S - 1), +-64 and a seeded offset (a different one per head); a table of ln(w), whose rows are
+    w-weighted means.  One key, one wave of keys +- 1, the T5 length, the LDS-heaviest legal shape"""
+    from lkgd_amd import ops
+    case = f"nb={nb},S={S},heads={heads},hd={hd}"
+    probes = [(f"zero,scale={scale}", ap.relbias_zero_probe(kind, nb, S, heads, hd, scale)) for scale in (1.0, None) for kind in ap.kinds(S)]
+    probes += [(f"d={list(o)}", ap.relbias_offset_probe(nb, S, heads, hd, o)) for o in ap.relbias_offsets(S, heads, hd)]
+    probes.append(("ln(w)", ap.relbias_weighted_probe(nb, S, heads, hd)))
+    for name, p in probes:
+        q, k, v = _dev(p)
+        out = torch.full((nb * S, heads * hd), NAN, dtype=torch.float16, device=DEV)
+        ops.attn_dense_relbias(q, k, v, out, nb, S, heads, hd, p.table.to(DEV), scale=p.scale)
+        _report("attn_dense_relbias", name, case, p.kind, p.check(out.cpu(), f"attn_dense_relbias {case} {name}"))

@@ -198,6 +198,17 @@ COGVAE_ENC_SYMBOLS = {
     "lkgd_cogvae_posterior": (_i32, [_vp, _i32, _vp, _vp, _vp, _f32, _i32, _i32, _i32, _i32, _i32, _vp]),
 }
 
+#: every symbol include/lkgd_hip_cogvae_tile.h declares (the seam operator of the tiled CogVideoX VAE: cross-fade with the upper / left
+#: neighbour tile and placement of the crop, on planes for the decode and on channels-last rows for the encode), bound on the same
+#: library object; tests/test_cogvideox_vae_tiling_cpu.py pins header, table and library to one another,
+#: tests/test_cogvideox_vae_tiling_gpu.py the footprint cases
+COGVAE_TILE_SYMBOLS = {
+    "lkgd_cogvae_tile_blend_planar": (_i32, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32,
+                                             _i32, _vp]),
+    "lkgd_cogvae_tile_blend_rows": (_i32, [_vp, _i32, _vp, _i32, _vp, _i32, _vp, _i32, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _i32,
+                                           _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
+}
+
 #: include/lkgd_hip_debug.h: A/B and test knobs, per host thread; bound on the same library object, not part of the product interface
 DEBUG_SYMBOLS = {
     "lkgd_debug_set_wide_tile_n": (None, [_i32]),
@@ -233,7 +244,7 @@ def lib() -> C.CDLL:
         except OSError as e:
             raise LkgdHipError(f"cannot load {LIB_PATH}: {e}") from e
         for table in (SYMBOLS, WINDOW_SYMBOLS, DIT_SYMBOLS, DIT_LOOP_SYMBOLS, DIT_TPATCH_SYMBOLS, DIT_DPM_SYMBOLS, FP8_SYMBOLS,
-                      T5_SYMBOLS, COGVAE_SYMBOLS, COGVAE_ENC_SYMBOLS, DEBUG_SYMBOLS):
+                      T5_SYMBOLS, COGVAE_SYMBOLS, COGVAE_ENC_SYMBOLS, COGVAE_TILE_SYMBOLS, DEBUG_SYMBOLS):
             for name, (res, args) in table.items():
                 fn = getattr(l, name)       # AttributeError here = header / library mismatch
                 fn.restype, fn.argtypes = res, args

@@ -32,9 +32,20 @@ inference/cli_vae_demo.py:63) runs frame batches of eight, the remainder in the 
 * ``CogVideoXDownsample3D``: ``lkgd_cogvae_time_pool`` (where ``compress_time``) in front of the stride-2 ``LKGD_A_CONV3X3`` with
   ``pad_off = 1`` (F.pad(0,1,0,1) + padding 0), one image per frame;
 * ``lkgd_cogvae_posterior`` turns ``conv_out``'s moment rows into the mean and the scaled sample, [B, 16, T, h, w].
+
+Tiling and slicing (every entry point of the reference calls ``vae.enable_slicing()`` and
+``vae.enable_tiling()``: inference/cli_demo.py:151-152, finetune/trainer.py:156-159).  With ``use_tiling`` an input larger than one tile
+(half the configured sample size: 240 x 360 pixels, 30 x 45 latents) is cut into overlapping tiles, every tile runs through the paths
+above ALONE - its own GroupNorm statistics, its own zero padding - and the seams are cross-faded, so a tiled result is another function
+of the input than an untiled one (``decode_tile_geometry`` / ``encode_tile_geometry`` hold diffusers' arithmetic).  Tiles run one at a
+time (``LKGD_COGVAE_TILE_BATCH=1``: tiles of equal shape as the entries of one batch - within the gate, but not the same bits, see
+``tile_batch``), and the seams and the placement of a tile are ONE launch per tile, ``lkgd_cogvae_tile_blend_planar`` on the decoded
+frames and ``lkgd_cogvae_tile_blend_rows`` on the encoder's moment rows (include/lkgd_hip_cogvae_tile.h).  With ``use_slicing`` a batch
+decodes entry by entry (``encode`` always does).
 """
 from __future__ import annotations
 
+import os
 from dataclasses import dataclass
 from types import SimpleNamespace
 from typing import List, Optional, Tuple
@@ -67,6 +78,93 @@ class CogVAEConfig:
     use_quant_conv: bool = False
     use_post_quant_conv: bool = False
     invert_scale_latents: bool = False
+    sample_height: int = 480                    # 768 / 1360 in the 1.5 checkpoints; half of each is the default tile
+    sample_width: int = 720
+
+
+@dataclass
+class TileGeometry:
+    """how one tiled pass cuts its input and assembles its output.  ``rows`` / ``cols``: (origin, size) of every tile row / column in
+    INPUT units (latents for the decode, pixels for the encode); ``step``: the distance of two origins, input units; ``extent``: the
+    rows / columns that are cross-faded with the neighbour, ``crop``: what a tile contributes, ``out_rows`` / ``out_cols``: (origin,
+    size) of every tile's crop in the output - all three in OUTPUT units (pixels for the decode, latents for the encode)"""
+    step: Tuple[int, int]
+    extent: Tuple[int, int]
+    crop: Tuple[int, int]
+    rows: List[Tuple[int, int]]
+    cols: List[Tuple[int, int]]
+    out_rows: List[Tuple[int, int]]
+    out_cols: List[Tuple[int, int]]
+
+
+def _tile_axis(n: int, size: int, step: int) -> List[Tuple[int, int]]:
+    return [(o, min(size, n - o)) for o in range(0, n, step)]
+
+
+def _crop_axis(tiles: List[int], crop: int, total: int, what: str) -> List[Tuple[int, int]]:
+    """(origin, size) of the tiles' crops laid side by side; they must add up to ``total`` (diffusers returns a tensor of another
+    size when they do not)"""
+    out, o = [], 0
+    for t in tiles:
+        out.append((o, min(crop, t)))
+        o += out[-1][1]
+    if o != total:
+        raise LkgdHipError(f"AutoencoderKLCogVideoX: the tiles do not add up - {what}: the cropped tiles cover {o}, the output has "
+                           f"{total}")
+    return out
+
+
+def decode_tile_geometry(h: int, w: int, S_h: int, S_w: int, L_h: int, L_w: int, f_h: float, f_w: float, up: int = 8) -> TileGeometry:
+    """``tiled_decode`` of diffusers over an h x w latent grid: tiles of L_h x L_w latents (the minimal latent tile) every
+    int(L * (1 - f)) latents, int(S * f) pixels cross-faded, S - int(S * f) pixels kept of every tile (S: the minimal sample tile,
+    f: the overlap factor).  The Python float expressions are diffusers'."""
+    step = (int(L_h * (1 - f_h)), int(L_w * (1 - f_w)))
+    extent = (int(S_h * f_h), int(S_w * f_w))
+    crop = (S_h - extent[0], S_w - extent[1])
+    what = (f"tile_sample_min {S_h} x {S_w}, tile_latent_min {L_h} x {L_w}, overlap factors {f_h:.4g} / {f_w:.4g} "
+            f"(step {step[0]} / {step[1]} latents, crop {crop[0]} / {crop[1]} pixels) over {h} x {w} latents")
+    if min(step) <= 0 or min(crop) <= 0:
+        raise LkgdHipError(f"AutoencoderKLCogVideoX: the tiles do not add up - {what}")
+    rows, cols = _tile_axis(h, L_h, step[0]), _tile_axis(w, L_w, step[1])
+    return TileGeometry(step, extent, crop, rows, cols, _crop_axis([up * s for _, s in rows], crop[0], up * h, what + ", height"),
+                        _crop_axis([up * s for _, s in cols], crop[1], up * w, what + ", width"))
+
+
+def encode_tile_geometry(H: int, W: int, S_h: int, S_w: int, L_h: int, L_w: int, f_h: float, f_w: float, down: int = 8) -> TileGeometry:
+    """``tiled_encode`` of diffusers over H x W pixels: tiles of S_h x S_w pixels every int(S * (1 - f)) pixels, int(L * f) latents
+    cross-faded, L - int(L * f) latents kept of every tile"""
+    step = (int(S_h * (1 - f_h)), int(S_w * (1 - f_w)))
+    extent = (int(L_h * f_h), int(L_w * f_w))
+    crop = (L_h - extent[0], L_w - extent[1])
+    what = (f"tile_sample_min {S_h} x {S_w}, tile_latent_min {L_h} x {L_w}, overlap factors {f_h:.4g} / {f_w:.4g} "
+            f"(step {step[0]} / {step[1]} pixels, crop {crop[0]} / {crop[1]} latents) over {H} x {W} pixels")
+    if min(step) <= 0 or min(crop) <= 0:
+        raise LkgdHipError(f"AutoencoderKLCogVideoX: the tiles do not add up - {what}")
+    rows, cols = _tile_axis(H, S_h, step[0]), _tile_axis(W, S_w, step[1])
+    for _, s in rows + cols:
+        if s % down:
+            raise LkgdHipError(f"AutoencoderKLCogVideoX: the tiles do not add up - {what}: a tile of {s} pixels is no multiple of {down}")
+    return TileGeometry(step, extent, crop, rows, cols, _crop_axis([s // down for _, s in rows], crop[0], H // down, what + ", height"),
+                        _crop_axis([s // down for _, s in cols], crop[1], W // down, what + ", width"))
+
+
+def _tile_groups(g: TileGeometry, batch: bool) -> List[List[Tuple[int, int]]]:
+    """the tiles (i, j) in the runs they are computed in: tiles of equal shape together (480 x 720: 4 + 2 + 2 + 1), or one by one"""
+    by_shape = {}
+    for i, (_, sy) in enumerate(g.rows):
+        for j, (_, sx) in enumerate(g.cols):
+            by_shape.setdefault((sy, sx), []).append((i, j))
+    runs = list(by_shape.values())
+    return runs if batch else [[ij] for run in runs for ij in run]
+
+
+def tile_batch() -> bool:
+    """``LKGD_COGVAE_TILE_BATCH=1``: tiles of equal shape run as the entries of one batch; the default (``0``) is one tile at a time.
+    A/B switch, read at every call.  The default is the form whose every tile is bit for bit what the untiled path gives for that
+    tile alone: the GEMM planner picks its program by the row count, so an entry of a batch is NOT bit-identical to a single run
+    (measured on the tiny decode: about a third of the elements differ in the last bits; both forms are 6e-4 - 1.2e-3 from the
+    oracle), and profiles/cogvideox_vae_tiling_bench.json records what batching would buy."""
+    return os.environ.get("LKGD_COGVAE_TILE_BATCH", "0") == "1"
 
 
 def chunk_bounds(T: int) -> List[Tuple[int, int]]:
@@ -473,6 +571,19 @@ class AutoencoderKLCogVideoX(nn.Module):
             _check_encoder_config(cfg)
             self.encoder = CogVideoXEncoder3D(cfg)
         self._packed = False
+        # diffusers' tiling / slicing state: off until enable_*; a tile is half the configured sample size
+        self.use_tiling = False
+        self.use_slicing = False
+        self.tile_sample_min_height = cfg.sample_height // 2
+        self.tile_sample_min_width = cfg.sample_width // 2
+        self.tile_overlap_factor_height = 1 / 6
+        self.tile_overlap_factor_width = 1 / 5
+        self._set_tile_latent_min()
+
+    def _set_tile_latent_min(self):
+        down = 2 ** (len(self.config.block_out_channels) - 1)
+        self.tile_latent_min_height = int(self.tile_sample_min_height / down)
+        self.tile_latent_min_width = int(self.tile_sample_min_width / down)
 
     @property
     def has_encoder(self) -> bool:
@@ -526,13 +637,41 @@ class AutoencoderKLCogVideoX(nn.Module):
         self._packed = False
         return r
 
-    def enable_tiling(self, *a, **k):
-        raise LkgdHipError("AutoencoderKLCogVideoX.enable_tiling is not built: a whole chunk decodes (a whole frame batch encodes) "
-                           "at once")
+    def _require_gpu(self, what: str):
+        if self.device.type != "cuda":
+            raise LkgdHipError(f"AutoencoderKLCogVideoX.{what}: this module is not on the GPU - move it to cuda first, then call "
+                               f"{what} (the reference's order: pipe.to('cuda'), then vae.{what}())")
 
-    def enable_slicing(self, *a, **k):
-        raise LkgdHipError("AutoencoderKLCogVideoX.enable_slicing is not built: the batch decodes at once (encode runs its batch "
-                           "entries one after the other as it is)")
+    def enable_tiling(self, tile_sample_min_height: Optional[int] = None, tile_sample_min_width: Optional[int] = None,
+                      tile_overlap_factor_height: Optional[float] = None, tile_overlap_factor_width: Optional[float] = None) -> None:
+        """diffusers' ``enable_tiling``: ``decode`` / ``encode`` of an input larger than one tile run tile by tile with cross-faded
+        seams.  Given values replace the current ones (the defaults: half the configured sample size, overlap 1/6 and 1/5); the
+        latent minima follow.  Refuses a module that is not on the GPU, as ``decode`` and ``encode`` do: move the module first - the
+        reference's order, ``pipe.to("cuda")`` and then ``pipe.vae.enable_tiling()``, works."""
+        self._require_gpu("enable_tiling")
+        self.use_tiling = True
+        self.tile_sample_min_height = tile_sample_min_height or self.tile_sample_min_height
+        self.tile_sample_min_width = tile_sample_min_width or self.tile_sample_min_width
+        self.tile_overlap_factor_height = tile_overlap_factor_height or self.tile_overlap_factor_height
+        self.tile_overlap_factor_width = tile_overlap_factor_width or self.tile_overlap_factor_width
+        self._set_tile_latent_min()
+
+    def disable_tiling(self) -> None:
+        self.use_tiling = False
+
+    def enable_slicing(self) -> None:
+        """diffusers' ``enable_slicing``: a batch decodes entry by entry (same bits, a lower peak); ``encode`` runs its entries one
+        after the other whatever the switch.  Refuses a module that is not on the GPU: move the module first, as for
+        ``enable_tiling``."""
+        self._require_gpu("enable_slicing")
+        self.use_slicing = True
+
+    def disable_slicing(self) -> None:
+        self.use_slicing = False
+
+    def _tiling_args(self):
+        return (self.tile_sample_min_height, self.tile_sample_min_width, self.tile_latent_min_height, self.tile_latent_min_width,
+                self.tile_overlap_factor_height, self.tile_overlap_factor_width, 2 ** (len(self.config.block_out_channels) - 1))
 
     # ---- packing -----------------------------------------------------------------------------------------------
     @torch.no_grad()
@@ -584,12 +723,43 @@ class AutoencoderKLCogVideoX(nn.Module):
         mom[:, t_out:t_out + c.T] = m.view(B, c.T, c.H * c.W, m.shape[1])
         return c.T
 
+    def _encode_clip(self, xc: torch.Tensor, mom: torch.Tensor, bounds, convs) -> None:
+        """the contiguous clip ``xc`` [n, Cin, T, H, W] through its frame batches, the conv caches carried from batch to batch and
+        cleared in front; the moment rows go to ``mom`` [n, T', h*w, 2 lc]"""
+        for m in convs:
+            m._cache = None
+        t_out = 0
+        for a, b in bounds:
+            t_out += self._encode_batch(xc, a, b, mom, t_out)
+
+    def _tiled_encode(self, x1: torch.Tensor, out: torch.Tensor, g: TileGeometry, bounds, convs) -> None:
+        """``tiled_encode`` of diffusers for one batch entry ``x1`` [1, Cin, T, H, W]: every pixel tile through ``_encode_clip``
+        (one at a time, or under ``tile_batch()`` tiles of equal shape as one batch), then in row-major order one
+        ``lkgd_cogvae_tile_blend_rows`` per tile -
+        the cross-fade of its moment rows with its upper and left neighbours' blended rows, and its crop into ``out`` [T', h, w, 2 lc]"""
+        down = 2 ** (len(self.config.block_out_channels) - 1)
+        Tl, C2 = out.shape[0], out.shape[3]
+        tiles = {}
+        for run in _tile_groups(g, tile_batch()):
+            sy, sx = g.rows[run[0][0]][1], g.cols[run[0][1]][1]
+            xt = torch.cat([x1[:, :, :, g.rows[i][0]:g.rows[i][0] + sy, g.cols[j][0]:g.cols[j][0] + sx] for i, j in run]).contiguous()
+            mt = torch.empty(len(run), Tl, (sy // down) * (sx // down), C2, dtype=torch.float16, device=x1.device)
+            self._encode_clip(xt, mt, bounds, convs)
+            for k, ij in enumerate(run):
+                tiles[ij] = mt[k].view(Tl, sy // down, sx // down, C2)
+        for i, (y0, _) in enumerate(g.out_rows):
+            for j, (x0, _) in enumerate(g.out_cols):
+                ops.cogvae_tile_blend_rows(tiles[i, j], tiles.get((i - 1, j)), tiles.get((i, j - 1)), out, y0, x0, g.extent[0],
+                                           g.extent[1], g.crop[0], g.crop[1])
+
     @torch.no_grad()
     def encode(self, x: torch.Tensor, return_dict: bool = True):
         """[B, 3, T, H, W] in [-1, 1] -> an output with ``.latent_dist`` (also its item 0): the posterior over [B, 16, T', H/8, W/8],
         T' = 1 + (T - 1)/4 for T = 4k + 1.  Frame batches of eight with the remainder in the first (49 -> 9|8|8|8|8|8), the conv caches
         carried from batch to batch; GroupNorm statistics span one batch's frames.  The batch entries are encoded one after the
-        other (the I2V pipeline encodes one image at a time): an entry's result does not depend on its neighbours."""
+        other (the I2V pipeline encodes one image at a time): an entry's result does not depend on its neighbours - which is all
+        ``use_slicing`` asks for.  With ``use_tiling`` a clip larger than ``tile_sample_min_height`` x ``tile_sample_min_width`` pixels
+        encodes tile by tile (``_tiled_encode``): the posterior is built from the blended moment rows."""
         if not self.has_encoder:
             raise LkgdHipError("AutoencoderKLCogVideoX.encode: this module was built without its encoder - construct it with "
                                "encoder=True (from_pretrained builds it when the checkpoint holds encoder.* keys, or with encoder=True)")
@@ -615,14 +785,15 @@ class AutoencoderKLCogVideoX(nn.Module):
 
         Tl, h, w = sum(frames_of(b - a) for a, b in bounds), H // down, W // down
         mom = torch.empty(B, Tl, h * w, 2 * lc, dtype=torch.float16, device=dev)
+        tiled = self.use_tiling and (W > self.tile_sample_min_width or H > self.tile_sample_min_height)
+        geo = encode_tile_geometry(H, W, *self._tiling_args()) if tiled else None
         convs = self._convs()
         try:
             for i in range(B):
-                for m in convs:
-                    m._cache = None
-                t_out = 0
-                for a, b in bounds:
-                    t_out += self._encode_batch(xh[i:i + 1], a, b, mom[i:i + 1], t_out)
+                if tiled:
+                    self._tiled_encode(xh[i:i + 1], mom[i].view(Tl, h, w, 2 * lc), geo, bounds, convs)
+                else:
+                    self._encode_clip(xh[i:i + 1], mom[i:i + 1], bounds, convs)
         finally:
             for m in convs:
                 m._cache = None
@@ -661,14 +832,35 @@ class AutoencoderKLCogVideoX(nn.Module):
     @torch.no_grad()
     def decode(self, z: torch.Tensor, return_dict: bool = True):
         """[B, 16, T, h, w] -> sample [B, 3, T', 8h, 8w] in z's dtype (T' = 1 + 4 (T - 1) for odd T, 4 T for even T): chunks of two
-        latent frames, the conv caches carried from chunk to chunk"""
+        latent frames, the conv caches carried from chunk to chunk.  With ``use_tiling`` a grid larger than ``tile_latent_min_height`` x
+        ``tile_latent_min_width`` decodes tile by tile (``_tiled_decode``); with ``use_slicing`` a batch decodes entry by entry.  With
+        both off the launches are what they were before the switches existed."""
         self.prepare()
         lc = self.config.latent_channels
         if z.dim() != 5 or z.shape[1] != lc:
             raise ValueError(f"expected [B, {lc}, T, h, w]")
-        B, _, T, h, w = z.shape
-        dev = self.device
-        zh = z.to(device=dev, dtype=torch.float16).permute(0, 2, 3, 4, 1).contiguous()           # [B, T, h, w, 16]
+        B = z.shape[0]
+        zh = z.to(device=self.device, dtype=torch.float16).permute(0, 2, 3, 4, 1).contiguous()   # [B, T, h, w, 16]
+        out_dtype = z.dtype if z.dtype in (torch.float16, torch.float32) else torch.float32
+        if self.use_slicing and B > 1:
+            out = torch.cat([self._decode_f16(zh[i:i + 1]) for i in range(B)])
+        else:
+            out = self._decode_f16(zh)
+        out = out.to(out_dtype)
+        if not return_dict:
+            return (out,)
+        return DecoderOutput(sample=out)
+
+    def _decode_f16(self, zh: torch.Tensor) -> torch.Tensor:
+        """``zh`` [B, T, h, w, 16] fp16 -> frames [B, 3, T', 8h, 8w] fp16: tile by tile iff tiling is on and the grid exceeds one tile"""
+        if self.use_tiling and (zh.shape[3] > self.tile_latent_min_width or zh.shape[2] > self.tile_latent_min_height):
+            return self._tiled_decode(zh)
+        return self._decode_whole(zh)
+
+    def _decode_whole(self, zh: torch.Tensor) -> torch.Tensor:
+        """the chunk loop over the whole latent grid of ``zh`` [B, T, h, w, 16]"""
+        B, T, h, w, _ = zh.shape
+        dev = zh.device
         bounds = chunk_bounds(T)
         nt = self.config.temporal_compression_ratio.bit_length() - 1
         up = 2 ** (len(self.config.block_out_channels) - 1)
@@ -679,7 +871,6 @@ class AutoencoderKLCogVideoX(nn.Module):
             return n
 
         Tout = sum(frames_of(b - a) for a, b in bounds)
-        out_dtype = z.dtype if z.dtype in (torch.float16, torch.float32) else torch.float32
         out = torch.empty(B, self.config.out_channels, Tout, up * h, up * w, dtype=torch.float16, device=dev)
         convs = self._convs()
         for m in convs:
@@ -691,10 +882,30 @@ class AutoencoderKLCogVideoX(nn.Module):
         finally:
             for m in convs:
                 m._cache = None
-        out = out.to(out_dtype)
-        if not return_dict:
-            return (out,)
-        return DecoderOutput(sample=out)
+        return out
+
+    def _tiled_decode(self, zh: torch.Tensor) -> torch.Tensor:
+        """``tiled_decode`` of diffusers: every latent tile through ``_decode_whole`` (its chunks, the conv caches cleared between
+        tiles; one at a time, or under ``tile_batch()`` tiles of equal shape as one batch), then in row-major order one
+        ``lkgd_cogvae_tile_blend_planar`` per
+        tile - the cross-fade with its upper and left neighbours' blended tiles, and its crop into the frames"""
+        B, T, h, w, _ = zh.shape
+        g = decode_tile_geometry(h, w, *self._tiling_args())
+        up = self._tiling_args()[-1]
+        tiles = {}
+        for run in _tile_groups(g, tile_batch()):
+            sy, sx = g.rows[run[0][0]][1], g.cols[run[0][1]][1]
+            zt = torch.cat([zh[:, :, g.rows[i][0]:g.rows[i][0] + sy, g.cols[j][0]:g.cols[j][0] + sx] for i, j in run]).contiguous()
+            o = self._decode_whole(zt)                                    # [len(run) * B, 3, T', 8 sy, 8 sx]
+            for k, ij in enumerate(run):
+                tiles[ij] = o[k * B:(k + 1) * B]
+        t00 = tiles[0, 0]
+        out = torch.empty(B, t00.shape[1], t00.shape[2], up * h, up * w, dtype=torch.float16, device=zh.device)
+        for i, (y0, _) in enumerate(g.out_rows):
+            for j, (x0, _) in enumerate(g.out_cols):
+                ops.cogvae_tile_blend_planar(tiles[i, j], tiles.get((i - 1, j)), tiles.get((i, j - 1)), out, y0, x0, g.extent[0],
+                                             g.extent[1], g.crop[0], g.crop[1])
+        return out
 
     def forward(self, z):
         return self.decode(z)

@@ -1224,3 +1224,73 @@ def cogvae_posterior(mom: torch.Tensor, B: int, lc: int, T: int, h: int, w: int,
     check(_L().lkgd_cogvae_posterior(mom.data_ptr(), _ld(mom), _ptr(noise), mean.data_ptr(), _ptr(sample), float(scale), B, lc, T, h, w,
                                      _stream()), "lkgd_cogvae_posterior")
     return mean, sample
+
+
+# ---- the seam operator of the tiled CogVideoX VAE (include/lkgd_hip_cogvae_tile.h) ------------------------------------------------------
+def _planes(t: torch.Tensor, name: str) -> Tuple[int, int, int]:
+    """(P, Y, X) of a contiguous fp16 [..., Y, X] tensor of planes"""
+    _req(t, torch.float16, name)
+    if t.dim() < 3 or not t.is_contiguous():
+        raise _lib.LkgdHipError(f"{name} must be contiguous [..., Y, X] planes, got {tuple(t.shape)} strides {tuple(t.stride())}")
+    return t.numel() // (t.shape[-2] * t.shape[-1]), t.shape[-2], t.shape[-1]
+
+
+def cogvae_tile_blend_planar(tile: torch.Tensor, up: Optional[torch.Tensor], left: Optional[torch.Tensor], out: torch.Tensor,
+                             y0: int, x0: int, e_y: int, e_x: int, c_y: int, c_x: int) -> torch.Tensor:
+    """one tile of a tiled decode (lkgd_cogvae_tile_blend_planar): ``tile`` fp16 [..., Yt, Xt] is cross-faded IN PLACE over its first
+    ``e_y`` rows with the last rows of ``up`` [..., Yu, Xt] and then over its first ``e_x`` columns with the last columns of ``left``
+    [..., Yt, Xl] (the neighbours' blended tiles, or None), and its first ``c_y`` x ``c_x`` elements go to ``out`` [..., Y, X] at
+    (y0, x0); returns ``tile``"""
+    P, Yt, Xt = _planes(tile, "tile")
+    Po, Y, X = _planes(out, "out")
+    Yu = Xl = 0
+    if up is not None:
+        Pu, Yu, Xu = _planes(up, "up")
+        if (Pu, Xu) != (P, Xt):
+            raise _lib.LkgdHipError(f"up must hold {P} planes {Xt} wide, got {tuple(up.shape)}")
+    if left is not None:
+        Pl, Yl, Xl = _planes(left, "left")
+        if (Pl, Yl) != (P, Yt):
+            raise _lib.LkgdHipError(f"left must hold {P} planes {Yt} high, got {tuple(left.shape)}")
+    if Po != P:
+        raise _lib.LkgdHipError(f"out must hold {P} planes, got {tuple(out.shape)}")
+    check(_L().lkgd_cogvae_tile_blend_planar(tile.data_ptr(), _ptr(up), _ptr(left), out.data_ptr(), P, Yt, Xt, Yu, Xl, Y, X, int(y0),
+                                             int(x0), int(e_y), int(e_x), int(c_y), int(c_x), _stream()),
+          "lkgd_cogvae_tile_blend_planar")
+    return tile
+
+
+def _image_rows(t: torch.Tensor, name: str) -> Tuple[int, int, int, int, int]:
+    """(P, Y, X, C, row stride) of fp16 channels-last images [P, Y, X, C] whose rows (p, y, x) lie one row stride apart"""
+    _req(t, torch.float16, name)
+    if t.dim() != 4:
+        raise _lib.LkgdHipError(f"{name} must be [P, Y, X, C] rows, got {tuple(t.shape)}")
+    P, Y, X, C_ = t.shape
+    ld = t.stride(2)
+    if t.stride(3) != 1 or (Y > 1 and t.stride(1) != X * ld) or (P > 1 and t.stride(0) != Y * X * ld):
+        raise _lib.LkgdHipError(f"{name}: the rows (p, y, x) of {tuple(t.shape)} must lie one row stride apart, got strides "
+                                f"{tuple(t.stride())}")
+    return P, Y, X, C_, ld
+
+
+def cogvae_tile_blend_rows(tile: torch.Tensor, up: Optional[torch.Tensor], left: Optional[torch.Tensor], out: torch.Tensor,
+                           y0: int, x0: int, e_y: int, e_x: int, c_y: int, c_x: int) -> torch.Tensor:
+    """one tile of a tiled encode (lkgd_cogvae_tile_blend_rows): as ``cogvae_tile_blend_planar`` on channels-last token rows -
+    ``tile`` [P, Yt, Xt, C], ``up`` [P, Yu, Xt, C], ``left`` [P, Yt, Xl, C], ``out`` [P, Y, X, C], each with its own row stride"""
+    P, Yt, Xt, C_, ldt = _image_rows(tile, "tile")
+    Po, Y, X, Co, ldo = _image_rows(out, "out")
+    Yu = Xl = ldu = ldl = 0
+    if up is not None:
+        Pu, Yu, Xu, Cu, ldu = _image_rows(up, "up")
+        if (Pu, Xu, Cu) != (P, Xt, C_):
+            raise _lib.LkgdHipError(f"up must be [{P}, Yu, {Xt}, {C_}], got {tuple(up.shape)}")
+    if left is not None:
+        Pl, Yl, Xl, Cl, ldl = _image_rows(left, "left")
+        if (Pl, Yl, Cl) != (P, Yt, C_):
+            raise _lib.LkgdHipError(f"left must be [{P}, {Yt}, Xl, {C_}], got {tuple(left.shape)}")
+    if (Po, Co) != (P, C_):
+        raise _lib.LkgdHipError(f"out must be [{P}, Y, X, {C_}], got {tuple(out.shape)}")
+    check(_L().lkgd_cogvae_tile_blend_rows(tile.data_ptr(), ldt, _ptr(up), ldu, _ptr(left), ldl, out.data_ptr(), ldo, P, C_, Yt, Xt, Yu,
+                                           Xl, Y, X, int(y0), int(x0), int(e_y), int(e_x), int(c_y), int(c_x), _stream()),
+          "lkgd_cogvae_tile_blend_rows")
+    return tile

@@ -82,6 +82,16 @@ class CogVAEConfig:
     sample_width: int = 720
 
 
+def _spatial_factor(cfg) -> int:
+    """pixels per latent in height and width: every block but the last halves (the encoder) or doubles (the decoder) them"""
+    return 2 ** (len(cfg.block_out_channels) - 1)
+
+
+def _time_levels(cfg) -> int:
+    """how many blocks, counted from the encoder's first / the decoder's first, also halve / double the frames"""
+    return cfg.temporal_compression_ratio.bit_length() - 1
+
+
 @dataclass
 class TileGeometry:
     """how one tiled pass cuts its input and assembles its output.  ``rows`` / ``cols``: (origin, size) of every tile row / column in
@@ -114,38 +124,43 @@ def _crop_axis(tiles: List[int], crop: int, total: int, what: str) -> List[Tuple
     return out
 
 
-def decode_tile_geometry(h: int, w: int, S_h: int, S_w: int, L_h: int, L_w: int, f_h: float, f_w: float, up: int = 8) -> TileGeometry:
-    """``tiled_decode`` of diffusers over an h x w latent grid: tiles of L_h x L_w latents (the minimal latent tile) every
-    int(L * (1 - f)) latents, int(S * f) pixels cross-faded, S - int(S * f) pixels kept of every tile (S: the minimal sample tile,
-    f: the overlap factor).  The Python float expressions are diffusers'."""
-    step = (int(L_h * (1 - f_h)), int(L_w * (1 - f_w)))
-    extent = (int(S_h * f_h), int(S_w * f_w))
-    crop = (S_h - extent[0], S_w - extent[1])
-    what = (f"tile_sample_min {S_h} x {S_w}, tile_latent_min {L_h} x {L_w}, overlap factors {f_h:.4g} / {f_w:.4g} "
-            f"(step {step[0]} / {step[1]} latents, crop {crop[0]} / {crop[1]} pixels) over {h} x {w} latents")
+def _tile_geometry(n_h: int, n_w: int, in_tile, out_tile, f, to_out, unit: int, what: str) -> TileGeometry:
+    """diffusers' tile arithmetic over an n_h x n_w input: tiles of ``in_tile`` (h, w) input units every int(in_tile * (1 - f)),
+    int(out_tile * f) output units cross-faded, out_tile - int(out_tile * f) kept of every tile (f: the overlap factors).  The
+    Python float expressions are diffusers'.  ``to_out``: input units -> output units; a tile must be a multiple of ``unit`` input
+    units; ``what`` names the setting in a refusal, with {} for the two steps and the two crops."""
+    step = (int(in_tile[0] * (1 - f[0])), int(in_tile[1] * (1 - f[1])))
+    extent = (int(out_tile[0] * f[0]), int(out_tile[1] * f[1]))
+    crop = (out_tile[0] - extent[0], out_tile[1] - extent[1])
+    what = what.format(*step, *crop)
     if min(step) <= 0 or min(crop) <= 0:
         raise LkgdHipError(f"AutoencoderKLCogVideoX: the tiles do not add up - {what}")
-    rows, cols = _tile_axis(h, L_h, step[0]), _tile_axis(w, L_w, step[1])
-    return TileGeometry(step, extent, crop, rows, cols, _crop_axis([up * s for _, s in rows], crop[0], up * h, what + ", height"),
-                        _crop_axis([up * s for _, s in cols], crop[1], up * w, what + ", width"))
+    rows, cols = _tile_axis(n_h, in_tile[0], step[0]), _tile_axis(n_w, in_tile[1], step[1])
+    for _, s in rows + cols:
+        if s % unit:
+            raise LkgdHipError(f"AutoencoderKLCogVideoX: the tiles do not add up - {what}: a tile of {s} pixels is no multiple of {unit}")
+    return TileGeometry(step, extent, crop, rows, cols,
+                        _crop_axis([to_out(s) for _, s in rows], crop[0], to_out(n_h), what + ", height"),
+                        _crop_axis([to_out(s) for _, s in cols], crop[1], to_out(n_w), what + ", width"))
+
+
+#: a tiling setting as a refusal names it: sample tile, latent tile, overlap factors, (input units, output units), input size and unit
+_TILING = ("tile_sample_min {} x {}, tile_latent_min {} x {}, overlap factors {:.4g} / {:.4g} (step {{}} / {{}} {}, crop {{}} / {{}} {}) "
+           "over {} x {} {}")
+
+
+def decode_tile_geometry(h: int, w: int, S_h: int, S_w: int, L_h: int, L_w: int, f_h: float, f_w: float, up: int = 8) -> TileGeometry:
+    """``tiled_decode`` of diffusers over an h x w latent grid: tiles of L_h x L_w latents (the minimal latent tile), pixels
+    cross-faded and kept (S: the minimal sample tile)"""
+    return _tile_geometry(h, w, (L_h, L_w), (S_h, S_w), (f_h, f_w), lambda s: up * s, 1,
+                          _TILING.format(S_h, S_w, L_h, L_w, f_h, f_w, "latents", "pixels", h, w, "latents"))
 
 
 def encode_tile_geometry(H: int, W: int, S_h: int, S_w: int, L_h: int, L_w: int, f_h: float, f_w: float, down: int = 8) -> TileGeometry:
-    """``tiled_encode`` of diffusers over H x W pixels: tiles of S_h x S_w pixels every int(S * (1 - f)) pixels, int(L * f) latents
-    cross-faded, L - int(L * f) latents kept of every tile"""
-    step = (int(S_h * (1 - f_h)), int(S_w * (1 - f_w)))
-    extent = (int(L_h * f_h), int(L_w * f_w))
-    crop = (L_h - extent[0], L_w - extent[1])
-    what = (f"tile_sample_min {S_h} x {S_w}, tile_latent_min {L_h} x {L_w}, overlap factors {f_h:.4g} / {f_w:.4g} "
-            f"(step {step[0]} / {step[1]} pixels, crop {crop[0]} / {crop[1]} latents) over {H} x {W} pixels")
-    if min(step) <= 0 or min(crop) <= 0:
-        raise LkgdHipError(f"AutoencoderKLCogVideoX: the tiles do not add up - {what}")
-    rows, cols = _tile_axis(H, S_h, step[0]), _tile_axis(W, S_w, step[1])
-    for _, s in rows + cols:
-        if s % down:
-            raise LkgdHipError(f"AutoencoderKLCogVideoX: the tiles do not add up - {what}: a tile of {s} pixels is no multiple of {down}")
-    return TileGeometry(step, extent, crop, rows, cols, _crop_axis([s // down for _, s in rows], crop[0], H // down, what + ", height"),
-                        _crop_axis([s // down for _, s in cols], crop[1], W // down, what + ", width"))
+    """``tiled_encode`` of diffusers over H x W pixels: tiles of S_h x S_w pixels, each a multiple of ``down`` pixels, latents
+    cross-faded and kept"""
+    return _tile_geometry(H, W, (S_h, S_w), (L_h, L_w), (f_h, f_w), lambda s: s // down, down,
+                          _TILING.format(S_h, S_w, L_h, L_w, f_h, f_w, "pixels", "latents", H, W, "pixels"))
 
 
 def _tile_groups(g: TileGeometry, batch: bool) -> List[List[Tuple[int, int]]]:
@@ -167,10 +182,51 @@ def tile_batch() -> bool:
     return os.environ.get("LKGD_COGVAE_TILE_BATCH", "0") == "1"
 
 
+def _group_bounds(T: int, size: int) -> List[Tuple[int, int]]:
+    """the frame ranges a clip runs in, one after the other: groups of ``size``, the remainder in the FIRST; fewer than ``size``
+    frames are one group"""
+    n, rem = max(T // size, 1), T % size
+    return [(size * i + (0 if i == 0 else rem), min(size * (i + 1) + rem, T)) for i in range(n)]
+
+
 def chunk_bounds(T: int) -> List[Tuple[int, int]]:
-    """the latent-frame ranges ``decode`` runs one after the other: chunks of two, the remainder in the first (13 -> 3|2|2|2|2|2)"""
-    n, rem = max(T // 2, 1), T % 2
-    return [(2 * i + (0 if i == 0 else rem), min(2 * (i + 1) + rem, T)) for i in range(n)]
+    """the latent-frame ranges ``decode`` runs one after the other: chunks of two (13 -> 3|2|2|2|2|2)"""
+    return _group_bounds(T, 2)
+
+
+def frame_batch_bounds(T: int) -> List[Tuple[int, int]]:
+    """the frame ranges ``encode`` runs one after the other: batches of eight (49 -> 9|8|8|8|8|8; AutoencoderKLCogVideoX._encode)"""
+    return _group_bounds(T, ENCODE_FRAME_BATCH)
+
+
+def _run_clip(step, clip: torch.Tensor, bounds, out: torch.Tensor) -> None:
+    """one clip through its frame groups: ``step(clip, a, b, out, t_out, caches)`` runs frames [a, b), writes its output frames
+    into ``out`` from ``t_out`` on and returns their count.  ``caches`` - {causal convolution: the last two frames of its previous
+    group's buffer} - belongs to this clip alone and is gone when the loop returns or raises: a tile, a batch entry and a slice
+    each start without context."""
+    caches, t_out = {}, 0
+    for a, b in bounds:
+        t_out += step(clip, a, b, out, t_out, caches)
+
+
+def _run_tiles(g: TileGeometry, cut, run, blend, new_out) -> torch.Tensor:
+    """one tiled pass.  The tiles are computed in the runs of ``_tile_groups`` (one at a time, or under ``tile_batch()`` tiles of
+    equal shape as one batch): ``cut(ys, xs)`` is that window of the input, ``run`` turns the concatenated windows into their
+    results, first dimension the tile.  Then in row-major order ONE ``blend`` launch per tile: the cross-fade with its upper and
+    left neighbours' blended tiles, and its crop into the output.  ``new_out()`` is asked for the output only then - the decoded
+    frames do not exist while the tiles run."""
+    tiles = {}
+    for grp in _tile_groups(g, tile_batch()):
+        sy, sx = g.rows[grp[0][0]][1], g.cols[grp[0][1]][1]
+        res = run(torch.cat([cut(slice(g.rows[i][0], g.rows[i][0] + sy), slice(g.cols[j][0], g.cols[j][0] + sx))
+                             for i, j in grp]).contiguous())
+        for k, ij in enumerate(grp):
+            tiles[ij] = res[k]
+    out = new_out()
+    for i, (y0, _) in enumerate(g.out_rows):
+        for j, (x0, _) in enumerate(g.out_cols):
+            blend(tiles[i, j], tiles.get((i - 1, j)), tiles.get((i, j - 1)), out, y0, x0, g.extent[0], g.extent[1], g.crop[0], g.crop[1])
+    return out
 
 
 def spatial_norm_tmap(Tz: int, T: int) -> List[int]:
@@ -193,19 +249,12 @@ def upsample_frame_map(T: int, compress_time: bool) -> List[int]:
     return [i // 2 for i in range(2 * T)]
 
 
-def frame_batch_bounds(T: int) -> List[Tuple[int, int]]:
-    """the frame ranges ``encode`` runs one after the other: batches of eight, the remainder in the FIRST (49 -> 9|8|8|8|8|8); fewer
-    than eight frames are one batch (AutoencoderKLCogVideoX._encode)"""
-    fb = ENCODE_FRAME_BATCH
-    n, rem = max(T // fb, 1), T % fb
-    return [(fb * i + (0 if i == 0 else rem), min(fb * (i + 1) + rem, T)) for i in range(n)]
-
-
 class _Chunk:
-    """what the blocks of one chunk share: geometry, the padded latent rows and the per-(Tz, T) frame tables"""
+    """what the blocks of one chunk share: geometry, the padded latent rows, the per-(Tz, T) frame tables and the clip's conv
+    caches (``_run_clip``)"""
 
-    def __init__(self, B, Tz, h, w, zq64):
-        self.B, self.Tz, self.h, self.w, self.zq64 = B, Tz, h, w, zq64
+    def __init__(self, B, Tz, h, w, zq64, caches):
+        self.B, self.Tz, self.h, self.w, self.zq64, self.caches = B, Tz, h, w, zq64, caches
         self.T, self.H, self.W, self.sh = Tz, h, w, 0
         self._tmaps = {}
 
@@ -229,7 +278,6 @@ class CogVideoXCausalConv3d(nn.Module):
         super().__init__()
         self.cin, self.cout, self.k = cin, cout, k
         self.conv = nn.Conv3d(cin, cout, k, padding=(0, k // 2, k // 2))
-        self._cache = None
 
     def pack(self, pad_cin: int = 0, pad_cout: int = 0):
         w, b = self.conv.weight.detach().float(), self.conv.bias.detach().float()
@@ -241,14 +289,14 @@ class CogVideoXCausalConv3d(nn.Module):
         self._w, self._b = pack_cconv3(w), b.contiguous()
 
     def run(self, P: torch.Tensor, c: _Chunk, res1=None, colstats: int = 0):
-        """``P`` = [B, T + 2, H*W, Cin] with the chunk's frames in place behind two free frames: puts the context there, keeps the
-        buffer's last two frames as the next chunk's context, convolves"""
-        if self._cache is None:
+        """``P`` = [B, T + 2, H*W, Cin] with the chunk's frames in place behind two free frames: puts the context there, leaves the
+        buffer's last two frames in ``c.caches`` as the next chunk's context, convolves"""
+        if self not in c.caches:
             P[:, 0] = P[:, 2]
             P[:, 1] = P[:, 2]
         else:
-            P[:, :2] = self._cache
-        self._cache = P[:, -2:].clone()
+            P[:, :2] = c.caches[self]
+        c.caches[self] = P[:, -2:].clone()
         M = c.B * c.T * c.H * c.W
         out = _new(M, self._n, P.device)
         ops.gemm(P.view(-1, self._cin), self._w, out, M=M, N=self._n, K=27 * self._cin, bias=self._b, mode=ops.A_CCONV3,
@@ -273,8 +321,9 @@ class CogVideoXSpatialNorm3D(nn.Module):
         self._wyb = torch.nn.functional.pad(w, (0, 64 - w.shape[1])).contiguous()
         self._byb = torch.cat([_f32(self.conv_y.conv.bias), _f32(self.conv_b.conv.bias)]).contiguous()
 
-    def run(self, x: torch.Tensor, c: _Chunk, P: torch.Tensor, silu: bool = True):
-        """norm (+ SiLU) of the chunk's rows ``x`` into ``P`` [B, T + 2, H*W, C] behind its two context frames"""
+    def run(self, x: torch.Tensor, c: _Chunk, silu: bool = True):
+        """norm (+ SiLU) of the chunk's rows ``x`` into a fresh [B, T + 2, H*W, C] buffer behind its two context frames"""
+        P = _prefixed(c, self.c, x.device)
         Mz = c.B * c.Tz * c.h * c.w
         yb = _new(Mz, 2 * self.c, x.device)
         ops.gemm(c.zq64, self._wyb, yb, M=Mz, N=2 * self.c, K=64, bias=self._byb)
@@ -285,13 +334,40 @@ class CogVideoXSpatialNorm3D(nn.Module):
         return P
 
 
+class CogVideoXGroupNorm(nn.GroupNorm):
+    """the plain GroupNorm of the encoder (its resnets' norm1 / norm2, norm_out) with the call shape of ``CogVideoXSpatialNorm3D``;
+    an ``nn.GroupNorm`` itself, so its state-dict keys are diffusers' ``...norm1.weight`` / ``...norm1.bias``"""
+
+    def pack(self):
+        self._g, self._bt = _f32(self.weight), _f32(self.bias)
+
+    def run(self, x: torch.Tensor, c: _Chunk, silu: bool = True):
+        """GroupNorm (+ SiLU) of the batch's rows ``x`` into a fresh [B, T + 2, H*W, C] buffer behind its two context frames: the
+        statistics span the batch's frames (from the producing GEMM's column sums where it left them), then one
+        ``lkgd_groupnorm_apply`` per batch entry - ``out`` behind that entry's context frames, ``stats`` offset to the entry"""
+        rows, C_ = c.T * c.H * c.W, x.shape[1]
+        stats = ops.groupnorm_stats(x, None, c.B, rows, self.eps)
+        P = _prefixed(c, C_, x.device)
+        for b in range(c.B):
+            ops.groupnorm_apply(x[b * rows:(b + 1) * rows], None, 1, rows, stats[b], self._g, self._bt, silu, P[b, 2:].view(rows, C_))
+        return P
+
+
+def _norm(c: int, cfg: CogVAEConfig, spatial_norm: bool) -> nn.Module:
+    if spatial_norm:
+        return CogVideoXSpatialNorm3D(c, cfg.latent_channels, cfg.norm_num_groups, cfg.norm_eps)
+    return CogVideoXGroupNorm(cfg.norm_num_groups, c, eps=cfg.norm_eps)
+
+
 class CogVideoXResnetBlock3D(nn.Module):
-    def __init__(self, cin: int, cout: int, cfg: CogVAEConfig):
+    """CogVideoXResnetBlock3D [EXT]: the decoder's with a spatial norm dimension (``spatial_norm``), the encoder's without one"""
+
+    def __init__(self, cin: int, cout: int, cfg: CogVAEConfig, spatial_norm: bool):
         super().__init__()
         self.cin, self.cout = cin, cout
-        self.norm1 = CogVideoXSpatialNorm3D(cin, cfg.latent_channels, cfg.norm_num_groups, cfg.norm_eps)
+        self.norm1 = _norm(cin, cfg, spatial_norm)
         self.conv1 = CogVideoXCausalConv3d(cin, cout, 3)
-        self.norm2 = CogVideoXSpatialNorm3D(cout, cfg.latent_channels, cfg.norm_num_groups, cfg.norm_eps)
+        self.norm2 = _norm(cout, cfg, spatial_norm)
         self.conv2 = CogVideoXCausalConv3d(cout, cout, 3)
         self.conv_shortcut = nn.Conv3d(cin, cout, 1) if cin != cout else None
 
@@ -301,11 +377,12 @@ class CogVideoXResnetBlock3D(nn.Module):
             self._ws, self._bs = pack_linear(self.conv_shortcut.weight.detach()), _f32(self.conv_shortcut.bias)
 
     def run(self, x: torch.Tensor, c: _Chunk):
-        """launches: [plain GEMM (conv_y | conv_b), GroupNorm statistics unless the producing GEMM left column sums, spatial norm,
-        causal conv] x 2, + the 1x1x1 shortcut GEMM where the channel count changes; the residual is conv2's epilogue"""
+        """launches: [the norm - spatial: plain GEMM (conv_y | conv_b), GroupNorm statistics unless the producing GEMM left column
+        sums, spatial norm; plain: the statistics likewise, GroupNorm apply per batch entry - then the causal conv] x 2, + the 1x1x1
+        shortcut GEMM where the channel count changes; the residual is conv2's epilogue"""
         rows = c.T * c.H * c.W
-        h = self.conv1.run(self.norm1.run(x, c, _prefixed(c, self.cin, x.device)), c, colstats=rows)
-        P2 = self.norm2.run(h, c, _prefixed(c, self.cout, x.device))
+        h = self.conv1.run(self.norm1.run(x, c), c, colstats=rows)
+        P2 = self.norm2.run(h, c)
         del h
         sc = x
         if self.conv_shortcut is not None:
@@ -340,15 +417,15 @@ class CogVideoXUpsample3D(nn.Module):
 
 
 class CogVideoXMidBlock3D(nn.Module):
-    def __init__(self, c: int, cfg: CogVAEConfig):
+    def __init__(self, c: int, cfg: CogVAEConfig, spatial_norm: bool):
         super().__init__()
-        self.resnets = nn.ModuleList([CogVideoXResnetBlock3D(c, c, cfg) for _ in range(2)])
+        self.resnets = nn.ModuleList([CogVideoXResnetBlock3D(c, c, cfg, spatial_norm) for _ in range(2)])
 
 
 class CogVideoXUpBlock3D(nn.Module):
     def __init__(self, cin, cout, layers, add_upsample, compress_time, cfg):
         super().__init__()
-        self.resnets = nn.ModuleList([CogVideoXResnetBlock3D(cin if i == 0 else cout, cout, cfg) for i in range(layers)])
+        self.resnets = nn.ModuleList([CogVideoXResnetBlock3D(cin if i == 0 else cout, cout, cfg, True) for i in range(layers)])
         self.upsamplers = nn.ModuleList([CogVideoXUpsample3D(cout, compress_time)]) if add_upsample else None
 
 
@@ -357,64 +434,18 @@ class CogVideoXDecoder3D(nn.Module):
         super().__init__()
         r = list(reversed(cfg.block_out_channels))
         self.conv_in = CogVideoXCausalConv3d(cfg.latent_channels, r[0], 3)
-        self.mid_block = CogVideoXMidBlock3D(r[0], cfg)
-        nt = cfg.temporal_compression_ratio.bit_length() - 1
+        self.mid_block = CogVideoXMidBlock3D(r[0], cfg, True)
         self.up_blocks = nn.ModuleList()
         c = r[0]
         for i, co in enumerate(r):
-            self.up_blocks.append(CogVideoXUpBlock3D(c, co, cfg.layers_per_block + 1, i != len(r) - 1, i < nt, cfg))
+            self.up_blocks.append(CogVideoXUpBlock3D(c, co, cfg.layers_per_block + 1, i != len(r) - 1, i < _time_levels(cfg), cfg))
             c = co
-        self.norm_out = CogVideoXSpatialNorm3D(r[-1], cfg.latent_channels, cfg.norm_num_groups, cfg.norm_eps)
+        self.norm_out = _norm(r[-1], cfg, True)
         self.conv_act = nn.SiLU()
         self.conv_out = CogVideoXCausalConv3d(r[-1], cfg.out_channels, 3)
 
 
 # ------------------------------------------------------------------------------------------------ the encoder's holders
-def _gn_prefixed(x: torch.Tensor, c: _Chunk, norm: nn.GroupNorm, g: torch.Tensor, bt: torch.Tensor) -> torch.Tensor:
-    """plain GroupNorm + SiLU of the batch's rows ``x`` into a fresh [B, T + 2, H*W, C] buffer behind its two context frames: the
-    statistics span the batch's frames (from the producing GEMM's column sums where it left them), then one
-    ``lkgd_groupnorm_apply`` per batch entry - ``out`` behind that entry's context frames, ``stats`` offset to the entry"""
-    rows, C_ = c.T * c.H * c.W, x.shape[1]
-    stats = ops.groupnorm_stats(x, None, c.B, rows, norm.eps)
-    P = _prefixed(c, C_, x.device)
-    for b in range(c.B):
-        ops.groupnorm_apply(x[b * rows:(b + 1) * rows], None, 1, rows, stats[b], g, bt, True, P[b, 2:].view(rows, C_))
-    return P
-
-
-class CogVideoXEncoderResnetBlock3D(nn.Module):
-    """CogVideoXResnetBlock3D [EXT] without a spatial norm dimension: norm1 / norm2 are plain GroupNorms"""
-
-    def __init__(self, cin: int, cout: int, cfg: CogVAEConfig):
-        super().__init__()
-        self.cin, self.cout = cin, cout
-        self.norm1 = nn.GroupNorm(cfg.norm_num_groups, cin, eps=cfg.norm_eps)
-        self.conv1 = CogVideoXCausalConv3d(cin, cout, 3)
-        self.norm2 = nn.GroupNorm(cfg.norm_num_groups, cout, eps=cfg.norm_eps)
-        self.conv2 = CogVideoXCausalConv3d(cout, cout, 3)
-        self.conv_shortcut = nn.Conv3d(cin, cout, 1) if cin != cout else None
-
-    def pack(self):
-        self._g1, self._bt1, self._g2, self._bt2 = (_f32(p) for p in (self.norm1.weight, self.norm1.bias, self.norm2.weight,
-                                                                      self.norm2.bias))
-        self.conv1.pack(); self.conv2.pack()
-        if self.conv_shortcut is not None:
-            self._ws, self._bs = pack_linear(self.conv_shortcut.weight.detach()), _f32(self.conv_shortcut.bias)
-
-    def run(self, x: torch.Tensor, c: _Chunk):
-        """launches: [GroupNorm statistics unless the producing GEMM left column sums, GroupNorm apply per batch entry, causal conv]
-        x 2, + the 1x1x1 shortcut GEMM where the channel count changes; the residual is conv2's epilogue"""
-        rows = c.T * c.H * c.W
-        h = self.conv1.run(_gn_prefixed(x, c, self.norm1, self._g1, self._bt1), c, colstats=rows)
-        P2 = _gn_prefixed(h, c, self.norm2, self._g2, self._bt2)
-        del h
-        sc = x
-        if self.conv_shortcut is not None:
-            sc = _new(x.shape[0], self.cout, x.device)
-            ops.gemm(x, self._ws, sc, M=x.shape[0], N=self.cout, K=self.cin, bias=self._bs)
-        return self.conv2.run(P2, c, res1=sc, colstats=rows)
-
-
 class CogVideoXDownsample3D(nn.Module):
     """CogVideoXDownsample3D(c, c, padding=0, compress_time) [EXT]: avg_pool1d(2, 2) along the frames (the first frame apart when the
     count is odd), then F.pad(0,1,0,1) and a 3x3 stride-2 convolution per frame"""
@@ -441,16 +472,10 @@ class CogVideoXDownsample3D(nn.Module):
         return out
 
 
-class CogVideoXEncoderMidBlock3D(nn.Module):
-    def __init__(self, c: int, cfg: CogVAEConfig):
-        super().__init__()
-        self.resnets = nn.ModuleList([CogVideoXEncoderResnetBlock3D(c, c, cfg) for _ in range(2)])
-
-
 class CogVideoXDownBlock3D(nn.Module):
     def __init__(self, cin, cout, layers, add_downsample, compress_time, cfg):
         super().__init__()
-        self.resnets = nn.ModuleList([CogVideoXEncoderResnetBlock3D(cin if i == 0 else cout, cout, cfg) for i in range(layers)])
+        self.resnets = nn.ModuleList([CogVideoXResnetBlock3D(cin if i == 0 else cout, cout, cfg, False) for i in range(layers)])
         self.downsamplers = nn.ModuleList([CogVideoXDownsample3D(cout, compress_time)]) if add_downsample else None
 
 
@@ -459,14 +484,13 @@ class CogVideoXEncoder3D(nn.Module):
         super().__init__()
         ch = list(cfg.block_out_channels)
         self.conv_in = CogVideoXCausalConv3d(cfg.in_channels, ch[0], 3)
-        nt = cfg.temporal_compression_ratio.bit_length() - 1
         self.down_blocks = nn.ModuleList()
         c = ch[0]
         for i, co in enumerate(ch):
-            self.down_blocks.append(CogVideoXDownBlock3D(c, co, cfg.layers_per_block, i != len(ch) - 1, i < nt, cfg))
+            self.down_blocks.append(CogVideoXDownBlock3D(c, co, cfg.layers_per_block, i != len(ch) - 1, i < _time_levels(cfg), cfg))
             c = co
-        self.mid_block = CogVideoXEncoderMidBlock3D(ch[-1], cfg)
-        self.norm_out = nn.GroupNorm(cfg.norm_num_groups, ch[-1], eps=1e-6)
+        self.mid_block = CogVideoXMidBlock3D(ch[-1], cfg, False)
+        self.norm_out = CogVideoXGroupNorm(cfg.norm_num_groups, ch[-1], eps=1e-6)
         self.conv_act = nn.SiLU()
         self.conv_out = CogVideoXCausalConv3d(ch[-1], 2 * cfg.latent_channels, 3)
 
@@ -476,7 +500,7 @@ class CogVideoXEncoder3D(nn.Module):
         wk = w.permute(0, 2, 3, 4, 1).reshape(w.shape[0], -1)
         self._w_in = torch.nn.functional.pad(wk, (0, 128 - wk.shape[1])).to(torch.float16).contiguous()
         self._b_in = _f32(self.conv_in.conv.bias)
-        self._g_out, self._bt_out = _f32(self.norm_out.weight), _f32(self.norm_out.bias)
+        self.norm_out.pack()
         self.conv_out.pack()
 
 
@@ -581,7 +605,7 @@ class AutoencoderKLCogVideoX(nn.Module):
         self._set_tile_latent_min()
 
     def _set_tile_latent_min(self):
-        down = 2 ** (len(self.config.block_out_channels) - 1)
+        down = _spatial_factor(self.config)
         self.tile_latent_min_height = int(self.tile_sample_min_height / down)
         self.tile_latent_min_width = int(self.tile_sample_min_width / down)
 
@@ -671,7 +695,21 @@ class AutoencoderKLCogVideoX(nn.Module):
 
     def _tiling_args(self):
         return (self.tile_sample_min_height, self.tile_sample_min_width, self.tile_latent_min_height, self.tile_latent_min_width,
-                self.tile_overlap_factor_height, self.tile_overlap_factor_width, 2 ** (len(self.config.block_out_channels) - 1))
+                self.tile_overlap_factor_height, self.tile_overlap_factor_width, _spatial_factor(self.config))
+
+    def _tiles(self, h: int, w: int, min_h: int, min_w: int) -> bool:
+        """tile by tile iff tiling is on and the input (latents for the decode, pixels for the encode) exceeds one tile"""
+        return self.use_tiling and (w > min_w or h > min_h)
+
+    def _frames_out(self, bounds, level) -> int:
+        """output frames of a clip run in the groups ``bounds``; ``level``: frames in -> frames out of one temporal level"""
+        total = 0
+        for a, b in bounds:
+            n = b - a
+            for _ in range(_time_levels(self.config)):
+                n = level(n)
+            total += n
+        return total
 
     # ---- packing -----------------------------------------------------------------------------------------------
     @torch.no_grad()
@@ -682,28 +720,22 @@ class AutoencoderKLCogVideoX(nn.Module):
             raise LkgdHipError("lkgd_amd CogVideoX VAE runs on MI355X only: move the module to cuda first")
         d = self.decoder
         for m in self.modules():
-            if isinstance(m, (CogVideoXResnetBlock3D, CogVideoXUpsample3D)):
+            if isinstance(m, (CogVideoXResnetBlock3D, CogVideoXUpsample3D, CogVideoXDownsample3D)):
                 m.pack()
         d.conv_in.pack(pad_cin=64)                  # the latent rows are padded to 64 channels with zeros
         d.norm_out.pack()
         d.conv_out.pack(pad_cout=4)                 # GEMM output granularity
         if self.has_encoder:
-            for m in self.encoder.modules():
-                if isinstance(m, (CogVideoXEncoderResnetBlock3D, CogVideoXDownsample3D)):
-                    m.pack()
             self.encoder.pack()
         self._packed = True
 
-    def _convs(self):
-        return [m for m in self.modules() if isinstance(m, CogVideoXCausalConv3d)]
-
     # ---- encode ------------------------------------------------------------------------------------------------
-    def _encode_batch(self, xh: torch.Tensor, a: int, b: int, mom: torch.Tensor, t_out: int) -> int:
+    def _encode_batch(self, xh: torch.Tensor, a: int, b: int, mom: torch.Tensor, t_out: int, caches) -> int:
         """frames [a, b) of the clip ``xh`` [B, Cin, T, H, W] (fp16) through the encoder; the moment rows of its latent frames go to
         mom[:, t_out:]"""
         e, dev = self.encoder, xh.device
         B, _, _, H, W = xh.shape
-        c = _Chunk(B, b - a, H, W, None)
+        c = _Chunk(B, b - a, H, W, None, caches)
         c0 = self.config.block_out_channels[0]
         M = B * c.T * H * W
         taps = ops.cogvae_pixel_taps(xh, a, b - a)           # the clip's own frames a - 2, a - 1 are conv_in's cache
@@ -717,40 +749,39 @@ class AutoencoderKLCogVideoX(nn.Module):
                 x = blk.downsamplers[0].run(x, c)
         for r in e.mid_block.resnets:
             x = r.run(x, c)
-        P = _gn_prefixed(x, c, e.norm_out, e._g_out, e._bt_out)
+        P = e.norm_out.run(x, c)
         del x
         m = e.conv_out.run(P, c)                                                # [B*T'*h*w, 2 lc]
         mom[:, t_out:t_out + c.T] = m.view(B, c.T, c.H * c.W, m.shape[1])
         return c.T
 
-    def _encode_clip(self, xc: torch.Tensor, mom: torch.Tensor, bounds, convs) -> None:
-        """the contiguous clip ``xc`` [n, Cin, T, H, W] through its frame batches, the conv caches carried from batch to batch and
-        cleared in front; the moment rows go to ``mom`` [n, T', h*w, 2 lc]"""
-        for m in convs:
-            m._cache = None
-        t_out = 0
-        for a, b in bounds:
-            t_out += self._encode_batch(xc, a, b, mom, t_out)
+    def _encode_clip(self, xc: torch.Tensor, mom: torch.Tensor, bounds) -> None:
+        """the contiguous clip ``xc`` [n, Cin, T, H, W] through its frame batches, the conv caches carried from batch to batch; the
+        moment rows go to ``mom`` [n, T', h*w, 2 lc]"""
+        _run_clip(self._encode_batch, xc, bounds, mom)
 
-    def _tiled_encode(self, x1: torch.Tensor, out: torch.Tensor, g: TileGeometry, bounds, convs) -> None:
-        """``tiled_encode`` of diffusers for one batch entry ``x1`` [1, Cin, T, H, W]: every pixel tile through ``_encode_clip``
-        (one at a time, or under ``tile_batch()`` tiles of equal shape as one batch), then in row-major order one
-        ``lkgd_cogvae_tile_blend_rows`` per tile -
-        the cross-fade of its moment rows with its upper and left neighbours' blended rows, and its crop into ``out`` [T', h, w, 2 lc]"""
-        down = 2 ** (len(self.config.block_out_channels) - 1)
-        Tl, C2 = out.shape[0], out.shape[3]
-        tiles = {}
-        for run in _tile_groups(g, tile_batch()):
-            sy, sx = g.rows[run[0][0]][1], g.cols[run[0][1]][1]
-            xt = torch.cat([x1[:, :, :, g.rows[i][0]:g.rows[i][0] + sy, g.cols[j][0]:g.cols[j][0] + sx] for i, j in run]).contiguous()
-            mt = torch.empty(len(run), Tl, (sy // down) * (sx // down), C2, dtype=torch.float16, device=x1.device)
-            self._encode_clip(xt, mt, bounds, convs)
-            for k, ij in enumerate(run):
-                tiles[ij] = mt[k].view(Tl, sy // down, sx // down, C2)
-        for i, (y0, _) in enumerate(g.out_rows):
-            for j, (x0, _) in enumerate(g.out_cols):
-                ops.cogvae_tile_blend_rows(tiles[i, j], tiles.get((i - 1, j)), tiles.get((i, j - 1)), out, y0, x0, g.extent[0],
-                                           g.extent[1], g.crop[0], g.crop[1])
+    def _tiled_encode(self, x1: torch.Tensor, mom: torch.Tensor, bounds) -> None:
+        """``tiled_encode`` of diffusers for one batch entry ``x1`` [1, Cin, T, H, W]: every pixel tile through ``_encode_clip``, the
+        seams by ``lkgd_cogvae_tile_blend_rows`` on the tiles' moment rows into ``mom`` [1, T', h*w, 2 lc] (``_run_tiles``)"""
+        H, W = x1.shape[3:]
+        g = encode_tile_geometry(H, W, *self._tiling_args())
+        down = _spatial_factor(self.config)
+        Tl, C2 = mom.shape[1], mom.shape[3]
+
+        def run(xt):
+            n, sy, sx = xt.shape[0], xt.shape[3] // down, xt.shape[4] // down
+            mt = torch.empty(n, Tl, sy * sx, C2, dtype=torch.float16, device=xt.device)
+            self._encode_clip(xt, mt, bounds)
+            return mt.view(n, Tl, sy, sx, C2)
+
+        _run_tiles(g, lambda ys, xs: x1[:, :, :, ys, xs], run, ops.cogvae_tile_blend_rows,
+                   lambda: mom[0].view(Tl, H // down, W // down, C2))
+
+    def _encode_f16(self, x1: torch.Tensor, mom: torch.Tensor, bounds) -> None:
+        """one batch entry ``x1`` [1, Cin, T, H, W] fp16 -> its moment rows ``mom`` [1, T', h*w, 2 lc]: tile by tile iff ``_tiles``"""
+        if self._tiles(x1.shape[3], x1.shape[4], self.tile_sample_min_height, self.tile_sample_min_width):
+            return self._tiled_encode(x1, mom, bounds)
+        return self._encode_clip(x1, mom, bounds)
 
     @torch.no_grad()
     def encode(self, x: torch.Tensor, return_dict: bool = True):
@@ -767,7 +798,7 @@ class AutoencoderKLCogVideoX(nn.Module):
         if x.dim() != 5 or x.shape[1] != ic:
             raise ValueError(f"expected [B, {ic}, T, H, W]")
         B, _, T, H, W = x.shape
-        down = 2 ** (len(self.config.block_out_channels) - 1)
+        down = _spatial_factor(self.config)
         if H % down or W % down:
             raise ValueError(f"height and width must be multiples of {down}, got {H} x {W}")
         if x.dtype == torch.bfloat16 or self.dtype == torch.bfloat16:
@@ -776,41 +807,25 @@ class AutoencoderKLCogVideoX(nn.Module):
         dev = self.device
         xh = x.to(device=dev, dtype=torch.float16).contiguous()
         bounds = frame_batch_bounds(T)
-        nt = self.config.temporal_compression_ratio.bit_length() - 1
-
-        def frames_of(n):
-            for _ in range(nt):
-                n = ops.pooled_frames(n)
-            return n
-
-        Tl, h, w = sum(frames_of(b - a) for a, b in bounds), H // down, W // down
+        Tl, h, w = self._frames_out(bounds, ops.pooled_frames), H // down, W // down
         mom = torch.empty(B, Tl, h * w, 2 * lc, dtype=torch.float16, device=dev)
-        tiled = self.use_tiling and (W > self.tile_sample_min_width or H > self.tile_sample_min_height)
-        geo = encode_tile_geometry(H, W, *self._tiling_args()) if tiled else None
-        convs = self._convs()
-        try:
-            for i in range(B):
-                if tiled:
-                    self._tiled_encode(xh[i:i + 1], mom[i].view(Tl, h, w, 2 * lc), geo, bounds, convs)
-                else:
-                    self._encode_clip(xh[i:i + 1], mom[i:i + 1], bounds, convs)
-        finally:
-            for m in convs:
-                m._cache = None
+        for i in range(B):
+            self._encode_f16(xh[i:i + 1], mom[i:i + 1], bounds)
         dist = DiagonalGaussianDistribution(mom.view(-1, 2 * lc), B, lc, Tl, h, w, self.dtype)
         if not return_dict:
             return (dist,)
         return AutoencoderKLOutput(dist)
 
     # ---- decode ------------------------------------------------------------------------------------------------
-    def _decode_chunk(self, zc: torch.Tensor, out: torch.Tensor, t_out: int) -> int:
-        """one chunk of latent frames ``zc`` [B, Tz, h, w, 16] (fp16) through the decoder; its frames go to out[:, :, t_out:]"""
-        d, dev = self.decoder, zc.device
+    def _decode_chunk(self, zh: torch.Tensor, a: int, b: int, out: torch.Tensor, t_out: int, caches) -> int:
+        """latent frames [a, b) of ``zh`` [B, T, h, w, 16] (fp16), one chunk, through the decoder; its frames go to out[:, :, t_out:]"""
+        d, dev = self.decoder, zh.device
+        zc = zh[:, a:b]
         B, Tz, h, w, lc = zc.shape
         P0 = torch.zeros(B, Tz + 2, h * w, 64, dtype=torch.float16, device=dev)
         P0[:, 2:, :, :lc] = zc.reshape(B, Tz, h * w, lc)
         zq64 = P0[:, 2:].reshape(B * Tz * h * w, 64).contiguous()
-        c = _Chunk(B, Tz, h, w, zq64)
+        c = _Chunk(B, Tz, h, w, zq64, caches)
         x = d.conv_in.run(P0, c, colstats=Tz * h * w)
         del P0
         for r in d.mid_block.resnets:
@@ -820,8 +835,7 @@ class AutoencoderKLCogVideoX(nn.Module):
                 x = r.run(x, c)
             if blk.upsamplers is not None:
                 x = blk.upsamplers[0].run(x, c)
-        c0 = self.config.block_out_channels[0]
-        P = d.norm_out.run(x, c, _prefixed(c, c0, dev))
+        P = d.norm_out.run(x, c)
         del x
         rgb = d.conv_out.run(P, c)                                              # [B*T*H*W, 4]
         oc = self.config.out_channels
@@ -852,60 +866,31 @@ class AutoencoderKLCogVideoX(nn.Module):
         return DecoderOutput(sample=out)
 
     def _decode_f16(self, zh: torch.Tensor) -> torch.Tensor:
-        """``zh`` [B, T, h, w, 16] fp16 -> frames [B, 3, T', 8h, 8w] fp16: tile by tile iff tiling is on and the grid exceeds one tile"""
-        if self.use_tiling and (zh.shape[3] > self.tile_latent_min_width or zh.shape[2] > self.tile_latent_min_height):
+        """``zh`` [B, T, h, w, 16] fp16 -> frames [B, 3, T', 8h, 8w] fp16: tile by tile iff ``_tiles``"""
+        if self._tiles(zh.shape[2], zh.shape[3], self.tile_latent_min_height, self.tile_latent_min_width):
             return self._tiled_decode(zh)
         return self._decode_whole(zh)
 
+    def _new_frames(self, B: int, T: int, h: int, w: int, dev) -> torch.Tensor:
+        """the frames [B, 3, T', 8h, 8w] that T latent frames of h x w decode to, uninitialised"""
+        Tout = self._frames_out(chunk_bounds(T), lambda n: len(upsample_frame_map(n, True)))
+        up = _spatial_factor(self.config)
+        return torch.empty(B, self.config.out_channels, Tout, up * h, up * w, dtype=torch.float16, device=dev)
+
     def _decode_whole(self, zh: torch.Tensor) -> torch.Tensor:
-        """the chunk loop over the whole latent grid of ``zh`` [B, T, h, w, 16]"""
+        """the chunk loop over the whole latent grid of ``zh`` [B, T, h, w, 16] (a chunk's activations are gone when it returns)"""
         B, T, h, w, _ = zh.shape
-        dev = zh.device
-        bounds = chunk_bounds(T)
-        nt = self.config.temporal_compression_ratio.bit_length() - 1
-        up = 2 ** (len(self.config.block_out_channels) - 1)
-
-        def frames_of(n):
-            for _ in range(nt):
-                n = len(upsample_frame_map(n, True))
-            return n
-
-        Tout = sum(frames_of(b - a) for a, b in bounds)
-        out = torch.empty(B, self.config.out_channels, Tout, up * h, up * w, dtype=torch.float16, device=dev)
-        convs = self._convs()
-        for m in convs:
-            m._cache = None
-        t_out = 0
-        try:
-            for a, b in bounds:
-                t_out += self._decode_chunk(zh[:, a:b], out, t_out)      # (a chunk's activations are gone when it returns)
-        finally:
-            for m in convs:
-                m._cache = None
+        out = self._new_frames(B, T, h, w, zh.device)
+        _run_clip(self._decode_chunk, zh, chunk_bounds(T), out)
         return out
 
     def _tiled_decode(self, zh: torch.Tensor) -> torch.Tensor:
-        """``tiled_decode`` of diffusers: every latent tile through ``_decode_whole`` (its chunks, the conv caches cleared between
-        tiles; one at a time, or under ``tile_batch()`` tiles of equal shape as one batch), then in row-major order one
-        ``lkgd_cogvae_tile_blend_planar`` per
-        tile - the cross-fade with its upper and left neighbours' blended tiles, and its crop into the frames"""
+        """``tiled_decode`` of diffusers: every latent tile through ``_decode_whole`` - all B entries of a tile together - and the
+        seams by ``lkgd_cogvae_tile_blend_planar`` on the decoded tiles (``_run_tiles``)"""
         B, T, h, w, _ = zh.shape
         g = decode_tile_geometry(h, w, *self._tiling_args())
-        up = self._tiling_args()[-1]
-        tiles = {}
-        for run in _tile_groups(g, tile_batch()):
-            sy, sx = g.rows[run[0][0]][1], g.cols[run[0][1]][1]
-            zt = torch.cat([zh[:, :, g.rows[i][0]:g.rows[i][0] + sy, g.cols[j][0]:g.cols[j][0] + sx] for i, j in run]).contiguous()
-            o = self._decode_whole(zt)                                    # [len(run) * B, 3, T', 8 sy, 8 sx]
-            for k, ij in enumerate(run):
-                tiles[ij] = o[k * B:(k + 1) * B]
-        t00 = tiles[0, 0]
-        out = torch.empty(B, t00.shape[1], t00.shape[2], up * h, up * w, dtype=torch.float16, device=zh.device)
-        for i, (y0, _) in enumerate(g.out_rows):
-            for j, (x0, _) in enumerate(g.out_cols):
-                ops.cogvae_tile_blend_planar(tiles[i, j], tiles.get((i - 1, j)), tiles.get((i, j - 1)), out, y0, x0, g.extent[0],
-                                             g.extent[1], g.crop[0], g.crop[1])
-        return out
+        return _run_tiles(g, lambda ys, xs: zh[:, :, ys, xs], lambda zt: self._decode_whole(zt).unflatten(0, (-1, B)),
+                          ops.cogvae_tile_blend_planar, lambda: self._new_frames(B, T, h, w, zh.device))
 
     def forward(self, z):
         return self.decode(z)

@@ -155,23 +155,31 @@ def test_enable_on_a_cpu_module_names_itself_and_says_to_move_first():
 
 
 def test_decode_tiles_iff_the_grid_exceeds_one_tile(on_gpu, monkeypatch):
+    """the decode over four latent grids, and the encode over the same four sizes x 8 pixels"""
     m = _module()
     calls = []
     monkeypatch.setattr(m, "_decode_whole", lambda zh: calls.append("whole") or zh)
     monkeypatch.setattr(m, "_tiled_decode", lambda zh: calls.append("tiled") or zh)
-    z = {hw: torch.zeros(1, 1, hw[0], hw[1], 16) for hw in ((6, 10), (7, 10), (6, 11), (12, 20))}
-    for hw in z:
-        m._decode_f16(z[hw])
-    assert calls == ["whole"] * 4                                         # off: never
-    del calls[:]
-    m.enable_tiling(48, 80)
-    for hw in z:
-        m._decode_f16(z[hw])
-    assert calls == ["whole", "tiled", "tiled", "tiled"]
-    del calls[:]
-    m.disable_tiling()
-    m._decode_f16(z[12, 20])
-    assert calls == ["whole"]
+    monkeypatch.setattr(m, "_encode_clip", lambda x1, mom, bounds: calls.append("whole"))
+    monkeypatch.setattr(m, "_tiled_encode", lambda x1, mom, bounds: calls.append("tiled"))
+    sizes = ((6, 10), (7, 10), (6, 11), (12, 20))
+    z = {hw: torch.zeros(1, 1, hw[0], hw[1], 16) for hw in sizes}
+    x = {hw: torch.zeros(1, 3, 1, 8 * hw[0], 8 * hw[1]) for hw in sizes}
+    for run, inp in ((m._decode_f16, z), (lambda x1: m._encode_f16(x1, None, None), x)):
+        del calls[:]
+        m.disable_tiling()
+        for hw in sizes:
+            run(inp[hw])
+        assert calls == ["whole"] * 4                                     # off: never
+        del calls[:]
+        m.enable_tiling(48, 80)
+        for hw in sizes:
+            run(inp[hw])
+        assert calls == ["whole", "tiled", "tiled", "tiled"]
+        del calls[:]
+        m.disable_tiling()
+        run(inp[12, 20])
+        assert calls == ["whole"]
 
 
 def test_tiled_equals_untiled_when_the_input_fits_one_tile():

@@ -128,6 +128,63 @@ def test_planner_sends_the_causal_conv_to_program_4(shape):
     assert _plan(**_cconv(1, 64, 640, 2, 6, 10))[1][3] == 320
 
 
+class _Rows:
+    """what ``ops.gemm_plan`` reads of a row matrix that lives off the device - shape, row stride, an aligned address - without its
+    memory (the 480 x 720 level's operands are 0.9 GB each)"""
+    is_cuda = False
+
+    def __init__(self, rows, cols):
+        self.shape = (rows, cols)
+
+    def dim(self):
+        return 2
+
+    def stride(self, i):
+        return (self.shape[1], 1)[i]
+
+    def data_ptr(self):
+        return P
+
+
+def _launch_form(shape, colstats, cus=256):
+    """(tile rows, tile columns, lds_out) of the launch CogVideoXCausalConv3d.run makes for ``shape``, as ops.gemm would plan it"""
+    from lkgd_amd import ops
+    B, Cin, N, T, H, W = shape
+    M = B * T * H * W
+    plan = ops.gemm_plan(_Rows(B * (T + 2) * H * W, Cin), _Rows(N, 27 * Cin), _Rows(M, N), cus=cus, M=M, N=N, K=27 * Cin,
+                         bias=torch.empty(N), mode=ops.A_CCONV3, Cin=Cin, cconv=(T, H, W), colstats=colstats)
+    assert plan.program == 4 and plan.k_slices == 1
+    return plan.tile_m, plan.tile_n, plan.lds_out
+
+
+def test_real_launches_run_a_form_the_width_tests_run():
+    """Every causal-conv launch of the real decode (REAL_SHAPES; the module asks for column sums over a chunk's T*H*W rows at every
+    convolution but conv_out) runs a form of the 256x320 program - tile rows, tile columns, rows through LDS or not - that a case of
+    tests/test_cogvideox_vae_widths_gpu.py holds to F.conv3d.  A planner change that sends a real launch to an untested form fails
+    here: add the form to that file's tables."""
+    import test_cogvideox_vae_widths_gpu as wt
+    tested = wt.case_forms()
+    assert tested <= {(m, n, l) for m in (192, 256) for n in (256, 320) for l in (0, 1)}
+    for shape in REAL_SHAPES:
+        B, Cin, N, T, H, W = shape
+        for colstats in (T * H * W, 0):
+            form = _launch_form(shape, colstats)
+            assert form in tested, f"{shape} with colstats={colstats} runs {form}: no case of the width tests runs that form"
+    # and the tables say what their own cases run: the plan of every case at the tile rows it forces
+    from lkgd_amd import _lib
+    L = _lib.lib()
+    try:
+        for rows in wt.TILE_ROWS:
+            L.lkgd_debug_set_wide_tile_m(rows)
+            for s in wt.direct_shapes():
+                assert _launch_form(s, 0) == (rows, wt.TILE_N[s[2]], 0), (s, rows)
+        for s, rows in wt.COLSTATS_CASES:
+            L.lkgd_debug_set_wide_tile_m(rows)
+            assert _launch_form(s, s[3] * s[4] * s[5]) == (rows, wt.TILE_N[s[2]], 1), (s, rows)
+    finally:
+        L.lkgd_debug_set_wide_tile_m(0)
+
+
 def test_planner_refuses_what_the_causal_conv_cannot_take():
     s = (1, 64, 64, 2, 6, 10)
     assert _plan(**_cconv(*s))[0] == OK

@@ -209,6 +209,15 @@ COGVAE_TILE_SYMBOLS = {
                                            _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
 }
 
+#: every symbol include/lkgd_hip_video.h declares (frames out and image in of the CogVideoX image-to-video pipeline: the planar fp16 clip
+#: to interleaved uint8 / fp32 frames or frame-major fp16, interleaved uint8 images to planar fp16 in [-1, 1]), bound on the same library
+#: object; tests/test_cogvideox_pipeline_cpu.py pins header, table and library to one another, tests/test_video_io_gpu.py the footprint
+#: cases
+VIDEO_SYMBOLS = {
+    "lkgd_video_postprocess": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
+    "lkgd_image_preprocess": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _vp]),
+}
+
 #: include/lkgd_hip_debug.h: A/B and test knobs, per host thread; bound on the same library object, not part of the product interface
 DEBUG_SYMBOLS = {
     "lkgd_debug_set_wide_tile_n": (None, [_i32]),
@@ -244,7 +253,7 @@ def lib() -> C.CDLL:
         except OSError as e:
             raise LkgdHipError(f"cannot load {LIB_PATH}: {e}") from e
         for table in (SYMBOLS, WINDOW_SYMBOLS, DIT_SYMBOLS, DIT_LOOP_SYMBOLS, DIT_TPATCH_SYMBOLS, DIT_DPM_SYMBOLS, FP8_SYMBOLS,
-                      T5_SYMBOLS, COGVAE_SYMBOLS, COGVAE_ENC_SYMBOLS, COGVAE_TILE_SYMBOLS, DEBUG_SYMBOLS):
+                      T5_SYMBOLS, COGVAE_SYMBOLS, COGVAE_ENC_SYMBOLS, COGVAE_TILE_SYMBOLS, VIDEO_SYMBOLS, DEBUG_SYMBOLS):
             for name, (res, args) in table.items():
                 fn = getattr(l, name)       # AttributeError here = header / library mismatch
                 fn.restype, fn.argtypes = res, args

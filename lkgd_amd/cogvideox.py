@@ -825,7 +825,16 @@ class CogVideoXDPMScheduler(_CogVideoXSchedule):
 
 def dpm_noise(shape, dtype, device, generator, order: int) -> torch.Tensor:
     """the draws of one DPM step: ``order`` calls of randn, the last one kept ([EXT] scheduling_dpm_cogvideox.py: a second-order step
-    draws twice and uses the second draw - with a caller's generator the discarded draw is observable in its state)"""
+    draws twice and uses the second draw - with a caller's generator the discarded draw is observable in its state).  A list of
+    generators, one per batch entry, draws every entry from its own ([EXT] diffusers ``randn_tensor``)"""
+    if isinstance(generator, (list, tuple)):
+        if len(generator) != shape[0]:
+            raise ValueError(f"You have passed a list of generators of length {len(generator)}, but requested an effective batch"
+                             f" size of {shape[0]}. Make sure the batch size matches the length of the generators.")
+        one = (1,) + tuple(shape[1:])
+        for _ in range(order):
+            eps = torch.cat([torch.randn(one, generator=g, device=g.device, dtype=dtype) for g in generator])
+        return eps.to(device)
     gdev = generator.device if generator is not None else device
     for _ in range(order):
         eps = torch.randn(tuple(shape), generator=generator, device=gdev, dtype=dtype)

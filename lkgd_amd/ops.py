@@ -1294,3 +1294,45 @@ def cogvae_tile_blend_rows(tile: torch.Tensor, up: Optional[torch.Tensor], left:
                                            Xl, Y, X, int(y0), int(x0), int(e_y), int(e_x), int(c_y), int(c_x), _stream()),
           "lkgd_cogvae_tile_blend_rows")
     return tile
+
+
+# ---- frames out and image in of the CogVideoX image-to-video pipeline (include/lkgd_hip_video.h) -----------------------------------------
+VIDEO_U8, VIDEO_F32, VIDEO_F16 = 0, 1, 2
+_VIDEO_OUT = {VIDEO_U8: torch.uint8, VIDEO_F32: torch.float32, VIDEO_F16: torch.float16}
+
+
+def video_postprocess(video: torch.Tensor, mode: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """the frames of a decoded clip (lkgd_video_postprocess): ``video`` fp16 [B, C <= 4, T, H, W] contiguous, denormalised and
+    clamped to [0, 1] -> ``VIDEO_U8`` uint8 [B, T, H, W, C] (x 255, rounded half to even), ``VIDEO_F32`` fp32 [B, T, H, W, C] or
+    ``VIDEO_F16`` fp16 [B, T, C, H, W]; one launch"""
+    _req(video, torch.float16, "video")
+    if video.dim() != 5 or not video.is_contiguous():
+        raise _lib.LkgdHipError(f"video must be a contiguous [B, C, T, H, W] clip, got {tuple(video.shape)} strides "
+                                f"{tuple(video.stride())}")
+    if mode not in _VIDEO_OUT:
+        raise _lib.LkgdHipError(f"video_postprocess: mode {mode!r}; built: VIDEO_U8, VIDEO_F32, VIDEO_F16")
+    B, C_, T, H, W = video.shape
+    shape = (B, T, C_, H, W) if mode == VIDEO_F16 else (B, T, H, W, C_)
+    if out is None:
+        out = torch.empty(shape, dtype=_VIDEO_OUT[mode], device=video.device)
+    _req(out, _VIDEO_OUT[mode], "out")
+    if tuple(out.shape) != shape or not out.is_contiguous():
+        raise _lib.LkgdHipError(f"out must be a contiguous {shape} tensor, got {tuple(out.shape)} strides {tuple(out.stride())}")
+    check(_L().lkgd_video_postprocess(video.data_ptr(), out.data_ptr(), int(mode), B, C_, T, H, W, _stream()), "lkgd_video_postprocess")
+    return out
+
+
+def image_preprocess(images: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """the pipeline's image input (lkgd_image_preprocess): ``images`` uint8 [N, H, W, C <= 4] contiguous -> fp16 [N, C, H, W] =
+    2 * (u / 255) - 1, the fp32 statements of the host chain rounded once to fp16; one launch"""
+    _req(images, torch.uint8, "images")
+    if images.dim() != 4 or not images.is_contiguous():
+        raise _lib.LkgdHipError(f"images must be contiguous [N, H, W, C], got {tuple(images.shape)} strides {tuple(images.stride())}")
+    N, H, W, C_ = images.shape
+    if out is None:
+        out = torch.empty(N, C_, H, W, dtype=torch.float16, device=images.device)
+    _req(out, torch.float16, "out")
+    if tuple(out.shape) != (N, C_, H, W) or not out.is_contiguous():
+        raise _lib.LkgdHipError(f"out must be a contiguous {(N, C_, H, W)} tensor, got {tuple(out.shape)} strides {tuple(out.stride())}")
+    check(_L().lkgd_image_preprocess(images.data_ptr(), out.data_ptr(), N, H, W, C_, _stream()), "lkgd_image_preprocess")
+    return out

@@ -1,0 +1,314 @@
+"""``CogVideoXImageToVideoPipeline``: the object the reference's launchers construct and call
+(CogVideo-main/finetune/models/cogvideox_i2v/pipeline_cogvideox_image2video.py:166-227 the constructor, :465-527 ``check_inputs``,
+:610-919 ``__call__``; inference/cli_demo.py and the trainers' validation go through it).  The stages are the free functions of
+lkgd_amd/cogvideox.py and lkgd_amd/cogvideox_vae.py - ``encode_prompt``, ``prepare_latents``, ``denoise``, ``decode_latents`` - called
+in the reference's order with the reference's glue between them; nothing of them is restated here.  Frames in and frames out go
+through :class:`lkgd_amd.video_processor.VideoProcessor` (include/lkgd_hip_video.h).
+
+What diffusers supplies around the reference's class - ``DiffusionPipeline.from_pretrained`` / ``to`` / the offload switches,
+``retrieve_timesteps``, ``VideoProcessor``, ``CogVideoXPipelineOutput`` - is restated from its published behaviour **[EXT], parity
+unpinned**: diffusers is not installable next to this package, so the reference's class itself cannot be executed.
+
+Arguments of ``__call__`` the loop (``denoise``) cannot honour raise ``LkgdHipError`` naming themselves; nothing is silently ignored:
+custom ``timesteps``, ``eta != 0``, ``attention_kwargs``, a ``callback_on_step_end`` that returns replaced ``latents`` /
+``prompt_embeds`` / ``negative_prompt_embeds`` or sets ``interrupt``, a missing ``domain_model`` / ``flow_model``.  Not built: the
+text-to-video and video-to-video pipelines, LoRA loading / fusing for the DiT, bf16, ``export_to_video``, a sharded ``__call__``."""
+from __future__ import annotations
+
+import os
+from dataclasses import dataclass
+from typing import Any, Callable, Dict, List, Optional, Union
+
+import torch
+
+from . import cogvideox as cx
+from ._lib import LkgdHipError
+from .cogvideox_vae import AutoencoderKLCogVideoX, decode_latents
+from .image_processor import PIL
+from .video_processor import VideoProcessor
+
+
+@dataclass
+class CogVideoXPipelineOutput:
+    """[EXT diffusers pipelines/cogvideo/pipeline_output.py]"""
+    frames: Any
+
+
+def additional_latent_frames(num_frames: int, temporal_factor: int, patch_size_t: Optional[int]):
+    """:779-786: (latent frames, additional latent frames, padded pixel frame count) - the 1.5 models pad the latent frames to a
+    multiple of ``patch_size_t`` and ask ``prepare_latents`` for the pixel frames that give them"""
+    latent_frames = (num_frames - 1) // temporal_factor + 1
+    additional = cx.temporal_padding_frames(latent_frames, patch_size_t)
+    return latent_frames, additional, num_frames + additional * temporal_factor
+
+
+class CogVideoXImageToVideoPipeline:
+    _optional_components: List[str] = []
+    model_cpu_offload_seq = "text_encoder->transformer->vae"
+    _callback_tensor_inputs = ["latents", "prompt_embeds", "negative_prompt_embeds"]
+
+    def __init__(self, tokenizer, text_encoder, vae, transformer, scheduler, domain_model=None, flow_model=None):
+        self.tokenizer, self.text_encoder, self.vae, self.transformer, self.scheduler = tokenizer, text_encoder, vae, transformer, scheduler
+        self.domain_model, self.flow_model = domain_model, flow_model
+        self.vae_scale_factor_spatial = 2 ** (len(vae.config.block_out_channels) - 1) if vae is not None else 8
+        self.vae_scale_factor_temporal = vae.config.temporal_compression_ratio if vae is not None else 4
+        self.vae_scaling_factor_image = vae.config.scaling_factor if vae is not None else 0.7
+        self.video_processor = VideoProcessor(vae_scale_factor=self.vae_scale_factor_spatial)
+        self._guidance_scale = None
+        self._num_timesteps = None
+        self._current_timestep = None
+        self._attention_kwargs = None
+        self._interrupt = False
+
+    # ---- [EXT] DiffusionPipeline ------------------------------------------------------------------------------------------------------
+    @property
+    def components(self) -> Dict[str, Any]:
+        return dict(tokenizer=self.tokenizer, text_encoder=self.text_encoder, vae=self.vae, transformer=self.transformer,
+                    scheduler=self.scheduler, domain_model=self.domain_model, flow_model=self.flow_model)
+
+    def to(self, device):
+        """every module of the pipeline moves to ``device``; returns the pipeline"""
+        for m in self.components.values():
+            if isinstance(m, torch.nn.Module):
+                m.to(device)
+        return self
+
+    @property
+    def device(self):
+        return self.transformer.device
+
+    _execution_device = device
+
+    def enable_model_cpu_offload(self, *args, **kwargs) -> None:
+        """does nothing: in the reference it only decides where the weights wait between stages, and the launchers call it
+        unconditionally.  Here every module stays where ``to(device)`` put it"""
+
+    def enable_sequential_cpu_offload(self, *args, **kwargs) -> None:
+        """does nothing, for the same reason as ``enable_model_cpu_offload``"""
+
+    def maybe_free_model_hooks(self) -> None:
+        """does nothing: there are no offload hooks"""
+
+    @classmethod
+    def from_pretrained(cls, path: str, torch_dtype=None, tokenizer=None, domain_model=None, flow_model=None):
+        """a local checkpoint directory in diffusers' layout: ``model_index.json`` and ``text_encoder/``, ``vae/``, ``transformer/``,
+        ``scheduler/``, each read by its own loader.  The VAE comes with its encoder (a ``vae/`` without ``encoder.*`` keys raises: an
+        image-to-video pipeline encodes its image).  ``tokenizer``: the caller's; omitted, ``tokenizer/`` is read with transformers'
+        ``T5Tokenizer`` where that can be imported, else it stays None (prompts as id tensors or ``prompt_embeds`` need none).  The domain
+        and flow ViTs are the trainer's (lora_trainer.py:56-84), not the checkpoint's: arguments"""
+        from .loading import load_config
+        from .t5 import T5EncoderModel
+        index = load_config(path, None, name="model_index.json")
+        for part in ("text_encoder", "vae", "transformer", "scheduler"):
+            if part not in index:
+                raise LkgdHipError(f"CogVideoXImageToVideoPipeline.from_pretrained({path!r}): model_index.json names no {part!r}")
+        text_encoder = T5EncoderModel.from_pretrained(path, subfolder="text_encoder", **({} if torch_dtype is None else {"torch_dtype": torch_dtype}))
+        vae = AutoencoderKLCogVideoX.from_pretrained(path, subfolder="vae", torch_dtype=torch_dtype)
+        if not vae.has_encoder:
+            raise LkgdHipError(f"CogVideoXImageToVideoPipeline.from_pretrained({path!r}): vae/ holds no encoder.* keys; the "
+                               "image-to-video pipeline encodes its image and needs the whole VAE")
+        transformer = cx.CogVideoXTransformer3DModel.from_pretrained(path, subfolder="transformer", torch_dtype=torch_dtype)
+        scheduler = cx.scheduler_from_config(path)
+        if tokenizer is None and os.path.isdir(os.path.join(path, "tokenizer")):
+            try:
+                from transformers import T5Tokenizer
+                tokenizer = T5Tokenizer.from_pretrained(os.path.join(path, "tokenizer"))
+            except ImportError:     # transformers or sentencepiece absent: the tokenizer stays the caller's business
+                tokenizer = None
+        return cls(tokenizer, text_encoder, vae, transformer, scheduler, domain_model, flow_model)
+
+    # ---- the reference's class ----------------------------------------------------------------------------------------------------
+    def encode_prompt(self, prompt, negative_prompt=None, do_classifier_free_guidance: bool = True, num_videos_per_prompt: int = 1,
+                      prompt_embeds=None, negative_prompt_embeds=None, max_sequence_length: int = 226, device=None, dtype=None):
+        """:273-352"""
+        return cx.encode_prompt(self.text_encoder, self.tokenizer, prompt, negative_prompt, do_classifier_free_guidance,
+                                num_videos_per_prompt, prompt_embeds, negative_prompt_embeds, max_sequence_length, device, dtype)
+
+    def prepare_latents(self, image, batch_size=1, num_channels_latents=16, num_frames=13, height=60, width=90, dtype=None, device=None,
+                        generator=None, latents=None):
+        """:354-427"""
+        return cx.prepare_latents(self.vae, self.scheduler, self.transformer.config, image, batch_size, num_channels_latents, num_frames,
+                                  height, width, dtype, device, generator, latents)
+
+    def decode_latents(self, latents: torch.Tensor) -> torch.Tensor:
+        """:430-435"""
+        return decode_latents(self.vae, latents)
+
+    def check_inputs(self, image, prompt, height, width, negative_prompt, callback_on_step_end_tensor_inputs, latents=None,
+                     prompt_embeds=None, negative_prompt_embeds=None):
+        """:465-527, the same errors.  A prompt may also be an int64 id tensor (``encode_prompt``)"""
+        if (not isinstance(image, torch.Tensor) and not (PIL is not None and isinstance(image, PIL.Image.Image))
+                and not isinstance(image, list)):
+            raise ValueError("`image` has to be of type `torch.Tensor` or `PIL.Image.Image` or `List[PIL.Image.Image]` but is"
+                             f" {type(image)}")
+        if height % 8 != 0 or width % 8 != 0:
+            raise ValueError(f"`height` and `width` have to be divisible by 8 but are {height} and {width}.")
+        if callback_on_step_end_tensor_inputs is not None and not all(
+                k in self._callback_tensor_inputs for k in callback_on_step_end_tensor_inputs):
+            raise ValueError(f"`callback_on_step_end_tensor_inputs` has to be in {self._callback_tensor_inputs}, but found "
+                             f"{[k for k in callback_on_step_end_tensor_inputs if k not in self._callback_tensor_inputs]}")
+        if prompt is not None and prompt_embeds is not None:
+            raise ValueError(f"Cannot forward both `prompt`: {prompt} and `prompt_embeds`: {prompt_embeds}. Please make sure to"
+                             " only forward one of the two.")
+        elif prompt is None and prompt_embeds is None:
+            raise ValueError("Provide either `prompt` or `prompt_embeds`. Cannot leave both `prompt` and `prompt_embeds` undefined.")
+        elif prompt is not None and not isinstance(prompt, (str, list, torch.Tensor)):
+            raise ValueError(f"`prompt` has to be of type `str` or `list` but is {type(prompt)}")
+        if prompt is not None and negative_prompt_embeds is not None:
+            raise ValueError(f"Cannot forward both `prompt`: {prompt} and `negative_prompt_embeds`:"
+                             f" {negative_prompt_embeds}. Please make sure to only forward one of the two.")
+        if negative_prompt is not None and negative_prompt_embeds is not None:
+            raise ValueError(f"Cannot forward both `negative_prompt`: {negative_prompt} and `negative_prompt_embeds`:"
+                             f" {negative_prompt_embeds}. Please make sure to only forward one of the two.")
+        if prompt_embeds is not None and negative_prompt_embeds is not None:
+            if prompt_embeds.shape != negative_prompt_embeds.shape:
+                raise ValueError("`prompt_embeds` and `negative_prompt_embeds` must have the same shape when passed directly, but"
+                                 f" got: `prompt_embeds` {prompt_embeds.shape} != `negative_prompt_embeds`"
+                                 f" {negative_prompt_embeds.shape}.")
+
+    def _prepare_rotary_positional_embeddings(self, height: int, width: int, num_frames: int, device=None):
+        """:544-586: ``num_frames`` are LATENT frames; ``rotary_tables`` holds both branches"""
+        tc = self.transformer.config
+        grid_height = height // (self.vae_scale_factor_spatial * tc.patch_size)
+        grid_width = width // (self.vae_scale_factor_spatial * tc.patch_size)
+        p_t = tc.patch_size_t
+        frames = num_frames if p_t is None else (num_frames + p_t - 1) // p_t
+        return cx.rotary_tables(tc, frames, grid_height, grid_width)
+
+    @property
+    def guidance_scale(self):
+        return self._guidance_scale
+
+    @property
+    def num_timesteps(self):
+        return self._num_timesteps
+
+    @property
+    def attention_kwargs(self):
+        return self._attention_kwargs
+
+    @property
+    def current_timestep(self):
+        return self._current_timestep
+
+    @property
+    def interrupt(self):
+        return self._interrupt
+
+    def _not_built(self, timesteps, eta, attention_kwargs) -> None:
+        if timesteps is not None:
+            raise LkgdHipError("CogVideoXImageToVideoPipeline: custom `timesteps` are not built - denoise takes the scheduler's "
+                               "trailing spacing of num_inference_steps")
+        if eta != 0.0:
+            raise LkgdHipError(f"CogVideoXImageToVideoPipeline: `eta`={eta} is not built - the DDIM and DPM steps are the eta = 0 ones")
+        if attention_kwargs is not None:
+            raise LkgdHipError("CogVideoXImageToVideoPipeline: `attention_kwargs` are not built - the DiT has no attention processors "
+                               "to hand them to")
+        for name in ("domain_model", "flow_model"):
+            if getattr(self, name) is None:
+                raise LkgdHipError(f"CogVideoXImageToVideoPipeline: `{name}` is missing - the transformer fuses its features into the "
+                                   "text tokens at every call (pass it to the constructor or to from_pretrained)")
+
+    @torch.no_grad()
+    def __call__(self, image, prompt: Optional[Union[str, List[str]]] = None, negative_prompt: Optional[Union[str, List[str]]] = None,
+                 height: Optional[int] = None, width: Optional[int] = None, num_frames: int = 49, num_inference_steps: int = 50,
+                 timesteps: Optional[List[int]] = None, guidance_scale: float = 6, use_dynamic_cfg: bool = False,
+                 num_videos_per_prompt: int = 1, eta: float = 0.0,
+                 generator: Optional[Union[torch.Generator, List[torch.Generator]]] = None, latents: Optional[torch.Tensor] = None,
+                 prompt_embeds: Optional[torch.Tensor] = None, negative_prompt_embeds: Optional[torch.Tensor] = None,
+                 output_type: str = "pil", return_dict: bool = True, attention_kwargs: Optional[Dict[str, Any]] = None,
+                 callback_on_step_end: Optional[Callable] = None, callback_on_step_end_tensor_inputs: List[str] = ["latents"],
+                 max_sequence_length: int = 226):
+        """:610-919, in its order.  The generator is consumed as there: the image posterior's sample(s), the initial noise, then the
+        DPM steps' noise; a list of generators is one per batch entry"""
+        if hasattr(callback_on_step_end, "tensor_inputs"):              # [EXT] PipelineCallback / MultiPipelineCallbacks
+            callback_on_step_end_tensor_inputs = callback_on_step_end.tensor_inputs
+        tc = self.transformer.config
+        height = height or tc.sample_height * self.vae_scale_factor_spatial
+        width = width or tc.sample_width * self.vae_scale_factor_spatial
+        num_frames = num_frames or tc.sample_frames
+        num_videos_per_prompt = 1                                                                   # :726
+
+        # 1. Check inputs
+        self.check_inputs(image=image, prompt=prompt, height=height, width=width, negative_prompt=negative_prompt,
+                          callback_on_step_end_tensor_inputs=callback_on_step_end_tensor_inputs, latents=latents,
+                          prompt_embeds=prompt_embeds, negative_prompt_embeds=negative_prompt_embeds)
+        self._not_built(timesteps, eta, attention_kwargs)
+        self._guidance_scale = guidance_scale
+        self._current_timestep = None
+        self._attention_kwargs = attention_kwargs
+        self._interrupt = False
+
+        # 2. Default call parameters
+        if prompt is not None and isinstance(prompt, str):
+            batch_size = 1
+        elif prompt is not None and isinstance(prompt, (list, torch.Tensor)):
+            batch_size = len(prompt)
+        else:
+            batch_size = prompt_embeds.shape[0]
+        device = self._execution_device
+        do_classifier_free_guidance = guidance_scale > 1.0
+
+        # 3. Encode input prompt; negative first in the concat (:772)
+        prompt_embeds, negative_prompt_embeds = self.encode_prompt(
+            prompt=prompt, negative_prompt=negative_prompt, do_classifier_free_guidance=do_classifier_free_guidance,
+            num_videos_per_prompt=num_videos_per_prompt, prompt_embeds=prompt_embeds, negative_prompt_embeds=negative_prompt_embeds,
+            max_sequence_length=max_sequence_length, device=device)
+        if do_classifier_free_guidance:
+            prompt_embeds = torch.cat([negative_prompt_embeds, prompt_embeds], dim=0)
+
+        # 4. Prepare timesteps ([EXT] retrieve_timesteps without custom timesteps)
+        self.scheduler.set_timesteps(num_inference_steps)
+        step_times = self.scheduler.timesteps
+        self._num_timesteps = len(step_times)
+
+        # 5. Prepare latents; the 1.5 models pad the latent frames (:779-786)
+        _, additional_frames, num_frames = additional_latent_frames(num_frames, self.vae_scale_factor_temporal, tc.patch_size_t)
+        image = self.video_processor.preprocess(image, height=height, width=width, device=device, dtype=prompt_embeds.dtype)
+
+        # the ViTs resize bilinearly to their own input size (lkgd_vit_patchify): :797's resize to 384 is theirs
+        domain_features = self.domain_model(image).unsqueeze(1)
+        flow_features = self.flow_model(image).unsqueeze(1)
+
+        latent_channels = tc.in_channels // 2
+        latents, image_latents = self.prepare_latents(image, batch_size * num_videos_per_prompt, latent_channels, num_frames, height,
+                                                      width, prompt_embeds.dtype, device, generator, latents)
+
+        # 7. Create rotary embeds if required
+        image_rotary_emb = (self._prepare_rotary_positional_embeddings(height, width, latents.size(1), device)
+                            if tc.use_rotary_positional_embeddings else None)
+
+        # 8. Denoising loop (ofs: denoise embeds :826's 2.0 where the config asks for it)
+        callback = None
+        if callback_on_step_end is not None:
+            handed = {"prompt_embeds": prompt_embeds, "negative_prompt_embeds": negative_prompt_embeds}
+
+            def callback(i, t, step_latents):
+                self._current_timestep = step_times[i]
+                handed["latents"] = step_latents
+                outputs = callback_on_step_end(self, i, step_times[i], {k: handed[k] for k in callback_on_step_end_tensor_inputs})
+                for name in self._callback_tensor_inputs:
+                    if outputs is not None and name in outputs and outputs[name] is not handed[name]:
+                        raise LkgdHipError(f"CogVideoXImageToVideoPipeline: `callback_on_step_end` returned a replaced `{name}` - the "
+                                           "loop updates its tensors in place and takes none back (callbacks observe)")
+                if self._interrupt:
+                    raise LkgdHipError("CogVideoXImageToVideoPipeline: `interrupt` was set from `callback_on_step_end` - the loop "
+                                       "cannot skip its remaining steps")
+
+        latents = cx.denoise(self.transformer, self.scheduler, latents, image_latents, prompt_embeds, domain_features, flow_features,
+                             num_inference_steps, guidance_scale, use_dynamic_cfg, callback, image_rotary_emb, None, generator)
+        if use_dynamic_cfg:                                             # :864 leaves the last step's value behind
+            self._guidance_scale = cx.dynamic_guidance(guidance_scale, num_inference_steps, int(step_times[-1]))
+        self._current_timestep = None
+
+        if not output_type == "latent":
+            latents = latents[:, additional_frames:]                    # :907 the 1.5 padding frames leave before the decode
+            video = self.decode_latents(latents)
+            video = self.video_processor.postprocess_video(video=video, output_type=output_type)
+        else:
+            video = latents
+
+        self.maybe_free_model_hooks()
+        if not return_dict:
+            return (video,)
+        return CogVideoXPipelineOutput(frames=video)

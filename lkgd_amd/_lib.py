@@ -47,8 +47,6 @@ class GemmPlanInfo(C.Structure):
                 ("colstats_block", C.c_int32), ("lds_out", C.c_int32)]
 
 
-#: every symbol include/lkgd_hip.h declares: name -> (restype, argtypes)
-_vp, _i32, _i64, _f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_float
 class FsmDesc(C.Structure):
     """struct lkgd_fsm_desc (include/lkgd_hip.h section 9)."""
     _fields_ = [
@@ -62,6 +60,8 @@ class FsmDesc(C.Structure):
     ]
 
 
+#: every symbol include/lkgd_hip.h declares: name -> (restype, argtypes)
+_vp, _i32, _i64, _f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_float
 SYMBOLS = {
     "lkgd_gemm_f16": (_i32, [C.POINTER(GemmDesc), _vp]),
     "lkgd_gemm_colstats_block": (_i32, [C.POINTER(GemmDesc)]),
@@ -117,22 +117,18 @@ SYMBOLS = {
     # debug / measurement knobs (process-global, not thread-safe: include/lkgd_hip.h, last section)
 }
 
-#: every symbol include/lkgd_hip_window.h declares (the windowed loop glue of the long-video smoothing pipeline), bound on the same
-#: library object; tests/test_smooth_cpu.py pins header, table and library to one another, tests/test_smooth_gpu.py the footprint cases
+#: include/lkgd_hip_window.h: the windowed loop glue of the long-video smoothing pipeline
 WINDOW_SYMBOLS = {
     "lkgd_window_prepare_input": (_i32, [_vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _vp, _vp]),
     "lkgd_window_cfg_euler_step": (_i32, [_vp, _vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _f32, _i32, _vp]),
 }
 
-#: every symbol include/lkgd_hip_dit.h declares (attention glue of the rotary CogVideoX DiT), bound on the same library object;
-#: tests/test_cogvideox_rope_cpu.py pins header, table and library to one another, tests/test_cogvideox_rope_gpu.py the footprint cases
+#: include/lkgd_hip_dit.h: attention glue of the rotary CogVideoX DiT
 DIT_SYMBOLS = {
     "lkgd_qk_norm_rope": (_i32, [_vp, _i32, _vp, _i32, _i64, _i32, _vp, _vp, _vp, _vp, _f32, _vp, _vp, _i32, _i32, _i32, _vp]),
 }
 
-#: every symbol include/lkgd_hip_dit_loop.h declares (the latent-knowledge fuse of the DiT's text tokens and the glue of its sampling
-#: loop), bound on the same library object; tests/test_cogvideox_loop_cpu.py pins header, table and library to one another,
-#: tests/test_cogvideox_loop_gpu.py the footprint cases
+#: include/lkgd_hip_dit_loop.h: the latent-knowledge fuse of the DiT's text tokens and the glue of its sampling loop
 DIT_LOOP_SYMBOLS = {
     "lkgd_lk_fuse_tokens": (_i32, [_vp, _i32, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _i32, _vp]),
     "lkgd_dit_patch_rows": (_i32, [_vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _vp]),
@@ -140,18 +136,14 @@ DIT_LOOP_SYMBOLS = {
                                       _vp]),
 }
 
-#: every symbol include/lkgd_hip_dit_tpatch.h declares (the loop glue for the temporal patches of the CogVideoX 1.5 models), bound on
-#: the same library object; tests/test_cogvideox15_cpu.py pins header, table and library to one another,
-#: tests/test_cogvideox15_gpu.py the footprint cases
+#: include/lkgd_hip_dit_tpatch.h: the loop glue for the temporal patches of the CogVideoX 1.5 models
 DIT_TPATCH_SYMBOLS = {
     "lkgd_dit_patch_rows_t": (_i32, [_vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _vp]),
     "lkgd_dit_cfg_ddim_step_t": (_i32, [_vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _f32, _f32, _f32,
                                         _f32, _vp]),
 }
 
-#: every symbol include/lkgd_hip_dit_dpm.h declares (CFG combine + DPM-Solver++ step of the CogVideoX loop, 2-D and temporal patches),
-#: bound on the same library object; tests/test_cogvideox_dpm_cpu.py pins header, table and library to one another,
-#: tests/test_cogvideox_dpm_gpu.py the footprint cases
+#: include/lkgd_hip_dit_dpm.h: CFG combine + DPM-Solver++ step of the CogVideoX loop, 2-D and temporal patches
 DIT_DPM_SYMBOLS = {
     "lkgd_dit_cfg_dpm_step": (_i32, [_vp, _i32, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _f32, _f32,
                                      _f32, _f32, _f32, _f32, _f32, _vp]),
@@ -159,9 +151,7 @@ DIT_DPM_SYMBOLS = {
                                        _f32, _f32, _f32, _f32, _f32, _f32, _vp]),
 }
 
-#: every symbol include/lkgd_hip_fp8.h declares (the FP8 e4m3 form of a DiT block's six linears: three dynamic per-row quantisers and
-#: the GEMM on the block-scaled matrix instruction), bound on the same library object; tests/test_fp8_cpu.py pins header, table and
-#: library to one another, tests/test_fp8_gpu.py the footprint cases
+#: include/lkgd_hip_fp8.h: the FP8 e4m3 form of a DiT block's six linears (three per-row quantisers, the block-scaled GEMM)
 FP8_SYMBOLS = {
     "lkgd_quant_rows_fp8": (_i32, [_vp, _i32, _vp, _i32, _vp, _i64, _i32, _vp]),
     "lkgd_gelu_tanh_quant_fp8": (_i32, [_vp, _i32, _vp, _i32, _vp, _i64, _i32, _vp]),
@@ -169,9 +159,7 @@ FP8_SYMBOLS = {
     "lkgd_gemm_fp8": (_i32, [_vp, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp]),
 }
 
-#: every symbol include/lkgd_hip_t5.h declares (the operators of the T5 text encoder in front of the CogVideoX loop: embedding rows, RMS
-#: norm, dense attention with a relative-position bias, gated tanh-GELU, fp32 residual add), bound on the same library object;
-#: tests/test_t5_cpu.py pins header, table and library to one another, tests/test_t5_gpu.py the footprint cases
+#: include/lkgd_hip_t5.h: the operators of the T5 text encoder in front of the CogVideoX loop
 T5_SYMBOLS = {
     "lkgd_t5_embed_rows": (_i32, [_vp, _vp, _i32, _i32, _i32, _vp, _i32, _i64, _vp]),
     "lkgd_t5_rmsnorm": (_i32, [_vp, _i32, _i64, _i32, _vp, _f32, _vp, _i32, _vp]),
@@ -180,28 +168,20 @@ T5_SYMBOLS = {
     "lkgd_t5_residual_add": (_i32, [_vp, _i32, _vp, _i32, _i64, _i32, _f32, _vp]),
 }
 
-#: every symbol include/lkgd_hip_cogvae.h declares (the latent-modulated norm of the CogVideoX 3-D causal VAE decoder), bound on the same
-#: library object; tests/test_cogvideox_vae_cpu.py pins header, table and library to one another, tests/test_cogvideox_vae_gpu.py the
-#: footprint cases
+#: include/lkgd_hip_cogvae.h: the latent-modulated norm of the CogVideoX 3-D causal VAE decoder
 COGVAE_SYMBOLS = {
     "lkgd_spatial_norm3d": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _i32, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _i32,
                                    _i32, _vp]),
 }
 
-#: every symbol include/lkgd_hip_cogvae_enc.h declares (the encoder of the CogVideoX 3-D causal VAE: conv_in's tap rows over the pixel
-#: channels, the downsamplers' temporal average pool, the posterior of conv_out's moment rows), bound on the same library object;
-#: tests/test_cogvideox_vae_encoder_cpu.py pins header, table and library to one another, tests/test_cogvideox_vae_encoder_gpu.py the
-#: footprint cases
+#: include/lkgd_hip_cogvae_enc.h: pixel tap rows, temporal average pool and posterior of the CogVideoX VAE encoder
 COGVAE_ENC_SYMBOLS = {
     "lkgd_cogvae_pixel_taps": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
     "lkgd_cogvae_time_pool": (_i32, [_vp, _i32, _vp, _i32, _i32, _i32, _i64, _i32, _vp]),
     "lkgd_cogvae_posterior": (_i32, [_vp, _i32, _vp, _vp, _vp, _f32, _i32, _i32, _i32, _i32, _i32, _vp]),
 }
 
-#: every symbol include/lkgd_hip_cogvae_tile.h declares (the seam operator of the tiled CogVideoX VAE: cross-fade with the upper / left
-#: neighbour tile and placement of the crop, on planes for the decode and on channels-last rows for the encode), bound on the same
-#: library object; tests/test_cogvideox_vae_tiling_cpu.py pins header, table and library to one another,
-#: tests/test_cogvideox_vae_tiling_gpu.py the footprint cases
+#: include/lkgd_hip_cogvae_tile.h: the seam operator (cross-fade + crop placement) of the tiled CogVideoX VAE
 COGVAE_TILE_SYMBOLS = {
     "lkgd_cogvae_tile_blend_planar": (_i32, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32,
                                              _i32, _vp]),
@@ -209,10 +189,7 @@ COGVAE_TILE_SYMBOLS = {
                                            _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
 }
 
-#: every symbol include/lkgd_hip_video.h declares (frames out and image in of the CogVideoX image-to-video pipeline: the planar fp16 clip
-#: to interleaved uint8 / fp32 frames or frame-major fp16, interleaved uint8 images to planar fp16 in [-1, 1]), bound on the same library
-#: object; tests/test_cogvideox_pipeline_cpu.py pins header, table and library to one another, tests/test_video_io_gpu.py the footprint
-#: cases
+#: include/lkgd_hip_video.h: frames out and image in of the CogVideoX image-to-video pipeline
 VIDEO_SYMBOLS = {
     "lkgd_video_postprocess": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
     "lkgd_image_preprocess": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _vp]),
@@ -237,6 +214,15 @@ DEBUG_SYMBOLS = {
     "lkgd_debug_set_gn_small_limits": (None, [_i64]),
 }
 
+#: header under include/ -> its table, all bound on the one library object.  tests/test_c_interface_cpu.py holds every header, its table
+#: and the built library to one another, name by name and type by type
+HEADERS = {
+    "lkgd_hip.h": SYMBOLS, "lkgd_hip_window.h": WINDOW_SYMBOLS, "lkgd_hip_dit.h": DIT_SYMBOLS, "lkgd_hip_dit_loop.h": DIT_LOOP_SYMBOLS,
+    "lkgd_hip_dit_tpatch.h": DIT_TPATCH_SYMBOLS, "lkgd_hip_dit_dpm.h": DIT_DPM_SYMBOLS, "lkgd_hip_fp8.h": FP8_SYMBOLS,
+    "lkgd_hip_t5.h": T5_SYMBOLS, "lkgd_hip_cogvae.h": COGVAE_SYMBOLS, "lkgd_hip_cogvae_enc.h": COGVAE_ENC_SYMBOLS,
+    "lkgd_hip_cogvae_tile.h": COGVAE_TILE_SYMBOLS, "lkgd_hip_video.h": VIDEO_SYMBOLS, "lkgd_hip_debug.h": DEBUG_SYMBOLS,
+}
+
 _lib = None
 
 
@@ -252,8 +238,7 @@ def lib() -> C.CDLL:
             l = C.CDLL(LIB_PATH)
         except OSError as e:
             raise LkgdHipError(f"cannot load {LIB_PATH}: {e}") from e
-        for table in (SYMBOLS, WINDOW_SYMBOLS, DIT_SYMBOLS, DIT_LOOP_SYMBOLS, DIT_TPATCH_SYMBOLS, DIT_DPM_SYMBOLS, FP8_SYMBOLS,
-                      T5_SYMBOLS, COGVAE_SYMBOLS, COGVAE_ENC_SYMBOLS, COGVAE_TILE_SYMBOLS, VIDEO_SYMBOLS, DEBUG_SYMBOLS):
+        for table in HEADERS.values():
             for name, (res, args) in table.items():
                 fn = getattr(l, name)       # AttributeError here = header / library mismatch
                 fn.restype, fn.argtypes = res, args

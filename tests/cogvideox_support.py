@@ -1,9 +1,7 @@
-"""What the CogVideoX DiT tests share (test_cogvideox*.py, test_fp8_*.py): the inputs of make_goldens.py, the half-rounded tiny oracle
-and its HIP twin, host stand-ins for the C interface, and the torch statements the loop's glue kernels replace - the patch unfold, the
-un-patchify, one ATen step, the ATen loop - for 2-D (``p_t`` None) and temporal patches."""
-import ctypes as C
+"""What the CogVideoX DiT tests share (test_cogvideox*.py, test_fp8_*.py): the inputs of make_goldens.py, the half-rounded tiny oracle and
+its HIP twin, and the torch statements the loop's glue kernels replace - the patch unfold, the un-patchify, one ATen step, the ATen
+loop - for 2-D (``p_t`` None) and temporal patches."""
 import os
-import re
 
 import torch
 
@@ -69,22 +67,6 @@ def loop_inputs(c=None, seed=5, f=3, cfg=True):
     img = (0.5 * torch.randn(1, f, 16, c.sample_height, c.sample_width, generator=g)).half().float()
     pe = torch.randn(2 if cfg else 1, c.max_text_seq_length, c.text_embed_dim, generator=g).half().float()
     return lat, img, pe, torch.randn(1, 1, 1000, generator=g), torch.randn(1, 1, 1000, generator=g)
-
-
-# ------------------------------------------------------------------------------------------------------------ the C interface
-def declared(header):
-    return set(re.findall(r"\b(lkgd_[a-z0-9_]+)\s*\(", open(os.path.join(REPO, "include", header)).read()))
-
-
-class Host:
-    """host memory standing in for device pointers: a refused call never launches, so nothing dereferences them (only the
-    array `w` is read on the host)"""
-
-    def __init__(self):
-        self.buf = C.create_string_buffer(4096 + 64)
-        base = C.addressof(self.buf)
-        self.p = (base + 63) & ~63           # 64-byte aligned
-        self.w = (C.c_void_p * 18)(*[self.p] * 18)
 
 
 # ------------------------------------------------------------------------------------------------------------- the glue

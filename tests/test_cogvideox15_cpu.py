@@ -1,11 +1,10 @@
-"""Host side of the CogVideoX 1.5 path without a GPU: include/lkgd_hip_dit_tpatch.h == ``_lib.DIT_TPATCH_SYMBOLS`` == the library, and
-its refusals; the 1.5 configurations (I2V with ``ofs_embed_dim``, T2V without) with the twin's names and shapes; the save / load
-round trip; every refused combination of the 1.5 keys; the slice rotary tables by their properties; the frame padding against the
-pipeline's statements; the fp32 twin (tests/cogvideox15_oracle.py) against tests/golden/cogvideox15.safetensors = the reference's
-own in-tree forward (make_goldens_cogvideox15.py)."""
+"""Host side of the CogVideoX 1.5 path without a GPU: the refusals of its two entry points; the 1.5 configurations (I2V with
+``ofs_embed_dim``, T2V without) with the twin's names and shapes; the save / load round trip; every refused combination of the 1.5
+keys; the slice rotary tables by their properties; the frame padding against the pipeline's statements; the fp32 twin
+(tests/cogvideox15_oracle.py) against tests/golden/cogvideox15.safetensors = the reference's own in-tree forward
+(make_goldens_cogvideox15.py)."""
 import json
 import os
-import re
 
 import pytest
 import torch
@@ -13,10 +12,8 @@ from safetensors import safe_open
 from safetensors.torch import load_file
 
 import cogvideox15_oracle as vo
-from cogvideox_support import DIT_SEED, REPO, Host, declared as _declared, dit_inputs as _inputs, hip_twin, rel as _rel
-
-NAMES = {"lkgd_dit_patch_rows_t", "lkgd_dit_cfg_ddim_step_t"}
-OK, NULL, SHAPE, ALIGN = 0, -1, -2, -3
+from c_interface import ALIGN, NULL, SHAPE, Host, entry
+from cogvideox_support import DIT_SEED, REPO, dit_inputs as _inputs, hip_twin, rel as _rel
 
 KW_15_I2V = dict(num_attention_heads=48, attention_head_dim=64, in_channels=32, out_channels=16, time_embed_dim=512,
                  text_embed_dim=4096, num_layers=42, sample_width=300, sample_height=300, sample_frames=81, patch_size=2,
@@ -26,58 +23,26 @@ KW_15_I2V = dict(num_attention_heads=48, attention_head_dim=64, in_channels=32, 
 
 
 # ------------------------------------------------------------------------------------------------------------ the C interface
-def test_dit_tpatch_symbols_agree_three_ways():
-    """header == table == exactly the two names, disjoint from the other five tables and the other five headers, exported by the
-    built library with the table's signature, and declared with as many parameters as the table binds"""
-    from lkgd_amd import _lib
-    hdr = open(os.path.join(REPO, "include", "lkgd_hip_dit_tpatch.h")).read()
-    declared = _declared("lkgd_hip_dit_tpatch.h")
-    assert declared == set(_lib.DIT_TPATCH_SYMBOLS) == NAMES, declared ^ set(_lib.DIT_TPATCH_SYMBOLS)
-    for other in (_lib.SYMBOLS, _lib.WINDOW_SYMBOLS, _lib.DIT_SYMBOLS, _lib.DIT_LOOP_SYMBOLS, _lib.DEBUG_SYMBOLS):
-        assert not declared & set(other)
-    for h in ("lkgd_hip.h", "lkgd_hip_window.h", "lkgd_hip_dit.h", "lkgd_hip_dit_loop.h", "lkgd_hip_debug.h"):
-        assert not declared & _declared(h), h
-    lib = _lib.lib()
-    for s, (res, args) in _lib.DIT_TPATCH_SYMBOLS.items():
-        fn = getattr(lib, s)
-        assert fn.restype is res and list(fn.argtypes) == list(args), s
-        decl = re.search(r"^int %s\s*\(([^;]*)\);" % s, hdr, re.M | re.S).group(1)
-        assert len(re.sub(r"/\*.*?\*/", "", decl).split(",")) == len(args), s
-    # the arguments of the 2-D pair (12, 17) plus p_t
-    assert [len(_lib.DIT_TPATCH_SYMBOLS[s][1]) for s in sorted(NAMES)] == [18, 13]
-    assert [len(_lib.DIT_LOOP_SYMBOLS[s[:-2]][1]) + 1 for s in sorted(NAMES)] == [18, 13]
-
-
 def test_dit_tpatch_refusals():
     """the errors of lkgd_dit_patch_rows / lkgd_dit_cfg_ddim_step, plus LKGD_E_SHAPE unless p_t == 2 and F % p_t == 0; host memory
     stands in for device pointers: a refused call never launches, so nothing dereferences them"""
-    from lkgd_amd import _lib
-    lib, h = _lib.lib(), Host()
-    hp = h.p
-
-    def patch(**kw):
-        a = dict(lat=hp, f32=0, img=hp, B=1, F=4, C=16, H=8, W=12, p=2, p_t=2, out=hp, ld=256)
-        a.update(kw)
-        return lib.lkgd_dit_patch_rows_t(a["lat"], a["f32"], a["img"], a["B"], a["F"], a["C"], a["H"], a["W"], a["p"], a["p_t"], a["out"],
-                                         a["ld"], None)
-
-    def step(**kw):
-        a = dict(noise=hp, ld=128, lat=hp, f32=1, B=1, F=4, C=16, H=8, W=12, p=2, p_t=2, cfg=2)
-        a.update(kw)
-        return lib.lkgd_dit_cfg_ddim_step_t(a["noise"], a["ld"], a["lat"], a["f32"], a["B"], a["F"], a["C"], a["H"], a["W"], a["p"], a["p_t"],
-                                            a["cfg"], 3.0, 0.9, 0.1, 0.8, 0.6, None)
-    assert patch(lat=None) == NULL and patch(out=None) == NULL
-    assert step(noise=None) == NULL and step(lat=None) == NULL
-    for fn in (patch, step):
-        for kw in (dict(p=1), dict(p=4), dict(W=13), dict(H=7), dict(B=0), dict(F=0), dict(C=0), dict(C=3), dict(ld=120),
-                   dict(ld=260),                      # p = 1, odd W, odd H, empty, C * 4 % 8, short ld, ld % 8
+    hp = Host().p
+    patch = entry("lkgd_dit_patch_rows_t", latents=hp, latents_is_f32=0, image_latents=hp, B=1, F=4, C=16, H=8, W=12, p=2, p_t=2,
+                  rows_out=hp, ldp=256)
+    step = entry("lkgd_dit_cfg_ddim_step_t", noise_rows=hp, ldn=128, latents=hp, latents_is_f32=1, B=1, F=4, C=16, H=8, W=12, p=2, p_t=2,
+                 cfg=2, guidance=3.0, a=0.9, b=0.1, sqrt_alpha=0.8, sqrt_beta=0.6)
+    assert patch(latents=None) == NULL and patch(rows_out=None) == NULL
+    assert step(noise_rows=None) == NULL and step(latents=None) == NULL
+    for name, fn, ld in (("patch", patch, "ldp"), ("step", step, "ldn")):
+        for kw in (dict(p=1), dict(p=4), dict(W=13), dict(H=7), dict(B=0), dict(F=0), dict(C=0), dict(C=3), {ld: 120},
+                   {ld: 260},                         # p = 1, odd W, odd H, empty, C * 4 % 8, short ld, ld % 8
                    dict(p_t=1), dict(p_t=0), dict(p_t=4), dict(p_t=3, F=3), dict(F=3), dict(F=5)):      # p_t != 2, F % p_t
-            assert fn(**kw) == SHAPE, (fn.__name__, kw)
-    assert patch(ld=128) == SHAPE                      # 2C channels with image latents: 256 columns
-    assert patch(img=None, ld=120) == SHAPE            # C channels without them: 128
+            assert fn(**kw) == SHAPE, (name, kw)
+    assert patch(ldp=128) == SHAPE                     # 2C channels with image latents: 256 columns
+    assert patch(image_latents=None, ldp=120) == SHAPE     # C channels without them: 128
     assert step(cfg=0) == SHAPE and step(cfg=3) == SHAPE
-    assert patch(out=hp + 8) == ALIGN and step(noise=hp + 2) == ALIGN
-    assert patch(lat=None, p_t=3) == NULL              # NULL comes first
+    assert patch(rows_out=hp + 8) == ALIGN and step(noise_rows=hp + 2) == ALIGN
+    assert patch(latents=None, p_t=3) == NULL          # NULL comes first
 
 
 # ------------------------------------------------------------------------------------------------------------- configuration

@@ -12,6 +12,7 @@ from safetensors.torch import load_file
 import cogvideox15_oracle as vo
 from cogvideox_support import DEV, DIT_SEED, P, aten_denoise, aten_step, dit_inputs as _inputs, glue_data, hip_twin, loop_inputs, patchify, \
     rel as _rel, unpatchify
+from c_interface import ALIGN, NULL, SHAPE, entry
 from footprint import run_case
 
 gpu = pytest.mark.gpu
@@ -102,11 +103,9 @@ def test_dit_cfg_ddim_step_t_bitwise(shape):
 @gpu
 def test_dit_tpatch_refusals():
     """every refusal returns its code and launches nothing: rows and latents come back untouched"""
-    from test_footprint_gpu import _lib_, _st
+    from test_footprint_gpu import _st
     from lkgd_amd import ops
     from lkgd_amd._lib import LkgdHipError
-    lib = _lib_()
-    NULL, SHAPE, ALIGN = -1, -2, -3
     shape = (1, 4, 16, 8, 12)
     lat, img, noise = (t.to(DEV) for t in glue_data(shape, 5, PT))
     lat = lat.half()
@@ -114,24 +113,17 @@ def test_dit_tpatch_refusals():
     lat0, rows0 = lat.clone(), rows.clone()
     odd = torch.zeros(96 * 128 + 8, dtype=torch.float16, device=DEV)[1:]                 # 2 bytes off a 16-byte boundary
 
-    def patch(**kw):
-        a = dict(lat=lat.data_ptr(), f32=0, img=img.data_ptr(), B=1, F=4, C=16, H=8, W=12, p=2, p_t=2, out=rows.data_ptr(), ld=256)
-        a.update(kw)
-        return lib.lkgd_dit_patch_rows_t(a["lat"], a["f32"], a["img"], a["B"], a["F"], a["C"], a["H"], a["W"], a["p"], a["p_t"], a["out"],
-                                         a["ld"], _st())
-
-    def step(**kw):
-        a = dict(noise=noise.data_ptr(), ld=128, lat=lat.data_ptr(), f32=0, B=1, F=4, C=16, H=8, W=12, p=2, p_t=2, cfg=2)
-        a.update(kw)
-        return lib.lkgd_dit_cfg_ddim_step_t(a["noise"], a["ld"], a["lat"], a["f32"], a["B"], a["F"], a["C"], a["H"], a["W"], a["p"], a["p_t"],
-                                            a["cfg"], 3.0, 0.9, 0.1, 0.8, 0.6, _st())
-    assert patch(lat=None) == NULL and patch(out=None) == NULL and step(noise=None) == NULL and step(lat=None) == NULL
-    for fn in (patch, step):
+    patch = entry("lkgd_dit_patch_rows_t", latents=lat.data_ptr(), latents_is_f32=0, image_latents=img.data_ptr(), B=1, F=4, C=16, H=8,
+                  W=12, p=2, p_t=2, rows_out=rows.data_ptr(), ldp=256, stream=_st())
+    step = entry("lkgd_dit_cfg_ddim_step_t", noise_rows=noise.data_ptr(), ldn=128, latents=lat.data_ptr(), latents_is_f32=0, B=1, F=4,
+                 C=16, H=8, W=12, p=2, p_t=2, cfg=2, guidance=3.0, a=0.9, b=0.1, sqrt_alpha=0.8, sqrt_beta=0.6, stream=_st())
+    assert patch(latents=None) == NULL and patch(rows_out=None) == NULL and step(noise_rows=None) == NULL and step(latents=None) == NULL
+    for name, fn, ld in (("patch", patch, "ldp"), ("step", step, "ldn")):
         for kw in (dict(p_t=1), dict(p_t=3), dict(p_t=4), dict(F=3), dict(F=5), dict(F=0), dict(p=1), dict(p=4), dict(W=13), dict(H=7),
-                   dict(B=0), dict(C=0), dict(C=3), dict(ld=120), dict(ld=260)):
-            assert fn(**kw) == SHAPE, (fn.__name__, kw)
-    assert patch(ld=128) == SHAPE and step(cfg=0) == SHAPE and step(cfg=3) == SHAPE
-    assert patch(out=odd.data_ptr()) == ALIGN and step(noise=odd.data_ptr()) == ALIGN
+                   dict(B=0), dict(C=0), dict(C=3), {ld: 120}, {ld: 260}):
+            assert fn(**kw) == SHAPE, (name, kw)
+    assert patch(ldp=128) == SHAPE and step(cfg=0) == SHAPE and step(cfg=3) == SHAPE
+    assert patch(rows_out=odd.data_ptr()) == ALIGN and step(noise_rows=odd.data_ptr()) == ALIGN
     torch.cuda.synchronize()
     assert torch.equal(lat, lat0) and torch.equal(rows, rows0)
     # the Python side's own errors
@@ -146,18 +138,6 @@ def test_dit_tpatch_refusals():
 
 
 # --------------------------------------------------------------------------------------------------------- footprint cases
-def test_footprint_registry_covers_every_dit_tpatch_symbol():
-    from lkgd_amd import _lib
-    assert set(FOOTPRINT) == set(_lib.DIT_TPATCH_SYMBOLS)
-    for name, cases in FOOTPRINT.items():
-        assert cases, name
-        for c in cases:
-            fn = globals().get(c)
-            assert callable(fn), f"{name}: no test {c} in this module"
-            marks = [m.name for m in getattr(fn, "pytestmark", [])]
-            assert "gpu" in marks and "skip" not in marks and "xfail" not in marks and "slow" not in marks, (name, c, marks)
-
-
 @gpu
 @pytest.mark.parametrize("shape,f32,with_img", [((1, 4, 16, 8, 12), 0, 1), ((2, 2, 16, 4, 6), 1, 1), ((1, 2, 2, 4, 4), 0, 0)])
 def test_dit_patch_rows_t_footprint(shape, f32, with_img):

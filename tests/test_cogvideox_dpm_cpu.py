@@ -1,80 +1,43 @@
-"""Host side of the CogVideoX DPM-Solver++ path without a GPU: include/lkgd_hip_dit_dpm.h == ``_lib.DIT_DPM_SYMBOLS`` == the library, and
-the two entry points' refusals; ``CogVideoXDPMScheduler.coefficients`` against tests/dpm_oracle.py and the known answers of the
-infinite cases; its ``step`` on CPU tensors against the fp64 oracle and its generator draws; ``scheduler_from_config``; the
+"""Host side of the CogVideoX DPM-Solver++ path without a GPU: the two entry points' refusals; ``CogVideoXDPMScheduler.coefficients``
+against tests/dpm_oracle.py and the known answers of the infinite cases; its ``step`` on CPU tensors against the fp64 oracle and its generator draws; ``scheduler_from_config``; the
 refusals of ``denoise`` and ``DistDiTDenoiser``."""
 import json
 import math
-import os
-import re
 
 import pytest
 import torch
 
 import dpm_oracle as do
-from cogvideox_support import REPO, Host, declared as _declared, tiny_cpu_model
+from c_interface import ALIGN, NULL, SHAPE, Host, entry
+from cogvideox_support import tiny_cpu_model
 
-NAMES = {"lkgd_dit_cfg_dpm_step", "lkgd_dit_cfg_dpm_step_t"}
-OK, NULL, SHAPE, ALIGN = 0, -1, -2, -3
 STEPS = (4, 6, 50)
 
 
 # ------------------------------------------------------------------------------------------------------------ the C interface
-def test_dit_dpm_symbols_agree_three_ways():
-    """header == table == exactly the two names, disjoint from every other table of _lib and every other header, exported by the
-    built library with the table's signature, and declared with as many parameters as the table binds"""
-    from lkgd_amd import _lib
-    hdr = open(os.path.join(REPO, "include", "lkgd_hip_dit_dpm.h")).read()
-    declared = _declared("lkgd_hip_dit_dpm.h")
-    assert declared == set(_lib.DIT_DPM_SYMBOLS) == NAMES, declared ^ set(_lib.DIT_DPM_SYMBOLS)
-    tables = {k: v for k, v in vars(_lib).items() if k.endswith("SYMBOLS") and isinstance(v, dict)}
-    assert len(tables) >= 8 and "DIT_DPM_SYMBOLS" in tables
-    for name, other in tables.items():
-        if name != "DIT_DPM_SYMBOLS":
-            assert not declared & set(other), name
-    for h in sorted(os.listdir(os.path.join(REPO, "include"))):
-        if h != "lkgd_hip_dit_dpm.h":
-            assert not declared & _declared(h), h
-    lib = _lib.lib()
-    for s, (res, args) in _lib.DIT_DPM_SYMBOLS.items():
-        fn = getattr(lib, s)
-        assert fn.restype is res and list(fn.argtypes) == list(args), s
-        decl = re.search(r"^int %s\s*\(([^;]*)\);" % s, hdr, re.M | re.S).group(1)
-        assert len(re.sub(r"/\*.*?\*/", "", decl).split(",")) == len(args), s
-    # the DDIM step's arguments (17, 18) without a, b (- 2), plus x0_state, eps, order, m1..m4, mn (+ 8)
-    assert [len(_lib.DIT_DPM_SYMBOLS[s][1]) for s in sorted(NAMES)] == [23, 24]
-    assert len(_lib.DIT_LOOP_SYMBOLS["lkgd_dit_cfg_ddim_step"][1]) + 6 == 23
-    assert len(_lib.DIT_TPATCH_SYMBOLS["lkgd_dit_cfg_ddim_step_t"][1]) + 6 == 24
-
-
-def _step_caller(lib, h, temporal):
-    def step(**kw):
-        a = dict(noise=h.p, ld=128 if temporal else 64, lat=h.p, f32=1, x0=h.p, eps=h.p, B=1, F=4, C=16, H=8, W=12, p=2, p_t=2, cfg=2,
-                 order=2, mn=0.7)
-        a.update(kw)
-        head = (a["noise"], a["ld"], a["lat"], a["f32"], a["x0"], a["eps"], a["B"], a["F"], a["C"], a["H"], a["W"], a["p"])
-        tail = (a["cfg"], a["order"], 3.0, 0.8, 0.6, 0.5, -0.35, 1.4, 0.4, a["mn"], None)
-        if temporal:
-            return lib.lkgd_dit_cfg_dpm_step_t(*head, a["p_t"], *tail)
-        return lib.lkgd_dit_cfg_dpm_step(*head, *tail)
-    return step
+def _step_caller(h, temporal):
+    common = dict(noise_rows=h.p, latents=h.p, latents_is_f32=1, x0_state=h.p, eps=h.p, B=1, F=4, C=16, H=8, W=12, p=2, cfg=2, order=2,
+                  guidance=3.0, sqrt_alpha=0.8, sqrt_beta=0.6, m1=0.5, m2=-0.35, m3=1.4, m4=0.4, mn=0.7)
+    if temporal:
+        return entry("lkgd_dit_cfg_dpm_step_t", ldn=128, p_t=2, **common)
+    return entry("lkgd_dit_cfg_dpm_step", ldn=64, **common)
 
 
 @pytest.mark.parametrize("temporal", [False, True])
 def test_dit_dpm_refusals(temporal):
     """one case per refusal of include/lkgd_hip_dit_dpm.h; host memory stands in for device pointers: a refused call never
     launches, so nothing dereferences them"""
-    from lkgd_amd import _lib
     h = Host()
-    step = _step_caller(_lib.lib(), h, temporal)
+    step = _step_caller(h, temporal)
     width = 128 if temporal else 64
     # LKGD_E_NULL
-    assert step(noise=None) == NULL and step(lat=None) == NULL and step(x0=None) == NULL
+    assert step(noise_rows=None) == NULL and step(latents=None) == NULL and step(x0_state=None) == NULL
     assert step(eps=None) == NULL                                  # mn != 0 needs the noise
     assert step(eps=None, mn=float("nan")) == NULL                 # NaN is not 0
-    assert step(eps=None, mn=0.0, lat=None) == NULL
+    assert step(eps=None, mn=0.0, latents=None) == NULL
     # LKGD_E_SHAPE: what dit_shape_ok refuses - p = 1, 4, odd W, odd H, empty, C * 4 % 8, short ld, ld % 8
-    for kw in (dict(p=1), dict(p=4), dict(W=13), dict(H=7), dict(B=0), dict(F=0), dict(C=0), dict(C=3), dict(ld=width - 8),
-               dict(ld=width + 4)):
+    for kw in (dict(p=1), dict(p=4), dict(W=13), dict(H=7), dict(B=0), dict(F=0), dict(C=0), dict(C=3), dict(ldn=width - 8),
+               dict(ldn=width + 4)):
         assert step(**kw) == SHAPE, kw
     if temporal:
         for kw in (dict(p_t=1), dict(p_t=0), dict(p_t=4), dict(p_t=3, F=3), dict(F=3), dict(F=5)):      # p_t != 2, F % p_t
@@ -82,10 +45,10 @@ def test_dit_dpm_refusals(temporal):
     for kw in (dict(cfg=0), dict(cfg=3), dict(order=0), dict(order=3)):
         assert step(**kw) == SHAPE, kw
     # LKGD_E_ALIGN: rows not 16 bytes, x0_state not 4 bytes aligned
-    assert step(noise=h.p + 2) == ALIGN and step(noise=h.p + 8) == ALIGN
-    assert step(x0=h.p + 2) == ALIGN and step(x0=h.p + 1) == ALIGN
+    assert step(noise_rows=h.p + 2) == ALIGN and step(noise_rows=h.p + 8) == ALIGN
+    assert step(x0_state=h.p + 2) == ALIGN and step(x0_state=h.p + 1) == ALIGN
     # the order of the checks: NULL, then SHAPE, then ALIGN
-    assert step(x0=None, cfg=3, noise=None) == NULL and step(cfg=3, noise=h.p + 2) == SHAPE
+    assert step(x0_state=None, cfg=3, noise_rows=None) == NULL and step(cfg=3, noise_rows=h.p + 2) == SHAPE
 
 
 # ------------------------------------------------------------------------------------------------------------- coefficients

@@ -141,18 +141,6 @@ def test_dit_cfg_dpm_step_misses_the_decoys(f32):
 
 
 # --------------------------------------------------------------------------------------------------------- footprint cases
-def test_footprint_registry_covers_every_dit_dpm_symbol():
-    from lkgd_amd import _lib
-    assert set(FOOTPRINT) == set(_lib.DIT_DPM_SYMBOLS)
-    for name, cases in FOOTPRINT.items():
-        assert cases, name
-        for c in cases:
-            fn = globals().get(c)
-            assert callable(fn), f"{name}: no test {c} in this module"
-            marks = [m.name for m in getattr(fn, "pytestmark", [])]
-            assert "gpu" in marks and "skip" not in marks and "xfail" not in marks and "slow" not in marks, (name, c, marks)
-
-
 def _footprint(shape, f32, cfg, order, noisy, p_t):
     """the noise rows between NaN guards and gaps, eps between NaN guards, the latents and x0_state - inputs AND outputs - between
     pattern guards: the call writes the two and nothing else, and NaN next to every operand changes nothing"""

@@ -1,49 +1,19 @@
-"""Host side of the CogVideoX loop kernels without a GPU: include/lkgd_hip_dit_loop.h == ``_lib.DIT_LOOP_SYMBOLS`` == the library;
-the three entry points refuse bad arguments with the documented codes before any launch; ``pack_lk_tokens`` packs the 18
-operands of the DiT's latent-knowledge fuse; ``fused_text`` has no CPU path; nothing under lkgd_amd/ calls rocFFT or ATen's
-interpolation any more."""
+"""Host side of the CogVideoX loop kernels without a GPU: the three entry points refuse bad arguments with the documented codes before any
+launch; ``pack_lk_tokens`` packs the 18 operands of the DiT's latent-knowledge fuse; ``fused_text`` has no CPU path; nothing under
+lkgd_amd/ calls rocFFT or ATen's interpolation any more."""
 import ctypes as C
 import glob
 import os
-import re
 
 import pytest
 import torch
 
-from cogvideox_support import REPO, Host as _Host, declared as _declared, tiny_cpu_model
-
-NAMES = {"lkgd_lk_fuse_tokens", "lkgd_dit_patch_rows", "lkgd_dit_cfg_ddim_step"}
-OK, NULL, SHAPE, ALIGN = 0, -1, -2, -3
-
-
-def test_dit_loop_symbols_agree_three_ways():
-    """header == table == exactly the three names, disjoint from the other four tables and the other four headers, exported by the
-    built library with the table's signature, and declared with as many parameters as the table binds"""
-    from lkgd_amd import _lib
-    hdr = open(os.path.join(REPO, "include", "lkgd_hip_dit_loop.h")).read()
-    declared = _declared("lkgd_hip_dit_loop.h")
-    assert declared == set(_lib.DIT_LOOP_SYMBOLS) == NAMES, declared ^ set(_lib.DIT_LOOP_SYMBOLS)
-    for other in (_lib.SYMBOLS, _lib.WINDOW_SYMBOLS, _lib.DIT_SYMBOLS, _lib.DEBUG_SYMBOLS):
-        assert not declared & set(other)
-    for h in ("lkgd_hip.h", "lkgd_hip_window.h", "lkgd_hip_dit.h", "lkgd_hip_debug.h"):
-        assert not declared & _declared(h), h
-    lib = _lib.lib()
-    for s, (res, args) in _lib.DIT_LOOP_SYMBOLS.items():
-        fn = getattr(lib, s)
-        assert fn.restype is res and list(fn.argtypes) == list(args), s
-        decl = re.search(r"^int %s\s*\(([^;]*)\);" % s, hdr, re.M | re.S).group(1)
-        assert len(re.sub(r"/\*.*?\*/", "", decl).split(",")) == len(args), s
-    assert [len(_lib.DIT_LOOP_SYMBOLS[s][1]) for s in sorted(NAMES)] == [17, 12, 11]
-
+from c_interface import ALIGN, NULL, SHAPE, Host, entry
+from cogvideox_support import REPO, tiny_cpu_model
 
 def test_lk_fuse_tokens_refusals():
-    from lkgd_amd import _lib
-    lib, h = _lib.lib(), _Host()
-
-    def call(**kw):
-        a = dict(e=h.p, lde=4096, d=h.p, f=h.p, B=2, L=5, Bd=1, w=h.w, out=h.p, ldo=4096)
-        a.update(kw)
-        return lib.lkgd_lk_fuse_tokens(a["e"], a["lde"], a["d"], a["f"], a["B"], a["L"], a["Bd"], a["w"], a["out"], a["ldo"], None)
+    h = Host()
+    call = entry("lkgd_lk_fuse_tokens", e=h.p, lde=4096, d=h.p, f=h.p, B=2, L=5, Bd=1, w=h.w, out=h.p, ldo=4096)
     for k in ("e", "d", "f", "w", "out"):
         assert call(**{k: None}) == NULL, k
     for i in (0, 7, 17):
@@ -61,29 +31,21 @@ def test_lk_fuse_tokens_refusals():
 
 
 def test_dit_glue_refusals():
-    from lkgd_amd import _lib
-    lib, h = _lib.lib(), _Host()
-
-    def patch(**kw):
-        a = dict(lat=h.p, f32=0, img=h.p, B=1, F=3, C=16, H=8, W=12, p=2, out=h.p, ld=128)
-        a.update(kw)
-        return lib.lkgd_dit_patch_rows(a["lat"], a["f32"], a["img"], a["B"], a["F"], a["C"], a["H"], a["W"], a["p"], a["out"], a["ld"], None)
-
-    def step(**kw):
-        a = dict(noise=h.p, ld=64, lat=h.p, f32=1, B=1, F=3, C=16, H=8, W=12, p=2, cfg=2)
-        a.update(kw)
-        return lib.lkgd_dit_cfg_ddim_step(a["noise"], a["ld"], a["lat"], a["f32"], a["B"], a["F"], a["C"], a["H"], a["W"], a["p"], a["cfg"],
-                                          3.0, 0.9, 0.1, 0.8, 0.6, None)
-    assert patch(lat=None) == NULL and patch(out=None) == NULL
-    assert step(noise=None) == NULL and step(lat=None) == NULL
-    for fn in (patch, step):
-        for kw in (dict(p=1), dict(p=4), dict(W=13), dict(H=7), dict(B=0), dict(F=0), dict(C=0), dict(C=3), dict(ld=56),
-                   dict(ld=132)):                      # p = 1, odd W, odd H, empty, C * 4 % 8, short ld, ld % 8
-            assert fn(**kw) == SHAPE, (fn.__name__, kw)
-    assert patch(ld=64) == SHAPE                       # 2C channels with image latents: 128 columns
-    assert patch(img=None, ld=56) == SHAPE             # C channels without them: 64
+    h = Host()
+    patch = entry("lkgd_dit_patch_rows", latents=h.p, latents_is_f32=0, image_latents=h.p, B=1, F=3, C=16, H=8, W=12, p=2, rows_out=h.p,
+                  ldp=128)
+    step = entry("lkgd_dit_cfg_ddim_step", noise_rows=h.p, ldn=64, latents=h.p, latents_is_f32=1, B=1, F=3, C=16, H=8, W=12, p=2, cfg=2,
+                 guidance=3.0, a=0.9, b=0.1, sqrt_alpha=0.8, sqrt_beta=0.6)
+    assert patch(latents=None) == NULL and patch(rows_out=None) == NULL
+    assert step(noise_rows=None) == NULL and step(latents=None) == NULL
+    for name, fn, ld in (("patch", patch, "ldp"), ("step", step, "ldn")):
+        for kw in (dict(p=1), dict(p=4), dict(W=13), dict(H=7), dict(B=0), dict(F=0), dict(C=0), dict(C=3), {ld: 56},
+                   {ld: 132}):                         # p = 1, odd W, odd H, empty, C * 4 % 8, short ld, ld % 8
+            assert fn(**kw) == SHAPE, (name, kw)
+    assert patch(ldp=64) == SHAPE                      # 2C channels with image latents: 128 columns
+    assert patch(image_latents=None, ldp=56) == SHAPE  # C channels without them: 64
     assert step(cfg=0) == SHAPE and step(cfg=3) == SHAPE
-    assert patch(out=h.p + 8) == ALIGN and step(noise=h.p + 2) == ALIGN
+    assert patch(rows_out=h.p + 8) == ALIGN and step(noise_rows=h.p + 2) == ALIGN
 
 
 def test_pack_lk_tokens_shapes_and_hamilton():

@@ -224,18 +224,6 @@ def test_forward_rows_shares_one_copy_of_the_patch_rows(lk):
 
 
 # --------------------------------------------------------------------------------------------------------- footprint cases
-def test_footprint_registry_covers_every_dit_loop_symbol():
-    from lkgd_amd import _lib
-    assert set(FOOTPRINT) == set(_lib.DIT_LOOP_SYMBOLS)
-    for name, cases in FOOTPRINT.items():
-        assert cases, name
-        for c in cases:
-            fn = globals().get(c)
-            assert callable(fn), f"{name}: no test {c} in this module"
-            marks = [m.name for m in getattr(fn, "pytestmark", [])]
-            assert "gpu" in marks and "skip" not in marks and "xfail" not in marks and "slow" not in marks, (name, c, marks)
-
-
 @gpu
 @pytest.mark.parametrize("B,L,Bd", [(2, 5, 2), (1, 9, 1)])
 def test_lk_fuse_tokens_footprint(B, L, Bd):

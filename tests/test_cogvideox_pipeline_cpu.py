@@ -1,11 +1,10 @@
-"""``CogVideoXImageToVideoPipeline`` and ``VideoProcessor`` without a GPU: header, symbol table and library of include/lkgd_hip_video.h
-agree; both entry points refuse before launching; ``check_inputs`` raises the reference's errors
+"""``CogVideoXImageToVideoPipeline`` and ``VideoProcessor`` without a GPU: both entry points of include/lkgd_hip_video.h
+refuse before launching; ``check_inputs`` raises the reference's errors
 (pipeline_cogvideox_image2video.py:465-527); the 1.5 frame padding (:779-786); every argument the loop cannot honour raises and names
 itself; ``from_pretrained`` of a directory assembled from tiny components; ``VideoProcessor`` on CPU data is ``VaeImageProcessor`` /
 ``tensor2vid``."""
 import json
 import os
-import re
 from types import SimpleNamespace
 
 import numpy as np
@@ -13,47 +12,16 @@ import pytest
 import torch
 
 import cogvideox_vae_encoder_oracle as eo
-from cogvideox_support import REPO, Host, declared, tiny_cpu_model
+from c_interface import ALIGN, MODE, NULL, SHAPE, Host, entry
+from cogvideox_support import tiny_cpu_model
 from t5_support import TINY_A
 
-NAMES = {"lkgd_video_postprocess", "lkgd_image_preprocess"}
-NULL, SHAPE, ALIGN, MODE = -1, -2, -3, -4
 
-
-# --------------------------------------------------------------------------------------------------------------- exports
-def test_video_symbols_agree_three_ways():
-    from lkgd_amd import _lib
-    hdr = open(os.path.join(REPO, "include", "lkgd_hip_video.h")).read()
-    assert declared("lkgd_hip_video.h") == set(_lib.VIDEO_SYMBOLS) == NAMES
-    for t in dir(_lib):
-        if t.endswith("SYMBOLS") and t != "VIDEO_SYMBOLS":
-            assert not NAMES & set(getattr(_lib, t)), t
-    for h in sorted(os.listdir(os.path.join(REPO, "include"))):
-        if h != "lkgd_hip_video.h":
-            assert not NAMES & declared(h), h
-    lib = _lib.lib()
-    nargs = {"lkgd_video_postprocess": 9, "lkgd_image_preprocess": 7}
-    for s, (res, args) in _lib.VIDEO_SYMBOLS.items():
-        fn = getattr(lib, s)
-        assert fn.restype is res and list(fn.argtypes) == list(args), s
-        decl = re.search(r"^int %s\s*\(([^;]*)\);" % s, hdr, re.M | re.S).group(1)
-        assert len(decl.split(",")) == len(args) == nargs[s], s
-    from lkgd_amd import ops
-    modes = dict(re.findall(r"(LKGD_VIDEO_\w+) = (\d)", hdr))
-    assert {k: int(v) for k, v in modes.items()} == {"LKGD_VIDEO_U8": ops.VIDEO_U8, "LKGD_VIDEO_F32": ops.VIDEO_F32,
-                                                      "LKGD_VIDEO_F16": ops.VIDEO_F16}
-
-
+# -------------------------------------------------------------------------------------------------------------- refusals
 def test_postprocess_refuses_before_launching():
     """every refusal include/lkgd_hip_video.h lists; host pointers: a refused call launches nothing"""
-    from lkgd_amd import _lib
-    lib, h = _lib.lib(), Host()
-
-    def call(**kw):
-        a = dict(x=h.p, out=h.p + 2048, mode=0, B=1, C=3, T=2, H=4, W=8)
-        a.update(kw)
-        return lib.lkgd_video_postprocess(a["x"], a["out"], a["mode"], a["B"], a["C"], a["T"], a["H"], a["W"], None)
-
+    h = Host()
+    call = entry("lkgd_video_postprocess", x=h.p, out=h.p + 2048, mode=0, B=1, C=3, T=2, H=4, W=8)
     for k in ("x", "out"):
         assert call(**{k: None}) == NULL, k
     for kw in (dict(B=0), dict(C=0), dict(T=0), dict(H=0), dict(W=0), dict(B=-1), dict(C=-3), dict(T=-1), dict(H=-4), dict(W=-8),
@@ -66,14 +34,8 @@ def test_postprocess_refuses_before_launching():
 
 
 def test_preprocess_refuses_before_launching():
-    from lkgd_amd import _lib
-    lib, h = _lib.lib(), Host()
-
-    def call(**kw):
-        a = dict(u=h.p, out=h.p + 2048, N=1, H=4, W=8, C=3)
-        a.update(kw)
-        return lib.lkgd_image_preprocess(a["u"], a["out"], a["N"], a["H"], a["W"], a["C"], None)
-
+    h = Host()
+    call = entry("lkgd_image_preprocess", u=h.p, out=h.p + 2048, N=1, H=4, W=8, C=3)
     for k in ("u", "out"):
         assert call(**{k: None}) == NULL, k
     for kw in (dict(N=0), dict(H=0), dict(W=0), dict(C=0), dict(N=-1), dict(H=-4), dict(W=-8), dict(C=-3), dict(C=5),

@@ -13,6 +13,7 @@ from safetensors.torch import load_file
 
 import cogvideox_rope_oracle as ro
 from cogvideox_support import DEV, DIT_SEED, dit_inputs as _inputs, hip_twin, loop_inputs, rel as _rel
+from c_interface import ALIGN, NULL, SHAPE, entry
 from footprint import run_case
 
 gpu = pytest.mark.gpu
@@ -148,18 +149,6 @@ def test_qk_norm_rope_three_loop_iterations():
             assert bool((qw[split:] != nq[split:]).any(dim=1).all())        # on every one of them
 
 
-def test_footprint_registry_covers_every_dit_symbol():
-    from lkgd_amd import _lib
-    assert set(FOOTPRINT) == set(_lib.DIT_SYMBOLS)
-    for name, cases in FOOTPRINT.items():
-        assert cases, name
-        for c in cases:
-            fn = globals().get(c)
-            assert callable(fn), f"{name}: no test {c} in this module"
-            marks = [m.name for m in getattr(fn, "pytestmark", [])]
-            assert "gpu" in marks and "skip" not in marks and "xfail" not in marks and "slow" not in marks, (name, c, marks)
-
-
 @gpu
 @pytest.mark.parametrize("heads,rpb,split,norm_only", [(2, 5, 2, 0), (11, 37, 2, 0), (48, 5, 0, 0), (30, 37, 37, 0), (8, 37, 2, 1)])
 def test_qk_norm_rope_footprint(heads, rpb, split, norm_only):
@@ -197,33 +186,26 @@ def test_qk_norm_rope_footprint(heads, rpb, split, norm_only):
 @gpu
 def test_qk_norm_rope_refusals():
     """every refusal returns its code and launches nothing: q and k come back untouched"""
-    from test_footprint_gpu import _lib_, _st
+    from test_footprint_gpu import _st
     from lkgd_amd import ops
     from lkgd_amd._lib import LkgdHipError
-    lib = _lib_()
     heads, rpb, split = 3, 5, 2
     q, k, aff, cos, sin = (_dev(t) for t in _qk_case(heads, rpb, split, 1))
     wide = torch.zeros(10, heads * 64 + 4, dtype=torch.float16, device=DEV)          # a row stride that is no multiple of 8
     odd = torch.zeros(10 * heads * 64 + 8, dtype=torch.float16, device=DEV)[1:]      # 2 bytes off a 16-byte boundary
     oddf = torch.zeros(3 * 64 + 8, dtype=torch.float32, device=DEV)[1:]
     q0, k0 = q.clone(), k.clone()
-    NULL, SHAPE, ALIGN = -1, -2, -3
-
-    def call(**kw):
-        a = dict(q=q.data_ptr(), ldq=heads * 64, k=k.data_ptr(), ldk=heads * 64, rows=10, heads=heads, gq=aff[0].data_ptr(),
-                 bq=aff[1].data_ptr(), gk=aff[2].data_ptr(), bk=aff[3].data_ptr(), cos=cos.data_ptr(), sin=sin.data_ptr(), ldt=64,
-                 rpb=rpb, split=split)
-        a.update(kw)
-        return lib.lkgd_qk_norm_rope(a["q"], a["ldq"], a["k"], a["ldk"], a["rows"], a["heads"], a["gq"], a["bq"], a["gk"], a["bk"], 1e-6,
-                                     a["cos"], a["sin"], a["ldt"], a["rpb"], a["split"], _st())
-    for kw, rc in ((dict(q=None), NULL), (dict(k=None), NULL), (dict(gq=None), NULL), (dict(bk=None), NULL),
-                   (dict(cos=None), NULL), (dict(sin=None), NULL),                      # exactly one table
+    call = entry("lkgd_qk_norm_rope", q=q.data_ptr(), ldq=heads * 64, k=k.data_ptr(), ldk=heads * 64, rows=10, heads=heads,
+                 gamma_q=aff[0].data_ptr(), beta_q=aff[1].data_ptr(), gamma_k=aff[2].data_ptr(), beta_k=aff[3].data_ptr(), eps=1e-6,
+                 cos_t=cos.data_ptr(), sin_t=sin.data_ptr(), ldt=64, rows_per_batch=rpb, split=split, stream=_st())
+    for kw, rc in ((dict(q=None), NULL), (dict(k=None), NULL), (dict(gamma_q=None), NULL), (dict(beta_k=None), NULL),
+                   (dict(cos_t=None), NULL), (dict(sin_t=None), NULL),                      # exactly one table
                    (dict(heads=0), SHAPE), (dict(heads=-1), SHAPE), (dict(rows=0), SHAPE), (dict(rows=9), SHAPE),   # rows % rpb
-                   (dict(rpb=0), SHAPE), (dict(split=-1), SHAPE), (dict(split=rpb + 1), SHAPE),
+                   (dict(rows_per_batch=0), SHAPE), (dict(split=-1), SHAPE), (dict(split=rpb + 1), SHAPE),
                    (dict(ldt=56), SHAPE), (dict(ldq=heads * 64 - 8), SHAPE),
                    (dict(q=wide.data_ptr(), ldq=heads * 64 + 4), ALIGN), (dict(k=wide.data_ptr(), ldk=heads * 64 + 4), ALIGN),
                    (dict(q=odd.data_ptr()), ALIGN), (dict(k=odd.data_ptr()), ALIGN),
-                   (dict(cos=oddf.data_ptr()), ALIGN), (dict(sin=oddf.data_ptr()), ALIGN), (dict(ldt=66), ALIGN)):
+                   (dict(cos_t=oddf.data_ptr()), ALIGN), (dict(sin_t=oddf.data_ptr()), ALIGN), (dict(ldt=66), ALIGN)):
         assert call(**kw) == rc, (kw, rc)
     torch.cuda.synchronize()
     assert torch.equal(q, q0) and torch.equal(k, k0)

@@ -1,11 +1,10 @@
 """Host side of the CogVideoX 3-D causal VAE decoder without a GPU: chunk boundaries and frame counts, the spatial norm's frame tables
 against ``F.interpolate``, the K order of ``pack_cconv3`` against ``F.conv3d``, what the GEMM planner answers for the new A-operand mode
 (and that it answers for the existing modes what it answered before the mode existed), state-dict names against the oracle, the
-oracle's own cache rule, the refusals, and header == table == library for the new entry point."""
+oracle's own cache rule, the refusals."""
 import ctypes as C
 import json
 import os
-import re
 
 import numpy as np
 import pytest
@@ -13,9 +12,9 @@ import torch
 import torch.nn.functional as F
 
 import cogvideox_vae_oracle as oc
-from cogvideox_support import REPO, Host, declared
+from c_interface import ALIGN, MODE, NULL, OK, SHAPE, Host, entry
+from cogvideox_support import REPO
 
-OK, NULL, SHAPE, ALIGN, MODE = 0, -1, -2, -3, -4
 A_CCONV3 = 4
 P = 1 << 12          # a non-NULL, 16-byte aligned stand-in: lkgd_gemm_plan with cus != 0 dereferences nothing
 
@@ -305,42 +304,15 @@ def test_refusals_name_what_they_refuse():
     assert callable(pv.decode_latents) and not hasattr(pv.AutoencoderKLCogVideoX, "decode_latents")
 
 
-# -------------------------------------------------------------------------------------------------------------- exports
-def test_cogvae_symbols_agree_three_ways():
-    from lkgd_amd import _lib
-    hdr = open(os.path.join(REPO, "include", "lkgd_hip_cogvae.h")).read()
-    names = declared("lkgd_hip_cogvae.h") - {"lkgd_gemm_f16", "lkgd_groupnorm_stats", "lkgd_groupnorm_stats_cols", "lkgd_groupnorm_apply"}
-    assert names == set(_lib.COGVAE_SYMBOLS) == {"lkgd_spatial_norm3d"}
-    for t in dir(_lib):
-        if t.endswith("SYMBOLS") and t != "COGVAE_SYMBOLS":
-            assert not names & set(getattr(_lib, t)), t
-    lib = _lib.lib()
-    for s, (res, args) in _lib.COGVAE_SYMBOLS.items():
-        fn = getattr(lib, s)
-        assert fn.restype is res and list(fn.argtypes) == list(args), s
-        decl = re.search(r"^int %s\s*\(([^;]*)\);" % s, hdr, re.M | re.S).group(1)
-        assert len(decl.split(",")) == len(args) == 20, s
-    main = open(os.path.join(REPO, "include", "lkgd_hip.h")).read()
-    assert re.search(r"LKGD_A_CCONV3\s*=\s*4\b", main)
-    from lkgd_amd import ops
-    assert ops.A_CCONV3 == 4
-
-
+# ------------------------------------------------------------------------------------------------------------- refusals
 def test_spatial_norm_refuses_before_launching():
-    from lkgd_amd import _lib
-    lib, h = _lib.lib(), Host()
-
-    def call(**kw):
-        a = dict(f=h.p, ldf=64, stats=h.p, gamma=h.p, beta=h.p, yb=h.p, ldyb=128, tmap=h.p, out=h.p, ldo=64, obr=2 * 6 * 10, B=1, T=2,
-                 H=6, W=10, C=64, Tz=2, sh=1, act=1)
-        a.update(kw)
-        return lib.lkgd_spatial_norm3d(a["f"], a["ldf"], a["stats"], a["gamma"], a["beta"], a["yb"], a["ldyb"], a["tmap"], a["out"],
-                                       a["ldo"], a["obr"], a["B"], a["T"], a["H"], a["W"], a["C"], a["Tz"], a["sh"], a["act"], None)
-
+    h = Host()
+    call = entry("lkgd_spatial_norm3d", f=h.p, ldf=64, stats=h.p, gamma=h.p, beta=h.p, yb=h.p, ldyb=128, tmap=h.p, out=h.p, ldo=64,
+                 out_batch_rows=2 * 6 * 10, B=1, T=2, H=6, W=10, C=64, Tz=2, sh=1, act=1)
     for k in ("f", "stats", "gamma", "beta", "yb", "tmap", "out"):
         assert call(**{k: None}) == NULL, k
     for kw in (dict(B=0), dict(T=0), dict(Tz=0), dict(C=32), dict(C=96), dict(sh=4), dict(sh=-1), dict(H=7), dict(W=9), dict(act=2),
-               dict(ldf=56), dict(ldo=56), dict(ldyb=120), dict(obr=119), dict(B=1 << 20, obr=1 << 12)):
+               dict(ldf=56), dict(ldo=56), dict(ldyb=120), dict(out_batch_rows=119), dict(B=1 << 20, out_batch_rows=1 << 12)):
         assert call(**kw) == SHAPE, kw
     for kw in (dict(f=h.p + 8), dict(yb=h.p + 8), dict(out=h.p + 8), dict(ldf=68), dict(ldo=68), dict(ldyb=132), dict(gamma=h.p + 8),
                dict(stats=h.p + 4), dict(tmap=h.p + 2)):

@@ -1,8 +1,5 @@
-"""Host side of the CogVideoX 3-D causal VAE encoder without a GPU: header == table == library for the three entry points and their
-refusals, state-dict names against the oracle, which checkpoints build an encoder, frame-batch bounds and pooled frame counts, the
-oracle's own decoys, ``prepare_latents`` / ``retrieve_latents`` on a stub VAE, and the refusals of ``encode``."""
-import os
-import re
+"""Host side of the CogVideoX 3-D causal VAE encoder without a GPU: the refusals of the three entry points, state-dict names against
+the oracle, which checkpoints build an encoder, frame-batch bounds and pooled frame counts, the oracle's own decoys, ``prepare_latents`` / ``retrieve_latents`` on a stub VAE, and the refusals of ``encode``."""
 from types import SimpleNamespace
 
 import pytest
@@ -10,42 +7,14 @@ import torch
 import torch.nn.functional as F
 
 import cogvideox_vae_encoder_oracle as eo
-from cogvideox_support import REPO, Host, declared, rel
-
-OK, NULL, SHAPE, ALIGN = 0, -1, -2, -3
-NAMES = {"lkgd_cogvae_pixel_taps", "lkgd_cogvae_time_pool", "lkgd_cogvae_posterior"}
+from c_interface import ALIGN, NULL, SHAPE, Host, entry
+from cogvideox_support import rel
 
 
-# -------------------------------------------------------------------------------------------------------------- exports
-def test_cogvae_enc_symbols_agree_three_ways():
-    from lkgd_amd import _lib
-    hdr = open(os.path.join(REPO, "include", "lkgd_hip_cogvae_enc.h")).read()
-    assert declared("lkgd_hip_cogvae_enc.h") == set(_lib.COGVAE_ENC_SYMBOLS) == NAMES
-    for t in dir(_lib):
-        if t.endswith("SYMBOLS") and t != "COGVAE_ENC_SYMBOLS":
-            assert not NAMES & set(getattr(_lib, t)), t
-    lib = _lib.lib()
-    nargs = {"lkgd_cogvae_pixel_taps": 11, "lkgd_cogvae_time_pool": 9, "lkgd_cogvae_posterior": 12}
-    for s, (res, args) in _lib.COGVAE_ENC_SYMBOLS.items():
-        fn = getattr(lib, s)
-        assert fn.restype is res and list(fn.argtypes) == list(args), s
-        decl = re.search(r"^int %s\s*\(([^;]*)\);" % s, hdr, re.M | re.S).group(1)
-        assert len(decl.split(",")) == len(args) == nargs[s], s
-    # the decoder's header and the main header are as they were
-    assert declared("lkgd_hip_cogvae.h") - {"lkgd_gemm_f16", "lkgd_groupnorm_stats", "lkgd_groupnorm_stats_cols",
-                                             "lkgd_groupnorm_apply"} == set(_lib.COGVAE_SYMBOLS) == {"lkgd_spatial_norm3d"}
-    assert not NAMES & declared("lkgd_hip.h")
-
-
+# ------------------------------------------------------------------------------------------------------------- refusals
 def test_pixel_taps_refuses_before_launching():
-    from lkgd_amd import _lib
-    lib, h = _lib.lib(), Host()
-
-    def call(**kw):
-        a = dict(x=h.p, out=h.p + 2048, ldo=128, B=1, Cin=3, T=5, H=6, W=10, t0=0, Tc=5)
-        a.update(kw)
-        return lib.lkgd_cogvae_pixel_taps(a["x"], a["out"], a["ldo"], a["B"], a["Cin"], a["T"], a["H"], a["W"], a["t0"], a["Tc"], None)
-
+    h = Host()
+    call = entry("lkgd_cogvae_pixel_taps", x=h.p, out=h.p + 2048, ldo=128, B=1, Cin=3, T=5, H=6, W=10, t0=0, Tc=5)
     for k in ("x", "out"):
         assert call(**{k: None}) == NULL, k
     for kw in (dict(B=0), dict(T=0), dict(H=0), dict(W=0), dict(Tc=0), dict(Cin=0), dict(Cin=5), dict(t0=-1), dict(t0=1), dict(Tc=6),
@@ -56,33 +25,20 @@ def test_pixel_taps_refuses_before_launching():
 
 
 def test_time_pool_refuses_before_launching():
-    from lkgd_amd import _lib
-    lib, h = _lib.lib(), Host()
-
-    def call(**kw):
-        a = dict(inp=h.p, ldi=64, out=h.p + (1 << 20), ldo=64, B=2, T=5, HW=15, C=64)
-        a.update(kw)
-        return lib.lkgd_cogvae_time_pool(a["inp"], a["ldi"], a["out"], a["ldo"], a["B"], a["T"], a["HW"], a["C"], None)
-
-    for k in ("inp", "out"):
+    h = Host()
+    call = entry("lkgd_cogvae_time_pool", in_=h.p, ldi=64, out=h.p + (1 << 20), ldo=64, B=2, T=5, HW=15, C=64)
+    for k in ("in_", "out"):
         assert call(**{k: None}) == NULL, k
     for kw in (dict(B=0), dict(T=0), dict(HW=0), dict(C=0), dict(C=60), dict(ldi=56), dict(ldo=56), dict(B=1 << 12, T=1 << 10, HW=1 << 9),
                dict(out=h.p), dict(out=h.p + 64), dict(out=h.p - 128)):           # the last three: in and out overlap
         assert call(**kw) == SHAPE, kw
-    for kw in (dict(inp=h.p + 8), dict(out=h.p + (1 << 20) + 8), dict(ldi=68), dict(ldo=68)):
+    for kw in (dict(in_=h.p + 8), dict(out=h.p + (1 << 20) + 8), dict(ldi=68), dict(ldo=68)):
         assert call(**kw) == ALIGN, kw
 
 
 def test_posterior_refuses_before_launching():
-    from lkgd_amd import _lib
-    lib, h = _lib.lib(), Host()
-
-    def call(**kw):
-        a = dict(mom=h.p, ldm=32, noise=h.p, mean=h.p, sample=h.p, scale=1.0, B=1, lc=16, T=1, h=6, w=10)
-        a.update(kw)
-        return lib.lkgd_cogvae_posterior(a["mom"], a["ldm"], a["noise"], a["mean"], a["sample"], a["scale"], a["B"], a["lc"], a["T"],
-                                         a["h"], a["w"], None)
-
+    h = Host()
+    call = entry("lkgd_cogvae_posterior", mom=h.p, ldm=32, noise=h.p, mean=h.p, sample=h.p, scale=1.0, B=1, lc=16, T=1, h=6, w=10)
     for k in ("mom", "mean", "sample"):
         assert call(**{k: None}) == NULL, k
     for kw in (dict(B=0), dict(T=0), dict(h=0), dict(w=0), dict(lc=0), dict(lc=12), dict(ldm=24), dict(scale=float("inf")),

@@ -19,6 +19,11 @@ from footprint import run_case
 
 pytestmark = pytest.mark.gpu
 
+#: every name in lkgd_amd._lib.COGVAE_SYMBOLS -> its footprint tests in this module
+FOOTPRINT = {
+    "lkgd_spatial_norm3d": ["test_footprint_spatial_norm"],
+}
+
 GATE = 1e-2
 DECOY_MIN = 10 * GATE
 

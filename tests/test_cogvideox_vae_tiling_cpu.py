@@ -1,6 +1,6 @@
 """Host side of the tiled / sliced CogVideoX VAE without a GPU: diffusers' tile geometry (the table of DESIGN.md section 19) through
 ``decode_tile_geometry`` / ``encode_tile_geometry`` and through the oracle's own expressions, when ``decode`` / ``encode`` tile, the
-switches, the refusals, header == table == library for the two seam entry points and their error codes, and the distances between the
+switches, the refusals, the two seam entry points' error codes, and the distances between the
 oracle's own forms that tests/test_cogvideox_vae_tiling_gpu.py relies on for its decoys.
 
 Distances measured here (fp32 oracle, tiny configuration, tile 48 x 80 pixels = 6 x 10 latents; relative L2 from the tiled truth):
@@ -14,19 +14,15 @@ Distances measured here (fp32 oracle, tiny configuration, tile 48 x 80 pixels = 
       T = 1, 112 x 176                0.740
 The untiled forms lie further than 10 gates (0.1) from the tiled ones and serve as decoys of the GPU parity tests; the two assembly
 decoys lie below that at the decode level and are caught by the bit-exact kernel tests instead."""
-import os
-import re
-
 import pytest
 import torch
 
 import cogvideox_vae_encoder_oracle as eo
 import cogvideox_vae_oracle as oc
 import cogvideox_vae_tiling_oracle as to
-from cogvideox_support import REPO, Host, declared, rel
+from c_interface import ALIGN, NULL, SHAPE, Host, entry
+from cogvideox_support import rel
 
-OK, NULL, SHAPE, ALIGN = 0, -1, -2, -3
-NAMES = {"lkgd_cogvae_tile_blend_planar", "lkgd_cogvae_tile_blend_rows"}
 GATE = 1e-2
 DECOY_MIN = 10 * GATE
 F_H, F_W = 1 / 6, 1 / 5
@@ -205,44 +201,19 @@ def test_config_round_trip_carries_the_sample_size(tmp_path):
     assert (r.tile_sample_min_height, r.tile_latent_min_width) == (384, 85)
 
 
-# --------------------------------------------------------------------------------------------------------------- exports
-def test_cogvae_tile_symbols_agree_three_ways():
-    from lkgd_amd import _lib
-    hdr = open(os.path.join(REPO, "include", "lkgd_hip_cogvae_tile.h")).read()
-    assert declared("lkgd_hip_cogvae_tile.h") == set(_lib.COGVAE_TILE_SYMBOLS) == NAMES
-    for t in dir(_lib):
-        if t.endswith("SYMBOLS") and t != "COGVAE_TILE_SYMBOLS":
-            assert not NAMES & set(getattr(_lib, t)), t
-    for h in sorted(os.listdir(os.path.join(REPO, "include"))):
-        if h != "lkgd_hip_cogvae_tile.h":
-            assert not NAMES & declared(h), h
-    lib = _lib.lib()
-    nargs = {"lkgd_cogvae_tile_blend_planar": 18, "lkgd_cogvae_tile_blend_rows": 23}
-    for s, (res, args) in _lib.COGVAE_TILE_SYMBOLS.items():
-        fn = getattr(lib, s)
-        assert fn.restype is res and list(fn.argtypes) == list(args), s
-        decl = re.search(r"^int %s\s*\(([^;]*)\);" % s, hdr, re.M | re.S).group(1)
-        assert len(decl.split(",")) == len(args) == nargs[s], s
-
-
+# -------------------------------------------------------------------------------------------------------------- refusals
 def planar_refusals():
     """every refusal include/lkgd_hip_cogvae_tile.h lists for the planar entry point; host pointers: a refused call launches nothing"""
-    from lkgd_amd import _lib
-    lib, h = _lib.lib(), Host()
+    h = Host()
     tile_bytes = 2 * 2 * 8 * 16
-
-    def call(**kw):
-        a = dict(tile=h.p, up=h.p + 1024, left=h.p + 2048, out=h.p + 3072, P=2, Yt=8, Xt=16, Yu=8, Xl=16, Y=8, X=16, y0=0, x0=0, ey=2,
-                 ex=8, cy=8, cx=16)
-        a.update(kw)
-        return lib.lkgd_cogvae_tile_blend_planar(a["tile"], a["up"], a["left"], a["out"], a["P"], a["Yt"], a["Xt"], a["Yu"], a["Xl"],
-                                                 a["Y"], a["X"], a["y0"], a["x0"], a["ey"], a["ex"], a["cy"], a["cx"], None)
+    call = entry("lkgd_cogvae_tile_blend_planar", tile=h.p, up=h.p + 1024, left=h.p + 2048, out=h.p + 3072, P=2, Yt=8, Xt=16, Yu=8, Xl=16,
+                 Y=8, X=16, y0=0, x0=0, e_y=2, e_x=8, c_y=8, c_x=16)
 
     for k in ("tile", "out"):
         assert call(**{k: None}) == NULL, k
-    for kw in (dict(P=0), dict(Yt=0), dict(Xt=0), dict(Y=0), dict(X=0), dict(Yu=0), dict(Xl=0), dict(ey=-1), dict(ex=-1), dict(cy=-1),
-               dict(cx=-1), dict(y0=-1), dict(x0=-1),
-               dict(y0=1), dict(x0=8), dict(Y=7), dict(X=15), dict(y0=4, cy=5), dict(x0=8, cx=9),          # the crop leaves out
+    for kw in (dict(P=0), dict(Yt=0), dict(Xt=0), dict(Y=0), dict(X=0), dict(Yu=0), dict(Xl=0), dict(e_y=-1), dict(e_x=-1), dict(c_y=-1),
+               dict(c_x=-1), dict(y0=-1), dict(x0=-1),
+               dict(y0=1), dict(x0=8), dict(Y=7), dict(X=15), dict(y0=4, c_y=5), dict(x0=8, c_x=9),          # the crop leaves out
                dict(up=h.p), dict(up=h.p + tile_bytes - 2), dict(left=h.p + 2), dict(out=h.p + tile_bytes - 2),      # tile overlaps
                dict(out=h.p - 2 * 2 * 8 * 16 + 2), dict(P=1 << 30, Yt=1 << 10)):
         assert call(**kw) == SHAPE, kw
@@ -253,22 +224,15 @@ def planar_refusals():
 
 def rows_refusals():
     """the same for the channels-last entry point"""
-    from lkgd_amd import _lib
-    lib, h = _lib.lib(), Host()
+    h = Host()
     tile_bytes = 2 * 1 * 2 * 4 * 32          # P = 1, 2 x 4 rows of 32 channels
-
-    def call(**kw):
-        a = dict(tile=h.p, ldt=32, up=h.p + 1024, ldu=32, left=h.p + 2048, ldl=32, out=h.p + 3072, ldo=32, P=1, C=32, Yt=2, Xt=4, Yu=2,
-                 Xl=4, Y=2, X=4, y0=0, x0=0, ey=1, ex=2, cy=2, cx=4)
-        a.update(kw)
-        return lib.lkgd_cogvae_tile_blend_rows(a["tile"], a["ldt"], a["up"], a["ldu"], a["left"], a["ldl"], a["out"], a["ldo"], a["P"],
-                                               a["C"], a["Yt"], a["Xt"], a["Yu"], a["Xl"], a["Y"], a["X"], a["y0"], a["x0"], a["ey"],
-                                               a["ex"], a["cy"], a["cx"], None)
+    call = entry("lkgd_cogvae_tile_blend_rows", tile=h.p, ldt=32, up=h.p + 1024, ldu=32, left=h.p + 2048, ldl=32, out=h.p + 3072, ldo=32,
+                 P=1, C=32, Yt=2, Xt=4, Yu=2, Xl=4, Y=2, X=4, y0=0, x0=0, e_y=1, e_x=2, c_y=2, c_x=4)
 
     for k in ("tile", "out"):
         assert call(**{k: None}) == NULL, k
     for kw in (dict(P=0), dict(C=0), dict(C=12), dict(Yt=0), dict(Xt=0), dict(Y=0), dict(X=0), dict(Yu=0), dict(Xl=0), dict(ldt=24),
-               dict(ldu=24), dict(ldl=24), dict(ldo=24), dict(ey=-1), dict(ex=-1), dict(cy=-1), dict(cx=-1), dict(y0=-1), dict(x0=-1),
+               dict(ldu=24), dict(ldl=24), dict(ldo=24), dict(e_y=-1), dict(e_x=-1), dict(c_y=-1), dict(c_x=-1), dict(y0=-1), dict(x0=-1),
                dict(y0=1), dict(x0=1), dict(Y=1), dict(X=3),
                dict(up=h.p + 16), dict(left=h.p + tile_bytes - 16), dict(out=h.p + 256), dict(P=1 << 30, Yt=1 << 10)):
         assert call(**kw) == SHAPE, kw

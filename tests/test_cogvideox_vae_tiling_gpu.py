@@ -127,13 +127,6 @@ def test_rows_kernel_equals_the_torch_loops_bitwise(case):
 
 
 # -------------------------------------------------------------------------------------------------------------- footprint
-def test_footprint_registry_covers_every_tile_symbol():
-    from lkgd_amd import _lib
-    assert set(FOOTPRINT) == set(_lib.COGVAE_TILE_SYMBOLS)
-    for name, cases in FOOTPRINT.items():
-        assert cases and all(c in globals() for c in cases), name
-
-
 def test_refusals_of_both_entry_points():
     assert host.planar_refusals() and host.rows_refusals()
 

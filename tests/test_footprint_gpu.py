@@ -77,7 +77,7 @@ REGISTRY = {
 
 
 def test_registry_covers_every_export():
-    """a new export cannot arrive without a footprint case (in the manner of test_library_exports_every_declared_symbol)"""
+    """a new export cannot arrive without a footprint case (tests/test_c_interface_cpu.py keeps the same rule for every header)"""
     from lkgd_amd import _lib
     assert set(REGISTRY) == set(_lib.SYMBOLS), (sorted(set(_lib.SYMBOLS) - set(REGISTRY)), sorted(set(REGISTRY) - set(_lib.SYMBOLS)))
     exempt = {n for n, v in REGISTRY.items() if isinstance(v, str)}

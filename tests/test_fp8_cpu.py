@@ -1,68 +1,30 @@
-"""Host side of the FP8 mode without a GPU: include/lkgd_hip_fp8.h == ``_lib.FP8_SYMBOLS`` == the library; the four entry points refuse
-bad arguments with the documented codes before any launch; ``quantize_weight`` against the independent restatement of
-tests/fp8_oracle.py; ``quantize_to_float8`` / ``dequantize`` state, the refusals and LKGD_DIT_FP8; the fake-quant twin against its fp32
-original at ``TINY_DIT`` (the distance ``e_q`` the GPU rule is built on)."""
-import os
-import re
-
+"""Host side of the FP8 mode without a GPU: the four entry points refuse bad arguments with the documented codes before any launch;
+``quantize_weight`` against the independent restatement of tests/fp8_oracle.py; ``quantize_to_float8`` / ``dequantize`` state, the
+refusals and LKGD_DIT_FP8; the fake-quant twin against its fp32 original at ``TINY_DIT`` (the distance ``e_q`` the GPU rule is built
+on)."""
 import pytest
 import torch
 
 import fp8_oracle as fo
-from cogvideox_support import REPO, Host as _Host, declared as _declared, dit_inputs as _inputs, tiny_cpu_model as _tiny_cpu_model, \
+from c_interface import ALIGN, NULL, SHAPE, Host, entry
+from cogvideox_support import dit_inputs as _inputs, tiny_cpu_model as _tiny_cpu_model, \
     tiny_oracle as _oracle
 
-NAMES = {"lkgd_quant_rows_fp8", "lkgd_gelu_tanh_quant_fp8", "lkgd_layernorm_quant_fp8", "lkgd_gemm_fp8"}
-OK, NULL, SHAPE, ALIGN = 0, -1, -2, -3
 DIT_SEED = 191                                                      # make_goldens.py
 
 
-def test_fp8_symbols_agree_three_ways():
-    """header == table == exactly the four names, disjoint from the other tables and headers, exported by the built library with the
-    table's signature, declared with as many parameters as the table binds"""
-    from lkgd_amd import _lib
-    hdr = open(os.path.join(REPO, "include", "lkgd_hip_fp8.h")).read()
-    declared = _declared("lkgd_hip_fp8.h")
-    assert declared == set(_lib.FP8_SYMBOLS) == NAMES, declared ^ set(_lib.FP8_SYMBOLS)
-    for other in (_lib.SYMBOLS, _lib.WINDOW_SYMBOLS, _lib.DIT_SYMBOLS, _lib.DIT_LOOP_SYMBOLS, _lib.DIT_TPATCH_SYMBOLS, _lib.DEBUG_SYMBOLS):
-        assert not declared & set(other)
-    for h in ("lkgd_hip.h", "lkgd_hip_window.h", "lkgd_hip_dit.h", "lkgd_hip_dit_loop.h", "lkgd_hip_dit_tpatch.h", "lkgd_hip_debug.h"):
-        assert not declared & _declared(h), h
-    lib = _lib.lib()
-    for s, (res, args) in _lib.FP8_SYMBOLS.items():
-        fn = getattr(lib, s)
-        assert fn.restype is res and list(fn.argtypes) == list(args), s
-        decl = re.search(r"^int %s\s*\(([^;]*)\);" % s, hdr, re.M | re.S).group(1)
-        assert len(re.sub(r"/\*.*?\*/", "", decl).split(",")) == len(args), s
-    assert [len(_lib.FP8_SYMBOLS[s][1]) for s in sorted(NAMES)] == [8, 13, 11, 8]
-
-
 def test_fp8_entry_points_refuse_before_launching():
-    from lkgd_amd import _lib
-    lib, h = _lib.lib(), _Host()
-
-    def quant(fn, **kw):
-        a = dict(x=h.p, ldx=128, q=h.p, ldq=128, scale=h.p, T=3, K=128)
-        a.update(kw)
-        return getattr(lib, fn)(a["x"], a["ldx"], a["q"], a["ldq"], a["scale"], a["T"], a["K"], None)
-
-    def lnq(**kw):
-        a = dict(x=h.p, ldx=128, T=3, C=128, gamma=h.p, beta=h.p, q=h.p, ldq=128, scale=h.p)
-        a.update(kw)
-        return lib.lkgd_layernorm_quant_fp8(a["x"], a["ldx"], a["T"], a["C"], a["gamma"], a["beta"], 1e-5, a["q"], a["ldq"], a["scale"], None)
-
-    def gemm(**kw):
-        a = dict(a=h.p, lda=128, a_scale=h.p, w=h.p, ldw=128, w_scale=h.p, bias=h.p, out=h.p, ldc=128, M=5, N=128, K=128)
-        a.update(kw)
-        return lib.lkgd_gemm_fp8(a["a"], a["lda"], a["a_scale"], a["w"], a["ldw"], a["w_scale"], a["bias"], a["out"], a["ldc"], a["M"],
-                                 a["N"], a["K"], None)
-    for fn in ("lkgd_quant_rows_fp8", "lkgd_gelu_tanh_quant_fp8"):
+    h = Host()
+    quants = {fn: entry(fn, x=h.p, ldx=128, q=h.p, ldq=128, scale=h.p, T=3, K=128) for fn in ("lkgd_quant_rows_fp8", "lkgd_gelu_tanh_quant_fp8")}
+    lnq = entry("lkgd_layernorm_quant_fp8", x=h.p, ldx=128, T=3, C=128, gamma=h.p, beta=h.p, eps=1e-5, q=h.p, ldq=128, scale=h.p)
+    gemm = entry("lkgd_gemm_fp8", a=h.p, lda=128, a_scale=h.p, w=h.p, ldw=128, w_scale=h.p, bias=h.p, out=h.p, ldc=128, M=5, N=128, K=128)
+    for fn, quant in quants.items():
         for k in ("x", "q", "scale"):
-            assert quant(fn, **{k: None}) == NULL, (fn, k)
+            assert quant(**{k: None}) == NULL, (fn, k)
         for kw in (dict(T=0), dict(K=0), dict(K=100), dict(K=12296, ldx=12296, ldq=12304), dict(ldx=120), dict(ldq=112)):
-            assert quant(fn, **kw) == SHAPE, (fn, kw)
+            assert quant(**kw) == SHAPE, (fn, kw)
         for kw in (dict(x=h.p + 2), dict(q=h.p + 8), dict(ldx=132), dict(ldq=136)):
-            assert quant(fn, **kw) == ALIGN, (fn, kw)
+            assert quant(**kw) == ALIGN, (fn, kw)
     for k in ("x", "q", "scale"):
         assert lnq(**{k: None}) == NULL, k
     assert lnq(gamma=None) == NULL and lnq(beta=None) == NULL            # both or neither

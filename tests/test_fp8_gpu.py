@@ -9,6 +9,7 @@ import torch
 import footprint
 import fp8_oracle as fo
 from cogvideox_support import DEV, dit_inputs as _inputs, hip_twin, loop_inputs as _loop_inputs, tiny_oracle as _oracle
+from c_interface import ALIGN, NULL, SHAPE, entry
 from footprint import run_case
 
 gpu = pytest.mark.gpu
@@ -323,7 +324,6 @@ def test_fp8_linear_against_the_fake_quant_linear(M, N, K):
 def test_fp8_refusals_leave_the_output_alone():
     from lkgd_amd import _lib
     lib = _lib.lib()
-    NULL, SHAPE, ALIGN = -1, -2, -3
     a = torch.zeros(8, 256, dtype=torch.uint8, device=DEV)
     w = torch.zeros(256, 256, dtype=torch.uint8, device=DEV)
     sa, sw = torch.ones(8, device=DEV), torch.ones(256, device=DEV)
@@ -332,13 +332,9 @@ def test_fp8_refusals_leave_the_output_alone():
     q = torch.full((8, 256), 0xAA, dtype=torch.uint8, device=DEV)
     st = torch.cuda.current_stream().cuda_stream
 
-    def gemm(**kw):
-        k = dict(a=a.data_ptr(), lda=256, sa=sa.data_ptr(), w=w.data_ptr(), ldw=256, sw=sw.data_ptr(), bias=None, out=out.data_ptr(),
-                 ldc=256, M=8, N=256, K=256)
-        k.update(kw)
-        return lib.lkgd_gemm_fp8(k["a"], k["lda"], k["sa"], k["w"], k["ldw"], k["sw"], k["bias"], k["out"], k["ldc"], k["M"], k["N"],
-                                 k["K"], st)
-    assert gemm(a=None) == NULL and gemm(sa=None) == NULL and gemm(w=None) == NULL and gemm(sw=None) == NULL and gemm(out=None) == NULL
+    gemm = entry("lkgd_gemm_fp8", a=a.data_ptr(), lda=256, a_scale=sa.data_ptr(), w=w.data_ptr(), ldw=256, w_scale=sw.data_ptr(), bias=None,
+                 out=out.data_ptr(), ldc=256, M=8, N=256, K=256, stream=st)
+    assert gemm(a=None) == NULL and gemm(a_scale=None) == NULL and gemm(w=None) == NULL and gemm(w_scale=None) == NULL and gemm(out=None) == NULL
     assert gemm(N=192) == SHAPE and gemm(K=192) == SHAPE and gemm(N=64) == SHAPE and gemm(K=64) == SHAPE and gemm(M=0) == SHAPE
     assert gemm(a=a.data_ptr() + 8) == ALIGN and gemm(w=w.data_ptr() + 4) == ALIGN and gemm(out=out.data_ptr() + 2) == ALIGN
     assert gemm(lda=264) == ALIGN and gemm(ldw=264) == ALIGN and gemm(ldc=260) == ALIGN
@@ -351,13 +347,6 @@ def test_fp8_refusals_leave_the_output_alone():
     assert lib.lkgd_layernorm_quant_fp8(x.data_ptr(), 256, 8, 3080, None, None, 1e-5, q.data_ptr(), 3088, sa.data_ptr(), st) == SHAPE
     torch.cuda.synchronize()
     assert bool((out == 7.0).all()) and bool((q == 0xAA).all()) and bool((sa == 1.0).all())
-
-
-def test_footprint_registry_covers_every_fp8_symbol():
-    from lkgd_amd import _lib
-    assert set(FOOTPRINT) == set(_lib.FP8_SYMBOLS)
-    for name, cases in FOOTPRINT.items():
-        assert cases and all(c in globals() for c in cases), name
 
 
 class _Fp8Windows(footprint.Windows):

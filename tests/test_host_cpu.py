@@ -1,6 +1,6 @@
-"""CPU-side checks of the product's host logic (no kernels run): the C-ABI library loads and exports every symbol the
-header declares, the scheduler host tables equal the reference's KAT, state-dict compatibility with the diffusers
-names, weight packing layouts, patch API bookkeeping, loud failure without a GPU."""
+"""CPU-side checks of the product's host logic (no kernels run): the debug knobs are per thread, the scheduler host
+tables equal the reference's KAT, state-dict compatibility with the diffusers names, weight packing layouts, patch API
+bookkeeping, loud failure without a GPU."""
 import ctypes
 import json
 import os
@@ -11,24 +11,6 @@ import pytest
 import torch
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def test_library_exports_every_declared_symbol():
-    from lkgd_amd import _lib
-    hdr = open(os.path.join(REPO, "include", "lkgd_hip.h")).read()
-    declared = set(re.findall(r"\b(lkgd_[a-z0-9_]+)\s*\(", hdr))
-    declared.discard("lkgd_gemm_desc")
-    assert declared == set(_lib.SYMBOLS), declared ^ set(_lib.SYMBOLS)
-    assert not any(s.startswith("lkgd_debug") for s in declared)          # the product header carries no knob
-    dbg = open(os.path.join(REPO, "include", "lkgd_hip_debug.h")).read()
-    dbg_declared = set(re.findall(r"^void (lkgd_debug_[a-z0-9_]+)\s*\(", dbg, re.M))
-    assert dbg_declared == set(_lib.DEBUG_SYMBOLS), dbg_declared ^ set(_lib.DEBUG_SYMBOLS)
-    lib = _lib.lib()                       # loads liblkgd_hip.so (links libamdhip64; no GPU needed to load)
-    for s in declared | dbg_declared:
-        assert hasattr(lib, s), s
-    assert lib.lkgd_version().decode().startswith("lkgd_hip")
-    # 31 int32/float fields, padded to 8; workspace + size; colstats; ln_colsum + ln_eps + pad
-    assert ctypes.sizeof(_lib.GemmDesc) == 9 * 8 + 31 * 4 + 4 + 16 + 8 + 16
 
 
 def test_debug_knobs_are_per_thread():

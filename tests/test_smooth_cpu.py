@@ -1,10 +1,9 @@
 """Host side of the long-video smoothing pipeline without a GPU: the frame windows (``smooth_chunks`` against the windows the
 reference's ``get_chunks`` drew, pipeline_stable_video_diffusion_smooth.py:526-533, and their partition properties), the
 pipeline class's ``__call__`` parameters against the reference's list (:320-341), argument validation of the two windowed entry
-points, and the agreement of include/lkgd_hip_window.h, ``_lib.WINDOW_SYMBOLS`` and the library."""
+points."""
 import inspect
 import os
-import re
 
 import numpy as np
 import pytest
@@ -81,46 +80,21 @@ def test_smooth_call_signature_matches_reference(golden):
 
 def test_window_entry_points_validate_without_gpu():
     """argument errors are reported before anything touches the device (no pointer below is ever dereferenced)"""
-    from lkgd_amd import _lib
-    L = _lib.lib()
+    from c_interface import ALIGN, MODE, NULL, SHAPE, entry
     p = 4096                                                     # aligned dummy addresses
-
-    def prep(**k):
-        return L.lkgd_window_prepare_input(k.get("lat", p), 0, k.get("img", p), k.get("T", 7), k.get("f0", 2), k.get("L", 3), 8, 8,
-                                           k.get("cfg", 2), k.get("sigma", 1.0), k.get("out", p), None)
-
-    def step(**k):
-        return L.lkgd_window_cfg_euler_step(k.get("noise", p), k.get("lat", p), 0, k.get("guid", p), k.get("T", 7), k.get("f0", 2),
-                                            k.get("L", 3), 8, 8, k.get("cfg", 2), k.get("sigma", 1.0), 0.5, k.get("pt", 1), None)
-    assert prep(lat=None) == -1 and prep(img=None) == -1 and prep(out=None) == -1                 # LKGD_E_NULL
-    assert step(noise=None) == -1 and step(lat=None) == -1 and step(guid=None) == -1              # cfg == 2 needs the guidance
-    for f in (prep, step):
+    prep = entry("lkgd_window_prepare_input", latents=p, latents_is_f32=0, image_latents=p, T=7, f0=2, L=3, H=8, W=8, cfg=2,
+                 sigma=1.0, tokens_out=p)
+    step = entry("lkgd_window_cfg_euler_step", noise_tokens=p, latents=p, latents_is_f32=0, guidance=p, T=7, f0=2, L=3, H=8, W=8,
+                 cfg=2, sigma=1.0, sigma_next=0.5, prediction_type=1)
+    assert prep(latents=None) == NULL and prep(image_latents=None) == NULL and prep(tokens_out=None) == NULL
+    assert step(noise_tokens=None) == NULL and step(latents=None) == NULL and step(guidance=None) == NULL   # cfg == 2 needs the guidance
+    for name, f in (("prep", prep), ("step", step)):
         for bad in (dict(cfg=0), dict(cfg=3), dict(sigma=0.0), dict(sigma=-1.0), dict(sigma=float("nan")), dict(f0=-1),
                     dict(L=0), dict(L=-3), dict(f0=5, L=3), dict(f0=7, L=1), dict(f0=0, L=8), dict(T=0),
                     dict(f0=2 ** 31 - 1, L=2 ** 31 - 1)):
-            assert f(**bad) == -2, (f.__name__, bad)                                              # LKGD_E_SHAPE
-    assert step(pt=2) == -4 and step(pt=-1) == -4                                                 # LKGD_E_MODE
-    assert prep(out=p + 8) == -3 and step(noise=p + 4) == -3                                      # LKGD_E_ALIGN
-
-
-def test_window_symbols_agree_three_ways():
-    """include/lkgd_hip_window.h == _lib.WINDOW_SYMBOLS, disjoint from _lib.SYMBOLS, all in the library (the rule
-    test_library_exports_every_declared_symbol keeps for include/lkgd_hip.h)"""
-    from lkgd_amd import _lib
-    hdr = open(os.path.join(REPO, "include", "lkgd_hip_window.h")).read()
-    declared = set(re.findall(r"\b(lkgd_[a-z0-9_]+)\s*\(", hdr))
-    assert declared == set(_lib.WINDOW_SYMBOLS), declared ^ set(_lib.WINDOW_SYMBOLS)
-    assert len(declared) == 2 and not declared & set(_lib.SYMBOLS) and not declared & set(_lib.DEBUG_SYMBOLS)
-    main = open(os.path.join(REPO, "include", "lkgd_hip.h")).read()
-    assert not declared & set(re.findall(r"\b(lkgd_[a-z0-9_]+)\s*\(", main))
-    lib = _lib.lib()
-    for s, (res, args) in _lib.WINDOW_SYMBOLS.items():
-        fn = getattr(lib, s)
-        assert fn.restype is res and list(fn.argtypes) == list(args), s
-    # the declared parameter lists have as many parameters as the ctypes tables
-    for s, (_, args) in _lib.WINDOW_SYMBOLS.items():
-        decl = re.search(r"^int %s\s*\(([^;]*)\);" % s, hdr, re.M | re.S).group(1)
-        assert len(re.sub(r"/\*.*?\*/", "", decl).split(",")) == len(args), s
+            assert f(**bad) == SHAPE, (name, bad)
+    assert step(prediction_type=2) == MODE and step(prediction_type=-1) == MODE
+    assert prep(tokens_out=p + 8) == ALIGN and step(noise_tokens=p + 4) == ALIGN
 
 
 def test_smooth_refusals_need_no_gpu():

@@ -1,75 +1,24 @@
-"""Host side of the T5 text encoder without a GPU: include/lkgd_hip_t5.h == ``_lib.T5_SYMBOLS`` == the library; the five entry points
-refuse bad arguments with the documented codes before any launch; the module tree carries transformers' state-dict names and shapes;
-the relative-position table expands to transformers' ``compute_bias`` exactly; the configuration refusals name what they refuse;
-``encode_prompt`` with a stub tokenizer and a stub encoder.  transformers [EXT] is the checker, never on the product path."""
-import os
-import re
-
+"""Host side of the T5 text encoder without a GPU: the five entry points refuse bad arguments with the documented codes before any launch;
+the module tree carries transformers' state-dict names and shapes; the relative-position table expands to transformers'
+``compute_bias`` exactly; the configuration refusals name what they refuse; ``encode_prompt`` with a stub tokenizer and a stub
+encoder.  transformers [EXT] is the checker, never on the product path."""
 import pytest
 import torch
 
 transformers = pytest.importorskip("transformers")
 
-from cogvideox_support import REPO, Host as _Host, declared as _declared
+from c_interface import ALIGN, NULL, SHAPE, Host, entry
 from t5_support import TINY_A, StubTokenizer, expand_bias_table, hf_model, hip_twin
-
-NAMES = {"lkgd_t5_embed_rows", "lkgd_t5_rmsnorm", "lkgd_attn_dense_relbias", "lkgd_t5_gated_gelu", "lkgd_t5_residual_add"}
-OK, NULL, SHAPE, ALIGN = 0, -1, -2, -3
-
-
-def test_t5_symbols_agree_three_ways():
-    """header == table == exactly the five names, disjoint from the other tables and headers, exported by the built library with the
-    table's signature, declared with as many parameters as the table binds"""
-    from lkgd_amd import _lib
-    hdr = open(os.path.join(REPO, "include", "lkgd_hip_t5.h")).read()
-    declared = _declared("lkgd_hip_t5.h")
-    assert declared == set(_lib.T5_SYMBOLS) == NAMES, declared ^ set(_lib.T5_SYMBOLS)
-    others = [getattr(_lib, t) for t in dir(_lib) if t.endswith("SYMBOLS") and t != "T5_SYMBOLS"]
-    assert len(others) >= 8
-    for other in others:
-        assert not declared & set(other)
-    for h in sorted(os.listdir(os.path.join(REPO, "include"))):
-        if h != "lkgd_hip_t5.h":
-            assert not declared & _declared(h), h
-    lib = _lib.lib()
-    for s, (res, args) in _lib.T5_SYMBOLS.items():
-        fn = getattr(lib, s)
-        assert fn.restype is res and list(fn.argtypes) == list(args), s
-        decl = re.search(r"^int %s\s*\(([^;]*)\);" % s, hdr, re.M | re.S).group(1)
-        assert len(re.sub(r"/\*.*?\*/", "", decl).split(",")) == len(args), s
-    assert [len(_lib.T5_SYMBOLS[s][1]) for s in sorted(NAMES)] == [15, 9, 7, 8, 9]
 
 
 def test_t5_entry_points_refuse_before_launching():
-    from lkgd_amd import _lib
-    lib, h = _lib.lib(), _Host()
-
-    def embed(**kw):
-        a = dict(ids=h.p, table=h.p, ldt=64, V=128, D=64, out=h.p, ldo=64, T=3)
-        a.update(kw)
-        return lib.lkgd_t5_embed_rows(a["ids"], a["table"], a["ldt"], a["V"], a["D"], a["out"], a["ldo"], a["T"], None)
-
-    def norm(**kw):
-        a = dict(x=h.p, ldx=64, T=3, C=64, weight=h.p, out=h.p, ldo=64)
-        a.update(kw)
-        return lib.lkgd_t5_rmsnorm(a["x"], a["ldx"], a["T"], a["C"], a["weight"], 1e-6, a["out"], a["ldo"], None)
-
-    def attn(**kw):
-        a = dict(q=h.p, ldq=192, k=h.p + 128, ldk=192, v=h.p + 256, ldv=192, out=h.p, ldo=64, nbatch=2, S=7, heads=4, head_dim=16,
-                 relbias=h.p)
-        a.update(kw)
-        return lib.lkgd_attn_dense_relbias(a["q"], a["ldq"], a["k"], a["ldk"], a["v"], a["ldv"], a["out"], a["ldo"], a["nbatch"], a["S"],
-                                           a["heads"], a["head_dim"], a["relbias"], 1.0, None)
-
-    def gelu(**kw):
-        a = dict(h=h.p, ldh=320, T=3, F=160, out=h.p, ldo=160)
-        a.update(kw)
-        return lib.lkgd_t5_gated_gelu(a["h"], a["ldh"], a["T"], a["F"], a["out"], a["ldo"], None)
-
-    def add(**kw):
-        a = dict(x=h.p, ldx=64, y=h.p, ldy=64, T=3, C=64)
-        a.update(kw)
-        return lib.lkgd_t5_residual_add(a["x"], a["ldx"], a["y"], a["ldy"], a["T"], a["C"], 64.0, None)
+    h = Host()
+    embed = entry("lkgd_t5_embed_rows", ids=h.p, table=h.p, ldt=64, V=128, D=64, out=h.p, ldo=64, T=3)
+    norm = entry("lkgd_t5_rmsnorm", x=h.p, ldx=64, T=3, C=64, weight=h.p, eps=1e-6, out=h.p, ldo=64)
+    attn = entry("lkgd_attn_dense_relbias", q=h.p, ldq=192, k=h.p + 128, ldk=192, v=h.p + 256, ldv=192, out=h.p, ldo=64, nbatch=2, S=7,
+                 heads=4, head_dim=16, relbias=h.p, scale=1.0)
+    gelu = entry("lkgd_t5_gated_gelu", h=h.p, ldh=320, T=3, F=160, out=h.p, ldo=160)
+    add = entry("lkgd_t5_residual_add", x=h.p, ldx=64, y=h.p, ldy=64, T=3, C=64, s=64.0)
 
     for k in ("ids", "table", "out"):
         assert embed(**{k: None}) == NULL, k

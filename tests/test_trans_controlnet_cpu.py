@@ -3,6 +3,8 @@ entry point, and the pipeline class's ``__call__`` parameters against the refere
 (pipeline_stable_video_diffusion_trans_controlnet.py:354-380)."""
 import inspect
 
+from c_interface import ALIGN, MODE, NULL, SHAPE, entry
+
 #: the reference's __call__ parameters, in order (pipeline_stable_video_diffusion_trans_controlnet.py:354-380)
 REFERENCE_PARAMS = [
     "image", "controlnet_condition", "height", "width", "num_frames", "num_inference_steps", "min_guidance_scale",
@@ -14,18 +16,16 @@ REFERENCE_PARAMS = [
 
 def test_cfg_fusion_euler_step_validation_without_gpu():
     """argument errors are reported before anything touches the device (no pointer below is ever dereferenced)"""
-    from lkgd_amd import _lib
-    f = _lib.lib().lkgd_cfg_fusion_euler_step
     p = 4096                                                      # aligned dummy addresses
-    args = lambda **k: [k.get("noise", p), k.get("lat", p), 0, k.get("guid", p), k.get("weight", p), k.get("B", 2), 4, 8, 8,  # noqa: E731
-                        k.get("cfg", 2), k.get("sigma", 1.0), 0.5, k.get("pt", 1), None]
-    assert f(*args(noise=None)) == -1 and f(*args(lat=None)) == -1 and f(*args(weight=None)) == -1   # LKGD_E_NULL
-    assert f(*args(guid=None)) == -1                              # cfg == 2 needs the per-frame guidance
+    f = entry("lkgd_cfg_fusion_euler_step", noise_tokens=p, latents=p, latents_is_f32=0, guidance=p, weight=p, B=2, F=4, H=8, W=8,
+              cfg=2, sigma=1.0, sigma_next=0.5, prediction_type=1)
+    assert f(noise_tokens=None) == NULL and f(latents=None) == NULL and f(weight=None) == NULL
+    assert f(guidance=None) == NULL                               # cfg == 2 needs the per-frame guidance
     for bad in (dict(B=3), dict(B=1), dict(B=0), dict(B=-2), dict(cfg=0), dict(cfg=3), dict(sigma=0.0),
                 dict(sigma=float("nan"))):
-        assert f(*args(**bad)) == -2, bad                         # LKGD_E_SHAPE
-    assert f(*args(pt=2)) == -4                                   # LKGD_E_MODE
-    assert f(*args(noise=p + 2)) == -3                            # LKGD_E_ALIGN
+        assert f(**bad) == SHAPE, bad
+    assert f(prediction_type=2) == MODE
+    assert f(noise_tokens=p + 2) == ALIGN
 
 
 def test_trans_controlnet_call_signature_matches_reference():

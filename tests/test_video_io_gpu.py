@@ -194,10 +194,3 @@ def test_footprint_preprocess(N, H, Wd, C_, ci, co):
         return {"planes": out}
 
     run_case(case, DEV, refs=lambda: {"planes": want}, close=_same, sync=torch.cuda.synchronize, guard=4)
-
-
-def test_every_symbol_has_footprint_cases():
-    from lkgd_amd import _lib
-    assert set(FOOTPRINT) == set(_lib.VIDEO_SYMBOLS)
-    for name, cases in FOOTPRINT.items():
-        assert cases and all(callable(globals().get(c)) for c in cases), name

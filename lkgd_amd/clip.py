@@ -19,7 +19,6 @@ random-init weights (transformers is third-party and not part of the reference t
 """
 from __future__ import annotations
 
-import os
 from dataclasses import dataclass
 from types import SimpleNamespace
 from typing import Optional
@@ -29,8 +28,10 @@ import torch.nn as nn
 
 from . import ops
 from ._lib import LkgdHipError
-from .loading import load_config
-from .packing import pack_geglu, pack_linear
+from .encoder import class_head, embed_rows, pack_layer, run_layers
+from .loading import build_from_transformers, load_config, save_transformers
+from .module import PackedModule
+from .packing import f32, pack_linear
 
 
 @dataclass
@@ -45,10 +46,6 @@ class CLIPVisionConfig:
     projection_dim: int = 1024
     hidden_act: str = "gelu"
     layer_norm_eps: float = 1e-5
-
-
-def _f32(p):
-    return p.detach().to(torch.float32).contiguous()
 
 
 class CLIPImageProcessor:
@@ -113,26 +110,10 @@ class CLIPEncoderLayer(nn.Module):
         self.layer_norm2 = nn.LayerNorm(cfg.hidden_size, eps=cfg.layer_norm_eps)
 
     def pack(self, act: str):
-        a, g1, b1 = self.self_attn, self.layer_norm1.weight.detach().float(), self.layer_norm1.bias.detach().float()
-        wqkv = torch.cat([a.q_proj.weight, a.k_proj.weight, a.v_proj.weight], dim=0).detach().float()
-        bqkv = torch.cat([a.q_proj.bias, a.k_proj.bias, a.v_proj.bias], dim=0).detach().float() + wqkv @ b1
-        g2, b2 = self.layer_norm2.weight.detach().float(), self.layer_norm2.bias.detach().float()
-        w1 = self.mlp.fc1.weight.detach().float()
-        bf1 = self.mlp.fc1.bias.detach().float() + w1 @ b2
-        w1 = w1 * g2[None, :]
-        pk = SimpleNamespace(wqkv=pack_linear(wqkv * g1[None, :]), bqkv=bqkv.contiguous(), wo=pack_linear(a.out_proj.weight),
-                             bo=_f32(a.out_proj.bias), b2=_f32(self.mlp.fc2.bias), act=act)
-        if act == "gelu":
-            # GELU(fc1 x) as GEGLU with a constant-one hidden half: hidden = 0 * x + 1, gate = fc1 x
-            wg = torch.cat([torch.zeros_like(w1), w1], dim=0)
-            bg = torch.cat([torch.ones_like(bf1), bf1], dim=0)
-            pk.w1, pk.b1, pk.half = pack_geglu(wg, bg)
-            pk.w2 = pack_linear(self.mlp.fc2.weight)
-        else:
-            # quick_gelu(x) = x * sigmoid(1.702 x) = silu(1.702 x) / 1.702
-            pk.w1, pk.b1, pk.half = pack_linear(w1 * 1.702), (bf1 * 1.702).contiguous(), 0
-            pk.w2 = pack_linear(self.mlp.fc2.weight.detach().float() / 1.702)
-        self._pk = pk
+        a = self.self_attn
+        wqkv = torch.cat([a.q_proj.weight, a.k_proj.weight, a.v_proj.weight], dim=0)
+        bqkv = torch.cat([a.q_proj.bias, a.k_proj.bias, a.v_proj.bias], dim=0)
+        return pack_layer(self.layer_norm1, wqkv, bqkv, a.out_proj, self.layer_norm2, self.mlp.fc1, self.mlp.fc2, act)
 
 
 class CLIPEncoder(nn.Module):
@@ -150,8 +131,10 @@ class CLIPVisionTransformer(nn.Module):
         self.post_layernorm = nn.LayerNorm(cfg.hidden_size, eps=cfg.layer_norm_eps)
 
 
-class CLIPVisionModelWithProjection(nn.Module):
+class CLIPVisionModelWithProjection(PackedModule):
     """transformers' class of the same name: parameter holder + HIP forward; ``model(pixel_values).image_embeds``"""
+
+    OFF_GPU = "lkgd_amd CLIP runs on MI355X only: move the module to cuda first"
 
     def __init__(self, config: Optional[CLIPVisionConfig] = None, **kw):
         super().__init__()
@@ -167,75 +150,33 @@ class CLIPVisionModelWithProjection(nn.Module):
         self.config = cfg
         self.vision_model = CLIPVisionTransformer(cfg)
         self.visual_projection = nn.Linear(d, cfg.projection_dim, bias=False)
-        self._pk = None
 
     # ---- loading ------------------------------------------------------------------------------------------------------
     @classmethod
     def from_pretrained(cls, path: str, subfolder: Optional[str] = None, torch_dtype=torch.float16, dtype=None,
                         variant: Optional[str] = None, **_ignored):
-        """a local ``image_encoder/`` directory: ``config.json`` + ``model[.<variant>].safetensors`` (or ``pytorch_model.bin``)"""
-        from .loading import load_state_dict
-        raw = load_config(path, subfolder)
-        known = {k: v for k, v in raw.items() if k in CLIPVisionConfig.__dataclass_fields__}
-        with torch.device("meta"):
-            model = cls(CLIPVisionConfig(**known))
-        try:
-            sd = load_state_dict(path, subfolder, variant, weights_name="model")
-        except OSError:
-            sd = load_state_dict(path, subfolder, variant, weights_name="pytorch_model")
-        sd = {k: v for k, v in sd.items() if not k.endswith("position_ids")}       # a persisted buffer of older checkpoints
-        model.load_state_dict(sd, strict=True, assign=True)
-        return model.to(dtype if dtype is not None else torch_dtype)
+        """a local ``image_encoder/`` directory: ``config.json`` + ``model[.<variant>].safetensors`` (or ``pytorch_model.bin``);
+        ``*position_ids`` keys, a persisted buffer of older checkpoints, are dropped"""
+        return build_from_transformers(cls, CLIPVisionConfig, path, subfolder, torch_dtype, dtype, variant, drop_suffix="position_ids")
 
     def save_pretrained(self, path: str, **_kw):
-        import json
-        from safetensors.torch import save_file
-        os.makedirs(path, exist_ok=True)
-        cfg = {"architectures": ["CLIPVisionModelWithProjection"], "model_type": "clip_vision_model"}
-        cfg.update(self.config.__dict__)
-        with open(os.path.join(path, "config.json"), "w") as fh:
-            json.dump(cfg, fh, indent=2)
-        save_file({k: v.detach().cpu().contiguous() for k, v in self.state_dict().items()}, os.path.join(path, "model.safetensors"))
-
-    @property
-    def device(self):
-        return self.visual_projection.weight.device
-
-    @property
-    def dtype(self):
-        return self.visual_projection.weight.dtype
-
-    def load_state_dict(self, *a, **k):
-        r = super().load_state_dict(*a, **k)
-        self._pk = None
-        return r
-
-    def _apply(self, fn, *a, **k):
-        r = super()._apply(fn, *a, **k)
-        self._pk = None
-        return r
+        save_transformers(self, path, {"architectures": ["CLIPVisionModelWithProjection"], "model_type": "clip_vision_model"})
 
     # ---- forward ------------------------------------------------------------------------------------------------------
-    @torch.no_grad()
-    def prepare(self):
-        if self._pk is not None:
-            return
-        if self.device.type != "cuda":
-            raise LkgdHipError("lkgd_amd CLIP runs on MI355X only: move the module to cuda first")
+    def _pack(self):
         cfg, vm = self.config, self.vision_model
-        for layer in vm.encoder.layers:
-            layer.pack(cfg.hidden_act)
+        layers = [layer.pack(cfg.hidden_act) for layer in vm.encoder.layers]
         emb = vm.embeddings
         kp = cfg.num_channels * cfg.patch_size ** 2
         kpad = (kp + 63) // 64 * 64
         wpe = torch.zeros(cfg.hidden_size, kpad, dtype=torch.float16, device=self.device)
         wpe[:, :kp] = emb.patch_embedding.weight.detach().reshape(cfg.hidden_size, kp).to(torch.float16)
         pos = emb.position_embedding.weight.detach().float()
-        self._pk = SimpleNamespace(
-            wpe=wpe, kp=kp, kpad=kpad, pos=pos[1:].to(torch.float16).contiguous(),
+        return SimpleNamespace(
+            layers=layers, wpe=wpe, kp=kp, kpad=kpad, pos=pos[1:].to(torch.float16).contiguous(),
             cls=(emb.class_embedding.detach().float() + pos[0]).to(torch.float16).contiguous(),
-            g_pre=_f32(vm.pre_layrnorm.weight), b_pre=_f32(vm.pre_layrnorm.bias),
-            g_post=_f32(vm.post_layernorm.weight), b_post=_f32(vm.post_layernorm.bias),
+            g_pre=f32(vm.pre_layrnorm.weight), b_pre=f32(vm.pre_layrnorm.bias),
+            g_post=f32(vm.post_layernorm.weight), b_post=f32(vm.post_layernorm.bias),
             wproj=pack_linear(self.visual_projection.weight))
 
     @torch.no_grad()
@@ -248,42 +189,16 @@ class CLIPVisionModelWithProjection(nn.Module):
         if pixel_values.dim() != 4 or tuple(pixel_values.shape[1:]) != (cfg.num_channels, cfg.image_size, cfg.image_size):
             raise ValueError(f"expected pixel_values [N, {cfg.num_channels}, {cfg.image_size}, {cfg.image_size}]")
         N, D, P = pixel_values.shape[0], cfg.hidden_size, g * g
-        S = P + 1
-        eps = cfg.layer_norm_eps
+        S, heads, eps = P + 1, cfg.num_attention_heads, cfg.layer_norm_eps
         # the patch rows [N*P, C*p*p] in the conv weight's (c, ky, kx) order, K zero-padded to a multiple of 64 (layout only)
         x = pixel_values.to(device=dev, dtype=torch.float16)
         patches = torch.zeros(N * P, pk.kpad, dtype=torch.float16, device=dev)
         patches[:, :pk.kp] = (x.reshape(N, cfg.num_channels, g, cfg.patch_size, g, cfg.patch_size)
                               .permute(0, 2, 4, 1, 3, 5).reshape(N * P, pk.kp))
-        emb = torch.empty(N * S, D, dtype=torch.float16, device=dev)
-        emb.view(N, S, D)[:, 0] = pk.cls
-        for n in range(N):       # one GEMM per image: its patch rows land behind the image's class row, + position[1 + m]
-            ops.gemm(patches[n * P:(n + 1) * P], pk.wpe, emb[n * S + 1:(n + 1) * S], M=P, N=D, K=pk.kpad,
-                     rowbias=pk.pos, rowmap=(1, 1, 1, 1 << 30))
+        emb = embed_rows(patches, pk.wpe, pk.cls, pk.pos, N, P)
         tok = ops.layernorm(emb, pk.g_pre, pk.b_pre, eps)
-        T, heads = N * S, cfg.num_attention_heads
-        hd = D // heads
-        for layer in self.vision_model.encoder.layers:
-            p = layer._pk
-            ln = ops.layernorm(tok, None, None, eps)
-            qkv = torch.empty(T, 3 * D, dtype=torch.float16, device=dev)
-            ops.gemm(ln, p.wqkv, qkv, M=T, N=3 * D, K=D, bias=p.bqkv)
-            att = torch.empty(T, D, dtype=torch.float16, device=dev)
-            ops.attn_dense(qkv[:, :D], qkv[:, D:2 * D], qkv[:, 2 * D:], att, N, S, heads, hd)
-            t1 = torch.empty(T, D, dtype=torch.float16, device=dev)
-            ops.gemm(att, p.wo, t1, M=T, N=D, K=D, bias=p.bo, res1=tok)
-            ln2 = ops.layernorm(t1, None, None, eps)
-            inner = p.w2.shape[1]
-            h = torch.empty(T, inner, dtype=torch.float16, device=dev)
-            if p.act == "gelu":
-                ops.gemm(ln2, p.w1, h, M=T, N=2 * inner, K=D, bias=p.b1, geglu=p.half)
-            else:
-                ops.gemm(ln2, p.w1, h, M=T, N=inner, K=D, bias=p.b1)
-                h = ops.silu(h)
-            tok = torch.empty(T, D, dtype=torch.float16, device=dev)
-            ops.gemm(h, p.w2, tok, M=T, N=D, K=inner, bias=p.b2, res1=t1)
-        cls = tok.view(N, S, D)[:, 0].contiguous()
-        pooled = ops.layernorm(cls, pk.g_post, pk.b_post, eps)
-        embeds = torch.empty(N, cfg.projection_dim, dtype=torch.float16, device=dev)
-        ops.gemm(pooled, pk.wproj, embeds, M=N, N=cfg.projection_dim, K=D)
+        # head_dim 80 for ViT-H: the dense short-sequence kernel (the flash kernel is head_dim 64 only)
+        tok = run_layers(tok, pk.layers, N, S, heads, eps,
+                         lambda q, k, v, out, n, s, h: ops.attn_dense(q, k, v, out, n, s, h, D // heads))
+        embeds = class_head(tok, N, S, pk.g_post, pk.b_post, eps, pk.wproj)
         return SimpleNamespace(image_embeds=embeds.to(self.dtype), last_hidden_state=tok.view(N, S, D))

@@ -65,7 +65,8 @@ from . import fp8 as fp8_mode
 from . import ops
 from ._lib import LkgdHipError
 from .lk_fuse import lk_fuse_tokens, pack_lk_tokens
-from .packing import pack_linear
+from .module import PackedModule
+from .packing import f32, pack_linear
 from .unet import QuaternionLinearAutograd, TimestepEmbedding
 
 
@@ -114,10 +115,6 @@ def check_temporal_config(patch_size_t, ofs_embed_dim, rotary: bool, learned: bo
     if not rotary:
         raise LkgdHipError(f"{where}: patch_size_t={patch_size_t!r} without use_rotary_positional_embeddings; the 1.5 models "
                            "are rotary, a sin-cos table over temporal patches is not built")
-
-
-def _f32(p):
-    return p.detach().to(torch.float32).contiguous()
 
 
 def _sincos_1d(embed_dim: int, pos: np.ndarray) -> np.ndarray:
@@ -281,12 +278,12 @@ class CogVideoXBlock(nn.Module):
         a, f = self.attn1, self.ff
 
         def lin(m):
-            bias = _f32(m.bias) if m.bias is not None else None
+            bias = f32(m.bias) if m.bias is not None else None
             if fp8:
                 return fp8_mode.quantize_weight(m.weight) + (bias,)
             return pack_linear(m.weight), bias
         self._pk = SimpleNamespace(q=lin(a.to_q), k=lin(a.to_k), v=lin(a.to_v), o=lin(a.to_out[0]),
-                                   nq=(_f32(a.norm_q.weight), _f32(a.norm_q.bias)), nk=(_f32(a.norm_k.weight), _f32(a.norm_k.bias)),
+                                   nq=(f32(a.norm_q.weight), f32(a.norm_q.bias)), nk=(f32(a.norm_k.weight), f32(a.norm_k.bias)),
                                    f1=lin(f.net[0].proj), f2=lin(f.net[2]))
 
     def run(self, st, X, eff_g, eff_b, gates):
@@ -372,7 +369,7 @@ class Transformer2DModelOutput:
     sample: torch.Tensor
 
 
-class CogVideoXTransformer3DModel(nn.Module):
+class CogVideoXTransformer3DModel(PackedModule):
     def __init__(self, config: Optional[DiTConfig] = None, **kw):
         super().__init__()
         cfg = config if config is not None else DiTConfig(**kw)
@@ -406,7 +403,6 @@ class CogVideoXTransformer3DModel(nn.Module):
         self.init_quaternion_modules()
         #: None, or "fp8" after ``lkgd_amd.fp8.quantize_to_float8`` (the block linears then pack and run as e4m3)
         self.quantization = None
-        self._pk = None
         self._pos = {}
 
     def init_quaternion_modules(self):
@@ -425,31 +421,20 @@ class CogVideoXTransformer3DModel(nn.Module):
         self.quaternion_lora_texts_fft_pha = nn.Parameter(torch.zeros(129))
 
     # ---- bookkeeping -------------------------------------------------------------------------------------------
-    @property
-    def device(self):
-        return self.proj_out.weight.device
+    OFF_GPU = "lkgd_amd DiT runs on MI355X only: move the module to cuda first"
+    config_class = DiTConfig
 
-    @property
-    def dtype(self):
-        return self.proj_out.weight.dtype
+    def _forget(self):
+        self._pos = {}                  # sin-cos tables in the module's device
 
-    def invalidate(self):
-        self._pk = None
-
-    def load_state_dict(self, *a, **k):
-        r = super().load_state_dict(*a, **k)
-        self._pk = None
-        return r
-
-    def _apply(self, fn, *a, **k):
-        r = super()._apply(fn, *a, **k)
-        self._pk = None
-        return r
+    @classmethod
+    def _build_options(cls, **_ignored):
+        return {"strict": False}        # from_pretrained checks the keys itself
 
     @classmethod
     def from_pretrained(cls, pretrained_model_name_or_path: str, subfolder: Optional[str] = None, torch_dtype=None,
-                        variant: Optional[str] = None, **_ignored):
-        from .loading import build_from_pretrained, load_config, load_state_dict
+                        variant: Optional[str] = None, **kw):
+        from .loading import load_config, load_state_dict
         raw = load_config(pretrained_model_name_or_path, subfolder)
         # before any weight is read: of the 1.5 keys only the released combination is built
         check_temporal_config(raw.get("patch_size_t"), raw.get("ofs_embed_dim"), bool(raw.get("use_rotary_positional_embeddings")),
@@ -457,7 +442,7 @@ class CogVideoXTransformer3DModel(nn.Module):
         # stock checkpoints have no quaternion_lora_* modules: those may be missing; anything else missing or unexpected
         # (a truncated shard, renamed parameters) would leave meta-initialised garbage behind a non-strict load
         sd_keys = set(load_state_dict(pretrained_model_name_or_path, subfolder, variant).keys())
-        m = build_from_pretrained(cls, DiTConfig, pretrained_model_name_or_path, subfolder, torch_dtype, variant, strict=False)
+        m = super().from_pretrained(pretrained_model_name_or_path, subfolder, torch_dtype, variant, **kw)
         own = set(m.state_dict().keys())
         missing = sorted(k for k in own - sd_keys if not k.startswith("quaternion_lora_"))
         unexpected = sorted(sd_keys - own)
@@ -467,21 +452,16 @@ class CogVideoXTransformer3DModel(nn.Module):
                                f"{'...' if len(unexpected) > 5 else ''}")
         return m
 
-    def save_pretrained(self, save_directory: str, variant: Optional[str] = None, **_ignored):
-        from .loading import save_pretrained
-        cfg = {k: v for k, v in self.config.__dict__.items() if k in DiTConfig.__dataclass_fields__}
-        save_pretrained(self, save_directory, cfg, type(self).__name__, variant)
+    def _saved_config(self):
+        return {k: v for k, v in self.config.__dict__.items() if k in DiTConfig.__dataclass_fields__}
 
-    @torch.no_grad()
-    def prepare(self):
-        if self._pk is not None:
-            return
-        fp8 = fp8_mode.active(self)
-        if fp8 and self.inner_dim % 128:
+    def _check_packable(self):
+        if fp8_mode.active(self) and self.inner_dim % 128:
             raise LkgdHipError(f"the FP8 mode (quantize_to_float8 / LKGD_DIT_FP8) tiles N and K by 128: inner dim {self.inner_dim} is "
                                "not a multiple")
-        if self.device.type != "cuda":
-            raise LkgdHipError("lkgd_amd DiT runs on MI355X only: move the module to cuda first")
+
+    def _pack(self):
+        fp8 = fp8_mode.active(self)
         for b in self.transformer_blocks:
             b.pack(fp8)
         self.time_embedding.pack()
@@ -491,21 +471,20 @@ class CogVideoXTransformer3DModel(nn.Module):
         # every block's two modulation linears as ONE [blocks * 2 * 6D, Te] GEMM per step (+ norm_out's [2D, Te])
         mods = [m for b in self.transformer_blocks for m in (b.norm1.linear, b.norm2.linear)] + [self.norm_out.linear]
         pk.w_mod = torch.cat([pack_linear(m.weight) for m in mods], dim=0).contiguous()
-        pk.b_mod = torch.cat([_f32(m.bias) for m in mods]).contiguous()
+        pk.b_mod = torch.cat([f32(m.bias) for m in mods]).contiguous()
         nb = len(self.transformer_blocks)
-        pk.ln_g = torch.stack([torch.stack([_f32(b.norm1.norm.weight), _f32(b.norm2.norm.weight)]) for b in self.transformer_blocks])
-        pk.ln_b = torch.stack([torch.stack([_f32(b.norm1.norm.bias), _f32(b.norm2.norm.bias)]) for b in self.transformer_blocks])
+        pk.ln_g = torch.stack([torch.stack([f32(b.norm1.norm.weight), f32(b.norm2.norm.weight)]) for b in self.transformer_blocks])
+        pk.ln_b = torch.stack([torch.stack([f32(b.norm1.norm.bias), f32(b.norm2.norm.bias)]) for b in self.transformer_blocks])
         pk.nb = nb
-        pk.fin = (_f32(self.norm_final.weight), _f32(self.norm_final.bias))
-        pk.out_g, pk.out_b = _f32(self.norm_out.norm.weight), _f32(self.norm_out.norm.bias)
+        pk.fin = (f32(self.norm_final.weight), f32(self.norm_final.bias))
+        pk.out_g, pk.out_b = f32(self.norm_out.norm.weight), f32(self.norm_out.norm.bias)
         pe = self.patch_embed
         # [D, C*p*p], k = (c, ky, kx); temporal patches: [D, C*p_t*p*p], k = (c, pt, ky, kx) - both the order of the weight itself
-        pk.w_pe, pk.b_pe = pack_linear(pe.proj.weight.detach()), (_f32(pe.proj.bias) if pe.proj.bias is not None else None)
-        pk.w_tx, pk.b_tx = pack_linear(pe.text_proj.weight), _f32(pe.text_proj.bias)
-        pk.w_po, pk.b_po = pack_linear(self.proj_out.weight), _f32(self.proj_out.bias)
+        pk.w_pe, pk.b_pe = pack_linear(pe.proj.weight.detach()), (f32(pe.proj.bias) if pe.proj.bias is not None else None)
+        pk.w_tx, pk.b_tx = pack_linear(pe.text_proj.weight), f32(pe.text_proj.bias)
+        pk.w_po, pk.b_po = pack_linear(self.proj_out.weight), f32(self.proj_out.bias)
         pk.learned = pe.pos_embedding[0].detach().to(torch.float16).contiguous() if self.config.use_learned_positional_embeddings else None
-        self._pk = pk
-        self._pos = {}
+        return pk
 
     def _learned_table(self, Tt: int, f: int, h: int, w: int) -> torch.Tensor:
         """the learned joint table [max_text_seq_length + T h w, D] fp16; it has rows for the configured grid only, so any

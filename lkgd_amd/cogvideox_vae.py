@@ -55,8 +55,9 @@ import torch.nn as nn
 
 from . import ops
 from ._lib import LkgdHipError
-from .packing import pack_cconv3, pack_conv3x3, pack_linear
-from .vae import DecoderOutput, _f32, _new, _pad_cout
+from .module import PackedModule
+from .packing import f32, pack_cconv3, pack_conv3x3, pack_linear
+from .vae import DecoderOutput, _new, _pad_cout
 
 #: frames per batch of ``encode`` (diffusers' num_sample_frames_batch_size)
 ENCODE_FRAME_BATCH = 8
@@ -315,11 +316,11 @@ class CogVideoXSpatialNorm3D(nn.Module):
         self.conv_b = CogVideoXCausalConv3d(zq, c, 1)
 
     def pack(self):
-        self._g, self._bt = _f32(self.norm_layer.weight), _f32(self.norm_layer.bias)
+        self._g, self._bt = f32(self.norm_layer.weight), f32(self.norm_layer.bias)
         wy, wb = pack_linear(self.conv_y.conv.weight.detach()), pack_linear(self.conv_b.conv.weight.detach())
         w = torch.cat([wy, wb])                                       # [2C, zq]: the 1x1x1 pair as one GEMM on the latent grid
         self._wyb = torch.nn.functional.pad(w, (0, 64 - w.shape[1])).contiguous()
-        self._byb = torch.cat([_f32(self.conv_y.conv.bias), _f32(self.conv_b.conv.bias)]).contiguous()
+        self._byb = torch.cat([f32(self.conv_y.conv.bias), f32(self.conv_b.conv.bias)]).contiguous()
 
     def run(self, x: torch.Tensor, c: _Chunk, silu: bool = True):
         """norm (+ SiLU) of the chunk's rows ``x`` into a fresh [B, T + 2, H*W, C] buffer behind its two context frames"""
@@ -339,7 +340,7 @@ class CogVideoXGroupNorm(nn.GroupNorm):
     an ``nn.GroupNorm`` itself, so its state-dict keys are diffusers' ``...norm1.weight`` / ``...norm1.bias``"""
 
     def pack(self):
-        self._g, self._bt = _f32(self.weight), _f32(self.bias)
+        self._g, self._bt = f32(self.weight), f32(self.bias)
 
     def run(self, x: torch.Tensor, c: _Chunk, silu: bool = True):
         """GroupNorm (+ SiLU) of the batch's rows ``x`` into a fresh [B, T + 2, H*W, C] buffer behind its two context frames: the
@@ -374,7 +375,7 @@ class CogVideoXResnetBlock3D(nn.Module):
     def pack(self):
         self.norm1.pack(); self.norm2.pack(); self.conv1.pack(); self.conv2.pack()
         if self.conv_shortcut is not None:
-            self._ws, self._bs = pack_linear(self.conv_shortcut.weight.detach()), _f32(self.conv_shortcut.bias)
+            self._ws, self._bs = pack_linear(self.conv_shortcut.weight.detach()), f32(self.conv_shortcut.bias)
 
     def run(self, x: torch.Tensor, c: _Chunk):
         """launches: [the norm - spatial: plain GEMM (conv_y | conv_b), GroupNorm statistics unless the producing GEMM left column
@@ -398,7 +399,7 @@ class CogVideoXUpsample3D(nn.Module):
         self.conv = nn.Conv2d(c, c, 3, padding=1)
 
     def pack(self):
-        self._w, self._b = pack_conv3x3(self.conv.weight.detach()), _f32(self.conv.bias)
+        self._w, self._b = pack_conv3x3(self.conv.weight.detach()), f32(self.conv.bias)
 
     def run(self, x: torch.Tensor, c: _Chunk):
         """conv(dup(x)) = dup(conv(x)): the T frames are convolved once (nearest 2x in height / width inside the gather), then each
@@ -456,7 +457,7 @@ class CogVideoXDownsample3D(nn.Module):
         self.conv = nn.Conv2d(c, c, 3, stride=2, padding=0)
 
     def pack(self):
-        self._w, self._b = pack_conv3x3(self.conv.weight.detach()), _f32(self.conv.bias)
+        self._w, self._b = pack_conv3x3(self.conv.weight.detach()), f32(self.conv.bias)
 
     def run(self, x: torch.Tensor, c: _Chunk):
         """the pool runs first, as diffusers does: the convolution then has half the rows"""
@@ -499,7 +500,7 @@ class CogVideoXEncoder3D(nn.Module):
         w = self.conv_in.conv.weight.detach().float()                                  # [c0, Cin, 3, 3, 3]
         wk = w.permute(0, 2, 3, 4, 1).reshape(w.shape[0], -1)
         self._w_in = torch.nn.functional.pad(wk, (0, 128 - wk.shape[1])).to(torch.float16).contiguous()
-        self._b_in = _f32(self.conv_in.conv.bias)
+        self._b_in = f32(self.conv_in.conv.bias)
         self.norm_out.pack()
         self.conv_out.pack()
 
@@ -576,12 +577,14 @@ def _check_config(cfg: CogVAEConfig) -> None:
         raise LkgdHipError(f"AutoencoderKLCogVideoX: temporal_compression_ratio = {t}: a power of two below 2^len(block_out_channels)")
 
 
-class AutoencoderKLCogVideoX(nn.Module):
+class AutoencoderKLCogVideoX(PackedModule):
     """diffusers' AutoencoderKLCogVideoX [EXT], PARITY UNPINNED: the decoder, and with ``encoder=True`` the encoder.  State-dict
     names are diffusers' (``decoder.conv_in.conv.weight``, ``encoder.down_blocks.0.resnets.0.norm1.weight`` ...).  ``quant_conv.*``
     keys of a checkpoint are accepted and dropped; so are ``encoder.*`` keys when the module has no encoder - with one they load
     strictly.  Any other missing or unexpected key raises."""
 
+    OFF_GPU = "lkgd_amd CogVideoX VAE runs on MI355X only: move the module to cuda first"
+    config_class = CogVAEConfig
     DROPPED_PREFIXES = ("encoder.", "quant_conv.")
 
     def __init__(self, config: Optional[CogVAEConfig] = None, encoder: bool = False, **kw):
@@ -594,7 +597,6 @@ class AutoencoderKLCogVideoX(nn.Module):
         if encoder:
             _check_encoder_config(cfg)
             self.encoder = CogVideoXEncoder3D(cfg)
-        self._packed = False
         # diffusers' tiling / slicing state: off until enable_*; a tile is half the configured sample size
         self.use_tiling = False
         self.use_slicing = False
@@ -617,48 +619,23 @@ class AutoencoderKLCogVideoX(nn.Module):
         return ("quant_conv.",) if self.has_encoder else self.DROPPED_PREFIXES
 
     # ---- reference API surface ---------------------------------------------------------------------------------
-    @property
-    def dtype(self):
-        return self.decoder.conv_in.conv.weight.dtype
-
-    @property
-    def device(self):
-        return self.decoder.conv_in.conv.weight.device
-
     @classmethod
-    def from_pretrained(cls, pretrained_model_name_or_path: str, subfolder: Optional[str] = None, torch_dtype=None,
-                        variant: Optional[str] = None, encoder: Optional[bool] = None, **_ignored):
-        """``encoder`` None: the encoder is built iff the checkpoint holds an ``encoder.`` key (a saved decoder-only module comes
-        back decoder-only); True / False: as the constructor"""
-        from .loading import build_from_pretrained
-
+    def _build_options(cls, encoder: Optional[bool] = None, **_ignored):
+        """``from_pretrained(..., encoder=None)``: the encoder is built iff the checkpoint holds an ``encoder.`` key (a saved
+        decoder-only module comes back decoder-only); True / False: as the constructor"""
         def ctor(sd):
             return {"encoder": any(k.startswith("encoder.") for k in sd) if encoder is None else bool(encoder)}
 
-        return build_from_pretrained(cls, CogVAEConfig, pretrained_model_name_or_path, subfolder, torch_dtype, variant,
-                                     ctor_from_state=ctor)
-
-    def save_pretrained(self, save_directory: str, variant: Optional[str] = None, **_ignored):
-        from .loading import save_pretrained
-        save_pretrained(self, save_directory, dict(self.config.__dict__), type(self).__name__, variant)
-
-    def invalidate(self):
-        self._packed = False
+        return {"ctor_from_state": ctor}
 
     def load_state_dict(self, state_dict, strict: bool = True, **k):
         """``quant_conv.*`` keys are dropped, ``encoder.*`` keys too when the module has no encoder; every other missing or unexpected
         key raises (whatever ``strict``)"""
         sd = {n: v for n, v in state_dict.items() if not n.startswith(self._dropped_prefixes())}
         r = super().load_state_dict(sd, strict=False, **k)
-        self._packed = False
         if r.missing_keys or r.unexpected_keys:
             raise RuntimeError(f"AutoencoderKLCogVideoX.load_state_dict: missing keys {list(r.missing_keys)[:5]}, "
                                f"unexpected keys {list(r.unexpected_keys)[:5]}")
-        return r
-
-    def _apply(self, fn, *a, **k):
-        r = super()._apply(fn, *a, **k)
-        self._packed = False
         return r
 
     def _require_gpu(self, what: str):
@@ -712,12 +689,7 @@ class AutoencoderKLCogVideoX(nn.Module):
         return total
 
     # ---- packing -----------------------------------------------------------------------------------------------
-    @torch.no_grad()
-    def prepare(self):
-        if self._packed:
-            return
-        if self.device.type != "cuda":
-            raise LkgdHipError("lkgd_amd CogVideoX VAE runs on MI355X only: move the module to cuda first")
+    def _pack(self):
         d = self.decoder
         for m in self.modules():
             if isinstance(m, (CogVideoXResnetBlock3D, CogVideoXUpsample3D, CogVideoXDownsample3D)):
@@ -727,7 +699,7 @@ class AutoencoderKLCogVideoX(nn.Module):
         d.conv_out.pack(pad_cout=4)                 # GEMM output granularity
         if self.has_encoder:
             self.encoder.pack()
-        self._packed = True
+        return True                 # the packed weights live on the submodules
 
     # ---- encode ------------------------------------------------------------------------------------------------
     def _encode_batch(self, xh: torch.Tensor, a: int, b: int, mom: torch.Tensor, t_out: int, caches) -> int:

@@ -29,8 +29,8 @@ import torch.nn as nn
 
 from . import ops
 from ._lib import LkgdHipError
-from .packing import pack_conv3x3, pack_linear
-from .unet import Ctx, UNetConfig, _UNetBase, _f32
+from .packing import f32, pack_conv3x3, pack_linear
+from .unet import Ctx, UNetConfig, _UNetBase
 
 
 @dataclass
@@ -64,13 +64,13 @@ class ControlNetConditioningEmbeddingSVD(nn.Module):
         w = conv.weight.detach().permute(0, 2, 3, 1)                       # [Cout, 3, 3, Cin]
         if w.shape[3] < cin_pad:
             w = torch.nn.functional.pad(w, (0, cin_pad - w.shape[3]))
-        return w.to(torch.float16).contiguous(), _f32(conv.bias)
+        return w.to(torch.float16).contiguous(), f32(conv.bias)
 
     def pack(self):
         pk = SimpleNamespace()
         pk.first = self._pack_small(self.conv_in, 8)                        # 3 input channels padded to 8
         pk.blocks = [self._pack_small(b, b.in_channels) + (b.stride[0],) for b in self.blocks]
-        pk.w_out, pk.b_out = pack_conv3x3(self.conv_out.weight.detach()), _f32(self.conv_out.bias)
+        pk.w_out, pk.b_out = pack_conv3x3(self.conv_out.weight.detach()), f32(self.conv_out.bias)
         self._pk = pk
 
     def run_until_out(self, cond: torch.Tensor):
@@ -121,15 +121,9 @@ class ControlNetSDVModel(_UNetBase):
         self._cond_cache = None
 
     @classmethod
-    def from_pretrained(cls, pretrained_model_name_or_path: str, subfolder: Optional[str] = None, torch_dtype=None,
-                        variant: Optional[str] = None, **_ignored):
-        from .loading import build_from_pretrained
-        return build_from_pretrained(cls, UNetConfig, pretrained_model_name_or_path, subfolder, torch_dtype, variant,
-                                     conditioning_channels=3, conditioning_embedding_out_channels=(16, 32, 96, 256))
-
-    def save_pretrained(self, save_directory: str, variant: Optional[str] = None, **_ignored):
-        from .loading import save_pretrained
-        save_pretrained(self, save_directory, dict(self.config.__dict__), type(self).__name__, variant)
+    def _build_options(cls, **_ignored):
+        # constructor keywords beside the UNetConfig: the directory's config.json overrides these defaults
+        return dict(conditioning_channels=3, conditioning_embedding_out_channels=(16, 32, 96, 256))
 
     @classmethod
     def from_unet(cls, unet, controlnet_conditioning_channel_order: str = "rgb",
@@ -148,10 +142,10 @@ class ControlNetSDVModel(_UNetBase):
 
     def _pack_extra(self, pk):
         self.controlnet_cond_embedding.pack()
-        pk.zero = [(pack_linear(m.weight.detach().reshape(m.out_channels, m.in_channels)), _f32(m.bias))
+        pk.zero = [(pack_linear(m.weight.detach().reshape(m.out_channels, m.in_channels)), f32(m.bias))
                    for m in self.controlnet_down_blocks]
         pk.zero_mid = (pack_linear(self.controlnet_mid_block.weight.detach().reshape(
-            self.controlnet_mid_block.out_channels, -1)), _f32(self.controlnet_mid_block.bias))
+            self.controlnet_mid_block.out_channels, -1)), f32(self.controlnet_mid_block.bias))
         self._cond_cache = None
 
     def _cond_tokens(self, cond: torch.Tensor, B: int, F: int, H: int, W: int):

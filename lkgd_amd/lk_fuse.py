@@ -28,18 +28,18 @@ def hamilton(q) -> torch.Tensor:
 def pack_lk(unet):
     """the 18 fp32 operands of lkgd_lk_fuse (include/lkgd_hip.h section 17), matrices as (in, out) row-major; built once per
     weight version (kept on the model's pack)"""
-    def f32(t):
+    def dev32(t):
         return t.detach().to(device=unet.device, dtype=torch.float32).contiguous()
     sf = unet.quaternion_lora_fuse_sf
     l0m, l0p = unet.quaternion_lora_fuse_fft_mag0, unet.quaternion_lora_fuse_fft_pha0
-    ws = [f32(unet.quaternion_lora_lconv.weight.reshape(256, 4)), f32(unet.quaternion_lora_dconv.weight.reshape(256, 4)),
-          f32(unet.quaternion_lora_fconv.weight.reshape(256, 4)), f32(unet.quaternion_lora_texts.reshape(256)),
-          f32(hamilton(unet.quaternion_lora_fuse)), f32(unet.quaternion_lora_fuse.bias),
-          f32(unet.quaternion_lora_texts_fft_mag.reshape(129)), f32(unet.quaternion_lora_texts_fft_pha.reshape(129)),
-          f32(hamilton(unet.quaternion_lora_fuse_fft_mag)), f32(unet.quaternion_lora_fuse_fft_mag.bias),
-          f32(hamilton(unet.quaternion_lora_fuse_fft_pha)), f32(unet.quaternion_lora_fuse_fft_pha.bias),
-          f32(torch.cat([l0m.weight.reshape(4), l0m.bias.reshape(1)])), f32(torch.cat([l0p.weight.reshape(4), l0p.bias.reshape(1)])),
-          f32(sf[0].weight.T), f32(sf[0].bias), f32(sf[2].weight.T), f32(sf[2].bias)]
+    ws = [dev32(unet.quaternion_lora_lconv.weight.reshape(256, 4)), dev32(unet.quaternion_lora_dconv.weight.reshape(256, 4)),
+          dev32(unet.quaternion_lora_fconv.weight.reshape(256, 4)), dev32(unet.quaternion_lora_texts.reshape(256)),
+          dev32(hamilton(unet.quaternion_lora_fuse)), dev32(unet.quaternion_lora_fuse.bias),
+          dev32(unet.quaternion_lora_texts_fft_mag.reshape(129)), dev32(unet.quaternion_lora_texts_fft_pha.reshape(129)),
+          dev32(hamilton(unet.quaternion_lora_fuse_fft_mag)), dev32(unet.quaternion_lora_fuse_fft_mag.bias),
+          dev32(hamilton(unet.quaternion_lora_fuse_fft_pha)), dev32(unet.quaternion_lora_fuse_fft_pha.bias),
+          dev32(torch.cat([l0m.weight.reshape(4), l0m.bias.reshape(1)])), dev32(torch.cat([l0p.weight.reshape(4), l0p.bias.reshape(1)])),
+          dev32(sf[0].weight.T), dev32(sf[0].bias), dev32(sf[2].weight.T), dev32(sf[2].bias)]
     shapes = [(256, 4)] * 3 + [(256,), (1024, 512), (512,), (129,), (129,), (512, 256), (256,), (512, 256), (256,), (5,), (5,),
               (1024, 256), (256,), (256, 1024), (1024,)]
     for w, shp in zip(ws, shapes):
@@ -98,19 +98,19 @@ def pack_lk_tokens(transformer):
     pack)"""
     dev = transformer.device
 
-    def f32(t):
+    def dev32(t):
         return t.detach().to(device=dev, dtype=torch.float32).contiguous()
     m = transformer
     sf = m.quaternion_lora_fuse_sf
     l0m, l0p = m.quaternion_lora_fuse_fft_mag0, m.quaternion_lora_fuse_fft_pha0
-    ws = [f32(m.quaternion_lora_lconv.weight.reshape(256, 16)), f32(m.quaternion_lora_dconv.weight.reshape(256, 4)),
-          f32(m.quaternion_lora_fconv.weight.reshape(256, 4)), f32(m.quaternion_lora_texts.reshape(256)),
-          f32(hamilton(m.quaternion_lora_fuse)), f32(m.quaternion_lora_fuse.bias),
-          f32(m.quaternion_lora_texts_fft_mag.reshape(129)), f32(m.quaternion_lora_texts_fft_pha.reshape(129)),
-          f32(hamilton(m.quaternion_lora_fuse_fft_mag)), f32(m.quaternion_lora_fuse_fft_mag.bias),
-          f32(hamilton(m.quaternion_lora_fuse_fft_pha)), f32(m.quaternion_lora_fuse_fft_pha.bias),
-          f32(torch.cat([l0m.weight.reshape(4), l0m.bias.reshape(1)])), f32(torch.cat([l0p.weight.reshape(4), l0p.bias.reshape(1)])),
-          f32(sf[0].weight.T), f32(sf[0].bias), f32(sf[2].weight.T), f32(sf[2].bias)]
+    ws = [dev32(m.quaternion_lora_lconv.weight.reshape(256, 16)), dev32(m.quaternion_lora_dconv.weight.reshape(256, 4)),
+          dev32(m.quaternion_lora_fconv.weight.reshape(256, 4)), dev32(m.quaternion_lora_texts.reshape(256)),
+          dev32(hamilton(m.quaternion_lora_fuse)), dev32(m.quaternion_lora_fuse.bias),
+          dev32(m.quaternion_lora_texts_fft_mag.reshape(129)), dev32(m.quaternion_lora_texts_fft_pha.reshape(129)),
+          dev32(hamilton(m.quaternion_lora_fuse_fft_mag)), dev32(m.quaternion_lora_fuse_fft_mag.bias),
+          dev32(hamilton(m.quaternion_lora_fuse_fft_pha)), dev32(m.quaternion_lora_fuse_fft_pha.bias),
+          dev32(torch.cat([l0m.weight.reshape(4), l0m.bias.reshape(1)])), dev32(torch.cat([l0p.weight.reshape(4), l0p.bias.reshape(1)])),
+          dev32(sf[0].weight.T), dev32(sf[0].bias), dev32(sf[2].weight.T), dev32(sf[2].bias)]
     for w, shp in zip(ws, LK_TOKENS_SHAPES):
         if tuple(w.shape) != shp:
             raise LkgdHipError(f"latent-knowledge fuse of the text tokens: parameter of shape {tuple(w.shape)}, expected {shp}")

@@ -5,7 +5,9 @@ The reference loads everything through diffusers' ``ModelMixin.from_pretrained``
 is ``config.json`` + ``diffusion_pytorch_model[.<variant>].safetensors`` (or a sharded ``*.safetensors.index.json``, or
 ``.bin``); a pipeline directory holds one sub-folder per component (``unet/``, ``vae/``, ``image_encoder/``,
 ``feature_extractor/``, ``scheduler/scheduler_config.json``) and a ``model_index.json``.  Reading that needs no diffusers:
-json + safetensors.  Weights go host -> HBM once; nothing here is on the hot path.
+json + safetensors.  Weights go host -> HBM once; nothing here is on the hot path.  The two encoders transformers owns
+(``text_encoder/``, ``image_encoder/``) are in its layout - ``model.safetensors`` / ``pytorch_model.bin`` and an ``architectures``
+header - read and written by the second pair of functions at the end.
 """
 from __future__ import annotations
 
@@ -97,3 +99,37 @@ def build_from_pretrained(cls, config_cls, path: str, subfolder: Optional[str] =
                            f"{'...' if len(unexpected) > 5 else ''}")
     m._name_or_path = os.path.join(path, subfolder) if subfolder else path
     return m
+
+
+# ---- the transformers directory layout (text_encoder/, image_encoder/) -------------------------------------------------------------
+def build_from_transformers(cls, config_cls, path: str, subfolder: Optional[str] = None, torch_dtype=torch.float16, dtype=None,
+                            variant: Optional[str] = None, drop_suffix: Optional[str] = None):
+    """shared body of ``T5EncoderModel`` / ``CLIPVisionModelWithProjection`` ``from_pretrained``: ``config.json`` (the keys the
+    dataclass knows) + ``model[.<variant>].safetensors``, its sharded index form, or ``pytorch_model.bin``; built on the meta device,
+    every key checked, the checkpoint's tensors assigned.  ``drop_suffix``: keys ending in it are left out (buffers older checkpoints
+    persisted).  ``dtype`` wins over ``torch_dtype``, as in transformers."""
+    raw = load_config(path, subfolder)
+    known = {k: v for k, v in raw.items() if k in config_cls.__dataclass_fields__}
+    with torch.device("meta"):
+        model = cls(config_cls(**known))
+    try:
+        sd = load_state_dict(path, subfolder, variant, weights_name="model")
+    except OSError:
+        sd = load_state_dict(path, subfolder, variant, weights_name="pytorch_model")
+    if drop_suffix:
+        sd = {k: v for k, v in sd.items() if not k.endswith(drop_suffix)}
+    model.load_state_dict(sd, strict=True, assign=True)
+    return model.to(dtype if dtype is not None else torch_dtype)
+
+
+def save_transformers(model: torch.nn.Module, path: str, header: Dict, omit=()) -> None:
+    """``config.json`` = ``header`` (``architectures`` / ``model_type`` ...) + the model's config, and one ``model.safetensors``
+    without the keys in ``omit`` (a safetensors file holds one tensor per storage: tied copies stay out)"""
+    from safetensors.torch import save_file
+    os.makedirs(path, exist_ok=True)
+    cfg = dict(header)
+    cfg.update(model.config.__dict__)
+    with open(os.path.join(path, "config.json"), "w") as fh:
+        json.dump(cfg, fh, indent=2)
+    save_file({k: v.detach().cpu().contiguous() for k, v in model.state_dict().items() if k not in omit},
+              os.path.join(path, "model.safetensors"))

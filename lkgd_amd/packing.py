@@ -7,6 +7,11 @@ from __future__ import annotations
 import torch
 
 
+def f32(p: torch.Tensor) -> torch.Tensor:
+    """a norm affine / bias as the kernels read it: detached, fp32, contiguous"""
+    return p.detach().to(torch.float32).contiguous()
+
+
 def pack_linear(w: torch.Tensor) -> torch.Tensor:
     """nn.Linear / 1x1 conv weight [N, K(,1,1)] -> fp16 [N, K]"""
     return w.reshape(w.shape[0], -1).to(torch.float16).contiguous()

@@ -26,7 +26,6 @@ built.
 from __future__ import annotations
 
 import math
-import os
 from collections import namedtuple
 from dataclasses import dataclass
 from types import SimpleNamespace
@@ -37,8 +36,9 @@ import torch.nn as nn
 
 from . import ops
 from ._lib import LkgdHipError
-from .loading import load_config, load_state_dict
-from .packing import pack_linear
+from .loading import build_from_transformers, save_transformers
+from .module import PackedModule
+from .packing import f32, pack_linear
 
 #: the closing projections' accumulator scale and the factor their residual add undoes it with (both powers of two: exact)
 S_ACC = 2.0 ** -6
@@ -105,10 +105,6 @@ def relative_bias_table(weight: torch.Tensor, S: int, num_buckets: int, max_dist
     return weight.detach().float()[bucket.to(weight.device)].t().contiguous()
 
 
-def _f32(p):
-    return p.detach().to(torch.float32).contiguous()
-
-
 # ---- the parameter holders: transformers' module tree ------------------------------------------------------------------------------
 class T5LayerNorm(nn.Module):
     def __init__(self, d: int, eps: float):
@@ -164,7 +160,7 @@ class T5Block(nn.Module):
         wo = torch.zeros(ff.wo.weight.shape[0], Fp, dtype=torch.float16, device=ff.wo.weight.device)
         wo[:, :F_] = ff.wo.weight.detach().to(torch.float16)
         self._pk = SimpleNamespace(
-            g1=_f32(self.layer[0].layer_norm.weight), g2=_f32(self.layer[1].layer_norm.weight),
+            g1=f32(self.layer[0].layer_norm.weight), g2=f32(self.layer[1].layer_norm.weight),
             wqkv=pack_linear(torch.cat([a.q.weight, a.k.weight, a.v.weight], dim=0).detach()), wo=pack_linear(a.o.weight.detach()),
             wi=wi, wo2=wo, Fp=Fp)
 
@@ -180,7 +176,7 @@ class T5Stack(nn.Module):
 TIED = ("shared.weight", "encoder.embed_tokens.weight")
 
 
-class T5EncoderModel(nn.Module):
+class T5EncoderModel(PackedModule):
     """transformers' class of the same name: parameter holder + HIP forward; ``model(input_ids)[0]`` is fp16 [B, S, d_model]"""
 
     def __init__(self, config: Optional[T5Config] = None, **kw):
@@ -190,8 +186,9 @@ class T5EncoderModel(nn.Module):
         self.config = cfg
         self.shared = nn.Embedding(cfg.vocab_size, cfg.d_model)
         self.encoder = T5Stack(cfg, self.shared)          # embed_tokens IS shared (transformers ties them): both keys, one tensor
-        self._pk = None
         self._bias_tables = {}
+
+    OFF_GPU = "lkgd_amd T5 runs on MI355X only: move the module to cuda first"
 
     # ---- loading ------------------------------------------------------------------------------------------------------
     @classmethod
@@ -199,36 +196,12 @@ class T5EncoderModel(nn.Module):
                         variant: Optional[str] = None, **_ignored):
         """a local ``text_encoder/`` directory: ``config.json`` + ``model[.<variant>].safetensors``, the sharded
         ``model.safetensors.index.json`` form of the released checkpoint, or ``pytorch_model.bin``; every key is checked"""
-        raw = load_config(path, subfolder)
-        known = {k: v for k, v in raw.items() if k in T5Config.__dataclass_fields__}
-        with torch.device("meta"):
-            model = cls(T5Config(**known))
-        try:
-            sd = load_state_dict(path, subfolder, variant, weights_name="model")
-        except OSError:
-            sd = load_state_dict(path, subfolder, variant, weights_name="pytorch_model")
-        model.load_state_dict(sd, strict=True, assign=True)
-        return model.to(dtype if dtype is not None else torch_dtype)
+        return build_from_transformers(cls, T5Config, path, subfolder, torch_dtype, dtype, variant)
 
     def save_pretrained(self, path: str, **_kw):
-        import json
-        from safetensors.torch import save_file
-        os.makedirs(path, exist_ok=True)
-        cfg = {"architectures": ["T5EncoderModel"], "model_type": "t5", "is_gated_act": True, "dense_act_fn": "gelu_new"}
-        cfg.update(self.config.__dict__)
-        with open(os.path.join(path, "config.json"), "w") as fh:
-            json.dump(cfg, fh, indent=2)
         # one tensor per storage: the tied copy is left out, as transformers' own save does
-        save_file({k: v.detach().cpu().contiguous() for k, v in self.state_dict().items() if k != TIED[1]},
-                  os.path.join(path, "model.safetensors"))
-
-    @property
-    def device(self):
-        return self.shared.weight.device
-
-    @property
-    def dtype(self):
-        return self.shared.weight.dtype
+        save_transformers(self, path, {"architectures": ["T5EncoderModel"], "model_type": "t5", "is_gated_act": True,
+                                       "dense_act_fn": "gelu_new"}, omit=(TIED[1],))
 
     def load_state_dict(self, state_dict, *a, **k):
         """``encoder.embed_tokens.weight`` is the tied copy of ``shared.weight``: either may be absent (a safetensors file holds one
@@ -240,19 +213,10 @@ class T5EncoderModel(nn.Module):
             sd[TIED[1]] = sd[TIED[0]]
         elif TIED[0] in sd or TIED[1] in sd:
             sd[TIED[0]] = sd[TIED[1]] = sd[TIED[0]] if TIED[0] in sd else sd[TIED[1]]
-        r = super().load_state_dict(sd, *a, **k)
-        self.invalidate()
-        return r
+        return super().load_state_dict(sd, *a, **k)
 
-    def _apply(self, fn, *a, **k):
-        r = super()._apply(fn, *a, **k)
-        self.invalidate()
-        return r
-
-    def invalidate(self):
-        """forget the packed weights and the bias tables (after the parameters changed)"""
-        self._pk = None
-        self._bias_tables = {}
+    def _forget(self):
+        self._bias_tables = {}          # built from layer 0's relative_attention_bias
 
     # ---- forward ------------------------------------------------------------------------------------------------------
     def bias_table(self, S: int) -> torch.Tensor:
@@ -264,16 +228,11 @@ class T5EncoderModel(nn.Module):
             t = self._bias_tables[S] = relative_bias_table(w, S, cfg.relative_attention_num_buckets, cfg.relative_attention_max_distance)
         return t
 
-    @torch.no_grad()
-    def prepare(self):
-        if self._pk is not None:
-            return
-        if self.device.type != "cuda":
-            raise LkgdHipError("lkgd_amd T5 runs on MI355X only: move the module to cuda first")
+    def _pack(self):
         for blk in self.encoder.block:
             blk.pack()
-        self._pk = SimpleNamespace(table=self.shared.weight.detach().to(torch.float16).contiguous(),
-                                   g_final=_f32(self.encoder.final_layer_norm.weight))
+        return SimpleNamespace(table=self.shared.weight.detach().to(torch.float16).contiguous(),
+                               g_final=f32(self.encoder.final_layer_norm.weight))
 
     @torch.no_grad()
     def forward(self, input_ids: torch.Tensor, attention_mask=None, **_kw):

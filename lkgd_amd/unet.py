@@ -38,7 +38,8 @@ from . import ops
 from . import replay as _replay
 from . import trace as _trace
 from ._lib import LkgdHipError
-from .packing import (pack_conv3x3, pack_conv3x3_c8, pack_ff_fused, pack_geglu, pack_linear, pack_ln_proj, pack_tblock,
+from .module import PackedModule
+from .packing import (f32, pack_conv3x3, pack_conv3x3_c8, pack_ff_fused, pack_geglu, pack_linear, pack_ln_proj, pack_tblock,
                       pack_tconv3, pack_tfront)
 
 #: row order of the temporal cross-attention context, see SURVEY.md App. C11.  "interleaved_0_27" reproduces
@@ -126,10 +127,6 @@ class Ctx:
         return torch.empty(rows, cols, dtype=torch.float16, device=self.device)
 
 
-def _f32(p: torch.Tensor) -> torch.Tensor:
-    return p.detach().to(torch.float32).contiguous()
-
-
 class _Packed:
     """marker base: modules that own kernel-layout copies of their weights"""
     _pk = None
@@ -147,8 +144,8 @@ class TimestepEmbedding(nn.Module):
         self.linear_2 = nn.Linear(time_embed_dim, out_dim if out_dim is not None else time_embed_dim)
 
     def pack(self):
-        self._pk = SimpleNamespace(w1=pack_linear(self.linear_1.weight), b1=_f32(self.linear_1.bias),
-                                   w2=pack_linear(self.linear_2.weight), b2=_f32(self.linear_2.bias))
+        self._pk = SimpleNamespace(w1=pack_linear(self.linear_1.weight), b1=f32(self.linear_1.bias),
+                                   w2=pack_linear(self.linear_2.weight), b2=f32(self.linear_2.bias))
 
     def run(self, x: torch.Tensor, res: Optional[torch.Tensor] = None) -> torch.Tensor:
         """x fp16 [M, in] -> linear_2(silu(linear_1(x))) (+ res)"""
@@ -190,7 +187,7 @@ class Attention(nn.Module):
             w, bqkv = _fold_ln(norm, w, None)
             bqkv = bqkv.contiguous()
         return SimpleNamespace(wqkv=pack_linear(w), bqkv=bqkv,
-                               wo=pack_linear(_eff_weight(self.to_out[0], ao)), bo=_f32(self.to_out[0].bias))
+                               wo=pack_linear(_eff_weight(self.to_out[0], ao)), bo=f32(self.to_out[0].bias))
 
     def pack_cross(self, norm: nn.LayerNorm):
         """literal cross-attention (context of more than one token): Q projection with the preceding LayerNorm folded in,
@@ -198,7 +195,7 @@ class Attention(nn.Module):
         wq, bq = _fold_ln(norm, _eff_weight(self.to_q), None)
         wkv = torch.cat([_eff_weight(self.to_k), _eff_weight(self.to_v)], dim=0)
         return SimpleNamespace(wq=pack_linear(wq), bq=bq.contiguous(), wkv=pack_linear(wkv),
-                               wo=pack_linear(_eff_weight(self.to_out[0])), bo=_f32(self.to_out[0].bias))
+                               wo=pack_linear(_eff_weight(self.to_out[0])), bo=f32(self.to_out[0].bias))
 
     def fold_cross(self, adapters=((), ())):
         """single key/value token => attn2(x, e) == to_out(to_v(e)): returns (W_o @ W_v [C,1024] fp32, b_o); LoRA on
@@ -206,7 +203,7 @@ class Attention(nn.Module):
         av, ao = adapters
         wo = _eff_weight(self.to_out[0], ao).to(torch.float32)
         wv = _eff_weight(self.to_v, av).to(torch.float32)
-        return wo @ wv, _f32(self.to_out[0].bias)
+        return wo @ wv, f32(self.to_out[0].bias)
 
 
 def _eff_weight(lin, adapters=()) -> torch.Tensor:
@@ -429,7 +426,7 @@ class FeedForward(nn.Module):
         if norm is not None:
             w, b = _fold_ln(norm, w, b)
         wp, bp, half = pack_geglu(w, b)
-        pk = SimpleNamespace(wp=wp, bp=bp, half=half, wo=pack_linear(self.net[2].weight), bo=_f32(self.net[2].bias),
+        pk = SimpleNamespace(wp=wp, bp=bp, half=half, wo=pack_linear(self.net[2].weight), bo=f32(self.net[2].bias),
                              wfused=None)
         w2 = self.net[2].weight.detach()
         if norm is not None and ops.ff_fused_ok(w.shape[1], w2.shape[1]) and w2.shape[0] == w.shape[1]:
@@ -519,7 +516,7 @@ class BasicTransformerBlock(nn.Module):
             pk.a1n = self.attn1n.pack_self(self.norm1)
             _pack_joint_post(self, pk, spatial=True)
         if hasattr(self, "conv_fuse"):      # FSM hook (lkgd_amd/patch_FSM.py)
-            pk.wfuse, pk.bfuse = pack_conv3x3(self.conv_fuse.weight), _f32(self.conv_fuse.bias)
+            pk.wfuse, pk.bfuse = pack_conv3x3(self.conv_fuse.weight), f32(self.conv_fuse.bias)
         pk.var = {}                         # masked-LoRA weight variants, built on demand (_attn_variant)
         self._pk = pk
 
@@ -826,9 +823,9 @@ class TransformerSpatioTemporalModel(nn.Module):
         self._posemb = {}
 
     def pack(self, model):
-        self._pk = SimpleNamespace(gn=(_f32(self.norm.weight), _f32(self.norm.bias)),
-                                   win=pack_linear(self.proj_in.weight), bin=_f32(self.proj_in.bias),
-                                   wout=pack_linear(self.proj_out.weight), bout=_f32(self.proj_out.bias))
+        self._pk = SimpleNamespace(gn=(f32(self.norm.weight), f32(self.norm.bias)),
+                                   win=pack_linear(self.proj_in.weight), bin=f32(self.proj_in.bias),
+                                   wout=pack_linear(self.proj_out.weight), bout=f32(self.proj_out.bias))
         self.time_pos_embed.pack()
         self._posemb = {}
         self._alpha = None
@@ -900,15 +897,15 @@ class SpatioTemporalResBlock(nn.Module):
     def pack(self, model):
         s, t = self.spatial_res_block, self.temporal_res_block
         pk = SimpleNamespace(
-            n1=(_f32(s.norm1.weight), _f32(s.norm1.bias)), n2=(_f32(s.norm2.weight), _f32(s.norm2.bias)),
-            w1=pack_conv3x3(s.conv1.weight.detach()), b1=_f32(s.conv1.bias),
-            w2=pack_conv3x3(s.conv2.weight.detach()), b2=_f32(s.conv2.bias),
-            tn1=(_f32(t.norm1.weight), _f32(t.norm1.bias)), tn2=(_f32(t.norm2.weight), _f32(t.norm2.bias)),
-            tw1=pack_tconv3(t.conv1.weight.detach()), tb1=_f32(t.conv1.bias),
-            tw2=pack_tconv3(t.conv2.weight.detach()), tb2=_f32(t.conv2.bias),
+            n1=(f32(s.norm1.weight), f32(s.norm1.bias)), n2=(f32(s.norm2.weight), f32(s.norm2.bias)),
+            w1=pack_conv3x3(s.conv1.weight.detach()), b1=f32(s.conv1.bias),
+            w2=pack_conv3x3(s.conv2.weight.detach()), b2=f32(s.conv2.bias),
+            tn1=(f32(t.norm1.weight), f32(t.norm1.bias)), tn2=(f32(t.norm2.weight), f32(t.norm2.bias)),
+            tw1=pack_tconv3(t.conv1.weight.detach()), tb1=f32(t.conv1.bias),
+            tw2=pack_tconv3(t.conv2.weight.detach()), tb2=f32(t.conv2.bias),
             eps=s.eps, teps=t.eps)
         if s.conv_shortcut is not None:
-            pk.ws, pk.bs = pack_linear(s.conv_shortcut.weight.detach()), _f32(s.conv_shortcut.bias)
+            pk.ws, pk.bs = pack_linear(s.conv_shortcut.weight.detach()), f32(s.conv_shortcut.bias)
         pk.toff_s = model._register_temb(s.time_emb_proj)
         pk.toff_t = model._register_temb(t.time_emb_proj)
         pk.alpha = None
@@ -1014,7 +1011,7 @@ class Downsample2D(nn.Module):
         self.conv = nn.Conv2d(channels, channels, 3, stride=2, padding=1)
 
     def pack(self, model):
-        self._pk = SimpleNamespace(w=pack_conv3x3(self.conv.weight.detach()), b=_f32(self.conv.bias))
+        self._pk = SimpleNamespace(w=pack_conv3x3(self.conv.weight.detach()), b=f32(self.conv.bias))
 
     def run(self, ctx: Ctx, x: torch.Tensor) -> torch.Tensor:
         C_ = self.channels
@@ -1033,7 +1030,7 @@ class Upsample2D(nn.Module):
         self.conv = nn.Conv2d(channels, channels, 3, padding=1)
 
     def pack(self, model):
-        self._pk = SimpleNamespace(w=pack_conv3x3(self.conv.weight.detach()), b=_f32(self.conv.bias))
+        self._pk = SimpleNamespace(w=pack_conv3x3(self.conv.weight.detach()), b=f32(self.conv.bias))
 
     def run(self, ctx: Ctx, x: torch.Tensor) -> torch.Tensor:
         C_ = self.channels
@@ -1203,7 +1200,9 @@ def get_up_block(t, num_layers, in_channels, out_channels, prev_output_channel, 
 
 
 # ----------------------------------------------------------------------------------------------- top level
-class _UNetBase(nn.Module):
+class _UNetBase(PackedModule):
+    OFF_GPU = "lkgd_amd UNet runs on MI355X only: move the module to cuda before forward()"
+    config_class = UNetConfig
     _encoder_only = False      # lkgd_amd.controlnet: conv_in, embeddings, down blocks and mid block only
 
     def __init__(self, config: Optional[UNetConfig] = None, **kw):
@@ -1242,7 +1241,6 @@ class _UNetBase(nn.Module):
         self._init_extra(cfg)
         self.mid_block = UNetMidBlockSpatioTemporal(boc[-1], ted, transformer_layers_per_block=tlpb[-1],
                                                     num_attention_heads=heads[-1], cross_attention_dim=cross[-1])
-        self._pk = None
         self._temb_reg: List[nn.Linear] = []
         self._cross_reg: List[Attention] = []
         if self._encoder_only:
@@ -1267,32 +1265,11 @@ class _UNetBase(nn.Module):
     def _pack_extra(self, pk):
         pass
 
-    # ---- reference API surface -----------------------------------------------------------------
-    @classmethod
-    def from_pretrained(cls, pretrained_model_name_or_path: str, subfolder: Optional[str] = None, torch_dtype=None,
-                        variant: Optional[str] = None, **_ignored):
-        """``ModelMixin.from_pretrained`` [EXT] for a local diffusers directory (``unet/config.json`` + safetensors), as
-        /root/reference/utils/util.py:607 / run_inference_svd.py:164 call it; hub / cache / device-map keywords are
-        accepted and ignored"""
-        from .loading import build_from_pretrained
-        return build_from_pretrained(cls, UNetConfig, pretrained_model_name_or_path, subfolder, torch_dtype, variant)
-
-    def save_pretrained(self, save_directory: str, variant: Optional[str] = None, **_ignored):
-        from .loading import save_pretrained
-        save_pretrained(self, save_directory, dict(self.config.__dict__), type(self).__name__, variant)
-
+    # ---- reference API surface: from_pretrained / save_pretrained are PackedModule's ----------------
     def set_adapters(self, adapter_names, weights=None):
         """``unet.set_adapters`` [EXT PeftAdapterMixin], /root/reference/utils/util.py:596"""
         from . import lora
         lora.set_adapters(self, adapter_names, weights)
-
-    @property
-    def dtype(self):
-        return self.conv_in.weight.dtype
-
-    @property
-    def device(self):
-        return self.conv_in.weight.device
 
     @property
     def attn_processors(self):
@@ -1323,27 +1300,7 @@ class _UNetBase(nn.Module):
         self._cross_reg.append(attn2)
         return off
 
-    def invalidate(self):
-        """call after changing parameters in place (load_state_dict / .to() do it automatically)"""
-        self._pk = None
-
-    def load_state_dict(self, *a, **k):
-        r = super().load_state_dict(*a, **k)
-        self._pk = None
-        return r
-
-    def _apply(self, fn, *a, **k):
-        r = super()._apply(fn, *a, **k)
-        self._pk = None
-        return r
-
-    @torch.no_grad()
-    def prepare(self):
-        """(re)build the kernel-layout weights; idempotent, runs once per weight version"""
-        if self._pk is not None:
-            return
-        if self.device.type != "cuda":
-            raise LkgdHipError("lkgd_amd UNet runs on MI355X only: move the module to cuda before forward()")
+    def _pack(self):
         self._temb_reg, self._cross_reg = [], []
         for name, mod in self.named_modules():          # dotted paths for the roctx ranges (lkgd_amd/trace.py)
             mod._trace_name = name or type(self).__name__
@@ -1353,15 +1310,15 @@ class _UNetBase(nn.Module):
             blk.pack(self)
         pk = SimpleNamespace()
         pk.w_in = pack_conv3x3_c8(self.conv_in.weight.detach())
-        pk.b_in = _f32(self.conv_in.bias)
+        pk.b_in = f32(self.conv_in.bias)
         if not self._encoder_only:
-            pk.gn_out = (_f32(self.conv_norm_out.weight), _f32(self.conv_norm_out.bias))
+            pk.gn_out = (f32(self.conv_norm_out.weight), f32(self.conv_norm_out.bias))
             pk.w_out = pack_conv3x3(self.conv_out.weight.detach())
-            pk.b_out = _f32(self.conv_out.bias)
+            pk.b_out = f32(self.conv_out.bias)
         self._pack_extra(pk)
         # all time_emb_proj layers of the model as ONE [sum C, 1280] GEMM per step
         pk.w_temb = torch.cat([pack_linear(l.weight) for l in self._temb_reg], dim=0).contiguous()
-        pk.b_temb = torch.cat([_f32(l.bias) for l in self._temb_reg]).contiguous()
+        pk.b_temb = torch.cat([f32(l.bias) for l in self._temb_reg]).contiguous()
         # all one-token cross-attentions folded to ONE [sum C, 1024] GEMM per forward
         folded = [a.fold_cross() for a in self._cross_reg]
         pk.w_x = torch.cat([w for w, _ in folded], dim=0).to(torch.float16).contiguous()
@@ -1369,7 +1326,7 @@ class _UNetBase(nn.Module):
         pk.x_var = {}                      # masked-LoRA variants of the folded cross-attention matrix (_cross_tables)
         from . import lora as _lora
         pk.has_lora = bool(_lora.lora_layers(self))
-        self._pk = pk
+        return pk
 
     # ---- forward pieces ---------------------------------------------------------------------------------------
     def _time_embed(self, ctx: Ctx, timestep, added_time_ids) -> None:
@@ -1619,8 +1576,7 @@ class UNetSpatioTemporalConditionModel(_UNetBase):
         self.quaternion_lora_texts_fft_pha = nn.Parameter(torch.zeros(129))
         self._lk_cache = None
 
-    def invalidate(self):
-        super().invalidate()
+    def _forget(self):
         self._lk_cache = None
 
     def fused_embedding(self, encoder_hidden_states, domain_features, flow_features) -> torch.Tensor:

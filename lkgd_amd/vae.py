@@ -35,7 +35,8 @@ import torch.nn as nn
 
 from . import ops
 from ._lib import LkgdHipError
-from .packing import pack_conv3x3, pack_conv3x3_c8, pack_linear, pack_tconv3
+from .module import PackedModule
+from .packing import f32, pack_conv3x3, pack_conv3x3_c8, pack_linear, pack_tconv3
 
 
 @dataclass
@@ -52,16 +53,12 @@ class VAEConfig:
     force_upcast: bool = True
 
 
-def _f32(p):
-    return p.detach().to(torch.float32).contiguous()
-
-
 def _gn(x, nsamples, rows, norm: nn.GroupNorm, silu=True):
     return ops.groupnorm_silu(x, None, nsamples, rows, norm._g, norm._b, norm.eps, silu=silu)
 
 
 def _pack_gn(norm: nn.GroupNorm):
-    norm._g, norm._b = _f32(norm.weight), _f32(norm.bias)
+    norm._g, norm._b = f32(norm.weight), f32(norm.bias)
 
 
 def _new(rows, cols, dev):
@@ -85,10 +82,10 @@ class ResnetBlock2D(nn.Module):
 
     def pack(self):
         _pack_gn(self.norm1); _pack_gn(self.norm2)
-        self._w1, self._b1 = pack_conv3x3(self.conv1.weight.detach()), _f32(self.conv1.bias)
-        self._w2, self._b2 = pack_conv3x3(self.conv2.weight.detach()), _f32(self.conv2.bias)
+        self._w1, self._b1 = pack_conv3x3(self.conv1.weight.detach()), f32(self.conv1.bias)
+        self._w2, self._b2 = pack_conv3x3(self.conv2.weight.detach()), f32(self.conv2.bias)
         if self.conv_shortcut is not None:
-            self._ws, self._bs = pack_linear(self.conv_shortcut.weight.detach()), _f32(self.conv_shortcut.bias)
+            self._ws, self._bs = pack_linear(self.conv_shortcut.weight.detach()), f32(self.conv_shortcut.bias)
 
     def run(self, x, N, H, W, next_rows=None):
         """``next_rows``: rows per sample of the GroupNorm that reads this block's output (default H*W: a spatial norm; the
@@ -121,8 +118,8 @@ class TemporalResnetBlock(nn.Module):
 
     def pack(self):
         _pack_gn(self.norm1); _pack_gn(self.norm2)
-        self._w1, self._b1 = pack_tconv3(self.conv1.weight.detach()), _f32(self.conv1.bias)
-        self._w2, self._b2 = pack_tconv3(self.conv2.weight.detach()), _f32(self.conv2.bias)
+        self._w1, self._b1 = pack_tconv3(self.conv1.weight.detach()), f32(self.conv1.bias)
+        self._w2, self._b2 = pack_tconv3(self.conv2.weight.detach()), f32(self.conv2.bias)
 
 
 class AlphaBlender(nn.Module):
@@ -176,10 +173,10 @@ class Attention(nn.Module):
 
     def pack(self):
         _pack_gn(self.group_norm)
-        self._wq, self._bq = pack_linear(self.to_q.weight.detach()), _f32(self.to_q.bias)
-        self._wk, self._bk = pack_linear(self.to_k.weight.detach()), _f32(self.to_k.bias)
-        self._wv, self._bv = pack_linear(self.to_v.weight.detach()), _f32(self.to_v.bias)
-        self._wo, self._bo = pack_linear(self.to_out[0].weight.detach()), _f32(self.to_out[0].bias)
+        self._wq, self._bq = pack_linear(self.to_q.weight.detach()), f32(self.to_q.bias)
+        self._wk, self._bk = pack_linear(self.to_k.weight.detach()), f32(self.to_k.bias)
+        self._wv, self._bv = pack_linear(self.to_v.weight.detach()), f32(self.to_v.bias)
+        self._wo, self._bo = pack_linear(self.to_out[0].weight.detach()), f32(self.to_out[0].bias)
 
     def run(self, x, N, H, W):
         c, S, dev = self.c, H * W, x.device
@@ -216,7 +213,7 @@ class Downsample2D(nn.Module):
         self.conv = nn.Conv2d(c, c, 3, stride=2, padding=0)
 
     def pack(self):
-        self._w, self._b = pack_conv3x3(self.conv.weight.detach()), _f32(self.conv.bias)
+        self._w, self._b = pack_conv3x3(self.conv.weight.detach()), f32(self.conv.bias)
 
     def run(self, x, N, H, W):
         Ho, Wo = (H - 2) // 2 + 1, (W - 2) // 2 + 1
@@ -233,7 +230,7 @@ class Upsample2D(nn.Module):
         self.conv = nn.Conv2d(c, c, 3, padding=1)
 
     def pack(self):
-        self._w, self._b = pack_conv3x3(self.conv.weight.detach()), _f32(self.conv.bias)
+        self._w, self._b = pack_conv3x3(self.conv.weight.detach()), f32(self.conv.bias)
 
     def run(self, x, N, H, W):
         Ho, Wo = 2 * H, 2 * W
@@ -343,7 +340,10 @@ def _pad_cout(w: torch.Tensor, b: torch.Tensor, n: int):
     return wp, bp
 
 
-class AutoencoderKLTemporalDecoder(nn.Module):
+class AutoencoderKLTemporalDecoder(PackedModule):
+    OFF_GPU = "lkgd_amd VAE runs on MI355X only: move the module to cuda first"
+    config_class = VAEConfig
+
     def __init__(self, config: Optional[VAEConfig] = None, **kw):
         super().__init__()
         cfg = config if config is not None else VAEConfig(**kw)
@@ -351,47 +351,9 @@ class AutoencoderKLTemporalDecoder(nn.Module):
         self.encoder = Encoder(cfg)
         self.decoder = TemporalDecoder(cfg)
         self.quant_conv = nn.Conv2d(2 * cfg.latent_channels, 2 * cfg.latent_channels, 1)
-        self._packed = False
-
-    # ---- reference API surface ---------------------------------------------------------------------------------
-    @property
-    def dtype(self):
-        return self.quant_conv.weight.dtype
-
-    @property
-    def device(self):
-        return self.quant_conv.weight.device
-
-    @classmethod
-    def from_pretrained(cls, pretrained_model_name_or_path: str, subfolder: Optional[str] = None, torch_dtype=None,
-                        variant: Optional[str] = None, **_ignored):
-        from .loading import build_from_pretrained
-        return build_from_pretrained(cls, VAEConfig, pretrained_model_name_or_path, subfolder, torch_dtype, variant)
-
-    def save_pretrained(self, save_directory: str, variant: Optional[str] = None, **_ignored):
-        from .loading import save_pretrained
-        save_pretrained(self, save_directory, dict(self.config.__dict__), type(self).__name__, variant)
-
-    def invalidate(self):
-        self._packed = False
-
-    def load_state_dict(self, *a, **k):
-        r = super().load_state_dict(*a, **k)
-        self._packed = False
-        return r
-
-    def _apply(self, fn, *a, **k):
-        r = super()._apply(fn, *a, **k)
-        self._packed = False
-        return r
 
     # ---- packing -----------------------------------------------------------------------------------------------
-    @torch.no_grad()
-    def prepare(self):
-        if self._packed:
-            return
-        if self.device.type != "cuda":
-            raise LkgdHipError("lkgd_amd VAE runs on MI355X only: move the module to cuda first")
+    def _pack(self):
         for m in self.modules():
             if isinstance(m, (SpatioTemporalResBlock, Attention, Downsample2D, Upsample2D)):
                 m.pack()
@@ -402,7 +364,7 @@ class AutoencoderKLTemporalDecoder(nn.Module):
         # encoder conv_in: direct small-channel kernel (3 -> 8 padded input channels)
         w = e.conv_in.weight.detach().permute(0, 2, 3, 1)
         w = torch.nn.functional.pad(w, (0, 8 - w.shape[3]))
-        e._w_in, e._b_in = w.to(torch.float16).contiguous(), _f32(e.conv_in.bias)
+        e._w_in, e._b_in = w.to(torch.float16).contiguous(), f32(e.conv_in.bias)
         _pack_gn(e.conv_norm_out)
         # quant_conv (1x1) folded into conv_out: W' = Wq . Wc (per tap), b' = Wq bc + bq
         wq = self.quant_conv.weight.detach().float().reshape(2 * lc, 2 * lc)
@@ -415,13 +377,13 @@ class AutoencoderKLTemporalDecoder(nn.Module):
         w = d.conv_in.weight.detach()
         wp = torch.zeros(w.shape[0], 8, 3, 3, dtype=w.dtype, device=w.device)
         wp[:, :w.shape[1]] = w
-        d._w_in, d._b_in = pack_conv3x3_c8(wp), _f32(d.conv_in.bias)
+        d._w_in, d._b_in = pack_conv3x3_c8(wp), f32(d.conv_in.bias)
         _pack_gn(d.conv_norm_out)
         wo, bo = _pad_cout(d.conv_out.weight.detach().float(), d.conv_out.bias.detach().float(), 8)
         d._w_out, d._b_out = pack_conv3x3(wo), bo.contiguous()
-        d._w_t = _f32(d.time_conv_out.weight.detach().reshape(3, 3, 3))          # [co][ci][kt]
-        d._b_t = _f32(d.time_conv_out.bias)
-        self._packed = True
+        d._w_t = f32(d.time_conv_out.weight.detach().reshape(3, 3, 3))          # [co][ci][kt]
+        d._b_t = f32(d.time_conv_out.bias)
+        return True                 # the packed weights live on the submodules
 
     # ---- encode ------------------------------------------------------------------------------------------------
     @torch.no_grad()

@@ -26,7 +26,9 @@ import torch.nn as nn
 
 from . import ops
 from ._lib import LkgdHipError
-from .packing import pack_geglu, pack_linear
+from .encoder import class_head, embed_rows, pack_layer, run_layers
+from .module import PackedModule
+from .packing import f32, pack_linear
 
 
 @dataclass
@@ -39,16 +41,6 @@ class ViTConfig:
     num_heads: int = 12
     mlp_ratio: int = 4
     num_classes: int = 1000
-
-
-def _f32(p):
-    return p.detach().to(torch.float32).contiguous()
-
-
-def _fold_ln(norm: nn.LayerNorm, w: torch.Tensor, b: torch.Tensor):
-    g, be = norm.weight.detach().float(), norm.bias.detach().float()
-    w32 = w.detach().float()
-    return w32 * g[None, :], w32 @ be + b.detach().float()
 
 
 class Attention(nn.Module):
@@ -76,15 +68,8 @@ class Block(nn.Module):
         self.mlp = Mlp(dim, dim * ratio)
 
     def pack(self):
-        wq, bq = _fold_ln(self.norm1, self.attn.qkv.weight, self.attn.qkv.bias)
-        w1, b1 = _fold_ln(self.norm2, self.mlp.fc1.weight, self.mlp.fc1.bias)
-        # GELU(fc1 x) as GEGLU with a constant-one hidden half: hidden = 0 * x + 1, gate = fc1 x
-        wg = torch.cat([torch.zeros_like(w1), w1], dim=0)
-        bg = torch.cat([torch.ones_like(b1), b1], dim=0)
-        wp, bp, half = pack_geglu(wg, bg)
-        self._pk = SimpleNamespace(wqkv=pack_linear(wq), bqkv=bq.contiguous(), wo=pack_linear(self.attn.proj.weight),
-                                   bo=_f32(self.attn.proj.bias), w1=wp, b1=bp, half=half, w2=pack_linear(self.mlp.fc2.weight),
-                                   b2=_f32(self.mlp.fc2.bias))
+        return pack_layer(self.norm1, self.attn.qkv.weight, self.attn.qkv.bias, self.attn.proj, self.norm2, self.mlp.fc1,
+                          self.mlp.fc2, "gelu")
 
 
 class PatchEmbed(nn.Module):
@@ -93,8 +78,10 @@ class PatchEmbed(nn.Module):
         self.proj = nn.Conv2d(cfg.in_chans, cfg.embed_dim, cfg.patch_size, stride=cfg.patch_size)
 
 
-class VisionTransformer(nn.Module):
+class VisionTransformer(PackedModule):
     """timm ``VisionTransformer`` (vit_base_patch16_384 by default) - parameter holder + HIP forward"""
+
+    OFF_GPU = "lkgd_amd ViT runs on MI355X only: move the module to cuda first"
 
     def __init__(self, config: Optional[ViTConfig] = None, **kw):
         super().__init__()
@@ -111,21 +98,6 @@ class VisionTransformer(nn.Module):
         self.blocks = nn.ModuleList([Block(cfg.embed_dim, cfg.num_heads, cfg.mlp_ratio) for _ in range(cfg.depth)])
         self.norm = nn.LayerNorm(cfg.embed_dim, eps=1e-6)
         self.head = nn.Linear(cfg.embed_dim, cfg.num_classes)
-        self._pk = None
-
-    @property
-    def device(self):
-        return self.cls_token.device
-
-    def load_state_dict(self, *a, **k):
-        r = super().load_state_dict(*a, **k)
-        self._pk = None
-        return r
-
-    def _apply(self, fn, *a, **k):
-        r = super()._apply(fn, *a, **k)
-        self._pk = None
-        return r
 
     def load_encoder_checkpoint(self, path_or_state):
         """train_svd_lora.py:1419-1433: keep the ``encoder.*`` keys of the checkpoint, strip the prefix, load strictly"""
@@ -133,21 +105,15 @@ class VisionTransformer(nn.Module):
         enc = {k[len("encoder."):]: v for k, v in sd.items() if k.startswith("encoder.")}
         return self.load_state_dict(enc)
 
-    @torch.no_grad()
-    def prepare(self):
-        if self._pk is not None:
-            return
-        if self.device.type != "cuda":
-            raise LkgdHipError("lkgd_amd ViT runs on MI355X only: move the module to cuda first")
-        for b in self.blocks:
-            b.pack()
+    def _pack(self):
+        layers = [b.pack() for b in self.blocks]
         pe = self.patch_embed.proj
         pos = self.pos_embed.detach().float()[0]
-        self._pk = SimpleNamespace(
-            wpe=pack_linear(pe.weight.detach()), bpe=_f32(pe.bias),
+        return SimpleNamespace(
+            layers=layers, wpe=pack_linear(pe.weight.detach()), bpe=f32(pe.bias),
             pos=pos[1:].to(torch.float16).contiguous(),
             cls=(self.cls_token.detach().float()[0, 0] + pos[0]).to(torch.float16).contiguous(),
-            gn=_f32(self.norm.weight), bn=_f32(self.norm.bias), wh=pack_linear(self.head.weight), bh=_f32(self.head.bias))
+            gn=f32(self.norm.weight), bn=f32(self.norm.bias), wh=pack_linear(self.head.weight), bh=f32(self.head.bias))
 
     @torch.no_grad()
     def forward(self, x: torch.Tensor) -> torch.Tensor:
@@ -157,37 +123,11 @@ class VisionTransformer(nn.Module):
         cfg, pk, dev = self.cfg, self._pk, self.device
         if x.dim() != 4 or x.shape[1] != cfg.in_chans:
             raise ValueError(f"expected [N, {cfg.in_chans}, H, W]")
-        N = x.shape[0]
-        D, g = cfg.embed_dim, cfg.img_size // cfg.patch_size
-        S, P = g * g + 1, g * g
+        N, P = x.shape[0], (cfg.img_size // cfg.patch_size) ** 2
         patches = ops.vit_patchify(x.to(device=dev, dtype=torch.float32), cfg.img_size, cfg.patch_size)     # [N*P, C*p*p]
-        tok = torch.empty(N * S, D, dtype=torch.float16, device=dev)
-        tok.view(N, S, D)[:, 0] = pk.cls
-        Kp = patches.shape[1]
-        for n in range(N):       # one GEMM per image: its patch rows land behind the image's cls row, + pos_embed[1 + m]
-            ops.gemm(patches[n * P:(n + 1) * P], pk.wpe, tok[n * S + 1:(n + 1) * S], M=P, N=D, K=Kp, bias=pk.bpe,
-                     rowbias=pk.pos, rowmap=(1, 1, 1, 1 << 30))
-        T, heads = N * S, cfg.num_heads
-        for b in self.blocks:
-            p = b._pk
-            ln = ops.layernorm(tok, None, None, 1e-6)
-            qkv = torch.empty(T, 3 * D, dtype=torch.float16, device=dev)
-            ops.gemm(ln, p.wqkv, qkv, M=T, N=3 * D, K=D, bias=p.bqkv)
-            att = torch.empty(T, D, dtype=torch.float16, device=dev)
-            ops.attn_spatial(qkv[:, :D], qkv[:, D:2 * D], qkv[:, 2 * D:], att, N, S, heads)
-            t1 = torch.empty(T, D, dtype=torch.float16, device=dev)
-            ops.gemm(att, p.wo, t1, M=T, N=D, K=D, bias=p.bo, res1=tok)
-            ln2 = ops.layernorm(t1, None, None, 1e-6)
-            inner = p.w2.shape[1]
-            h = torch.empty(T, inner, dtype=torch.float16, device=dev)
-            ops.gemm(ln2, p.w1, h, M=T, N=2 * inner, K=D, bias=p.b1, geglu=p.half)
-            tok = torch.empty(T, D, dtype=torch.float16, device=dev)
-            ops.gemm(h, p.w2, tok, M=T, N=D, K=inner, bias=p.b2, res1=t1)
-        cls = tok.view(N, S, D)[:, 0].contiguous()                      # global_pool = "token"
-        cls = ops.layernorm(cls, pk.gn, pk.bn, 1e-6)
-        logits = torch.empty(N, cfg.num_classes, dtype=torch.float16, device=dev)
-        ops.gemm(cls, pk.wh, logits, M=N, N=cfg.num_classes, K=D, bias=pk.bh)
-        return logits.float()
+        tok = embed_rows(patches, pk.wpe, pk.cls, pk.pos, N, P, bias=pk.bpe)
+        tok = run_layers(tok, pk.layers, N, P + 1, cfg.num_heads, 1e-6, ops.attn_spatial)      # head_dim 64: the flash kernel
+        return class_head(tok, N, P + 1, pk.gn, pk.bn, 1e-6, pk.wh, bias=pk.bh).float()        # global_pool = "token"
 
     @torch.no_grad()
     def clip_features(self, pixel_values: torch.Tensor) -> torch.Tensor:

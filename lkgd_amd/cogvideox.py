@@ -48,10 +48,16 @@ MI355X design - the UNet's kernels, one joint token buffer:
   rows).  Residual stream, norms, q/k norm + rope, attention, gates and every other linear stay as they are.
 * ``encode_prompt``: the pipeline's method in front of the loop, with the T5 text encoder of ``lkgd_amd/t5.py``
   (include/lkgd_hip_t5.h) and the caller's tokenizer as arguments; its embeddings are what ``denoise`` takes.
+* LoRA adapters (the reference's fine-tune, finetune/trainer.py:247-257): the six block linears may sit in
+  ``lkgd_amd.lora.Linear`` wrappers (peft's state-dict names).  An adapter that applies to every row is a different WEIGHT: a wrapped
+  linear packs the fp16 (or e4m3) form of ``W + sum_a c_a B_a A_a``, folded in fp32 when the model packs, and the sampling loop
+  issues the launch list it issues without adapters.  There is no per-step low-rank path.
 """
 from __future__ import annotations
 
+import logging
 import math
+import re
 from collections import namedtuple
 from dataclasses import dataclass
 from types import SimpleNamespace
@@ -62,12 +68,15 @@ import torch
 import torch.nn as nn
 
 from . import fp8 as fp8_mode
+from . import lora as _lora
 from . import ops
 from ._lib import LkgdHipError
 from .lk_fuse import lk_fuse_tokens, pack_lk_tokens
 from .module import PackedModule
 from .packing import f32, pack_linear
 from .unet import QuaternionLinearAutograd, TimestepEmbedding
+
+_log = logging.getLogger(__name__)
 
 
 @dataclass
@@ -265,6 +274,18 @@ class FeedForward(nn.Module):
         self.net = nn.ModuleList([GELU(dim, 4 * dim), nn.Dropout(0.0), nn.Linear(4 * dim, dim), nn.Dropout(0.0)])
 
 
+def pack_block_linear(m, fp8: bool = False):
+    """one of a block's six linears as its GEMM reads it: (fp16 [N, K], bias), or in the FP8 mode (e4m3 bytes [N, K], fp32 scale [N],
+    bias).  A linear inside a ``lora.Linear`` wrapper packs its folded weight: fp32 ``W + sum_a c_a B_a A_a`` over the wrapper's
+    effective adapters (one sum, on the module's device), rounded ONCE to fp16 - in the FP8 mode that fp32 weight goes to
+    ``quantize_weight`` (fold, then quantise: what quantising a fused model computes)"""
+    bias = f32(m.bias) if m.bias is not None else None
+    w = m.effective_weight(m.effective_adapters()) if isinstance(m, _lora.Linear) else m.weight
+    if fp8:
+        return fp8_mode.quantize_weight(w) + (bias,)
+    return pack_linear(w), bias
+
+
 class CogVideoXBlock(nn.Module):
     def __init__(self, dim, heads, head_dim, time_embed_dim, attention_bias, eps):
         super().__init__()
@@ -274,14 +295,12 @@ class CogVideoXBlock(nn.Module):
         self.ff = FeedForward(dim)
 
     def pack(self, fp8: bool = False):
-        """``fp8``: the six linears pack as (e4m3 bytes [N, K], fp32 scale [N], bias) and their fp16 copies are not made"""
+        """``fp8``: the six linears pack as (e4m3 bytes [N, K], fp32 scale [N], bias) and their fp16 copies are not made
+        (``pack_block_linear``)"""
         a, f = self.attn1, self.ff
 
         def lin(m):
-            bias = f32(m.bias) if m.bias is not None else None
-            if fp8:
-                return fp8_mode.quantize_weight(m.weight) + (bias,)
-            return pack_linear(m.weight), bias
+            return pack_block_linear(m, fp8)
         self._pk = SimpleNamespace(q=lin(a.to_q), k=lin(a.to_k), v=lin(a.to_v), o=lin(a.to_out[0]),
                                    nq=(f32(a.norm_q.weight), f32(a.norm_q.bias)), nk=(f32(a.norm_k.weight), f32(a.norm_k.bias)),
                                    f1=lin(f.net[0].proj), f2=lin(f.net[2]))
@@ -423,6 +442,86 @@ class CogVideoXTransformer3DModel(PackedModule):
     # ---- bookkeeping -------------------------------------------------------------------------------------------
     OFF_GPU = "lkgd_amd DiT runs on MI355X only: move the module to cuda first"
     config_class = DiTConfig
+    #: lkgd_amd.lora: the modules adapters fold into (``CogVideoXBlock.pack``), and the sentence for every other key
+    lora_targetable = (re.compile(r"^transformer_blocks\.\d+\.(attn1\.(to_q|to_k|to_v|to_out\.0)|ff\.net\.(0\.proj|2))$"),
+                       "the DiT folds adapters into the six block linears (attn1.to_q / to_k / to_v / to_out.0, ff.net.0.proj, "
+                       "ff.net.2 of transformer_blocks.<i>) only")
+
+    # ---- LoRA adapters (lkgd_amd/lora.py).  Module state only: all of it works before ``.to("cuda")`` -------
+    def load_lora_adapter(self, state_dict, adapter_name: Optional[str] = None, network_alphas=None):
+        """diffusers' ``transformer.load_lora_adapter`` [EXT] for a state dict whose ``transformer.`` prefix is already stripped:
+        ``<module>.lora_A.weight`` / ``.lora_B.weight`` pairs become the adapter ``adapter_name`` (default ``default_<n>``) on
+        ``lora.Linear`` wrappers - rank per module from ``lora_B.shape[1]``, ``lora_alpha = r`` (scaling 1.0) unless
+        ``network_alphas`` names one; the trainer's alpha / rank enters through ``fuse_lora(lora_scale=)`` or ``set_adapters``' weights,
+        as the reference's tools pass it.  ``quaternion_lora_*`` keys replace the module's own parameters (shape-checked).  Every key
+        is checked before anything changes; a key naming any other module raises and names it.  Returns the ``quaternion_lora_*``
+        state-dict names the dict did NOT hold (they stay as they are; logged once per call)."""
+        have = _lora.adapter_names(self)
+        if adapter_name is None:
+            n = 0
+            while f"default_{n}" in have:
+                n += 1
+            adapter_name = f"default_{n}"
+        if adapter_name in have:
+            raise ValueError(f"Adapter name '{adapter_name}' already in use in the model - please select a new adapter name.")
+        own = {k: v for k, v in self.state_dict().items() if k.startswith("quaternion_lora_")}
+        lk = {k: v for k, v in state_dict.items() if k.startswith("quaternion_lora_")}
+        for k, v in lk.items():
+            if k not in own:
+                raise LkgdHipError(f"LoRA file key '{k}': the model has no such latent-knowledge parameter")
+            if tuple(v.shape) != tuple(own[k].shape):
+                raise ValueError(f"LoRA file key '{k}' has shape {tuple(v.shape)}, the model's parameter {tuple(own[k].shape)}")
+        rest = {k: v for k, v in state_dict.items() if k not in lk}
+        if rest:
+            _lora.load_lora_into_model(rest, network_alphas, self, adapter_name, prefix="transformer.")
+        elif not lk:
+            raise ValueError("empty LoRA state dict")
+        with torch.no_grad():
+            for k, v in lk.items():
+                own[k].copy_(v)         # state_dict() tensors share the parameters' storage
+        self.invalidate()
+        absent = sorted(k for k in own if k not in lk)
+        if absent:
+            _log.warning("load_lora_adapter('%s'): %d quaternion_lora_* tensors are not in the file and stay as they are: %s",
+                         adapter_name, len(absent), ", ".join(absent))
+        return absent
+
+    def set_adapters(self, adapter_names, weights=None):
+        """``transformer.set_adapters`` [EXT PeftAdapterMixin]: the named adapters are the active ones, ``weights`` scale them"""
+        _lora.set_adapters(self, adapter_names, weights)
+
+    def fuse_lora(self, lora_scale: float = 1.0, adapter_names=None):
+        """[EXT] ``fuse_lora``.  The base parameters are never written while adapters are present: the fused adapters are marked, and
+        the pack folds ``W + sum_a c_a B_a A_a`` with c_a = set_adapters weight x ``lora_scale`` x lora_alpha_a / r_a.  So
+        ``unfuse_lora`` restores the base forward to the bit; peft's fp16 add followed by a subtract does not."""
+        _lora.fuse(self, lora_scale, adapter_names)
+
+    def unfuse_lora(self):
+        _lora.unfuse(self)
+
+    def enable_lora(self):
+        _lora.set_enabled(self, True)
+
+    def disable_lora(self):
+        _lora.set_enabled(self, False)
+
+    def unload_lora(self):
+        """[EXT] ``unload_lora``: while fused the base weights take the fp16 values of the fold first (fuse-then-unload); otherwise
+        they stay as they were.  The state-dict names are the stock ones afterwards"""
+        _lora.unload(self)
+
+    def active_adapters(self):
+        """the adapters the next pack folds, in order"""
+        seen = []
+        for _, m in _lora.lora_layers(self):
+            if not m.disable_adapters:
+                seen += [a for a in m.effective_adapters() if a not in seen]
+        return seen
+
+    def lora_coefficients(self):
+        """{module name: {adapter: c}} of ``W + sum_a c_a B_a A_a`` as the next pack folds it"""
+        return {n: ({} if m.disable_adapters else {a: m.coefficient(a) for a in m.effective_adapters()})
+                for n, m in _lora.lora_layers(self)}
 
     def _forget(self):
         self._pos = {}                  # sin-cos tables in the module's device

@@ -19,6 +19,12 @@ fp32 at pack time (one packed variant per distinct adapter subset, built on dema
 GEMM launch per run of consecutive batch entries that share a variant (rows of a batch entry are contiguous in the
 [(batch, frame, y, x), C] token layout of both the spatial and the temporal blocks).  All-ones masks / the plain peft
 forward are the one-variant case; ``merge_lora`` makes that permanent.
+
+The CogVideoX DiT (lkgd_amd/cogvideox.py) carries the same wrappers and has no masks: every adapter applies to every row, so there
+is ONE folded weight per linear, made when the model packs.  What differs between the two hosts is a host attribute:
+``lora_targetable`` (which module names may be wrapped, and the sentence that says so); the helpers below are shared.  The DiT's
+fused state (``fuse_lora`` / ``unfuse_lora`` / ``unload_lora``) is bookkeeping on the wrappers (``Linear.fuse_scale``): the base
+parameters are not written while a wrapper holds them.
 """
 from __future__ import annotations
 
@@ -52,6 +58,8 @@ class Linear(nn.Module):
         self.scaling: Dict[str, float] = {}
         self.use_dora: Dict[str, bool] = {}
         self.merged_adapters: List[str] = []
+        #: adapter -> ``fuse_lora``'s lora_scale while the adapter is fused (the base weight is NOT written: ``fuse_lora``)
+        self.fuse_scale: Dict[str, float] = {}
         self.disable_adapters = False
         self._active_adapter: List[str] = []
         self.in_features, self.out_features = base_layer.in_features, base_layer.out_features
@@ -94,11 +102,20 @@ class Linear(nn.Module):
             nn.init.kaiming_uniform_(self.lora_A[adapter_name].weight, a=math.sqrt(5))
             nn.init.zeros_(self.lora_B[adapter_name].weight)
 
+    def coefficient(self, adapter: str) -> float:
+        """c of ``W + c B A``: ``scaling`` (set_adapters weight x lora_alpha / r) x the fuse scale while the adapter is fused"""
+        return float(self.scaling[adapter]) * float(self.fuse_scale.get(adapter, 1.0))
+
+    def effective_adapters(self) -> List[str]:
+        """the adapters a single folded weight holds: the fused ones while any is fused (peft runs a merged layer as its base layer
+        alone: active adapters that were not merged do not act), else the active ones"""
+        return list(self.fuse_scale) if self.fuse_scale else self.active_adapters
+
     def get_delta_weight(self, adapter: str) -> torch.Tensor:
         """lora_layer.py:383-415: B @ A * scaling, fp32"""
         a = self.lora_A[adapter].weight.detach().to(torch.float32)
         b = self.lora_B[adapter].weight.detach().to(torch.float32)
-        return (b @ a) * float(self.scaling[adapter])
+        return (b @ a) * self.coefficient(adapter)
 
     def effective_weight(self, adapters: Iterable[str]) -> torch.Tensor:
         """fp32 base weight + the deltas of `adapters` (those already merged into the base are skipped)"""
@@ -137,7 +154,23 @@ def _matches(name: str, targets: Sequence[str]) -> bool:
     return any(name == t or name.endswith("." + t) for t in targets)
 
 
-_ATTN_PROJ = re.compile(r"(^|\.)(attn1|attn2|attn1n)\.(to_q|to_k|to_v|to_out\.0)$")
+#: the UNet's rule; a host with another one names it in ``lora_targetable`` = (compiled pattern, the sentence after "LoRA on '<key>': ")
+_ATTN_PROJ = (re.compile(r"(^|\.)(attn1|attn2|attn1n)\.(to_q|to_k|to_v|to_out\.0)$"),
+              "the HIP path folds adapters into the attention projections (to_q / to_k / to_v / to_out.0 of attn1, attn2, attn1n) only")
+
+
+def _targetable(dm):
+    return getattr(dm, "lora_targetable", _ATTN_PROJ)
+
+
+def _swap(dm, name: str, new: nn.Module) -> None:
+    """put ``new`` where the module ``name`` sits"""
+    parent_name, _, child = name.rpartition(".")
+    parent = dm.get_submodule(parent_name) if parent_name else dm
+    if isinstance(parent, (nn.ModuleList, nn.Sequential)):
+        parent[int(child)] = new
+    else:
+        setattr(parent, child, new)
 
 
 def add_adapter(model, adapter_name: str, r: int = 8, lora_alpha: float = 8.0,
@@ -147,6 +180,7 @@ def add_adapter(model, adapter_name: str, r: int = 8, lora_alpha: float = 8.0,
     attention projections): wraps the matching nn.Linear layers in ``lora.Linear`` (or adds the adapter to an existing
     wrapper).  Returns the wrapped module names."""
     dm = _model(model)
+    pattern, sentence = _targetable(dm)
     done = []
     for name, m in list(dm.named_modules()):
         if isinstance(m, Linear):
@@ -158,21 +192,14 @@ def add_adapter(model, adapter_name: str, r: int = 8, lora_alpha: float = 8.0,
             continue
         if not _matches(key, target_modules):
             continue
-        if not _ATTN_PROJ.search(key):
-            raise LkgdHipError(f"LoRA on '{key}': the HIP path folds adapters into the attention projections "
-                               "(to_q / to_k / to_v / to_out.0 of attn1, attn2, attn1n) only")
+        if not pattern.search(key):
+            raise LkgdHipError(f"LoRA on '{key}': {sentence}")
         rr = (ranks or {}).get(key, r)
         aa = (alphas or {}).get(key, lora_alpha)
         if isinstance(m, Linear):
             m.update_layer(adapter_name, rr, aa, init_lora_weights)
         else:
-            parent_name, _, child = key.rpartition(".")
-            parent = dm.get_submodule(parent_name) if parent_name else dm
-            wrapped = Linear(m, adapter_name, rr, aa, init_lora_weights)
-            if isinstance(parent, (nn.ModuleList, nn.Sequential)):
-                parent[int(child)] = wrapped
-            else:
-                setattr(parent, child, wrapped)
+            _swap(dm, key, Linear(m, adapter_name, rr, aa, init_lora_weights))
         done.append(key)
     if not done:
         raise ValueError(f"Target modules {list(target_modules)} not found in the base model.")
@@ -180,31 +207,36 @@ def add_adapter(model, adapter_name: str, r: int = 8, lora_alpha: float = 8.0,
     return done
 
 
-def lora_state_dict(path: str, weight_name: Optional[str] = None):
+def lora_state_dict(path, weight_name: Optional[str] = None):
     """``StableDiffusionPipeline.lora_state_dict(dir)`` [EXT diffusers loaders/lora.py]: reads
-    ``pytorch_lora_weights.safetensors`` (or ``.bin``) and splits off the ``.alpha`` entries -> (state_dict, network_alphas)"""
-    if os.path.isdir(path):
-        for cand in ([weight_name] if weight_name else ["pytorch_lora_weights.safetensors", "pytorch_lora_weights.bin"]):
-            f = os.path.join(path, cand)
-            if os.path.exists(f):
-                path = f
-                break
-        else:
-            raise FileNotFoundError(f"no pytorch_lora_weights.safetensors / .bin under {path}")
-    if path.endswith(".safetensors"):
-        from safetensors.torch import load_file
-        sd = load_file(path)
+    ``pytorch_lora_weights.safetensors`` (or ``.bin``) and splits off the ``.alpha`` entries -> (state_dict, network_alphas).
+    ``path``: a directory, a file, or the state dict itself"""
+    if isinstance(path, dict):
+        sd = dict(path)
     else:
-        sd = torch.load(path, map_location="cpu", weights_only=True)
+        path = os.fspath(path)
+        if os.path.isdir(path):
+            for cand in ([weight_name] if weight_name else ["pytorch_lora_weights.safetensors", "pytorch_lora_weights.bin"]):
+                f = os.path.join(path, cand)
+                if os.path.exists(f):
+                    path = f
+                    break
+            else:
+                raise FileNotFoundError(f"no {weight_name or 'pytorch_lora_weights.safetensors / .bin'} under {path}")
+        if path.endswith(".safetensors"):
+            from safetensors.torch import load_file
+            sd = load_file(path)
+        else:
+            sd = torch.load(path, map_location="cpu", weights_only=True)
     alphas = {k: float(v) for k, v in sd.items() if k.endswith(".alpha")}
     sd = {k: v for k, v in sd.items() if not k.endswith(".alpha")}
     return sd, (alphas or None)
 
 
-def _split_key(k: str, adapter_name: str):
+def _split_key(k: str, adapter_name: str, prefix: str = "unet."):
     """-> (module path, 'A' | 'B') for the key formats diffusers / peft write"""
-    if k.startswith("unet."):
-        k = k[len("unet."):]
+    if k.startswith(prefix):
+        k = k[len(prefix):]
     for pat, which in ((f".lora_A.{adapter_name}.weight", "A"), (f".lora_B.{adapter_name}.weight", "B"),
                        (".lora_A.weight", "A"), (".lora_B.weight", "B"),
                        (".lora.down.weight", "A"), (".lora.up.weight", "B"),
@@ -214,45 +246,80 @@ def _split_key(k: str, adapter_name: str):
     return None, None
 
 
-def load_lora_into_unet(state_dict: Dict[str, torch.Tensor], network_alphas: Optional[Dict[str, float]], unet,
-                        adapter_name: str = "default") -> List[str]:
-    """``StableDiffusionPipeline.load_lora_into_unet(state_dict, network_alphas, unet=, adapter_name=)`` [EXT] as the
-    reference calls it (utils/util.py:574-576): rank per module from the lora_A shapes, alpha from ``network_alphas`` (default
-    = rank, i.e. scaling 1), adapters injected into the matching projections and filled.  Keys of other components
-    (``text_encoder.``) are ignored."""
-    dm = _model(unet)
+def load_lora_into_model(state_dict: Dict[str, torch.Tensor], network_alphas: Optional[Dict[str, float]], model,
+                         adapter_name: str = "default", prefix: str = "unet.") -> List[str]:
+    """the body of diffusers' ``load_lora_into_unet`` / ``load_lora_into_transformer`` [EXT] for a host of ``lora.Linear`` wrappers:
+    rank per module from ``lora_B.shape[1]``, alpha from ``network_alphas`` (default = rank, i.e. scaling 1), adapters injected into
+    the named modules and filled; the new adapter is then the active one.  Every key is checked BEFORE the model is touched: a key
+    that is no LoRA key, names a module the model does not have or one the host does not fold adapters into
+    (``lora_targetable``), or holds matrices that do not fit the module raises and names it."""
+    dm = _model(model)
     per: Dict[str, Dict[str, torch.Tensor]] = {}
     for k, v in state_dict.items():
-        if k.startswith("text_encoder"):
-            continue
-        mod, which = _split_key(k, adapter_name)
+        mod, which = _split_key(k, adapter_name, prefix)
         if mod is None:
             raise ValueError(f"unrecognised LoRA key '{k}'")
         per.setdefault(mod, {})[which] = v
     if not per:
         raise ValueError("empty LoRA state dict")
+    pattern, sentence = _targetable(dm)
     ranks, alphas = {}, {}
     for mod, ab in per.items():
         if "A" not in ab or "B" not in ab:
             raise ValueError(f"LoRA module '{mod}' lacks its {'A' if 'A' not in ab else 'B'} matrix")
-        ranks[mod] = ab["A"].shape[0]
+        try:
+            target = dm.get_submodule(mod)
+        except AttributeError:
+            raise ValueError(f"LoRA on '{mod}': target module not found in the base model") from None
+        if not pattern.search(mod) or not isinstance(target, (nn.Linear, Linear)):
+            raise LkgdHipError(f"LoRA on '{mod}': {sentence}")
+        ranks[mod] = ab["B"].shape[1] if ab["B"].dim() == 2 else 0
+        n_out, n_in = tuple(target.weight.shape)
+        if ranks[mod] <= 0 or tuple(ab["A"].shape) != (ranks[mod], n_in) or tuple(ab["B"].shape) != (n_out, ranks[mod]):
+            raise ValueError(f"LoRA shapes of '{mod}' do not fit the projection "
+                             f"({tuple(ab['A'].shape)}, {tuple(ab['B'].shape)})")
         alphas[mod] = ranks[mod]
         if network_alphas:
-            for cand in (mod + ".alpha", "unet." + mod + ".alpha"):
+            for cand in (mod + ".alpha", prefix + mod + ".alpha"):
                 if cand in network_alphas:
                     alphas[mod] = float(network_alphas[cand])
     add_adapter(dm, adapter_name, target_modules=list(per.keys()), init_lora_weights=False, ranks=ranks, alphas=alphas)
     with torch.no_grad():
         for mod, ab in per.items():
             w = dm.get_submodule(mod)
-            if tuple(w.lora_A[adapter_name].weight.shape) != tuple(ab["A"].shape) or \
-                    tuple(w.lora_B[adapter_name].weight.shape) != tuple(ab["B"].shape):
-                raise ValueError(f"LoRA shapes of '{mod}' do not fit the projection "
-                                 f"({tuple(ab['A'].shape)}, {tuple(ab['B'].shape)})")
             w.lora_A[adapter_name].weight.copy_(ab["A"])
             w.lora_B[adapter_name].weight.copy_(ab["B"])
     set_adapters(dm, [adapter_name])
     return list(per.keys())
+
+
+def load_lora_into_unet(state_dict: Dict[str, torch.Tensor], network_alphas: Optional[Dict[str, float]], unet,
+                        adapter_name: str = "default") -> List[str]:
+    """``StableDiffusionPipeline.load_lora_into_unet(state_dict, network_alphas, unet=, adapter_name=)`` [EXT] as the
+    reference calls it (utils/util.py:574-576).  Keys of other components (``text_encoder.``) are ignored."""
+    own = {k: v for k, v in state_dict.items() if not k.startswith("text_encoder")}
+    return load_lora_into_model(own, network_alphas, unet, adapter_name, prefix="unet.")
+
+
+def adapter_state_dict(model, adapter_name: str) -> Dict[str, torch.Tensor]:
+    """peft's ``get_peft_model_state_dict(model, adapter_name=)`` [EXT]: the adapter's matrices under ``<module>.lora_A.weight`` /
+    ``<module>.lora_B.weight`` (the adapter's name removed) - what ``save_lora_weights`` takes"""
+    out = {}
+    for name, m in lora_layers(model):
+        if adapter_name in m.lora_A:
+            out[f"{name}.lora_A.weight"] = m.lora_A[adapter_name].weight.detach()
+            out[f"{name}.lora_B.weight"] = m.lora_B[adapter_name].weight.detach()
+    if not out:
+        raise ValueError(f"Adapter '{adapter_name}' not found in the model.")
+    return out
+
+
+def adapter_names(model) -> List[str]:
+    """every adapter some wrapper of the model holds, in loading order"""
+    seen: List[str] = []
+    for _, m in lora_layers(model):
+        seen += [a for a in m.lora_A.keys() if a not in seen]
+    return seen
 
 
 def set_adapters(model, adapter_names, weights=None) -> None:
@@ -263,6 +330,7 @@ def set_adapters(model, adapter_names, weights=None) -> None:
     if len(ws) != len(names):
         raise ValueError(f"Length of adapter names {len(names)} is not equal to the length of the weights {len(ws)}")
     dm = _model(model)
+    _known(dm, names)
     for _, m in lora_layers(dm):
         m.set_adapter([n for n in names if n in m.lora_A])
         for n, w in zip(names, ws):
@@ -294,12 +362,74 @@ def merge_lora(model, adapter_names: Optional[Sequence[str]] = None, unload: boo
     for name, m, names in todo:
         m.merge(names)
         if unload:
-            parent_name, _, child = name.rpartition(".")
-            parent = dm.get_submodule(parent_name) if parent_name else dm
-            if isinstance(parent, (nn.ModuleList, nn.Sequential)):
-                parent[int(child)] = m.base_layer
-            else:
-                setattr(parent, child, m.base_layer)
+            _swap(dm, name, m.base_layer)
+    _invalidate(dm)
+
+
+def _known(dm, names: Sequence[str]) -> None:
+    have = adapter_names(dm)
+    missing = [n for n in names if n not in have]
+    if missing:
+        raise ValueError(f"Adapter name(s) {missing} not in the list of present adapters: {have}.")
+
+
+# ---- one folded weight per linear: fuse / unfuse / unload as bookkeeping (the CogVideoX DiT) ---------------------------------------
+def fuse(model, lora_scale: float = 1.0, names: Optional[Sequence[str]] = None) -> None:
+    """diffusers' ``fuse_lora(lora_scale=, adapter_names=)`` [EXT] without writing the base weights: the named adapters (default: the
+    active ones of each wrapper) are marked fused with ``lora_scale``; the pack then folds exactly those, ``coefficient`` carrying the
+    scale.  ``unfuse`` therefore restores the base forward to the bit - peft's fp16 ``W += d`` followed by ``W -= d`` does not.
+    Fusing an adapter that is fused already raises (diffusers would add it a second time)."""
+    dm = _model(model)
+    layers = lora_layers(dm)
+    if not layers:
+        raise ValueError("fuse_lora: the model holds no LoRA adapters (load_lora_weights first)")
+    if names is not None:
+        names = [names] if isinstance(names, str) else list(names)
+        _known(dm, names)
+    todo = []
+    for name, m in layers:
+        mine = [a for a in (m.active_adapters if names is None else names) if a in m.lora_A]
+        twice = [a for a in mine if a in m.fuse_scale]
+        if twice:
+            raise LkgdHipError(f"fuse_lora: adapter(s) {twice} are fused already on '{name}': unfuse_lora first")
+        todo.append((m, mine))
+    for m, mine in todo:
+        for a in mine:
+            m.fuse_scale[a] = float(lora_scale)
+    _invalidate(dm)
+
+
+def unfuse(model) -> None:
+    """``unfuse_lora`` [EXT]: forgets the fused marks; the base parameters were never written"""
+    dm = _model(model)
+    for _, m in lora_layers(dm):
+        m.fuse_scale.clear()
+    _invalidate(dm)
+
+
+def is_fused(model) -> bool:
+    return any(m.fuse_scale for _, m in lora_layers(model))
+
+
+def set_enabled(model, enabled: bool) -> None:
+    """``enable_lora`` / ``disable_lora`` [EXT]: a disabled wrapper folds nothing"""
+    dm = _model(model)
+    for _, m in lora_layers(dm):
+        m.disable_adapters = not enabled
+    _invalidate(dm)
+
+
+def unload(model) -> None:
+    """``unload_lora_weights`` [EXT]: the wrappers leave and the state-dict names are the stock ones again.  While fused - diffusers'
+    fuse-then-unload idiom - each base weight first takes the fp16 rounding of its folded fp32 weight (the values the pack held);
+    otherwise the base weights stay as they were."""
+    dm = _model(model)
+    for name, m in lora_layers(dm):
+        if m.fuse_scale and not m.disable_adapters:
+            with torch.no_grad():
+                w = m.base_layer.weight
+                w.copy_(m.effective_weight(m.effective_adapters()).to(torch.float16).to(w.dtype))
+        _swap(dm, name, m.base_layer)
     _invalidate(dm)
 
 

@@ -12,7 +12,13 @@ unpinned**: diffusers is not installable next to this package, so the reference'
 Arguments of ``__call__`` the loop (``denoise``) cannot honour raise ``LkgdHipError`` naming themselves; nothing is silently ignored:
 custom ``timesteps``, ``eta != 0``, ``attention_kwargs``, a ``callback_on_step_end`` that returns replaced ``latents`` /
 ``prompt_embeds`` / ``negative_prompt_embeds`` or sets ``interrupt``, a missing ``domain_model`` / ``flow_model``.  Not built: the
-text-to-video and video-to-video pipelines, LoRA loading / fusing for the DiT, bf16, ``export_to_video``, a sharded ``__call__``."""
+text-to-video and video-to-video pipelines, bf16, ``export_to_video``, a sharded ``__call__``.
+
+LoRA ([EXT] diffusers ``CogVideoXLoraLoaderMixin``, parity unpinned): ``lora_state_dict``, ``load_lora_weights``,
+``save_lora_weights``, ``fuse_lora`` / ``unfuse_lora``, ``set_adapters``, ``get_active_adapters``, ``enable_lora`` / ``disable_lora``,
+``unload_lora_weights`` with diffusers' names and keywords, for the ``transformer`` component (any other raises, naming itself).  They
+change module state only - the adapters are folded into the weights when the DiT packs - so ``__call__`` is the same call with and
+without adapters, and they work before ``to("cuda")`` (the order of inference/cli_demo.py:128-132)."""
 from __future__ import annotations
 
 import os
@@ -22,6 +28,7 @@ from typing import Any, Callable, Dict, List, Optional, Union
 import torch
 
 from . import cogvideox as cx
+from . import lora as _lora
 from ._lib import LkgdHipError
 from .cogvideox_vae import AutoencoderKLCogVideoX, decode_latents
 from .image_processor import PIL
@@ -116,6 +123,89 @@ class CogVideoXImageToVideoPipeline:
             except ImportError:     # transformers or sentencepiece absent: the tokenizer stays the caller's business
                 tokenizer = None
         return cls(tokenizer, text_encoder, vae, transformer, scheduler, domain_model, flow_model)
+
+    # ---- [EXT] CogVideoXLoraLoaderMixin ----------------------------------------------------------------------------------------------
+    _lora_loadable_modules = ["transformer"]
+
+    @classmethod
+    def _only_transformer(cls, components, where: str) -> None:
+        if isinstance(components, str) or len(components) == 0:
+            raise ValueError(f"{where}: `components` has to be a non-empty list, got {components!r}")
+        for c in components:
+            if c not in cls._lora_loadable_modules:
+                raise LkgdHipError(f"{where}: component {c!r} - LoRA is built for {cls._lora_loadable_modules} only")
+
+    @classmethod
+    def lora_state_dict(cls, pretrained_model_name_or_path_or_dict, weight_name: str = "pytorch_lora_weights.safetensors", **_hub):
+        """a directory (holding ``weight_name``), a file, or a state dict -> the transformer's LoRA state dict: the keys under
+        ``transformer.`` are kept, without the prefix (a key without a component prefix counts as the transformer's).  A
+        ``text_encoder.`` key raises: text-encoder LoRA is not built.  ``.alpha`` entries (kohya / ``network_alphas`` files) raise as
+        well; the file's metadata is not read.  Hub / cache keywords are accepted and ignored"""
+        sd, alphas = _lora.lora_state_dict(pretrained_model_name_or_path_or_dict, weight_name)
+        if alphas:
+            raise LkgdHipError(f"lora_state_dict: '{sorted(alphas)[0]}' - `.alpha` entries (kohya / network_alphas files) are not built")
+        out = {}
+        for k, v in sd.items():
+            if k.startswith("text_encoder"):
+                raise LkgdHipError(f"lora_state_dict: key '{k}' - text-encoder LoRA is not built")
+            out[k[len("transformer."):] if k.startswith("transformer.") else k] = v
+        return out
+
+    def load_lora_weights(self, pretrained_model_name_or_path_or_dict, weight_name: str = "pytorch_lora_weights.safetensors",
+                          adapter_name: Optional[str] = None, **_hub):
+        """``lora_state_dict`` + the transformer's ``load_lora_adapter``; the adapter (default name ``default_0``, ``default_1``, ...)
+        is the active one afterwards.  Returns the ``quaternion_lora_*`` names the file did not hold"""
+        sd = self.lora_state_dict(pretrained_model_name_or_path_or_dict, weight_name)
+        return self.transformer.load_lora_adapter(sd, adapter_name=adapter_name)
+
+    @classmethod
+    def save_lora_weights(cls, save_directory, transformer_lora_layers=None, is_main_process: bool = True,
+                          weight_name: Optional[str] = "pytorch_lora_weights.safetensors", save_function=None,
+                          safe_serialization: bool = True):
+        """writes ``transformer_lora_layers`` (``lora.adapter_state_dict(transformer, name)``, plus any ``quaternion_lora_*`` tensors the
+        caller adds) under the ``transformer.`` prefix: ``weight_name`` as safetensors, or with ``safe_serialization=False`` by
+        ``torch.save``"""
+        if not transformer_lora_layers:
+            raise ValueError("You must pass `transformer_lora_layers`.")
+        if save_function is not None:
+            raise LkgdHipError("save_lora_weights: `save_function` is not built")
+        sd = {f"transformer.{k}": v.detach().to("cpu").contiguous() for k, v in transformer_lora_layers.items()}
+        if not is_main_process:
+            return
+        os.makedirs(save_directory, exist_ok=True)
+        if weight_name is None:
+            weight_name = "pytorch_lora_weights.safetensors" if safe_serialization else "pytorch_lora_weights.bin"
+        path = os.path.join(save_directory, weight_name)
+        if safe_serialization:
+            from safetensors.torch import save_file
+            save_file(sd, path, metadata={"format": "pt"})
+        else:
+            torch.save(sd, path)
+
+    def fuse_lora(self, components: List[str] = ["transformer"], lora_scale: float = 1.0, safe_fusing: bool = False,
+                  adapter_names: Optional[List[str]] = None):
+        """the transformer's ``fuse_lora``: the base weights are not written, the pack folds the fused adapters at ``lora_scale``"""
+        self._only_transformer(components, "fuse_lora")
+        self.transformer.fuse_lora(lora_scale, adapter_names)
+
+    def unfuse_lora(self, components: List[str] = ["transformer"]):
+        self._only_transformer(components, "unfuse_lora")
+        self.transformer.unfuse_lora()
+
+    def set_adapters(self, adapter_names, adapter_weights=None):
+        self.transformer.set_adapters(adapter_names, adapter_weights)
+
+    def get_active_adapters(self) -> List[str]:
+        return self.transformer.active_adapters()
+
+    def enable_lora(self):
+        self.transformer.enable_lora()
+
+    def disable_lora(self):
+        self.transformer.disable_lora()
+
+    def unload_lora_weights(self):
+        self.transformer.unload_lora()
 
     # ---- the reference's class ----------------------------------------------------------------------------------------------------
     def encode_prompt(self, prompt, negative_prompt=None, do_classifier_free_guidance: bool = True, num_videos_per_prompt: int = 1,

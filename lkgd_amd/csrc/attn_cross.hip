@@ -92,9 +92,7 @@ extern "C" int lkgd_attn_cross(const void* q, int32_t ldq, const void* k, int32_
   if (nblk > 0x7fffffffLL) return LKGD_E_SHAPE;
   const int nkv = ncontexts * Lk;
   LKGD_DEVICE_ONCE_BEGIN
-    if (hipFuncSetAttribute((const void*)attn_cross_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, XA_MAXKV * 64 * 2 * 2) !=
-        hipSuccess)
-      return LKGD_E_LAUNCH;
+    if (!lkgd_dynamic_lds(XA_MAXKV * 64 * 2 * 2, attn_cross_kernel)) return LKGD_E_LAUNCH;
   LKGD_DEVICE_ONCE_END
   hipLaunchKernelGGL(attn_cross_kernel, dim3((unsigned)nblk, (unsigned)heads), dim3(XA_NT), (size_t)nkv * 64 * 2 * 2,
                      (hipStream_t)stream, (const half_t*)q, ldq, (const half_t*)k, ldk, (const half_t*)v, ldv, (half_t*)out,

@@ -18,17 +18,6 @@
 #define AD_MAXD 128
 #define AD_LDS_MAX (160 * 1024)
 
-__device__ __forceinline__ float ad_wave_max(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-  return v;
-}
-__device__ __forceinline__ float ad_wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 template <bool RELBIAS>
 __global__ __launch_bounds__(AD_NT) void attn_dense_kernel(const half_t* __restrict__ q, int ldq, const half_t* __restrict__ k, int ldk,
                                                            const half_t* __restrict__ v, int ldv, half_t* __restrict__ out, int ldo,
@@ -78,14 +67,14 @@ __global__ __launch_bounds__(AD_NT) void attn_dense_kernel(const half_t* __restr
       sp[key] = s;
       mx = fmaxf(mx, s);
     }
-    mx = ad_wave_max(mx);
+    mx = wave_max(mx);
     float l = 0.f;
     for (int key = lane; key < S; key += 64) {
       const float p = __expf(sp[key] - mx);
       sp[key] = p;
       l += p;
     }
-    l = ad_wave_sum(l);
+    l = wave_sum(l);
     __builtin_amdgcn_s_waitcnt(0xc07f);
     // ---- O = P . V: lane = channel pair
     if (lane < D2) {
@@ -123,8 +112,7 @@ static int attn_dense_launch(const void* q, int32_t ldq, const void* k, int32_t 
       ((uintptr_t)relbias & 3))
     return LKGD_E_ALIGN;
   LKGD_DEVICE_ONCE_BEGIN
-    if (hipFuncSetAttribute((const void*)attn_dense_kernel<RELBIAS>, hipFuncAttributeMaxDynamicSharedMemorySize, AD_LDS_MAX) != hipSuccess)
-      return LKGD_E_LAUNCH;
+    if (!lkgd_dynamic_lds(AD_LDS_MAX, attn_dense_kernel<RELBIAS>)) return LKGD_E_LAUNCH;
   LKGD_DEVICE_ONCE_END
   const long long nbh = (long long)nbatch * heads;
   if (nbh > 0x7fffffffLL) return LKGD_E_SHAPE;

@@ -327,9 +327,7 @@ static int attn_launch(const void* q, int32_t ldq, const void* k, int32_t ldk, c
                        hipStream_t stream) {
   constexpr int LDS = ATT_NST * 2 * KVB * 128;
   LKGD_DEVICE_ONCE_BEGIN
-    if (hipFuncSetAttribute((const void*)attn_spatial_kernel<NW, KVB>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS) !=
-        hipSuccess)
-      return LKGD_E_LAUNCH;
+    if (!lkgd_dynamic_lds(LDS, attn_spatial_kernel<NW, KVB>)) return LKGD_E_LAUNCH;
   LKGD_DEVICE_ONCE_END
   const int QBLK = NW * 32;
   const int nqb = (Sq + QBLK - 1) / QBLK;

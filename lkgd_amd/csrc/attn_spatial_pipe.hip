@@ -12,7 +12,7 @@
 // keys [S - 128, S) - it overlaps the stage before it by dup = 128 - S % 128 keys - and those duplicates are masked through a
 // second k-slot of the bias k-step (1.0 on the key side for exactly those rows, -30000 on the query side), so nothing is read
 // beyond the S rows of a batch entry.  Short sequences stay on attn_spatial.hip.
-#include "common.h"
+#include "asm_host.h"
 #include "attn_spatial_pipe.inc"
 #include "attn_spatial_pipe_masked.inc"     // the same program for S % 128 != 0 (ATTN_GEN_OPT=w2+mask)
 
@@ -20,25 +20,10 @@
 #define AP_STAGE 32768
 #define AP_LDS (3 * AP_STAGE)
 
-template <int REG>
-__device__ __forceinline__ float ap_agpr_read() {
-  float v;
-  asm volatile("v_accvgpr_read_b32 %0, a[%1]" : "=v"(v) : "i"(REG));
-  return v;
-}
-template <int REG>
-__device__ __forceinline__ void ap_agpr_write(unsigned v) {
-  asm volatile("v_accvgpr_write_b32 a[%1], %0" : : "v"(v), "i"(REG));
-}
-template <int V> struct ApIC { static constexpr int value = V; };
-template <class F, int... Is> __device__ __forceinline__ void ap_static_for(F&& f, ApIC<Is>...) { (f(ApIC<Is>{}), ...); }
-template <class F> __device__ __forceinline__ void ap_for4(F&& f) { ap_static_for(f, ApIC<0>{}, ApIC<1>{}, ApIC<2>{}, ApIC<3>{}); }
-template <class F> __device__ __forceinline__ void ap_for2(F&& f) { ap_static_for(f, ApIC<0>{}, ApIC<1>{}); }
-
 // Q fragments of one tile -> a[BASE .. BASE+15]: lane holds Q[qrow][16*ks + 8*h + 0..7] * scale*log2e (B operand of S^T = K.Q^T)
 template <int BASE>
 __device__ __forceinline__ void ap_load_q(const half_t* qp, float scale_log2e) {
-  ap_for4([&](auto ks_) {
+  for_n<4>([&](auto ks_) {
     constexpr int ks = decltype(ks_)::value;
     const half8_t raw = *(const half8_t*)(qp + ks * 16);
     half8_t sc;
@@ -46,25 +31,25 @@ __device__ __forceinline__ void ap_load_q(const half_t* qp, float scale_log2e) {
     for (int e = 0; e < 8; ++e) sc[e] = (half_t)((float)raw[e] * scale_log2e);
     typedef unsigned uint4_t __attribute__((ext_vector_type(4)));
     const uint4_t u = __builtin_bit_cast(uint4_t, sc);
-    ap_agpr_write<BASE + 4 * ks + 0>(u[0]);
-    ap_agpr_write<BASE + 4 * ks + 1>(u[1]);
-    ap_agpr_write<BASE + 4 * ks + 2>(u[2]);
-    ap_agpr_write<BASE + 4 * ks + 3>(u[3]);
+    agpr_write<BASE + 4 * ks + 0>(u[0]);
+    agpr_write<BASE + 4 * ks + 1>(u[1]);
+    agpr_write<BASE + 4 * ks + 2>(u[2]);
+    agpr_write<BASE + 4 * ks + 3>(u[3]);
   });
 }
 
 // normalise and store one tile: lane owns query row qrow, d = 32*df + 8*g + 4*h + e  <-  a[OBASE + 16*df + 4*g + e]
 template <int OBASE>
 __device__ __forceinline__ void ap_store_tile(half_t* op, float inv, bool valid) {
-  ap_for2([&](auto df_) {
+  for_n<2>([&](auto df_) {
     constexpr int df = decltype(df_)::value;
-    ap_for4([&](auto g_) {
+    for_n<4>([&](auto g_) {
       constexpr int g = decltype(g_)::value;
       half4_t o;
-      o[0] = (half_t)(ap_agpr_read<OBASE + 16 * df + 4 * g + 0>() * inv);
-      o[1] = (half_t)(ap_agpr_read<OBASE + 16 * df + 4 * g + 1>() * inv);
-      o[2] = (half_t)(ap_agpr_read<OBASE + 16 * df + 4 * g + 2>() * inv);
-      o[3] = (half_t)(ap_agpr_read<OBASE + 16 * df + 4 * g + 3>() * inv);
+      o[0] = (half_t)(agpr_readf<OBASE + 16 * df + 4 * g + 0>() * inv);
+      o[1] = (half_t)(agpr_readf<OBASE + 16 * df + 4 * g + 1>() * inv);
+      o[2] = (half_t)(agpr_readf<OBASE + 16 * df + 4 * g + 2>() * inv);
+      o[3] = (half_t)(agpr_readf<OBASE + 16 * df + 4 * g + 3>() * inv);
       if (valid) *(half4_t*)(op + 32 * df + 8 * g) = o;
     });
   });
@@ -139,8 +124,8 @@ __global__ __launch_bounds__(AP_NW * 64, 1) __attribute__((amdgpu_num_vgpr(ATTN_
   const int row1 = (MASKED && nstages == 2) ? S - 128 : 128;     // first key of stage 1
   const unsigned long long kp = (unsigned long long)(uintptr_t)kbase + (unsigned long long)row1 * ldk * 2;
   const unsigned long long vp = (unsigned long long)(uintptr_t)vbase + (unsigned long long)row1 * ldv * 2;
-  const unsigned klo = __builtin_amdgcn_readfirstlane((unsigned)kp), khi = __builtin_amdgcn_readfirstlane((unsigned)(kp >> 32));
-  const unsigned vlo = __builtin_amdgcn_readfirstlane((unsigned)vp), vhi = __builtin_amdgcn_readfirstlane((unsigned)(vp >> 32));
+  const auto [klo, khi] = sgpr_ptr(kp);
+  const auto [vlo, vhi] = sgpr_ptr(vp);
   const unsigned dst1 = __builtin_amdgcn_readfirstlane(lds0 + AP_STAGE + w * 1024);
   const unsigned ldsend = __builtin_amdgcn_readfirstlane(lds0 + 3 * AP_STAGE);
   const unsigned nst = __builtin_amdgcn_readfirstlane((unsigned)nstages);
@@ -193,9 +178,7 @@ int lkgd_attn_pipe_launch(const void* q, int32_t ldq, const void* k, int32_t ldk
   // the statement addresses K / V rows with 32-bit byte offsets inside a 64-row half stage
   if ((long long)64 * ldk * 2 > 0x7fffffffLL || (long long)64 * ldv * 2 > 0x7fffffffLL) return LKGD_E_SHAPE;
   LKGD_DEVICE_ONCE_BEGIN
-    if (hipFuncSetAttribute((const void*)attn_pipe_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, AP_LDS) != hipSuccess ||
-        hipFuncSetAttribute((const void*)attn_pipe_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, AP_LDS) != hipSuccess)
-      return LKGD_E_LAUNCH;
+    if (!lkgd_dynamic_lds(AP_LDS, attn_pipe_kernel<false>, attn_pipe_kernel<true>)) return LKGD_E_LAUNCH;
   LKGD_DEVICE_ONCE_END
   const int QBLK = AP_NW * 64;
   const int nqb = (Sq + QBLK - 1) / QBLK;

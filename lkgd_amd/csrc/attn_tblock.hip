@@ -13,7 +13,7 @@
 // (tools/gen_tblock_asm.py -> attn_tblock_loop.inc, packing.pack_tblock); Y^T (320 x 32 per wave) lives in a[0:159].
 // This file is the prologue (token rows, LayerNorm) and the epilogue (bias, residual, store) around that statement - the
 // same as ff_fused.hip's.
-#include "common.h"
+#include "asm_host.h"
 #include "attn_tblock_loop.inc"
 
 #define TB_WAVES 4
@@ -21,29 +21,6 @@
 #define TB_PIX 8                               // pixels per panel
 #define TB_BO_OFF (TB_NSLOT * TB_SLOT)         // the out-projection bias, 320 floats behind the ring
 #define TB_LDS (TB_BO_OFF + TB_C * 4)
-
-template <int REG>
-__device__ __forceinline__ float tb_agpr_read() {
-  float v;
-  asm volatile("v_accvgpr_read_b32 %0, a[%1]" : "=v"(v) : "i"(REG));
-  return v;
-}
-template <int REG>
-__device__ __forceinline__ void tb_agpr_write(unsigned v) {
-  asm volatile("v_accvgpr_write_b32 a[%1], %0" : : "v"(v), "i"(REG));
-}
-// lanes 32..63 of `a` <-> lanes 0..31 of `b` (through the builtin: the compiler's hazard recogniser has to see it)
-__device__ __forceinline__ void tb_swap32(unsigned& a, unsigned& b) {
-  const auto r = __builtin_amdgcn_permlane32_swap(a, b, false, false);
-  a = r[0];
-  b = r[1];
-}
-template <int V> struct TbIC { static constexpr int value = V; };
-template <class F, int... Is> __device__ __forceinline__ void tb_static_for(F&& f, TbIC<Is>...) { (f(TbIC<Is>{}), ...); }
-template <class F> __device__ __forceinline__ void tb_for20(F&& f) {
-  tb_static_for(f, TbIC<0>{}, TbIC<1>{}, TbIC<2>{}, TbIC<3>{}, TbIC<4>{}, TbIC<5>{}, TbIC<6>{}, TbIC<7>{}, TbIC<8>{}, TbIC<9>{},
-                TbIC<10>{}, TbIC<11>{}, TbIC<12>{}, TbIC<13>{}, TbIC<14>{}, TbIC<15>{}, TbIC<16>{}, TbIC<17>{}, TbIC<18>{}, TbIC<19>{});
-}
 
 struct tb_params {
   const half_t* x; int ldx;
@@ -79,13 +56,8 @@ __global__ __launch_bounds__(TB_WAVES * 64, 1) __attribute__((amdgpu_num_vgpr(25
   for (int i = t; i < TB_C; i += TB_WAVES * 64) ((float*)(smem + TB_BO_OFF))[i] = p.bo[i];
   const unsigned lds0 = (unsigned)(uintptr_t)(__attribute__((address_space(3))) char*)smem;
   const unsigned long long sp0 = (unsigned long long)(uintptr_t)p.wstream;
-  const unsigned sp0lo = __builtin_amdgcn_readfirstlane((unsigned)sp0), sp0hi = __builtin_amdgcn_readfirstlane((unsigned)(sp0 >> 32));
-  unsigned splo, sphi;
-  {
-    const unsigned long long sp = sp0 + 3ull * TB_W1_BYTES;
-    splo = __builtin_amdgcn_readfirstlane((unsigned)sp);
-    sphi = __builtin_amdgcn_readfirstlane((unsigned)(sp >> 32));
-  }
+  const auto [sp0lo, sp0hi] = sgpr_ptr(sp0);
+  auto [splo, sphi] = sgpr_ptr(sp0 + 3ull * TB_W1_BYTES);
   const unsigned ldsw = __builtin_amdgcn_readfirstlane(lds0 + (unsigned)w * 1024u);
   const unsigned lds0u = __builtin_amdgcn_readfirstlane(lds0);
   const unsigned fa0 = lds0 + lane * 16, fa1 = fa0 + 2 * TB_SLOT, fa2 = fa0 + 4 * TB_SLOT;
@@ -142,7 +114,7 @@ __global__ __launch_bounds__(TB_WAVES * 64, 1) __attribute__((amdgpu_num_vgpr(25
     const float nm = -mean * rstd;
     ln_mean = mean;
     ln_sigma = (var + p.eps) * rstd;
-    tb_for20([&](auto kc) {
+    for_n<20>([&](auto kc) {
       constexpr int ks = decltype(kc)::value;
       asm volatile("" : "+v"(raw[ks]));        // (the second pass converts the fp16 rows again: see ff_fused.hip)
       half8_t z;
@@ -150,10 +122,10 @@ __global__ __launch_bounds__(TB_WAVES * 64, 1) __attribute__((amdgpu_num_vgpr(25
       for (int e = 0; e < 8; ++e) z[e] = (half_t)fmaf((float)raw[ks][e], rstd, nm);
       typedef unsigned uint4_t __attribute__((ext_vector_type(4)));
       const uint4_t u = __builtin_bit_cast(uint4_t, z);
-      tb_agpr_write<TB_ZF + 4 * ks + 0>(u[0]);
-      tb_agpr_write<TB_ZF + 4 * ks + 1>(u[1]);
-      tb_agpr_write<TB_ZF + 4 * ks + 2>(u[2]);
-      tb_agpr_write<TB_ZF + 4 * ks + 3>(u[3]);
+      agpr_write<TB_ZF + 4 * ks + 0>(u[0]);
+      agpr_write<TB_ZF + 4 * ks + 1>(u[1]);
+      agpr_write<TB_ZF + 4 * ks + 2>(u[2]);
+      agpr_write<TB_ZF + 4 * ks + 3>(u[3]);
     });
   };
 
@@ -199,37 +171,37 @@ __global__ __launch_bounds__(TB_WAVES * 64, 1) __attribute__((amdgpu_num_vgpr(25
     const float* bop = (const float*)(smem + TB_BO_OFF) + 4 * h2;
     half_t* op = p.out + (long long)row2 * p.ldo + 8 * h2;
 #ifdef TB_X_NOEPI       /* timing knob: no epilogue (one accumulator read keeps the statement alive) */
-    if (live && tb_agpr_read<TB_YACC>() == 12345.678f) *op = (half_t)1.f;
+    if (live && agpr_readf<TB_YACC>() == 12345.678f) *op = (half_t)1.f;
     if (false)
 #endif
-    tb_for20([&](auto kc) {
+    for_n<20>([&](auto kc) {
       constexpr int ks = decltype(kc)::value;
       constexpr int i = ks >> 1, g0 = 2 * (ks & 1);
       asm volatile("" ::: "memory");       // (a scheduling fence per k-step: see ff_fused.hip)
       unsigned z[4];
-      z[0] = __builtin_bit_cast(unsigned, tb_agpr_read<TB_ZF + 4 * ks + 0>());
-      z[1] = __builtin_bit_cast(unsigned, tb_agpr_read<TB_ZF + 4 * ks + 1>());
-      z[2] = __builtin_bit_cast(unsigned, tb_agpr_read<TB_ZF + 4 * ks + 2>());
-      z[3] = __builtin_bit_cast(unsigned, tb_agpr_read<TB_ZF + 4 * ks + 3>());
-      tb_swap32(z[0], z[2]);
-      tb_swap32(z[1], z[3]);
+      z[0] = agpr_read<TB_ZF + 4 * ks + 0>();
+      z[1] = agpr_read<TB_ZF + 4 * ks + 1>();
+      z[2] = agpr_read<TB_ZF + 4 * ks + 2>();
+      z[3] = agpr_read<TB_ZF + 4 * ks + 3>();
+      swap32(z[0], z[2]);
+      swap32(z[1], z[3]);
       unsigned rr[4];
       if (RB) {        // 16 bytes of the lane's STORE group, exchanged back into the accumulator layout
         const uint4_t rv = rbraw[ks];
         rr[0] = rv[0]; rr[1] = rv[1]; rr[2] = rv[2]; rr[3] = rv[3];
-        tb_swap32(rr[0], rr[2]);
-        tb_swap32(rr[1], rr[3]);
+        swap32(rr[0], rr[2]);
+        swap32(rr[1], rr[3]);
       }
       unsigned o[4];
-      tb_static_for([&](auto jc) {
+      static_for([&](auto jc) {
         constexpr int j = decltype(jc)::value;
         constexpr int c0 = 32 * i + 8 * (g0 + j);
         const float4_t bb = *(const float4_t*)(bop + c0);
         float4_t y;
-        y[0] = tb_agpr_read<TB_YACC + 16 * i + 4 * (g0 + j) + 0>();
-        y[1] = tb_agpr_read<TB_YACC + 16 * i + 4 * (g0 + j) + 1>();
-        y[2] = tb_agpr_read<TB_YACC + 16 * i + 4 * (g0 + j) + 2>();
-        y[3] = tb_agpr_read<TB_YACC + 16 * i + 4 * (g0 + j) + 3>();
+        y[0] = agpr_readf<TB_YACC + 16 * i + 4 * (g0 + j) + 0>();
+        y[1] = agpr_readf<TB_YACC + 16 * i + 4 * (g0 + j) + 1>();
+        y[2] = agpr_readf<TB_YACC + 16 * i + 4 * (g0 + j) + 2>();
+        y[3] = agpr_readf<TB_YACC + 16 * i + 4 * (g0 + j) + 3>();
         const half2_t z0 = __builtin_bit_cast(half2_t, z[2 * j]), z1 = __builtin_bit_cast(half2_t, z[2 * j + 1]);
         const float4_t xs = {fmaf((float)z0[0], ln_sigma, ln_mean), fmaf((float)z0[1], ln_sigma, ln_mean),
                              fmaf((float)z1[0], ln_sigma, ln_mean), fmaf((float)z1[1], ln_sigma, ln_mean)};
@@ -241,9 +213,9 @@ __global__ __launch_bounds__(TB_WAVES * 64, 1) __attribute__((amdgpu_num_vgpr(25
         const half2_t a = {(half_t)ov[0], (half_t)ov[1]}, bq = {(half_t)ov[2], (half_t)ov[3]};
         o[2 * j] = __builtin_bit_cast(unsigned, a);
         o[2 * j + 1] = __builtin_bit_cast(unsigned, bq);
-      }, TbIC<0>{}, TbIC<1>{});
-      tb_swap32(o[0], o[2]);
-      tb_swap32(o[1], o[3]);
+      }, IC<0>{}, IC<1>{});
+      swap32(o[0], o[2]);
+      swap32(o[1], o[3]);
       if (live) *(uint4_t*)(op + 16 * ks) = (uint4_t){o[0], o[1], o[2], o[3]};
     });
 
@@ -262,9 +234,7 @@ extern "C" int lkgd_tattn_block_c320(const void* x, int32_t ldx, const void* wst
   if (ldx % 8 || ldo % 8 || ldx < TB_C || ldo < TB_C) return LKGD_E_ALIGN;
   if (!aligned16(x) || !aligned16(wstream) || !aligned16(out) || !aligned16(bo)) return LKGD_E_ALIGN;
   LKGD_DEVICE_ONCE_BEGIN
-    if (hipFuncSetAttribute((const void*)tattn_block_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, TB_LDS) != hipSuccess ||
-        hipFuncSetAttribute((const void*)tattn_block_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, TB_LDS) != hipSuccess)
-      return LKGD_E_LAUNCH;
+    if (!lkgd_dynamic_lds(TB_LDS, tattn_block_kernel<false>, tattn_block_kernel<true>)) return LKGD_E_LAUNCH;
   LKGD_DEVICE_ONCE_END
   const int cus = lkgd_cu_count();      // cached per device (common.h)
   tb_params p;

@@ -174,9 +174,7 @@ extern "C" int lkgd_attn_temporal(const void* q, int32_t ldq, const void* k, int
   if (nblk > 0x7fffffffLL) return LKGD_E_SHAPE;
   const float c = scale * 1.4426950408889634f;
   LKGD_DEVICE_ONCE_BEGIN
-    if (hipFuncSetAttribute((const void*)attn_temporal_kernel<32>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            2 * 32 * TP * TROW) != hipSuccess)
-      return LKGD_E_LAUNCH;
+    if (!lkgd_dynamic_lds(2 * 32 * TP * TROW, attn_temporal_kernel<32>)) return LKGD_E_LAUNCH;
   LKGD_DEVICE_ONCE_END
   if (F <= 16)
     hipLaunchKernelGGL(attn_temporal_kernel<16>, dim3((unsigned)nblk, B), dim3(16 * TP), 2 * F * TP * TROW,

@@ -21,7 +21,7 @@
 //     softmax over the keys of a query = 4 registers + the 4 lanes lq (two shuffles); keys >= F are masked;
 //   * the head's 64 output channels of the wave's 32 rows leave through a wave-private LDS patch as 16-byte pieces of
 //     128-byte row segments.
-#include "common.h"
+#include "asm_host.h"
 
 // timing-experiment knobs (tools/micro/tfront_knobs.sh; results are wrong with any of them): never defined in the product build
 #ifdef TF_X_NOMFMA
@@ -45,33 +45,6 @@
 #define TF_PATCH (32 * TF_PATCH_PITCH)
 #define TF_BIAS_BYTES (3 * TF_C * 4)   // the projection bias, staged once (a global load at its use would expose an L2 round trip per chunk)
 #define TF_LDS (TF_STAGES * TF_CHUNK_BYTES + TF_WAVES * TF_PATCH + TF_BIAS_BYTES)
-
-template <int REG>
-__device__ __forceinline__ unsigned tf_agpr_read() {
-  unsigned v;
-  asm volatile("v_accvgpr_read_b32 %0, a[%1]" : "=v"(v) : "i"(REG));
-  return v;
-}
-template <int REG>
-__device__ __forceinline__ void tf_agpr_write(unsigned v) {
-  asm volatile("v_accvgpr_write_b32 a[%1], %0" : : "v"(v), "i"(REG));
-}
-template <int BASE>
-__device__ __forceinline__ float4_t tf_read_acc() {
-  float a, b, c, d;
-  asm volatile("v_accvgpr_read_b32 %0, a[%4]\n\tv_accvgpr_read_b32 %1, a[%4+1]\n\t"
-               "v_accvgpr_read_b32 %2, a[%4+2]\n\tv_accvgpr_read_b32 %3, a[%4+3]"
-               : "=v"(a), "=v"(b), "=v"(c), "=v"(d)
-               : "i"(BASE));
-  return (float4_t){a, b, c, d};
-}
-
-template <int V> struct TfIC { static constexpr int value = V; };
-template <class F, int... Is> __device__ __forceinline__ void tf_static_for(F&& f, TfIC<Is>...) { (f(TfIC<Is>{}), ...); }
-template <class F> __device__ __forceinline__ void tf_for4(F&& f) { tf_static_for(f, TfIC<0>{}, TfIC<1>{}, TfIC<2>{}, TfIC<3>{}); }
-template <class F> __device__ __forceinline__ void tf_for10(F&& f) {
-  tf_static_for(f, TfIC<0>{}, TfIC<1>{}, TfIC<2>{}, TfIC<3>{}, TfIC<4>{}, TfIC<5>{}, TfIC<6>{}, TfIC<7>{}, TfIC<8>{}, TfIC<9>{});
-}
 
 // the 80 token-fragment loads of a panel: x[j][ks] = a[32 + (j*10 + ks)*4 ..] <- 16 bytes at row(j) + ks*64 (+ lq*16 in the pointers)
 __device__ __forceinline__ void tf_load_x(const half_t* p0, const half_t* p1) {
@@ -176,22 +149,22 @@ __global__ __launch_bounds__(TF_NT, 2) __attribute__((amdgpu_num_vgpr(144))) voi
         float s = 0.f, q2 = 0.f;
         // (j is a runtime-unrolled index: the AGPR numbers must be immediates, so both fragments are written out)
         if (j == 0) {
-          tf_for10([&](auto kc) {
+          for_n<10>([&](auto kc) {
             constexpr int ks = decltype(kc)::value;
-            tf_for4([&](auto rc) {
+            for_n<4>([&](auto rc) {
               constexpr int r = decltype(rc)::value;
-              const half2_t u = __builtin_bit_cast(half2_t, tf_agpr_read<32 + ks * 4 + r>());
+              const half2_t u = __builtin_bit_cast(half2_t, agpr_read<32 + ks * 4 + r>());
               const half2_t one = {(half_t)1.f, (half_t)1.f};
               s = __builtin_amdgcn_fdot2(u, one, s, false);
               q2 = __builtin_amdgcn_fdot2(u, u, q2, false);
             });
           });
         } else {
-          tf_for10([&](auto kc) {
+          for_n<10>([&](auto kc) {
             constexpr int ks = decltype(kc)::value;
-            tf_for4([&](auto rc) {
+            for_n<4>([&](auto rc) {
               constexpr int r = decltype(rc)::value;
-              const half2_t u = __builtin_bit_cast(half2_t, tf_agpr_read<72 + ks * 4 + r>());
+              const half2_t u = __builtin_bit_cast(half2_t, agpr_read<72 + ks * 4 + r>());
               const half2_t one = {(half_t)1.f, (half_t)1.f};
               s = __builtin_amdgcn_fdot2(u, one, s, false);
               q2 = __builtin_amdgcn_fdot2(u, u, q2, false);
@@ -207,14 +180,14 @@ __global__ __launch_bounds__(TF_NT, 2) __attribute__((amdgpu_num_vgpr(144))) voi
         const float nm = -mean * rstd;
         auto norm = [&](auto regc) {
           constexpr int reg = decltype(regc)::value;
-          const half2_t u = __builtin_bit_cast(half2_t, tf_agpr_read<reg>());
+          const half2_t u = __builtin_bit_cast(half2_t, agpr_read<reg>());
           const half2_t o = {(half_t)fmaf((float)u.x, rstd, nm), (half_t)fmaf((float)u.y, rstd, nm)};
-          tf_agpr_write<reg>(__builtin_bit_cast(unsigned, o));
+          agpr_write<reg>(__builtin_bit_cast(unsigned, o));
         };
         if (j == 0) {
-          tf_for10([&](auto kc) { tf_for4([&](auto rc) { norm(TfIC<32 + decltype(kc)::value * 4 + decltype(rc)::value>{}); }); });
+          for_n<10>([&](auto kc) { for_n<4>([&](auto rc) { norm(IC<32 + decltype(kc)::value * 4 + decltype(rc)::value>{}); }); });
         } else {
-          tf_for10([&](auto kc) { tf_for4([&](auto rc) { norm(TfIC<72 + decltype(kc)::value * 4 + decltype(rc)::value>{}); }); });
+          for_n<10>([&](auto kc) { for_n<4>([&](auto rc) { norm(IC<72 + decltype(kc)::value * 4 + decltype(rc)::value>{}); }); });
         }
       }
     }
@@ -255,18 +228,18 @@ __global__ __launch_bounds__(TF_NT, 2) __attribute__((amdgpu_num_vgpr(144))) voi
 #endif
           // acc[d][token] + bias[d] -> fp16 (q also times softmax scale * log2 e)
           const float sc = which == 0 ? qscale : 1.0f;
-          tf_for4([&](auto ic) {
+          for_n<4>([&](auto ic) {
             constexpr int i = decltype(ic)::value;
             const float4_t bb = *(const float4_t*)(bias + i * 16 + 4 * lq);
-            tf_static_for([&](auto jc) {
+            static_for([&](auto jc) {
               constexpr int j = decltype(jc)::value;
-              const float4_t v = (tf_read_acc<(2 * i + j) * 4>() + bb) * sc;
+              const float4_t v = (agpr_read4<(2 * i + j) * 4>() + bb) * sc;
               const half4_t o = {(half_t)v[0], (half_t)v[1], (half_t)v[2], (half_t)v[3]};
               // k-slots of the S^T MFMAs: fragments 2s, 2s+1 of a lane form one 8-slot operand
               half8_t& dst = which == 0 ? qp[i >> 1][j] : kp[i >> 1][j];
               if ((i & 1) == 0) { dst[0] = o[0]; dst[1] = o[1]; dst[2] = o[2]; dst[3] = o[3]; }
               else { dst[4] = o[0]; dst[5] = o[1]; dst[6] = o[2]; dst[7] = o[3]; }
-            }, TfIC<0>{}, TfIC<1>{});
+            }, IC<0>{}, IC<1>{});
           });
           if (which == 1) {
             // ---- S^T = K . Q^T per pixel (two k-steps of 32 head channels), softmax over the keys
@@ -298,10 +271,10 @@ __global__ __launch_bounds__(TF_NT, 2) __attribute__((amdgpu_num_vgpr(144))) voi
           // acc[token][d] (lane = head channel d = 16i + l15, 4 tokens 4lq..) + bias[d] -> fp16 k-slots of O = V^T . P
           // (every accumulator is read before the first attention MFMA below: see tf_mfma)
           half8_t vp[4][2];
-          tf_for4([&](auto ic) {
+          for_n<4>([&](auto ic) {
             constexpr int i = decltype(ic)::value;
             const float bb = bias[i * 16 + l15];
-            const float4_t v0 = tf_read_acc<(2 * i) * 4>() + bb, v1 = tf_read_acc<(2 * i + 1) * 4>() + bb;
+            const float4_t v0 = agpr_read4<(2 * i) * 4>() + bb, v1 = agpr_read4<(2 * i + 1) * 4>() + bb;
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
               vp[i][0][r] = (half_t)v0[r]; vp[i][0][4 + r] = (half_t)0.f;
@@ -352,8 +325,7 @@ extern "C" int lkgd_tattn_front(const void* x, int32_t ldx, const void* wpack, c
   if (B <= 0 || F <= 0 || F > 16 || HW <= 0 || HW % 16 || heads * 64 != TF_C) return LKGD_E_SHAPE;
   if (ldx % 8 || ldo % 8 || ldx < TF_C || ldo < TF_C || !aligned16(x) || !aligned16(wpack) || !aligned16(out)) return LKGD_E_ALIGN;
   LKGD_DEVICE_ONCE_BEGIN
-    if (hipFuncSetAttribute((const void*)tattn_front_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, TF_LDS) != hipSuccess)
-      return LKGD_E_LAUNCH;
+    if (!lkgd_dynamic_lds(TF_LDS, tattn_front_kernel)) return LKGD_E_LAUNCH;
   LKGD_DEVICE_ONCE_END
   const int cus = lkgd_cu_count();      // cached per device (common.h)
   const int panels_per_clip = HW / 16;

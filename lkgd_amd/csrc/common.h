@@ -54,8 +54,20 @@ __device__ __forceinline__ float wave_sum(float v) {
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
   return v;
 }
+__device__ __forceinline__ float wave_max(float v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
+  return v;
+}
 
 static inline bool aligned16(const void* p) { return (((uintptr_t)p) & 15u) == 0; }
+
+// opt the kernels in to `bytes` of dynamic LDS (above the 64 KiB a launch gets without asking); stops at the first failure.
+// Per device: call it inside LKGD_DEVICE_ONCE_BEGIN / _END below.
+template <class... K>
+static inline bool lkgd_dynamic_lds(int bytes, K... kernels) {
+  return ((hipFuncSetAttribute((const void*)kernels, hipFuncAttributeMaxDynamicSharedMemorySize, bytes) == hipSuccess) && ...);
+}
 
 // hipFuncSetAttribute and the CU count are per DEVICE.  Launchers remember, per device ordinal, that they have set their
 // kernels' attributes (setting one twice is harmless, so a relaxed bit mask is all concurrent callers need).

@@ -8,41 +8,13 @@
 // loop consumes it (tools/gen_ff_asm.py -> ff_fused_loop.inc, packing.pack_ff_fused); hidden * gelu(gate) stays in registers
 // and IS the B operand of the second product; Y^T (320 x 32 per wave) lives in a[0:159] for the whole panel.  The statement
 // of one panel is generated asm; this file is the prologue (token rows, LayerNorm) and the epilogue (bias, residuals, store).
-#include "common.h"
+#include "asm_host.h"
 #include "ff_fused_loop.inc"
 
 #define FF_WAVES 4
 #define FF_C 320
 #define FF_B2_OFF (FF_NSLOT * FF_SLOT)       // the output bias, 320 floats behind the ring
 #define FF_LDS (FF_B2_OFF + FF_C * 4)
-
-template <int REG>
-__device__ __forceinline__ float ff_agpr_read() {
-  float v;
-  asm volatile("v_accvgpr_read_b32 %0, a[%1]" : "=v"(v) : "i"(REG));
-  return v;
-}
-template <int REG>
-__device__ __forceinline__ void ff_agpr_write(unsigned v) {
-  asm volatile("v_accvgpr_write_b32 a[%1], %0" : : "v"(v), "i"(REG));
-}
-// v_permlane32_swap_b32: lanes 32..63 of `a` <-> lanes 0..31 of `b`.  Through the builtin, not inline asm: the instruction has
-// wait-state requirements after a VALU write of its operands that only the compiler's hazard recogniser sees
-__device__ __forceinline__ void ff_swap32(unsigned& a, unsigned& b) {
-  const auto r = __builtin_amdgcn_permlane32_swap(a, b, false, false);
-  a = r[0];
-  b = r[1];
-}
-template <int V> struct FfIC { static constexpr int value = V; };
-template <class F, int... Is> __device__ __forceinline__ void ff_static_for(F&& f, FfIC<Is>...) { (f(FfIC<Is>{}), ...); }
-template <class F> __device__ __forceinline__ void ff_for4(F&& f) { ff_static_for(f, FfIC<0>{}, FfIC<1>{}, FfIC<2>{}, FfIC<3>{}); }
-template <class F> __device__ __forceinline__ void ff_for10(F&& f) {
-  ff_static_for(f, FfIC<0>{}, FfIC<1>{}, FfIC<2>{}, FfIC<3>{}, FfIC<4>{}, FfIC<5>{}, FfIC<6>{}, FfIC<7>{}, FfIC<8>{}, FfIC<9>{});
-}
-template <class F> __device__ __forceinline__ void ff_for20(F&& f) {
-  ff_static_for(f, FfIC<0>{}, FfIC<1>{}, FfIC<2>{}, FfIC<3>{}, FfIC<4>{}, FfIC<5>{}, FfIC<6>{}, FfIC<7>{}, FfIC<8>{}, FfIC<9>{},
-                FfIC<10>{}, FfIC<11>{}, FfIC<12>{}, FfIC<13>{}, FfIC<14>{}, FfIC<15>{}, FfIC<16>{}, FfIC<17>{}, FfIC<18>{}, FfIC<19>{});
-}
 
 struct ff_params {
   const half_t* x; int ldx; long long T;
@@ -79,13 +51,8 @@ __global__ __launch_bounds__(FF_WAVES * 64, 1) __attribute__((amdgpu_num_vgpr(25
   for (int i = t; i < FF_C; i += FF_WAVES * 64) ((float*)(smem + FF_B2_OFF))[i] = p.b2[i];
   const unsigned lds0 = (unsigned)(uintptr_t)(__attribute__((address_space(3))) char*)smem;
   const unsigned long long sp0 = (unsigned long long)(uintptr_t)p.wstream;
-  const unsigned sp0lo = __builtin_amdgcn_readfirstlane((unsigned)sp0), sp0hi = __builtin_amdgcn_readfirstlane((unsigned)(sp0 >> 32));
-  unsigned splo, sphi;
-  {
-    const unsigned long long sp = sp0 + 3ull * FF_W1_BYTES;
-    splo = __builtin_amdgcn_readfirstlane((unsigned)sp);
-    sphi = __builtin_amdgcn_readfirstlane((unsigned)(sp >> 32));
-  }
+  const auto [sp0lo, sp0hi] = sgpr_ptr(sp0);
+  auto [splo, sphi] = sgpr_ptr(sp0 + 3ull * FF_W1_BYTES);
   const unsigned ldsw = __builtin_amdgcn_readfirstlane(lds0 + (unsigned)w * 1024u);
   const unsigned lds0u = __builtin_amdgcn_readfirstlane(lds0);
   const unsigned fa0 = lds0 + lane * 16, fa1 = fa0 + 2 * FF_SLOT, fa2 = fa0 + 4 * FF_SLOT;
@@ -137,7 +104,7 @@ __global__ __launch_bounds__(FF_WAVES * 64, 1) __attribute__((amdgpu_num_vgpr(25
     const float nm = -mean * rstd;
     ln_mean = mean;
     ln_sigma = (var + p.eps) * rstd;
-    ff_for20([&](auto kc) {
+    for_n<20>([&](auto kc) {
       constexpr int ks = decltype(kc)::value;
       // (opaque copies: the second pass converts the fp16 rows AGAIN instead of keeping 160 fp32 values of the first
       // pass alive - those would not fit the vector registers and the compiler would park them in accumulation registers)
@@ -152,10 +119,10 @@ __global__ __launch_bounds__(FF_WAVES * 64, 1) __attribute__((amdgpu_num_vgpr(25
       }
       typedef unsigned uint4_t __attribute__((ext_vector_type(4)));
       const uint4_t u = __builtin_bit_cast(uint4_t, z);
-      ff_agpr_write<FF_ZF + 4 * ks + 0>(u[0]);
-      ff_agpr_write<FF_ZF + 4 * ks + 1>(u[1]);
-      ff_agpr_write<FF_ZF + 4 * ks + 2>(u[2]);
-      ff_agpr_write<FF_ZF + 4 * ks + 3>(u[3]);
+      agpr_write<FF_ZF + 4 * ks + 0>(u[0]);
+      agpr_write<FF_ZF + 4 * ks + 1>(u[1]);
+      agpr_write<FF_ZF + 4 * ks + 2>(u[2]);
+      agpr_write<FF_ZF + 4 * ks + 3>(u[3]);
     });
   };
 
@@ -206,39 +173,39 @@ __global__ __launch_bounds__(FF_WAVES * 64, 1) __attribute__((amdgpu_num_vgpr(25
     half_t* op = p.out + tok2c * p.ldo + 8 * h2;
     const float sa = p.s_acc, r2 = p.r2;
 #ifdef FF_X_NOEPI       /* timing knob: no epilogue (one accumulator read keeps the statement alive) */
-    if (live && ff_agpr_read<FF_YACC>() == 12345.678f) *op = (half_t)1.f;
+    if (live && agpr_readf<FF_YACC>() == 12345.678f) *op = (half_t)1.f;
     if (false)
 #endif
-    ff_for20([&](auto kc) {
+    for_n<20>([&](auto kc) {
       constexpr int ks = decltype(kc)::value;
       constexpr int i = ks >> 1, g0 = 2 * (ks & 1);            // output tile, first of the k-step's two 4-channel groups
       // (a scheduling fence per k-step: without it the compiler hoists all forty bias loads, runs out of vector registers
       // and parks values in ACCUMULATION registers - the ones that still hold Y^T and z^T here)
       asm volatile("" ::: "memory");
       unsigned z[4];
-      z[0] = __builtin_bit_cast(unsigned, ff_agpr_read<FF_ZF + 4 * ks + 0>());
-      z[1] = __builtin_bit_cast(unsigned, ff_agpr_read<FF_ZF + 4 * ks + 1>());
-      z[2] = __builtin_bit_cast(unsigned, ff_agpr_read<FF_ZF + 4 * ks + 2>());
-      z[3] = __builtin_bit_cast(unsigned, ff_agpr_read<FF_ZF + 4 * ks + 3>());
-      ff_swap32(z[0], z[2]);
-      ff_swap32(z[1], z[3]);
+      z[0] = agpr_read<FF_ZF + 4 * ks + 0>();
+      z[1] = agpr_read<FF_ZF + 4 * ks + 1>();
+      z[2] = agpr_read<FF_ZF + 4 * ks + 2>();
+      z[3] = agpr_read<FF_ZF + 4 * ks + 3>();
+      swap32(z[0], z[2]);
+      swap32(z[1], z[3]);
       unsigned rr[4];
       if (R2) {        // the second residual: 16 bytes of the lane's STORE group, exchanged back into the accumulator layout
         const uint4_t rv = r2raw[ks];
         rr[0] = rv[0]; rr[1] = rv[1]; rr[2] = rv[2]; rr[3] = rv[3];
-        ff_swap32(rr[0], rr[2]);
-        ff_swap32(rr[1], rr[3]);
+        swap32(rr[0], rr[2]);
+        swap32(rr[1], rr[3]);
       }
       unsigned o[4];
-      ff_static_for([&](auto jc) {
+      static_for([&](auto jc) {
         constexpr int j = decltype(jc)::value;                  // group g0 + j: channels 32 i + 8 (g0 + j) + 4 h + 0..3
         constexpr int c0 = 32 * i + 8 * (g0 + j);
         const float4_t bb = *(const float4_t*)(b2p + c0);
         float4_t y;
-        y[0] = ff_agpr_read<FF_YACC + 16 * i + 4 * (g0 + j) + 0>();
-        y[1] = ff_agpr_read<FF_YACC + 16 * i + 4 * (g0 + j) + 1>();
-        y[2] = ff_agpr_read<FF_YACC + 16 * i + 4 * (g0 + j) + 2>();
-        y[3] = ff_agpr_read<FF_YACC + 16 * i + 4 * (g0 + j) + 3>();
+        y[0] = agpr_readf<FF_YACC + 16 * i + 4 * (g0 + j) + 0>();
+        y[1] = agpr_readf<FF_YACC + 16 * i + 4 * (g0 + j) + 1>();
+        y[2] = agpr_readf<FF_YACC + 16 * i + 4 * (g0 + j) + 2>();
+        y[3] = agpr_readf<FF_YACC + 16 * i + 4 * (g0 + j) + 3>();
         const half2_t z0 = __builtin_bit_cast(half2_t, z[2 * j]), z1 = __builtin_bit_cast(half2_t, z[2 * j + 1]);
         const float4_t xs = {fmaf((float)z0[0], ln_sigma, ln_mean), fmaf((float)z0[1], ln_sigma, ln_mean),
                              fmaf((float)z1[0], ln_sigma, ln_mean), fmaf((float)z1[1], ln_sigma, ln_mean)};
@@ -250,11 +217,11 @@ __global__ __launch_bounds__(FF_WAVES * 64, 1) __attribute__((amdgpu_num_vgpr(25
         const half2_t a = {(half_t)ov[0], (half_t)ov[1]}, bq = {(half_t)ov[2], (half_t)ov[3]};
         o[2 * j] = __builtin_bit_cast(unsigned, a);
         o[2 * j + 1] = __builtin_bit_cast(unsigned, bq);
-      }, FfIC<0>{}, FfIC<1>{});
+      }, IC<0>{}, IC<1>{});
       // lanes 0..31 (channels 0..3 | 8..11 of the k-step) give away 8..11 and take the partner's 4..7; lanes 32..63 hold
       // 8..15 afterwards: both halves have their eight channels in order
-      ff_swap32(o[0], o[2]);
-      ff_swap32(o[1], o[3]);
+      swap32(o[0], o[2]);
+      swap32(o[1], o[3]);
       if (live) *(uint4_t*)(op + 16 * ks) = (uint4_t){o[0], o[1], o[2], o[3]};
     });
 
@@ -279,10 +246,8 @@ extern "C" int lkgd_ff_fused_c320(const void* x, int32_t ldx, int64_t T, const v
   if (rowbias && (ldrb % 8 || ldrb < FF_C || rb_d1 <= 0 || rb_md <= 0 || !aligned16(rowbias))) return LKGD_E_SHAPE;
   if (res2 && (ldr2 % 8 || ldr2 < FF_C || !aligned16(res2))) return LKGD_E_ALIGN;
   LKGD_DEVICE_ONCE_BEGIN
-    if (hipFuncSetAttribute((const void*)ff_fused_kernel<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, FF_LDS) != hipSuccess ||
-        hipFuncSetAttribute((const void*)ff_fused_kernel<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, FF_LDS) != hipSuccess ||
-        hipFuncSetAttribute((const void*)ff_fused_kernel<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, FF_LDS) != hipSuccess ||
-        hipFuncSetAttribute((const void*)ff_fused_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, FF_LDS) != hipSuccess)
+    if (!lkgd_dynamic_lds(FF_LDS, ff_fused_kernel<false, false>, ff_fused_kernel<true, false>, ff_fused_kernel<false, true>,
+                          ff_fused_kernel<true, true>))
       return LKGD_E_LAUNCH;
   LKGD_DEVICE_ONCE_END
   const int cus = lkgd_cu_count();      // cached per device (common.h)

@@ -824,12 +824,8 @@ extern "C" int lkgd_gemm_f16(const lkgd_gemm_desc* d, lkgd_stream_t stream) {
   int rc = check_desc(d);
   if (rc != LKGD_OK) return rc;
   LKGD_DEVICE_ONCE_BEGIN
-    if (hipFuncSetAttribute((const void*)lkgd_gemm_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, GEMM_LDS) !=
-            hipSuccess ||
-        hipFuncSetAttribute((const void*)lkgd_gemm_kernel_256, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            GEMM2_LDS) != hipSuccess ||
-        hipFuncSetAttribute((const void*)lkgd_gemm_mid_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, MID_LDS) !=
-            hipSuccess)
+    if (!lkgd_dynamic_lds(GEMM_LDS, lkgd_gemm_kernel) || !lkgd_dynamic_lds(GEMM2_LDS, lkgd_gemm_kernel_256) ||
+        !lkgd_dynamic_lds(MID_LDS, lkgd_gemm_mid_kernel))
       return LKGD_E_LAUNCH;
   LKGD_DEVICE_ONCE_END
   int cus = 0;

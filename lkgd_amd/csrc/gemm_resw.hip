@@ -19,6 +19,7 @@
 //   * workgroup c of an XCD (blocks b, b + 8, ... share one) keeps slab c % nslab and sweeps part c / nslab of that XCD's
 //     rows: the nslab workgroups that read the same token rows run on one XCD and meet in its L2.
 #include "gemm_common.h"
+#include "asm_host.h"
 
 // timing-experiment knobs (tools/micro/resw_knobs.sh; results are wrong with any of them): never defined in the product build
 #ifdef RESW_X_NOREAD
@@ -54,16 +55,7 @@ extern "C" int lkgd_debug_resw_stamps(unsigned long long* host, int n) {
 #define RW_PITCH 336           // bytes per staged output row (320 + 16: rows start on different banks)
 #define RW_STAGE (16 * RW_PITCH)
 
-// accumulator fragment (channel fragment i, token fragment j) out of the AGPRs; BASE = (2i + j) * 4
-template <int BASE>
-__device__ __forceinline__ float4_t resw_read_acc() {
-  float a, b, c, d;
-  asm volatile("v_accvgpr_read_b32 %0, a[%4]\n\tv_accvgpr_read_b32 %1, a[%4+1]\n\t"
-               "v_accvgpr_read_b32 %2, a[%4+2]\n\tv_accvgpr_read_b32 %3, a[%4+3]"
-               : "=v"(a), "=v"(b), "=v"(c), "=v"(d)
-               : "i"(BASE));
-  return (float4_t){a, b, c, d};
-}
+// (accumulator fragment (channel fragment i, token fragment j): agpr_read4<(2i + j) * 4>, asm_host.h)
 
 // 16-byte store of one row piece, issued by every lane's wave whatever the mask (the K-loop's counted vmcnt relies on
 // the number of store instructions between two K-loops); lanes whose row is past M are masked off
@@ -78,15 +70,6 @@ __device__ __forceinline__ void resw_store16(half_t* ptr, half8_t v, int mr, int
                : "=&s"(sv)
                : "v"(ptr), "v"(v), "s"(M), "v"(mr)
                : "vcc", "memory");
-}
-
-template <int V> struct ReswIC { static constexpr int value = V; };
-template <class F, int... Is> __device__ __forceinline__ void resw_static_for(F&& f, ReswIC<Is>...) { (f(ReswIC<Is>{}), ...); }
-template <class F> __device__ __forceinline__ void resw_for10(F&& f) {
-  resw_static_for(f, ReswIC<0>{}, ReswIC<1>{}, ReswIC<2>{}, ReswIC<3>{}, ReswIC<4>{}, ReswIC<5>{}, ReswIC<6>{}, ReswIC<7>{}, ReswIC<8>{}, ReswIC<9>{});
-}
-template <class F> __device__ __forceinline__ void resw_for5(F&& f) {
-  resw_static_for(f, ReswIC<0>{}, ReswIC<1>{}, ReswIC<2>{}, ReswIC<3>{}, ReswIC<4>{});
 }
 
 // K-loop of one block (generated asm, tools/gen_resw_asm.py).  YOUNGER = vector-memory operations that are certainly
@@ -250,7 +233,7 @@ __global__ __launch_bounds__(RW_NT, 2) __attribute__((amdgpu_num_vgpr(96))) void
       }
       auto issue = [&](ReswPiece& pc, int j, auto hc) {
         constexpr int h = decltype(hc)::value;
-        resw_for5([&](auto ic) {
+        for_n<5>([&](auto ic) {
           constexpr int i5 = decltype(ic)::value;
           if (HAS_RB) pc.rb[i5] = resw_ld8<h * 5 + i5>(rbr[j]);
           if (HAS_R1) pc.r1[i5] = resw_ld8<h * 5 + i5>(r1r[j]);
@@ -264,9 +247,9 @@ __global__ __launch_bounds__(RW_NT, 2) __attribute__((amdgpu_num_vgpr(96))) void
 #pragma unroll
           for (int i5 = 0; i5 < 5; ++i5) bv[i5] = *(const float4_t*)(bsm + (h * 5 + i5) * 16 + 4 * lq);
         }
-        resw_for5([&](auto ic) {
+        for_n<5>([&](auto ic) {
           constexpr int i5 = decltype(ic)::value, i = h * 5 + i5;
-          float4_t v = resw_read_acc<(2 * i + j) * 4>();
+          float4_t v = agpr_read4<(2 * i + j) * 4>();
           if (has_bias) v += bv[i5];
           if (HAS_RB) {
 #pragma unroll
@@ -333,11 +316,11 @@ __global__ __launch_bounds__(RW_NT, 2) __attribute__((amdgpu_num_vgpr(96))) void
         }
       };
       // two pieces in flight; every wait names the operations younger than the piece it needs (loads issued after it, stores)
-      if (NSRC) { issue(pc0, 0, ReswIC<0>{}); issue(pc1, 0, ReswIC<1>{}); resw_wait<PL, SRC>(pc0); }
-      compute(pc0, ReswIC<0>{}, ReswIC<0>{});
-      if (NSRC) { issue(pc0, 1, ReswIC<0>{}); resw_wait<PL, SRC>(pc1); }
-      compute(pc1, ReswIC<0>{}, ReswIC<1>{});
-      if (NSRC) issue(pc1, 1, ReswIC<1>{});
+      if (NSRC) { issue(pc0, 0, IC<0>{}); issue(pc1, 0, IC<1>{}); resw_wait<PL, SRC>(pc0); }
+      compute(pc0, IC<0>{}, IC<0>{});
+      if (NSRC) { issue(pc0, 1, IC<0>{}); resw_wait<PL, SRC>(pc1); }
+      compute(pc1, IC<0>{}, IC<1>{});
+      if (NSRC) issue(pc1, 1, IC<1>{});
       colsum(0);
 #ifdef RESW_X_STAMPS
       unsigned long long qa, qb;
@@ -349,9 +332,9 @@ __global__ __launch_bounds__(RW_NT, 2) __attribute__((amdgpu_num_vgpr(96))) void
       b_s += qb - qa; b_e -= qb - qa;
 #endif
       if (NSRC) resw_wait<5 + PL, SRC>(pc0);
-      compute(pc0, ReswIC<1>{}, ReswIC<0>{});
+      compute(pc0, IC<1>{}, IC<0>{});
       if (NSRC) resw_wait<5, SRC>(pc1);
-      compute(pc1, ReswIC<1>{}, ReswIC<1>{});
+      compute(pc1, IC<1>{}, IC<1>{});
       RSTAMP(q2)
       colsum(1);
       rows(1);
@@ -369,10 +352,10 @@ __global__ __launch_bounds__(RW_NT, 2) __attribute__((amdgpu_num_vgpr(96))) void
           bh[i] = *(const float4_t*)(bsm + i * 16 + 4 * lq);
           bg[i] = *(const float4_t*)(bsm + 80 + i * 16 + 4 * lq);
         }
-        resw_for5([&](auto ic) {
+        for_n<5>([&](auto ic) {
           constexpr int i = decltype(ic)::value;
-          const float4_t hv = resw_read_acc<(2 * i + j) * 4>() + bh[i];
-          const float4_t gv = resw_read_acc<(2 * (i + 5) + j) * 4>() + bg[i];
+          const float4_t hv = agpr_read4<(2 * i + j) * 4>() + bh[i];
+          const float4_t gv = agpr_read4<(2 * (i + 5) + j) * 4>() + bg[i];
           const float2_t lo = __builtin_shufflevector(hv, hv, 0, 1) * gelu_erf2(__builtin_shufflevector(gv, gv, 0, 1));
           const float2_t hi = __builtin_shufflevector(hv, hv, 2, 3) * gelu_erf2(__builtin_shufflevector(gv, gv, 2, 3));
           const half4_t o = {(half_t)lo.x, (half_t)lo.y, (half_t)hi.x, (half_t)hi.y};
@@ -395,10 +378,10 @@ __global__ __launch_bounds__(RW_NT, 2) __attribute__((amdgpu_num_vgpr(96))) void
           resw_store16(outp + (unsigned long long)(unsigned)(mrow0 + row) * (unsigned)p.ldc + slab * 80 + cc * 8, v[kk], mr, p.M);
         }
       };
-      epi(ReswIC<0>{});
+      epi(IC<0>{});
       __builtin_amdgcn_sched_barrier(0);
       RSTAMP(q2)
-      epi(ReswIC<1>{});
+      epi(IC<1>{});
     }
 #ifdef RESW_X_STAMPS
     RSTAMP(q3)

@@ -21,6 +21,8 @@
 #define RP_NT 512
 #define RP_NBUF 3
 
+// gemm_stream.hip's gelu_fast, kept apart: spelled as one expression here and through a named temporary there, and this
+// kernel's device code changes with either spelling swapped in (tools/isa_identity.py), so neither moved to common.h
 __device__ __forceinline__ float gelu_fast_rp(float x) {
   const float z = fabsf(x) * 0.70710678118654752440f;
   const float t = __builtin_amdgcn_rcpf(fmaf(0.3275911f, z, 1.0f));
@@ -363,11 +365,11 @@ extern "C" int lkgd_gemm_rowpanel_launch(const lkgd_gemm_desc* d, hipStream_t st
   const int lds = RP_NBUF * RP_BN * d->K * 2 + 8 * 4608;
   LKGD_DEVICE_ONCE_BEGIN
     const int mx = RP_NBUF * RP_BN * 320 * 2 + 8 * 4608;
-#define RP_ATTR(NKV, L) (hipFuncSetAttribute((const void*)lkgd_gemm_rowpanel_kernel<NKV, L>, hipFuncAttributeMaxDynamicSharedMemorySize, mx) != hipSuccess)
-    if (RP_ATTR(1, false) || RP_ATTR(2, false) || RP_ATTR(3, false) || RP_ATTR(4, false) || RP_ATTR(5, false) ||
-        RP_ATTR(3, true) || RP_ATTR(4, true) || RP_ATTR(5, true))
+#define RP_K(NKV, L) lkgd_gemm_rowpanel_kernel<NKV, L>
+    if (!lkgd_dynamic_lds(mx, RP_K(1, false), RP_K(2, false), RP_K(3, false), RP_K(4, false), RP_K(5, false), RP_K(3, true),
+                          RP_K(4, true), RP_K(5, true)))
       return LKGD_E_LAUNCH;
-#undef RP_ATTR
+#undef RP_K
   LKGD_DEVICE_ONCE_END
   const int panels = (d->M + RP_ROWS - 1) / RP_ROWS;
   const int tiles_n = (d->N + RP_BN - 1) / RP_BN;

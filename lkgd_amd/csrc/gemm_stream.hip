@@ -347,9 +347,7 @@ extern "C" int lkgd_debug_read_stamps(unsigned long long* host_out) {
 
 extern "C" int lkgd_gemm_stream_launch(const lkgd_gemm_desc* d, hipStream_t stream, int cus) {
   LKGD_DEVICE_ONCE_BEGIN
-    if (hipFuncSetAttribute((const void*)lkgd_gemm_stream_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, SLDS) !=
-        hipSuccess)
-      return LKGD_E_LAUNCH;
+    if (!lkgd_dynamic_lds(SLDS, lkgd_gemm_stream_kernel)) return LKGD_E_LAUNCH;
   LKGD_DEVICE_ONCE_END
   int tiles_m = (d->M + SBM - 1) / SBM, tiles_n = (d->N + SBN - 1) / SBN;
   long long ntiles = (long long)tiles_m * tiles_n;

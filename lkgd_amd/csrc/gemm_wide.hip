@@ -12,6 +12,7 @@
 //     swapped-operand register epilogue exactly as gemm_stream.hip;
 //   * GEGLU: packed rows interleave 80 hidden | 80 gate per wave (5 + 5 fragments): both factors in the same lane/register.
 #include "gemm_common.h"
+#include "asm_host.h"
 
 // timing-experiment knobs (tools/micro/wide_knobs.sh; results are wrong with NOSTORE): never defined in the product build
 #ifdef WIDE_X_NOSTORE
@@ -144,32 +145,7 @@ __device__ __forceinline__ void wide_ktile_b(const half8_t (&x1)[4], half8_t w0,
 #undef WIDE_STMT_B
 }
 
-// accumulator fragment (weight fragment i, token fragment j) out of the AGPRs; BASE = (4i + j) * 4
-template <int BASE>
-__device__ __forceinline__ float4_t wide_read_acc() {
-  float a, b, c, d;
-  asm volatile("v_accvgpr_read_b32 %0, a[%4]\n\tv_accvgpr_read_b32 %1, a[%4+1]\n\t"
-               "v_accvgpr_read_b32 %2, a[%4+2]\n\tv_accvgpr_read_b32 %3, a[%4+3]"
-               : "=v"(a), "=v"(b), "=v"(c), "=v"(d)
-               : "i"(BASE));
-  return (float4_t){a, b, c, d};
-}
-
-template <int V> struct WideIC { static constexpr int value = V; };
-template <class F, int... Is> __device__ __forceinline__ void wide_static_for(F&& f, WideIC<Is>...) { (f(WideIC<Is>{}), ...); }
-template <class F> __device__ __forceinline__ void wide_for10(F&& f) {
-  wide_static_for(f, WideIC<0>{}, WideIC<1>{}, WideIC<2>{}, WideIC<3>{}, WideIC<4>{}, WideIC<5>{}, WideIC<6>{}, WideIC<7>{}, WideIC<8>{}, WideIC<9>{});
-}
-template <class F> __device__ __forceinline__ void wide_for8(F&& f) {
-  wide_static_for(f, WideIC<0>{}, WideIC<1>{}, WideIC<2>{}, WideIC<3>{}, WideIC<4>{}, WideIC<5>{}, WideIC<6>{}, WideIC<7>{});
-}
-template <int NF, class F> __device__ __forceinline__ void wide_for_nf(F&& f) {     // over a wave's weight fragments
-  if constexpr (NF == 8) wide_for8(f);
-  else wide_for10(f);
-}
-template <class F> __device__ __forceinline__ void wide_for5(F&& f) {
-  wide_static_for(f, WideIC<0>{}, WideIC<1>{}, WideIC<2>{}, WideIC<3>{}, WideIC<4>{});
-}
+// (accumulator fragment (weight fragment i, token fragment j): agpr_read4<(4i + j) * 4>, asm_host.h)
 
 // SPLIT = false is the production instantiation: ksplit folds to 1 and the slice bookkeeping disappears (with it in, the
 // allocator spilled 19-34 instead of 2-20 registers around the K-loop and every launch of this kernel got ~2 % slower)
@@ -415,9 +391,9 @@ __device__ __forceinline__ void wide_body(const lkgd_gemm_desc& p, int tiles_m, 
         if (!lds_out && !live) return;
         if (SPLIT) {                 // fp32 partial tile of this K slice; bias / residuals / rounding happen in the reduce pass
           float* dst = ws + ((long long)slice * p.M + m) * p.N;
-          wide_for_nf<NF>([&](auto ic) {
+          for_n<NF>([&](auto ic) {
             constexpr int i = decltype(ic)::value;
-            const float4_t ev = wide_read_acc<(4 * i + j) * 4>();
+            const float4_t ev = agpr_read4<(4 * i + j) * 4>();
             if (n0 + i * 16 < p.N) *(float4_t*)(dst + n0 + i * 16) = ev;
           });
           return;
@@ -428,10 +404,10 @@ __device__ __forceinline__ void wide_body(const lkgd_gemm_desc& p, int tiles_m, 
           if (rbp && !rb_lds && live) idx = (((unsigned)m / (unsigned)p.rb_d1) * (unsigned)p.rb_m1 + ((unsigned)m % (unsigned)p.rb_d2) +
                                              (unsigned)p.rb_c0) % (unsigned)p.rb_md;
           const int rb_sel = (unsigned)m < rb_bound ? 0 : WRB_STRIP / 2;
-          wide_for_nf<NF>([&](auto ic) {
+          for_n<NF>([&](auto ic) {
             constexpr int i = decltype(ic)::value;
             const int n = n0 + i * 16;
-            float4_t v = wide_read_acc<(4 * i + j) * 4>();
+            float4_t v = agpr_read4<(4 * i + j) * 4>();
             if (n < p.N) {
               if (p.bias) v += *(const float4_t*)(bl + i * 16);
               if (rbp && live) {
@@ -461,9 +437,9 @@ __device__ __forceinline__ void wide_body(const lkgd_gemm_desc& p, int tiles_m, 
         } else {
           // wave channels [0,80) = hidden, [80,160) = gate of output columns tn*160 + wc*80 + [0,80)
           const int oc0 = tn * 160 + wc * 80 + 4 * lq;
-          wide_for5([&](auto ic) {
+          for_n<5>([&](auto ic) {
             constexpr int i = decltype(ic)::value;
-            float4_t hv = wide_read_acc<(4 * i + j) * 4>(), gv = wide_read_acc<(4 * (i + 5) + j) * 4>();
+            float4_t hv = agpr_read4<(4 * i + j) * 4>(), gv = agpr_read4<(4 * (i + 5) + j) * 4>();
             if (p.bias) {
               hv += *(const float4_t*)(bl + i * 16);
               gv += *(const float4_t*)(bl + 80 + i * 16);
@@ -522,7 +498,7 @@ __device__ __forceinline__ void wide_body(const lkgd_gemm_desc& p, int tiles_m, 
       };
 #define WIDE_EPI(J)                                                                                                \
   {                                                                                                                \
-    epi(WideIC<J>{});                                                                                              \
+    epi(IC<J>{});                                                                                              \
     __builtin_amdgcn_sched_barrier(0);  /* keep one token fragment's loads/stores from piling onto the next */   \
   }
       WIDE_EPI(0) WIDE_EPI(1) WIDE_EPI(2)
@@ -598,13 +574,10 @@ static void wide_go(const lkgd_gemm_desc* d, hipStream_t stream, int grid, int t
 }
 template <int MODE>
 static bool wide_set_lds(const void* split_fn) {
-  const void* fns[] = {(const void*)lkgd_gemm_wide_kernel<MODE, false, 10, 4>, (const void*)lkgd_gemm_wide_kernel<MODE, true, 10, 4>,
-                       (const void*)lkgd_gemm_wide_kernel<MODE, false, 8, 4>,  (const void*)lkgd_gemm_wide_kernel<MODE, true, 8, 4>,
-                       (const void*)lkgd_gemm_wide_kernel<MODE, false, 10, 3>, (const void*)lkgd_gemm_wide_kernel<MODE, true, 10, 3>,
-                       (const void*)lkgd_gemm_wide_kernel<MODE, false, 8, 3>,  (const void*)lkgd_gemm_wide_kernel<MODE, true, 8, 3>, split_fn};
-  for (const void* f : fns)
-    if (hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, WLDS) != hipSuccess) return false;
-  return true;
+  return lkgd_dynamic_lds(WLDS, lkgd_gemm_wide_kernel<MODE, false, 10, 4>, lkgd_gemm_wide_kernel<MODE, true, 10, 4>,
+                          lkgd_gemm_wide_kernel<MODE, false, 8, 4>, lkgd_gemm_wide_kernel<MODE, true, 8, 4>,
+                          lkgd_gemm_wide_kernel<MODE, false, 10, 3>, lkgd_gemm_wide_kernel<MODE, true, 10, 3>,
+                          lkgd_gemm_wide_kernel<MODE, false, 8, 3>, lkgd_gemm_wide_kernel<MODE, true, 8, 3>, split_fn);
 }
 
 // do the output rows of this launch leave through LDS?  1 = yes, 0 = direct 8-byte stores, LKGD_E_SHAPE = column sums asked for

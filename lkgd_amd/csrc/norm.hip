@@ -561,10 +561,7 @@ extern "C" int lkgd_groupnorm_silu(const void* x0, int32_t c0, int32_t ld0, cons
     if (rc) return rc;
     if (!gamma || !beta || !out) return LKGD_E_NULL;
     LKGD_DEVICE_ONCE_BEGIN
-      if (hipFuncSetAttribute((const void*)gn_small_kernel<8>, hipFuncAttributeMaxDynamicSharedMemorySize, GN_SMALL_LDS) != hipSuccess ||
-          hipFuncSetAttribute((const void*)gn_small_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, GN_SMALL_LDS) != hipSuccess ||
-          hipFuncSetAttribute((const void*)gn_small_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, GN_SMALL_LDS) != hipSuccess)
-        return LKGD_E_LAUNCH;
+      if (!lkgd_dynamic_lds(GN_SMALL_LDS, gn_small_kernel<8>, gn_small_kernel<4>, gn_small_kernel<2>)) return LKGD_E_LAUNCH;
     LKGD_DEVICE_ONCE_END
     const size_t lds = (size_t)rows_per_sample * ((c0 + c1) / GN_GROUPS) * 2;
     const dim3 grid(GN_GROUPS, (unsigned)nsamples);

@@ -6,22 +6,12 @@
 // order the generated statement consumes them (tools/gen_qkv_asm.py -> qkv_fused_loop.inc, packing.pack_ln_proj).  The statement
 // also STORES: tile n's accumulators leave as two 16-byte pieces per lane (after a half-wave exchange) in the MFMA gaps of tile n + 1, and it fetches the next
 // panel's token rows into its output registers - this file is the first panel's load, the LayerNorm and the launch.
-#include "common.h"
-#include <utility>
+#include "asm_host.h"
 #include "qkv_fused_loop.inc"
 #include "qkv640_fused_loop.inc"        // QKV_GEN_C=640: the 36x64 level (60 tiles, two chunks per tile, z in a[0:159])
 
 #define QK_WAVES 4
 #define QK_LDS (QK_NSLOT * QK_SLOT)
-
-template <int REG>
-__device__ __forceinline__ void qk_agpr_write(unsigned v) {
-  asm volatile("v_accvgpr_write_b32 a[%1], %0" : : "v"(v), "i"(REG));
-}
-template <int V> struct QkIC { static constexpr int value = V; };
-template <class F, int... Is> __device__ __forceinline__ void qk_static_for(F&& f, QkIC<Is>...) { (f(QkIC<Is>{}), ...); }
-template <class F, int... Is> __device__ __forceinline__ void qk_for_seq(F&& f, std::integer_sequence<int, Is...>) { (f(QkIC<Is>{}), ...); }
-template <int N, class F> __device__ __forceinline__ void qk_for(F&& f) { qk_for_seq(f, std::make_integer_sequence<int, N>{}); }
 
 struct qk_params {
   const half_t* x; int ldx; long long T;
@@ -55,13 +45,8 @@ __global__ __launch_bounds__(QK_WAVES * 64, 1) __attribute__((amdgpu_num_vgpr(25
   }
   const unsigned lds0 = (unsigned)(uintptr_t)(__attribute__((address_space(3))) char*)smem;
   const unsigned long long sp0 = (unsigned long long)(uintptr_t)p.wstream;
-  const unsigned sp0lo = __builtin_amdgcn_readfirstlane((unsigned)sp0), sp0hi = __builtin_amdgcn_readfirstlane((unsigned)(sp0 >> 32));
-  unsigned splo, sphi;
-  {
-    const unsigned long long sp = sp0 + ahead_bytes;
-    splo = __builtin_amdgcn_readfirstlane((unsigned)sp);
-    sphi = __builtin_amdgcn_readfirstlane((unsigned)(sp >> 32));
-  }
+  const auto [sp0lo, sp0hi] = sgpr_ptr(sp0);
+  auto [splo, sphi] = sgpr_ptr(sp0 + ahead_bytes);
   const unsigned ldsw = __builtin_amdgcn_readfirstlane(lds0 + (unsigned)w * 1024u);
   const unsigned lds0u = __builtin_amdgcn_readfirstlane(lds0);
   const unsigned fa0 = lds0 + lane * 16, fa1 = fa0 + 2 * QK_SLOT, fa2 = fa0 + 4 * QK_SLOT;
@@ -95,7 +80,7 @@ __global__ __launch_bounds__(QK_WAVES * 64, 1) __attribute__((amdgpu_num_vgpr(25
     var = var < 0.f ? 0.f : var;
     const float rstd = __builtin_amdgcn_rsqf(var + p.eps);
     const float nm = -mean * rstd;
-    qk_for<NKS>([&](auto kc) {
+    for_n<NKS>([&](auto kc) {
       constexpr int ks = decltype(kc)::value;
       asm volatile("" : "+v"(raw[ks]));
       half8_t z;
@@ -103,10 +88,10 @@ __global__ __launch_bounds__(QK_WAVES * 64, 1) __attribute__((amdgpu_num_vgpr(25
       for (int e = 0; e < 8; ++e) z[e] = (half_t)fmaf((float)raw[ks][e], rstd, nm);
       typedef unsigned uint4_t __attribute__((ext_vector_type(4)));
       const uint4_t u = __builtin_bit_cast(uint4_t, z);
-      qk_agpr_write<QK_ZF + 4 * ks + 0>(u[0]);
-      qk_agpr_write<QK_ZF + 4 * ks + 1>(u[1]);
-      qk_agpr_write<QK_ZF + 4 * ks + 2>(u[2]);
-      qk_agpr_write<QK_ZF + 4 * ks + 3>(u[3]);
+      agpr_write<QK_ZF + 4 * ks + 0>(u[0]);
+      agpr_write<QK_ZF + 4 * ks + 1>(u[1]);
+      agpr_write<QK_ZF + 4 * ks + 2>(u[2]);
+      agpr_write<QK_ZF + 4 * ks + 3>(u[3]);
     });
   };
 
@@ -169,8 +154,7 @@ static int ln_qkv_launch(const void* x, int32_t ldx, int64_t T, const void* wstr
   if (ldx % 8 || ldo % 8 || ldx < C || ldo < 3 * C) return LKGD_E_ALIGN;
   if (!aligned16(x) || !aligned16(wstream) || !aligned16(out)) return LKGD_E_ALIGN;
   LKGD_DEVICE_ONCE_BEGIN
-    if (hipFuncSetAttribute((const void*)ln_qkv_kernel<C>, hipFuncAttributeMaxDynamicSharedMemorySize, QK_LDS) != hipSuccess)
-      return LKGD_E_LAUNCH;
+    if (!lkgd_dynamic_lds(QK_LDS, ln_qkv_kernel<C>)) return LKGD_E_LAUNCH;
   LKGD_DEVICE_ONCE_END
   const int cus = lkgd_cu_count();      // cached per device (common.h)
   const long long npanels = (T + QK_WAVES * 32 - 1) / (QK_WAVES * 32);

@@ -331,6 +331,37 @@ def test_generated_loop_kernels_keep_their_accumulation_registers(src, kernel, a
                  agprs if isinstance(agprs, tuple) else (agprs,)), "the check must notice a compiler write to an a-register"
 
 
+def test_isa_identity_compares_everything_but_the_source_hash():
+    """tools/isa_identity.py, the gate of a refactor that must leave every kernel alone: two device-ISA texts are the same if
+    they differ in nothing but their __hip_cuid_<hash of the source text> lines; one changed instruction, or one changed
+    metadata value, is a difference, and it is reported with the kernel it belongs to."""
+    sys.path.insert(0, os.path.join(REPO, "tools"))
+    from isa_identity import compare
+    def isa(cuid, op="v_add_f32_e32 v1, v2, v3", vgprs=12):
+        return "\n".join([
+            '\t.amdgcn_target "amdgcn-amd-amdhsa--gfx950"', "\t.text",
+            "\t.protected\tk_one ; -- Begin function k_one", "\t.type\tk_one,@function", "k_one:", "\ts_load_dwordx2 s[0:1], s[0:1], 0x0",
+            "\ts_endpgm", "\t.amdhsa_kernel k_one", "\t\t.amdhsa_next_free_vgpr 4", "\t.end_amdhsa_kernel",
+            "\t.protected\tk_two ; -- Begin function k_two", "\t.type\tk_two,@function", "k_two:", "\t" + op, "\ts_endpgm",
+            "\t.amdhsa_kernel k_two", "\t\t.amdhsa_next_free_vgpr 12", "\t.end_amdhsa_kernel",
+            "\t.type\t__hip_cuid_%s,@object ; @__hip_cuid_%s" % (cuid, cuid), "\t.globl\t__hip_cuid_%s" % cuid, "__hip_cuid_%s:" % cuid,
+            "\t.byte\t0", "\t.size\t__hip_cuid_%s, 1" % cuid, "\t.addrsig_sym __hip_cuid_%s" % cuid,
+            "\t.amdgpu_metadata", "---", "amdhsa.kernels:",
+            "  - .agpr_count:     0", "    .args:", "      - .name:           x", "        .size:           8", "    .name:           k_one",
+            "    .vgpr_count:     4",
+            "  - .agpr_count:     0", "    .args:", "      - .name:           y", "        .size:           8", "    .name:           k_two",
+            "    .vgpr_count:     %d" % vgprs, "...", "\t.end_amdgpu_metadata", ""])
+    base = isa("49abf5c6b4c29cac")
+    assert compare(base, isa("0123456789abcdef")) is None
+    assert compare(base, base) is None
+    diff = compare(base, isa("0123456789abcdef", op="v_add_f32_e32 v1, v2, v4"))
+    assert diff == ("k_two", "v_add_f32_e32 v1, v2, v3", "v_add_f32_e32 v1, v2, v4"), diff
+    assert compare(base, isa("49abf5c6b4c29cac", op="v_add_f32_e32 v1, v2, v4")) is not None      # with the same hash too
+    diff = compare(base, isa("0123456789abcdef", vgprs=13))
+    assert diff is not None and diff[0] == "k_two", diff
+    assert compare(base, base + "\ts_nop 0\n") is not None                                         # a longer text
+
+
 def test_clip_module_takes_transformers_state_dict_names(tmp_path):
     """lkgd_amd.clip keeps transformers' parameter names (image_encoder/ checkpoints load as they are), round-trips through
     save_pretrained / from_pretrained, ignores the persisted position_ids of older checkpoints, and refuses to run off the GPU"""

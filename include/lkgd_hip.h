@@ -87,7 +87,7 @@ enum {
  *                       and width); there is no test in time - the caller puts the context in place (the chunk's first frame
  *                       twice, or the last two frames of the previous chunk's buffer) and keeps the last two frames of this
  *                       buffer as the next context.  All 27 taps accumulate in fp32 in one launch.  a1 unused (csplit = Cin).
- *                       Program 4 only (M < 2^24, no GEGLU, K never sliced): LKGD_E_SHAPE otherwise
+ *                       LKGD_GEMM_WIDE only (M < 2^24, no GEGLU, K never sliced): LKGD_E_SHAPE otherwise
  *
  *    Replaces (reference call sites):
  *      F.linear      - attention to_q/k/v/to_out, GEGLU proj + FF out, proj_in/out, time_emb_proj
@@ -160,14 +160,17 @@ int lkgd_gemm_colstats_block(const lkgd_gemm_desc* d);
  * cus = compute units to plan for; 0 = ask the current device.  With cus != 0 nothing touches the device and no pointer of the
  * descriptor is dereferenced: only NULL-ness and alignment of the pointers matter (introspection for tests and tools; honours the
  * calling thread's debug knobs like the launch does).  Returns 0 or the LKGD_E_* lkgd_gemm_f16 would return before launching. */
+/* the tile programs (values frozen): 128x128 two-stage, 256x128 ring, persistent 256x128, 256x320 family, row-panel,
+ * resident-weight, 128x128 on the four-stage ring */
+enum { LKGD_GEMM_TILE128 = 1, LKGD_GEMM_TILE256 = 2, LKGD_GEMM_STREAM = 3, LKGD_GEMM_WIDE = 4, LKGD_GEMM_ROWPANEL = 5,
+       LKGD_GEMM_RESW = 6, LKGD_GEMM_MID = 7 };
 typedef struct lkgd_gemm_plan_info {
-  int32_t program;        /* 1 = 128x128 two-stage, 2 = 256x128 ring, 3 = persistent 256x128, 4 = 256x320 family, 5 = row-panel,
-                             6 = resident-weight, 7 = 128x128 on the four-stage ring */
-  int32_t k_slices;       /* 1 = K not cut; > 1: that many partial launches + the reduce pass (programs 1, 4, 7) */
-  int32_t tile_m, tile_n; /* rows x columns of one tile: program 4's form (256 | 192) x (320 | 256); 128x128, 256x128, the
+  int32_t program;        /* LKGD_GEMM_* */
+  int32_t k_slices;       /* 1 = K not cut; > 1: that many partial launches + the reduce pass (LKGD_GEMM_TILE128, _WIDE, _MID) */
+  int32_t tile_m, tile_n; /* rows x columns of one tile: LKGD_GEMM_WIDE's form (256 | 192) x (320 | 256); 128x128, 256x128, the
                              row-panel's 256x64, the resident-weight program's 32 rows per wave x 160-column slab */
   int32_t colstats_block; /* = lkgd_gemm_colstats_block(d) at this cus */
-  int32_t lds_out;        /* program 4: 1 = output rows leave through LDS, 0 = direct stores (always 0 for other programs) */
+  int32_t lds_out;        /* LKGD_GEMM_WIDE: 1 = output rows leave through LDS, 0 = direct stores (always 0 for other programs) */
 } lkgd_gemm_plan_info;
 int lkgd_gemm_plan(const lkgd_gemm_desc* d, int32_t cus, lkgd_gemm_plan_info* out);
 /* tile columns of the widest tile program for an output of N columns: 320, or 256 where 256 divides N and 320-column tiles would

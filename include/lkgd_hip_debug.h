@@ -5,11 +5,10 @@
  * launches the calling host thread makes afterwards and to nobody else's - a second pipeline on another thread keeps the
  * automatic behaviour (tests/test_host_cpu.py::test_debug_knobs_are_per_thread).  Value 0 (or -1 where noted) restores the
  * automatic behaviour.
- *      lkgd_debug_set_gemm_variant(v)   force a tile program of lkgd_gemm_f16 where it applies: 1 = 128x128, 2 = 256x128 ring,
- *                                       7 = 128x128 on a four-stage ring (few-row problems), 3 = persistent 256x128, 4 = 256x320,
- *                                       5 = row-panel, 6 = resident-weight; 0 = auto
+ *      lkgd_debug_set_gemm_variant(v)   force a tile program of lkgd_gemm_f16 where it applies: LKGD_GEMM_TILE128, _TILE256,
+ *                                       _STREAM, _WIDE, _ROWPANEL, _RESW or _MID (include/lkgd_hip.h); 0 = auto
  *      lkgd_debug_set_gemm_splitk(on)   0 = never cut K into slices
- *      lkgd_debug_set_mid_model(tk, fix, red, tbs, forced)   cost model of the four-stage 128x128 program's K slicing (us per
+ *      lkgd_debug_set_mid_model(tk, fix, red, tbs, forced)   cost model of the LKGD_GEMM_MID program's K slicing (us per
  *                                       K-tile, us per workgroup, us per reduce pass, TB/s of the reduce pass; <= 0 keeps a value);
  *                                       forced > 0 = that many slices where legal
  *      lkgd_debug_set_wide_ksplit(k)    force k K-slices on the 256x320 program where legal; 0 = rule

@@ -60,7 +60,7 @@ __device__ __forceinline__ float wave_max(float v) {
   return v;
 }
 
-static inline bool aligned16(const void* p) { return (((uintptr_t)p) & 15u) == 0; }
+#include "aligned16.h"
 
 // opt the kernels in to `bytes` of dynamic LDS (above the 64 KiB a launch gets without asking); stops at the first failure.
 // Per device: call it inside LKGD_DEVICE_ONCE_BEGIN / _END below.
@@ -84,18 +84,25 @@ struct lkgd_device_once {
   void done(int dev) { mask.fetch_or(1ull << dev, std::memory_order_release); }
 };
 // CU count of the current device, queried once per device ordinal (hipGetDeviceProperties is a slow host call; the launchers
-// of the persistent kernels need the count on every launch to size their grids); 256 if the query fails
-static inline int lkgd_cu_count() {
+// of the persistent kernels need the count on every launch to size their grids); false if there is no device to ask
+static inline bool lkgd_cu_query(int* cus_out) {
   static std::atomic<int> cus_of[64];
   int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev > 63) return 256;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev > 63) return false;
   int cus = cus_of[dev].load(std::memory_order_relaxed);
   if (!cus) {
     hipDeviceProp_t prop;
-    cus = (hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) ? prop.multiProcessorCount : 256;
+    if (hipGetDeviceProperties(&prop, dev) != hipSuccess) return false;
+    cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
     cus_of[dev].store(cus, std::memory_order_relaxed);
   }
-  return cus;
+  *cus_out = cus;
+  return true;
+}
+// the same for callers that size a grid and would rather run on a guess than refuse: 256 if the query fails
+static inline int lkgd_cu_count() {
+  int cus = 0;
+  return lkgd_cu_query(&cus) ? cus : 256;
 }
 #define LKGD_DEVICE_ONCE_BEGIN                     \
   {                                                \

@@ -1,8 +1,9 @@
 // Shared pieces of the MFMA GEMM kernels: the implicit-convolution A-operand gather and the epilogue row map.
 #pragma once
 #include "common.h"
+#include "gemm_plan.h"
 
-#define BK 64
+using namespace lkgd_gemm;   // BK and the other tile sizes, the plan, the launchers
 
 // K order of the 3x3 implicit convolution (weights packed by lkgd_amd/packing.py::pack_conv3x3):
 //   k = ((ky * (Cin/64) + c/64) * 3 + kx) * 64 + c % 64

@@ -49,7 +49,7 @@ extern "C" int lkgd_debug_resw_stamps(unsigned long long* host, int n) {
 #define RSTAMP(var)
 #endif
 
-#define RW_SLAB 160
+// RW_SLAB = 160 weight rows per slab: gemm_plan.h
 #define RW_NT 512
 #define RW_WAVES 8
 #define RW_PITCH 336           // bytes per staged output row (320 + 16: rows start on different banks)
@@ -397,13 +397,7 @@ __global__ __launch_bounds__(RW_NT, 2) __attribute__((amdgpu_num_vgpr(96))) void
 #endif
 }
 
-// Which (K, epilogue sources) instantiations exist: the ones hipcc allocates WITHOUT scratch spills inside the 96-register
-// budget (tests/test_host_cpu.py compiles this file with -Rpass-analysis and checks it).  A spill would be more than
-// slow here: the residual loads are issued and awaited by hand, and spill code placed between a load and its wait would
-// save a register whose data has not arrived yet.
-static constexpr bool resw_has(int nk, int src) { return nk >= 4 ? src <= 5 : (src == 0 || src == 1 || src == 2 || src == 4 || src == 6); }
-static constexpr bool resw_has_cs(int nk, int src) { return src == 0 || src == 2; }      // bare / bias, + one residual (proj_out)
-
+// which (K, epilogue sources) instantiations exist: gemm_plan.h::resw_has / resw_has_cs, the table the planner reads too
 template <int NK>
 static void resw_launch_nk(const lkgd_gemm_desc* d, hipStream_t stream, int grid, int lds, int nslab, int per, bool attr_only) {
   const int src = (d->rowbias ? 1 : 0) | (d->res1 ? 2 : 0) | (d->res2 ? 4 : 0);
@@ -422,32 +416,11 @@ static void resw_launch_nk(const lkgd_gemm_desc* d, hipStream_t stream, int grid
 #undef RW_ONE
 }
 
-// may a launch of this descriptor on the resident-weight kernel carry column statistics?
-extern "C" int lkgd_gemm_resw_colstats_ok(const lkgd_gemm_desc* d) {
-  const int src = (d->rowbias ? 1 : 0) | (d->res1 ? 2 : 0) | (d->res2 ? 4 : 0);
-  return !d->geglu && resw_has_cs(d->K / 64, src);
-}
-
-// does the resident-weight kernel cover this problem on a device with `cus` compute units?  (lkgd_gemm_f16's dispatch)
-extern "C" int lkgd_gemm_resw_ok(const lkgd_gemm_desc* d, int cus) {
-  const int nk = d->K / 64;
-  if (nk < 1 || nk > 5 || d->K % 64 || d->mode != LKGD_A_PLAIN || d->csplit < d->K) return 0;
-  if (d->N % RW_SLAB || (d->geglu != 0 && d->geglu != 80) || d->N / RW_SLAB > cus / 8) return 0;
-  if (d->geglu && (d->rowbias || d->res1 || d->res2)) return 0;
-  const int src = (d->rowbias ? 1 : 0) | (d->res1 ? 2 : 0) | (d->res2 ? 4 : 0);
-  if (!d->geglu && !resw_has(nk, src)) return 0;
-  // 16-byte row pieces of out, 8-byte pieces of the sources, 16-byte token fragments; 32-bit row arithmetic
-  if (d->ldc % 8 || !aligned16(d->out) || d->lda0 % 8 || !aligned16(d->a0) || !aligned16(d->w)) return 0;
-  if ((d->res1 && (d->ldr1 % 4 || ((uintptr_t)d->res1 & 7))) || (d->res2 && (d->ldr2 % 4 || ((uintptr_t)d->res2 & 7))) ||
-      (d->rowbias && (d->ldrb % 4 || ((uintptr_t)d->rowbias & 7))))
-    return 0;
-  return d->M >= 1 && d->M < (1 << 26);
-}
-
 // grid = 8 XCD classes x (per x nslab) workgroups: every XCD runs all nslab slabs over its eighth of the rows
-extern "C" int lkgd_gemm_resw_launch(const lkgd_gemm_desc* d, hipStream_t stream, int cus) {
-  if (!lkgd_gemm_resw_ok(d, cus)) return LKGD_E_SHAPE;
-  if (d->colstats && !lkgd_gemm_resw_colstats_ok(d)) return LKGD_E_SHAPE;
+int lkgd_gemm::gemm_resw_launch(const lkgd_gemm_desc* d, lkgd_stream_t stream_, int cus, const gemm_plan& pl) {
+  if (pl.program != GEMM_RESW || !gemm_resw_ok(d, cus)) return LKGD_E_SHAPE;
+  if (d->colstats && !gemm_resw_colstats_ok(d)) return LKGD_E_SHAPE;
+  hipStream_t stream = (hipStream_t)stream_;
   const int nk = d->K / 64;
   const int nslab = d->N / RW_SLAB;
   const int per = (cus / 8) / nslab;

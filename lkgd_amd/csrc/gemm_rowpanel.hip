@@ -358,7 +358,9 @@ __global__ __launch_bounds__(RP_NT, 2) void lkgd_gemm_rowpanel_kernel(const lkgd
 #endif
 }
 
-extern "C" int lkgd_gemm_rowpanel_launch(const lkgd_gemm_desc* d, hipStream_t stream, int cus) {
+int lkgd_gemm::gemm_rowpanel_launch(const lkgd_gemm_desc* d, lkgd_stream_t stream_, int cus, const gemm_plan& pl) {
+  if (pl.program != GEMM_ROWPANEL) return LKGD_E_SHAPE;
+  hipStream_t stream = (hipStream_t)stream_;
   const int nk = d->K / 64;
   if (nk < 1 || nk > 5 || d->mode != LKGD_A_PLAIN || d->csplit < d->K) return LKGD_E_SHAPE;
   if (d->ln_colsum && (d->geglu || d->K != nk * 64)) return LKGD_E_SHAPE;

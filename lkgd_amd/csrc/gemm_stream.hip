@@ -345,7 +345,9 @@ extern "C" int lkgd_debug_read_stamps(unsigned long long* host_out) {
 }
 #endif
 
-extern "C" int lkgd_gemm_stream_launch(const lkgd_gemm_desc* d, hipStream_t stream, int cus) {
+int lkgd_gemm::gemm_stream_launch(const lkgd_gemm_desc* d, lkgd_stream_t stream_, int cus, const gemm_plan& pl) {
+  if (pl.program != GEMM_STREAM) return LKGD_E_SHAPE;
+  hipStream_t stream = (hipStream_t)stream_;
   LKGD_DEVICE_ONCE_BEGIN
     if (!lkgd_dynamic_lds(SLDS, lkgd_gemm_stream_kernel)) return LKGD_E_LAUNCH;
   LKGD_DEVICE_ONCE_END

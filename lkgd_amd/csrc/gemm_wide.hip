@@ -38,8 +38,7 @@
 #define WIDE_ST(ptr, v) (*(ptr) = (v))
 #endif
 #define WIDE_OUT_PITCH 336      // bytes per staged output row (320 + 16: rows start on different banks)
-#define WBM 256
-#define WBN 320
+// WBM x WBN = 256 x 320: gemm_plan.h
 #define WNT 512
 #define WSTAGE_BYTES ((WBM + WBN) * BK * 2)   // 72 KiB
 #define WBIAS_OFF (2 * WSTAGE_BYTES)          // two 320-float bias strips (tile parity) behind the stages
@@ -542,23 +541,6 @@ __global__ __launch_bounds__(WNT, 2) __attribute__((amdgpu_num_vgpr(96))) void l
   wide_body<MODE, true, false, 10, 4>(p, tiles_m, tiles_n, ksplit, ws);
 }
 
-// ksplit > 1: K is cut into ksplit equal slices (ksplit divides K / 64); the caller runs lkgd_gemm_splitk_reduce afterwards
-static thread_local int wide_lds_out_override = -1;     // A/B knob: 0 = direct 8-byte stores everywhere, 1 / -1 = rows through LDS where used
-extern "C" void lkgd_debug_set_wide_lds_out(int on) { wide_lds_out_override = on; }
-
-// the 256x256 form serves channel counts that are whole 256-column tiles and not whole 320-column ones (256, 512, 768 ...)
-// and would leave more than a tenth of the 320-wide tile columns idle (3072 = 9.6 x 320 stays on 320)
-static thread_local int wide_tile_n_forced = 0;      // A/B knob (tools/micro/wide_tile_n.py): 256 / 320 where that width divides N, 0 = the rule
-extern "C" void lkgd_debug_set_wide_tile_n(int wn) { wide_tile_n_forced = (wn == 256 || wn == 320) ? wn : 0; }
-extern "C" int lkgd_debug_wide_tile_n_forced() { return wide_tile_n_forced; }
-static thread_local int wide_tile_m_forced = 0;      // A/B knob: 192 / 256 tile rows (0 = the rule of gemm.hip::gemm_wide_form)
-extern "C" void lkgd_debug_set_wide_tile_m(int wm) { wide_tile_m_forced = (wm == 192 || wm == 256) ? wm : 0; }
-extern "C" int lkgd_debug_wide_tile_m_forced() { return wide_tile_m_forced; }
-extern "C" int lkgd_gemm_wide_tile_n(int N) {
-  if (wide_tile_n_forced && N % wide_tile_n_forced == 0) return wide_tile_n_forced;
-  return (N % WBN != 0 && N % 256 == 0 && (long long)((N + WBN - 1) / WBN) * WBN * 10 > (long long)N * 11) ? 256 : WBN;
-}
-
 template <int MODE>
 static void wide_go(const lkgd_gemm_desc* d, hipStream_t stream, int grid, int tiles_m, int tiles_n, bool lds_out, int wn, int wm) {
 #define WIDE_GO(...) \
@@ -580,18 +562,12 @@ static bool wide_set_lds(const void* split_fn) {
                           lkgd_gemm_wide_kernel<MODE, false, 8, 3>, lkgd_gemm_wide_kernel<MODE, true, 8, 3>, split_fn);
 }
 
-// do the output rows of this launch leave through LDS?  1 = yes, 0 = direct 8-byte stores, LKGD_E_SHAPE = column sums asked for
-// where the rows cannot go through LDS (host-side: also what lkgd_gemm_plan reports)
-extern "C" int lkgd_gemm_wide_lds_out(const lkgd_gemm_desc* d, int ksplit, int wn) {
-  // plain linears without GEGLU, whole tile columns, 16-byte aligned output rows: the rows leave through LDS (see the epilogue)
-  // (the convolutions only when column statistics are asked for: they are summed from the rows in LDS)
-  const bool lds_ok = ksplit == 1 && !d->geglu && d->N % wn == 0 && d->ldc % 8 == 0 && aligned16(d->out);
-  if (d->colstats && !lds_ok) return LKGD_E_SHAPE;
-  return lds_ok && (d->colstats ? true : (wide_lds_out_override != 0 && d->mode == LKGD_A_PLAIN)) ? 1 : 0;
-}
-
-// wn = tile columns (320 | 256), wm = tile rows (256 | 192): the caller's choice (gemm.hip: gemm_wide_form)
-extern "C" int lkgd_gemm_wide_launch(const lkgd_gemm_desc* d, hipStream_t stream, int cus, int ksplit, int wn, int wm) {
+// pl.wn = tile columns (320 | 256), pl.wm = tile rows (256 | 192): the planner's choice (gemm_plan.cpp: gemm_wide_form).
+// pl.ks > 1: K is cut into pl.ks equal slices (pl.ks divides K / 64); the caller runs lkgd_gemm_splitk_reduce afterwards
+int lkgd_gemm::gemm_wide_launch(const lkgd_gemm_desc* d, lkgd_stream_t stream_, int cus, const gemm_plan& pl) {
+  if (pl.program != GEMM_WIDE) return LKGD_E_SHAPE;
+  hipStream_t stream = (hipStream_t)stream_;
+  const int ksplit = pl.ks, wn = pl.wn, wm = pl.wm;
   LKGD_DEVICE_ONCE_BEGIN
     if (!wide_set_lds<LKGD_A_PLAIN>((const void*)lkgd_gemm_wide_split_kernel<LKGD_A_PLAIN>) ||
         !wide_set_lds<LKGD_A_CONV3X3>((const void*)lkgd_gemm_wide_split_kernel<LKGD_A_CONV3X3>) ||
@@ -609,8 +585,9 @@ extern "C" int lkgd_gemm_wide_launch(const lkgd_gemm_desc* d, hipStream_t stream
   int grid = ntiles < cus ? (int)ntiles : cus;
   if (d->M >= (1 << 24)) return LKGD_E_SHAPE;            // float-reciprocal row decomposition (gemm_common.h)
   float* ws = (float*)d->workspace;
-  const int lo = lkgd_gemm_wide_lds_out(d, ksplit, wn);
+  const int lo = gemm_wide_lds_out(d, ksplit, wn);
   if (lo < 0) return lo;
+  if ((lo != 0) != (pl.lds_out != 0)) return LKGD_E_SHAPE;
   const bool lds_out = lo != 0;
 #define WIDE_LAUNCH(MODE_)                                                                                              \
   {                                                                                                                     \

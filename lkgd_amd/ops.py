@@ -13,6 +13,10 @@ from . import _lib
 from ._lib import GemmDesc, check
 
 A_PLAIN, A_CONV3X3, A_TCONV3, A_CONV3X3_C8, A_CCONV3 = 0, 1, 2, 3, 4
+# the tile programs of lkgd_gemm_f16 (include/lkgd_hip.h: LKGD_GEMM_*), as lkgd_gemm_plan reports and lkgd_debug_set_gemm_variant forces them
+GEMM_TILE128, GEMM_TILE256, GEMM_STREAM, GEMM_WIDE, GEMM_ROWPANEL, GEMM_RESW, GEMM_MID = 1, 2, 3, 4, 5, 6, 7
+GEMM_PROGRAMS = {"tile128": GEMM_TILE128, "tile256": GEMM_TILE256, "stream": GEMM_STREAM, "wide": GEMM_WIDE,
+                 "rowpanel": GEMM_ROWPANEL, "resw": GEMM_RESW, "mid": GEMM_MID}
 
 _zeros = {}
 

@@ -5,6 +5,7 @@ header needs a ``HEADERS`` row, a ``PINS`` row and a ``FOOTPRINT_MODULES`` row -
 import ctypes
 import importlib
 import os
+import subprocess
 
 import pytest
 
@@ -86,6 +87,20 @@ def test_library_exports_the_table(header):
     for name, (restype, argtypes) in _lib.HEADERS[header].items():
         fn = getattr(lib, name)
         assert fn.restype is restype and list(fn.argtypes or []) == list(argtypes), name
+
+
+#: exported and declared by no header, on purpose: the diagnostic build (`make dbg`, tools/gemm_phase_stamps.py) defines these two
+#: readers of its in-kernel phase stamps; the product library does not have them
+UNDECLARED_EXPORTS = {"lkgd_debug_read_stamps", "lkgd_debug_resw_stamps"}
+
+
+def test_library_exports_nothing_but_the_tables():
+    """the converse of the test above: every dynamic symbol lkgd_* the library defines is a row of a header's table (a cross-file
+    helper that is `extern "C"` would be an export nobody declared)"""
+    out = subprocess.run(["nm", "-D", "--defined-only", _lib.LIB_PATH], capture_output=True, text=True, check=True).stdout
+    exported = {l.split()[-1] for l in out.splitlines() if l.split() and l.split()[-1].startswith("lkgd_")}
+    declared = {n for t in _lib.HEADERS.values() for n in t}
+    assert declared <= exported <= declared | UNDECLARED_EXPORTS, sorted(exported ^ declared)
 
 
 def test_version_string_and_descriptor_size():

@@ -152,7 +152,7 @@ def _launch_form(shape, colstats, cus=256):
     M = B * T * H * W
     plan = ops.gemm_plan(_Rows(B * (T + 2) * H * W, Cin), _Rows(N, 27 * Cin), _Rows(M, N), cus=cus, M=M, N=N, K=27 * Cin,
                          bias=torch.empty(N), mode=ops.A_CCONV3, Cin=Cin, cconv=(T, H, W), colstats=colstats)
-    assert plan.program == 4 and plan.k_slices == 1
+    assert plan.program == ops.GEMM_WIDE and plan.k_slices == 1
     return plan.tile_m, plan.tile_n, plan.lds_out
 
 

@@ -130,7 +130,7 @@ def _launch(shape, rows, x, w, bias, res, colstats=0):
     B, Cin, N, T, H, W = shape
     M = B * T * H * W
     out = torch.full((M, N), float("nan"), dtype=torch.float16, device=DEV)
-    form = dict(program=4, k_slices=1, tile_m=rows, tile_n=TILE_N[N], lds_out=1 if colstats else 0)
+    form = dict(program=ops.GEMM_WIDE, k_slices=1, tile_m=rows, tile_n=TILE_N[N], lds_out=1 if colstats else 0)
     if colstats:
         form["colstats_block"] = rows
     _gemm_as(ops, form, _prefix(x).to(DEV), pack_cconv3(w).to(DEV), out, M=M, N=N, K=27 * Cin, bias=None if bias is None else bias.to(DEV),

@@ -15,6 +15,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from lkgd_amd import ops
 from footprint import GUARD, INT_POISON, Windows, pattern_bytes, run_case
 
 gpu = pytest.mark.gpu
@@ -1398,7 +1399,7 @@ def test_ff_fused(T):
 
 
 # ================================================================================================== GEMM
-GEMM_VARIANTS = {"auto": 0, "tile128": 1, "tile256": 2, "stream": 3, "wide": 4, "rowpanel": 5, "resw": 6, "mid": 7}
+GEMM_VARIANTS = {"auto": 0, **ops.GEMM_PROGRAMS}
 
 
 @pytest.fixture(params=list(GEMM_VARIANTS))
@@ -1735,7 +1736,7 @@ def test_gemm_wide_forms(wm, wn, lds_out):
     L = _lib_()
     g = _gen(wm + wn + lds_out)
     N, K = (512, 128) if wn else (328, 128)
-    L.lkgd_debug_set_gemm_variant(4)
+    L.lkgd_debug_set_gemm_variant(ops.GEMM_WIDE)
     L.lkgd_debug_set_wide_tile_m(wm)
     L.lkgd_debug_set_wide_tile_n(wn)
     L.lkgd_debug_set_wide_lds_out(lds_out)

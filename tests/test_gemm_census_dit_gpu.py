@@ -28,6 +28,7 @@ import torch
 import fp8_oracle as fo
 import gemm_oracle as go
 from test_gemm_census_gpu import DEV, GUARD, SENTINEL, _census, _lib, _recorded, _view, check_signature
+from lkgd_amd import ops
 from tools import gemm_census as gc
 
 pytestmark = pytest.mark.gpu
@@ -95,11 +96,11 @@ def test_census_notices_a_wrong_tile_column(monkeypatch):
 
 
 #: what the ladder is there to reach: (program, tile rows, tile columns or None = any, K slices > 1)
-LADDER_PLANS = {"program 7 with K slices": lambda p: p["program"] == 7 and p["k_slices"] > 1,
-                "program 4 with K slices": lambda p: p["program"] == 4 and p["k_slices"] > 1,
+LADDER_PLANS = {"program 7 with K slices": lambda p: p["program"] == ops.GEMM_MID and p["k_slices"] > 1,
+                "program 4 with K slices": lambda p: p["program"] == ops.GEMM_WIDE and p["k_slices"] > 1,
                 "program 4 at 256x256": lambda p: (p["program"], p["tile_m"], p["tile_n"]) == (4, 256, 256),
                 "program 4 at 192x320": lambda p: (p["program"], p["tile_m"], p["tile_n"]) == (4, 192, 320),
-                "program 1": lambda p: p["program"] == 1}
+                "program 1": lambda p: p["program"] == ops.GEMM_TILE128}
 
 
 def _ladder(D):

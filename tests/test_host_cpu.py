@@ -410,7 +410,7 @@ def test_clip_module_takes_transformers_state_dict_names(tmp_path):
 
 GEMM_CLASSES = ("plain", "rowmap", "two-source", "geglu", "conv3x3 stride 1 ups 0", "conv3x3 stride 2 ups 0", "conv3x3 stride 1 ups 1",
                 "tconv")
-#: the operand / epilogue classes each forced variant supports (lkgd_amd/csrc/gemm.hip::gemm_pick: the row-panel and resident-weight
+#: the operand / epilogue classes each forced variant supports (lkgd_amd/csrc/gemm_plan.cpp::gemm_pick: the row-panel and resident-weight
 #: programs take a plain single-source A with K <= 320; the 80-wide GEGLU interleave exists on the 256x320 and resident-weight
 #: programs only, the 32-wide one on the others)
 VARIANT_CLASSES = {1: GEMM_CLASSES, 2: GEMM_CLASSES, 3: GEMM_CLASSES, 4: GEMM_CLASSES, 5: ("plain", "rowmap", "geglu"),
@@ -422,19 +422,19 @@ def test_gemm_plan_reports_what_the_front_end_would_launch():
     e = lambda *s, dt=torch.float16: torch.empty(*s, dtype=dt)       # noqa: E731
     M, N, K = 4032, 1280, 3840
     p = ops.gemm_plan(e(M, K), e(N, K), e(M, N), M=M, N=N, K=K, bias=e(N, dt=torch.float32), cus=256)
-    assert (p.program, p.k_slices, p.tile_m, p.tile_n) == (4, 4, 256, 320)       # 64 tiles, deep K: four equal K slices
+    assert (p.program, p.k_slices, p.tile_m, p.tile_n) == (ops.GEMM_WIDE, 4, 256, 320)       # 64 tiles, deep K: four equal K slices
     # without the workspace ops.gemm hands to problems below 12288 rows there is nothing to slice into
     p = ops.gemm_plan(e(12288, K), e(N, K), e(12288, N), M=12288, N=N, K=K, cus=256)
-    assert p.program == 4 and p.k_slices == 1
+    assert p.program == ops.GEMM_WIDE and p.k_slices == 1
     # column sums: asked for -> the tile rows divide the sample, the rows leave through LDS, the block is the tile's rows
     p = ops.gemm_plan(e(16128, 640), e(640, 640), e(16128, 640), M=16128, N=640, K=640, colstats=576, cus=256)
-    assert p.program == 4 and p.colstats_block == p.tile_m and 576 % p.tile_m == 0 and p.lds_out == 1
+    assert p.program == ops.GEMM_WIDE and p.colstats_block == p.tile_m and 576 % p.tile_m == 0 and p.lds_out == 1
     # rows that are not 16-byte pieces keep the persistent programs out
     p = ops.gemm_plan(e(40000, 320), e(324, 320), e(40000, 324), M=40000, N=324, K=320, cus=256)
-    assert p.program in (1, 2, 7)
+    assert p.program in (ops.GEMM_TILE128, ops.GEMM_TILE256, ops.GEMM_MID)
     # the CU count is an input: fewer CUs, fewer idle ones to fill with K slices
     p64 = ops.gemm_plan(e(M, K), e(N, K), e(M, N), M=M, N=N, K=K, cus=64)
-    assert p64.program == 4 and p64.k_slices == 1
+    assert p64.program == ops.GEMM_WIDE and p64.k_slices == 1
     with pytest.raises(_lib.LkgdHipError):
         ops.gemm_plan(e(M, K), e(N, K), e(M, N), M=M, N=N, K=K)                 # cus = 0 asks a device
     with pytest.raises(_lib.LkgdHipError):
@@ -460,7 +460,7 @@ def test_forced_variant_matrix_reaches_every_program():
             for cls, kw in cases:
                 kw = dict(kw)
                 p = ops.gemm_plan(kw.pop("a0"), kw.pop("w"), kw.pop("out"), cus=256, **kw)
-                assert 1 <= p.program <= 7
+                assert p.program in ops.GEMM_PROGRAMS.values()
                 if p.program == v:
                     reached.setdefault(v, set()).add(cls)
     finally:
@@ -501,18 +501,19 @@ CENSUS_NOT_COVERED = {
 
 
 def test_gemm_census_covers_every_program_and_tile_form():
+    from lkgd_amd import ops
     from tools import gemm_census as gc
     rows = gc.load_table()
     progs = {e["plan"]["program"] for e in rows}
-    forms = {(e["plan"]["tile_m"], e["plan"]["tile_n"]) for e in rows if e["plan"]["program"] == 4}
+    forms = {(e["plan"]["tile_m"], e["plan"]["tile_n"]) for e in rows if e["plan"]["program"] == ops.GEMM_WIDE}
     want = {f"program {p}" for p in range(1, 8)} | {f"form {m}x{n}" for m in (256, 192) for n in (320, 256)}
     have = {f"program {p}" for p in progs} | {f"form {m}x{n}" for m, n in forms}
     assert have | set(CENSUS_NOT_COVERED) == want, sorted(want - have - set(CENSUS_NOT_COVERED))
     assert not have & set(CENSUS_NOT_COVERED), f"now covered, drop from the list: {sorted(have & set(CENSUS_NOT_COVERED))}"
     # all three split-K schemes, both output paths of the 256x320 program, both colstats block sizes
     sliced = {e["plan"]["program"] for e in rows if e["plan"]["k_slices"] > 1}
-    assert {4, 7} <= sliced, sliced
-    assert {e["plan"]["lds_out"] for e in rows if e["plan"]["program"] == 4} == {0, 1}
+    assert {ops.GEMM_WIDE, ops.GEMM_MID} <= sliced, sliced
+    assert {e["plan"]["lds_out"] for e in rows if e["plan"]["program"] == ops.GEMM_WIDE} == {0, 1}
     assert {256, 192, 32} <= {e["plan"]["colstats_block"] for e in rows}
 
 

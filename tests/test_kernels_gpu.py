@@ -6,6 +6,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from lkgd_amd import ops
+
 pytestmark = pytest.mark.gpu
 
 DEV = "cuda:0"
@@ -24,7 +26,7 @@ def _close(got, ref, rtol=4e-3, what=""):
     assert rel < 3e-3, f"{what}: relative L2 {rel:.4g}"
 
 
-VARIANTS = {"tile128": 1, "tile256": 2, "stream": 3, "wide": 4, "rowpanel": 5, "resw": 6, "mid": 7}
+VARIANTS = dict(ops.GEMM_PROGRAMS)
 
 # Shapes of the tests that run under the `ops` fixture (every forced variant).  Module constants, so that
 # tests/test_host_cpu.py::test_forced_variant_matrix_reaches_every_program can ask lkgd_gemm_plan - without a GPU - which program
@@ -655,7 +657,7 @@ def test_gemm_four_stage_ring_k_slices():
     from lkgd_amd import _lib, ops
     L = _lib.lib()
     g = torch.Generator().manual_seed(77)
-    L.lkgd_debug_set_gemm_variant(7)
+    L.lkgd_debug_set_gemm_variant(ops.GEMM_MID)
     try:
         for M, N, K, forced in ((576, 1280, 1280, 3), (301, 320, 704, 5), (2304, 640, 1920, 2), (130, 128, 64 * 11, 4)):
             a = _h(torch.randn(M, K, generator=g))
@@ -669,7 +671,7 @@ def test_gemm_four_stage_ring_k_slices():
                 L.lkgd_debug_set_gemm_splitk(1 if f else 0)
                 out = torch.empty(M, N, dtype=torch.float16, device=DEV)
                 per = -(-(K // 64) // f) if f else K // 64            # K-tiles per slice; every slice non-empty
-                _gemm_as(ops, dict(program=7, k_slices=-(-(K // 64) // per)), a.to(DEV), w.to(DEV), out, M=M, N=N, K=K,
+                _gemm_as(ops, dict(program=ops.GEMM_MID, k_slices=-(-(K // 64) // per)), a.to(DEV), w.to(DEV), out, M=M, N=N, K=K,
                          bias=b.to(DEV), res1=res.to(DEV), r1=0.5)
                 outs.append(out.cpu())
             _close(outs[0], ref, what=f"four-stage ring, {forced} K slices, {M}x{N}x{K}")
@@ -698,12 +700,12 @@ def test_gemm_split_k_on_256x320_tiles():
     rows = torch.arange(0, M, 53)
     ref = a[rows].float() @ w.float().T + b + 0.5 * res[rows].float()
     outs = []
-    L.lkgd_debug_set_gemm_variant(4)
+    L.lkgd_debug_set_gemm_variant(ops.GEMM_WIDE)
     for ks in (2, 0):
         L.lkgd_debug_set_wide_ksplit(ks)
         L.lkgd_debug_set_gemm_splitk(1 if ks else 0)
         out = torch.empty(M, N, dtype=torch.float16, device=DEV)
-        _gemm_as(ops, dict(program=4, k_slices=ks or 1), a.to(DEV), w.to(DEV), out, M=M, N=N, K=K, bias=b.to(DEV),
+        _gemm_as(ops, dict(program=ops.GEMM_WIDE, k_slices=ks or 1), a.to(DEV), w.to(DEV), out, M=M, N=N, K=K, bias=b.to(DEV),
                  res1=res.to(DEV), r1=0.5)
         outs.append(out.cpu())
     L.lkgd_debug_set_gemm_splitk(1)
@@ -723,7 +725,7 @@ def test_gemm_split_k_on_256x320_tiles():
         L.lkgd_debug_set_wide_ksplit(ks)
         L.lkgd_debug_set_gemm_splitk(1 if ks else 0)
         out = torch.empty(Nimg * H * W, Cout, dtype=torch.float16, device=DEV)
-        _gemm_as(ops, dict(program=4, k_slices=ks or 1), _tokens(x0).to(DEV), pack_conv3x3(wc).to(DEV), out, M=Nimg * H * W, N=Cout,
+        _gemm_as(ops, dict(program=ops.GEMM_WIDE, k_slices=ks or 1), _tokens(x0).to(DEV), pack_conv3x3(wc).to(DEV), out, M=Nimg * H * W, N=Cout,
                  K=9 * (C0 + C1), a1=_tokens(x1).to(DEV), csplit=C0, bias=bc.to(DEV), mode=ops.A_CONV3X3, Cin=C0 + C1,
                  conv=(H, W, H, W, 1, 0))
         outs.append(out.cpu())
@@ -740,7 +742,7 @@ def test_gemm_split_k_on_256x320_tiles():
         b = torch.randn(N, generator=g)
         rows = torch.arange(0, M, 37)
         out = torch.empty(M, N, dtype=torch.float16, device=DEV)
-        _gemm_as(ops, dict(program=4, k_slices=slices), a.to(DEV), w.to(DEV), out, M=M, N=N, K=K, bias=b.to(DEV))
+        _gemm_as(ops, dict(program=ops.GEMM_WIDE, k_slices=slices), a.to(DEV), w.to(DEV), out, M=M, N=N, K=K, bias=b.to(DEV))
         _close(out.cpu()[rows], a[rows].float() @ w.float().T + b, what=f"auto split {M}x{N}x{K}")
 
 
@@ -770,7 +772,7 @@ def test_gemm_wide_rows_through_lds_match_direct_stores(tile_rows):
         assert torch.equal(outs[0], outs[1])
         return outs[1]
 
-    L.lkgd_debug_set_gemm_variant(4)
+    L.lkgd_debug_set_gemm_variant(ops.GEMM_WIDE)
     L.lkgd_debug_set_wide_tile_m(tile_rows)
     try:
         # plain, ragged M, residual + row bias, output = columns [64, 64+640) of a 768-wide buffer
@@ -780,7 +782,7 @@ def test_gemm_wide_rows_through_lds_match_direct_stores(tile_rows):
         res = _h(torch.randn(M, N, generator=g))
         table = _h(torch.randn(5, N, generator=g))
         idx = (torch.arange(M) // 300) % 5
-        form = dict(program=4, k_slices=1, tile_m=tile_rows, tile_n=320)
+        form = dict(program=ops.GEMM_WIDE, k_slices=1, tile_m=tile_rows, tile_n=320)
         out = both(lambda o: _gemm_as(ops, dict(form, lds_out=path["lds_out"]), a.to(DEV), w.to(DEV), o, M=M, N=N, K=K,
                                       bias=b.to(DEV), res1=res.to(DEV), r1=0.5, rowbias=table.to(DEV), rowmap=(300, 1, 1, 5, 0)),
                    (M + 3, 768), cols=(64, 64 + N))
@@ -850,7 +852,7 @@ def test_gemm_wide_256_column_tiles(tile_rows):
         assert torch.equal(outs[0], outs[1])
         return outs[1]
 
-    L.lkgd_debug_set_gemm_variant(4)
+    L.lkgd_debug_set_gemm_variant(ops.GEMM_WIDE)
     L.lkgd_debug_set_wide_tile_m(tile_rows)
     try:
         for M, N, K, d1 in ((256 * 5 + 77, 512, 320, 300), (256 * 9, 256, 1024, 40), (700, 768, 128, 256)):
@@ -859,7 +861,7 @@ def test_gemm_wide_256_column_tiles(tile_rows):
             res = _h(torch.randn(M, N, generator=g))
             table = _h(torch.randn(5, N, generator=g))
             idx = (torch.arange(M) // d1) % 5
-            form = dict(program=4, k_slices=1, tile_m=tile_rows, tile_n=256)
+            form = dict(program=ops.GEMM_WIDE, k_slices=1, tile_m=tile_rows, tile_n=256)
             out = both(lambda o: _gemm_as(ops, dict(form, lds_out=path["lds_out"]), a.to(DEV), w.to(DEV), o, M=M, N=N, K=K,
                                           bias=b.to(DEV), res1=res.to(DEV), r1=0.5, rowbias=table.to(DEV), rowmap=(d1, 1, 1, 5, 0)),
                        (M + 3, N + 128), cols=(64, 64 + N))
@@ -970,7 +972,7 @@ def test_attn_spatial_fewer_queries_than_keys(ops):
 
 def test_gemm_resident_weight_kernel():
     """lkgd_gemm_resw_kernel (K <= 320, N % 160 == 0: a 160-channel weight slab resident in LDS, waves independent): every
-    epilogue source combination the program is instantiated for (gemm_resw.hip::resw_has - the ones that fit its 96-register
+    epilogue source combination the program is instantiated for (gemm_plan.h::resw_has - the ones that fit its 96-register
     budget: all but both residuals together from K = 256, all pairs but rowbias + a residual below; the plan is asserted, and for
     the others that the forced variant falls back to the 128x128 program), ragged M (partial 32-row block, fewer blocks than waves, one row), 1 / 2 / 6 slabs,
     K = 64 .. 320, GEGLU with the 80 | 80 interleave - against fp32, and bitwise against the 256x320 kernel where both apply"""
@@ -1001,18 +1003,18 @@ def test_gemm_resident_weight_kernel():
                     kw.update(res2=r2.to(DEV), r2=0.3)
                     ref = ref + 0.3 * r2.float()
                 out = torch.full((M, N), float("nan"), dtype=torch.float16, device=DEV)
-                L.lkgd_debug_set_gemm_variant(6)
+                L.lkgd_debug_set_gemm_variant(ops.GEMM_RESW)
                 has = src <= 5 if K >= 256 else src in (0, 1, 2, 4, 6)
-                _gemm_as(ops, dict(program=6 if has else 1), ad, wd, out, M=M, N=N, K=K, bias=bias.to(DEV), s_acc=0.7, **kw)
+                _gemm_as(ops, dict(program=ops.GEMM_RESW if has else ops.GEMM_TILE128), ad, wd, out, M=M, N=N, K=K, bias=bias.to(DEV), s_acc=0.7, **kw)
                 _close(out, ref, what=f"resw {M}x{N}x{K} src {src}")
                 if N % 320 == 0 and K >= 64:
                     out4 = torch.full((M, N), float("nan"), dtype=torch.float16, device=DEV)
-                    L.lkgd_debug_set_gemm_variant(4)
+                    L.lkgd_debug_set_gemm_variant(ops.GEMM_WIDE)
                     ops.gemm(ad, wd, out4, M=M, N=N, K=K, bias=bias.to(DEV), s_acc=0.7, **kw)
                     assert torch.equal(out, out4), f"resw vs 256x320 {M}x{N}x{K} src {src}"
             out = torch.full((M, N), float("nan"), dtype=torch.float16, device=DEV)
-            L.lkgd_debug_set_gemm_variant(6)
-            _gemm_as(ops, dict(program=6), ad, wd, out, M=M, N=N, K=K)                     # no bias, no sources (QKV)
+            L.lkgd_debug_set_gemm_variant(ops.GEMM_RESW)
+            _gemm_as(ops, dict(program=ops.GEMM_RESW), ad, wd, out, M=M, N=N, K=K)                     # no bias, no sources (QKV)
             _close(out, acc, what=f"resw bare {M}x{N}x{K}")
         for M, C in ((700, 320), (32 * 300 + 5, 320), (40, 64)):
             a = _h(torch.randn(M, C, generator=g))
@@ -1024,11 +1026,11 @@ def test_gemm_resident_weight_kernel():
                 continue
             wp, bp, half = pack_geglu(w, b, half=80)
             out = torch.full((M, 4 * C), float("nan"), dtype=torch.float16, device=DEV)
-            L.lkgd_debug_set_gemm_variant(6)
-            _gemm_as(ops, dict(program=6), a.to(DEV), wp.to(DEV), out, M=M, N=8 * C, K=C, bias=bp.to(DEV), geglu=half)
+            L.lkgd_debug_set_gemm_variant(ops.GEMM_RESW)
+            _gemm_as(ops, dict(program=ops.GEMM_RESW), a.to(DEV), wp.to(DEV), out, M=M, N=8 * C, K=C, bias=bp.to(DEV), geglu=half)
             _close(out, hid * F.gelu(gate), what=f"resw geglu {M}x{C}")
             out4 = torch.full((M, 4 * C), float("nan"), dtype=torch.float16, device=DEV)
-            L.lkgd_debug_set_gemm_variant(4)
+            L.lkgd_debug_set_gemm_variant(ops.GEMM_WIDE)
             ops.gemm(a.to(DEV), wp.to(DEV), out4, M=M, N=8 * C, K=C, bias=bp.to(DEV), geglu=half)
             assert torch.equal(out, out4), f"resw geglu vs 256x320 {M}x{C}"
     finally:
@@ -1077,7 +1079,7 @@ def test_groupnorm_statistics_from_gemm_epilogues():
 
     # (small shapes: the 256x320 program is forced - the automatic dispatch would give 16 tiles to the 128x128 program,
     # which attaches nothing, as the last case checks)
-    _lib.lib().lkgd_debug_set_gemm_variant(4)
+    _lib.lib().lkgd_debug_set_gemm_variant(ops.GEMM_WIDE)
     # 3x3 conv 320 -> 640 with time-embedding row bias (ResnetBlock conv1 -> norm2)
     x = _h(torch.randn(T, 320, generator=g)).to(DEV)
     w = torch.randn(640, 320, 3, 3, generator=g) / (9 * 320) ** 0.5
@@ -1113,7 +1115,7 @@ def test_groupnorm_statistics_from_gemm_epilogues():
     a = _h(torch.randn(M, 640, generator=g)).to(DEV)
     wl = _h(torch.randn(640, 640, generator=g) / 640 ** 0.5).to(DEV)
     out5 = torch.empty(M, 640, dtype=torch.float16, device=DEV)
-    _lib.lib().lkgd_debug_set_gemm_variant(4)
+    _lib.lib().lkgd_debug_set_gemm_variant(ops.GEMM_WIDE)
     try:
         ops.gemm(a, wl, out5, M=M, N=640, K=640, res1=a, colstats=256)
     finally:

@@ -7,6 +7,9 @@ tests/test_host_cpu.py re-derives every stored plan from the stored fields witho
 
     python tools/gemm_census.py --write      regenerate the table on a GPU box (weights: the seeded real-width fixtures)
     python tools/gemm_census.py              print a summary of the stored table (no GPU needed)
+    python tools/gemm_census.py --dump-plans one line per stored signature x DUMP_CUS x forced variant x DUMP_KNOBS with the plan or
+                                             the error code (no GPU needed): run at two revisions, the outputs of a refactor of the
+                                             dispatcher are byte-equal
 
 Forwards (geometry of BASELINE configs[1]: CFG 2 x 14 frames x 72x128 latents):
     unet_2x14                     the full forward
@@ -35,7 +38,7 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if REPO not in sys.path:
     sys.path.insert(0, REPO)
 
-from lkgd_amd import _lib                     # noqa: E402
+from lkgd_amd import _lib, ops                # noqa: E402
 from lkgd_amd._lib import GemmDesc, GemmPlanInfo   # noqa: E402
 
 TABLE = os.path.join(REPO, "tests", "golden", "gemm_census.json")
@@ -113,9 +116,9 @@ def second_program(sig: dict, cus: int = PLAN_CUS):
         finally:
             lib.lkgd_debug_set_gemm_variant(0)
     if sig["fields"].get("geglu") == 80:
-        other = 6 if auto["program"] == 4 else 4
+        other = ops.GEMM_RESW if auto["program"] == ops.GEMM_WIDE else ops.GEMM_WIDE
         return (other, None) if forced(other)["program"] == other else (None, "geglu80")
-    for v in (1, 7, 2):                                  # 128x128 two-stage; where that IS the automatic program, another one
+    for v in (ops.GEMM_TILE128, ops.GEMM_MID, ops.GEMM_TILE256):      # where the first IS the automatic program, another one
         pl = forced(v)
         if (pl["program"], pl["k_slices"]) != (auto["program"], auto["k_slices"]):
             return v, None
@@ -457,7 +460,43 @@ def summary(rows) -> str:
     return "\n".join(lines)
 
 
+#: the compute-unit counts and the knob settings of --dump-plans: (label, setter, arguments, arguments that restore the default)
+DUMP_CUS = (64, 128, 256, 304)
+DUMP_KNOBS = (("auto", None, (), ()),
+              ("splitk=0", "lkgd_debug_set_gemm_splitk", (0,), (1,)),
+              ("wide_ksplit=2", "lkgd_debug_set_wide_ksplit", (2,), (0,)),
+              ("wide_ksplit=4", "lkgd_debug_set_wide_ksplit", (4,), (0,)),
+              ("wide_tile_m=192", "lkgd_debug_set_wide_tile_m", (192,), (0,)),
+              ("wide_tile_n=256", "lkgd_debug_set_wide_tile_n", (256,), (0,)),
+              ("wide_lds_out=0", "lkgd_debug_set_wide_lds_out", (0,), (-1,)),
+              ("mid_model forced 3", "lkgd_debug_set_mid_model", (0.0, 0.0, 0.0, 0.0, 3), (0.0, 0.0, 0.0, 0.0, 0)))
+
+
+def dump_plans(rows, out=sys.stdout):
+    """what lkgd_gemm_plan answers for every stored signature at every DUMP_CUS x forced variant 0..7 x DUMP_KNOBS, one line each"""
+    lib = _lib.lib()
+    info = GemmPlanInfo()
+    for i, e in enumerate(rows):
+        d = desc_from_signature(e)
+        for label, setter, on, off in DUMP_KNOBS:
+            if setter:
+                getattr(lib, setter)(*on)
+            try:
+                for variant in range(8):
+                    lib.lkgd_debug_set_gemm_variant(variant)
+                    for cus in DUMP_CUS:
+                        rc = lib.lkgd_gemm_plan(C.byref(d), cus, C.byref(info))
+                        got = " ".join(f"{n}={int(getattr(info, n))}" for n in PLAN_FIELDS) if rc == 0 else f"error {rc}"
+                        out.write(f"{i} cus={cus} variant={variant} {label}: {got}\n")
+            finally:
+                lib.lkgd_debug_set_gemm_variant(0)
+                if setter:
+                    getattr(lib, setter)(*off)
+
+
 def main(argv):
+    if "--dump-plans" in argv:
+        return dump_plans(load_table())
     if "--write" in argv:
         fp8_calls = []
         rows = reduce(record_all(build_c1_unet(), fp8_out=fp8_calls))

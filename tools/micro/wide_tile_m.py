@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """192- against 256-row tiles (and 256- against 320-column ones) of the 256x320 program on the unsliced shapes of sharded
-ranks and of the full forward: the per-tile cost factors behind gemm.hip::gemm_wide_form.  GPU box only."""
+ranks and of the full forward: the per-tile cost factors behind gemm_plan.cpp::gemm_wide_form.  GPU box only."""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import torch

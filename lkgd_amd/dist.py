@@ -128,6 +128,37 @@ def all_gather_into(buf: torch.Tensor, send: torch.Tensor, group=None) -> None:
     buf.copy_(hb)
 
 
+def new_frame_group(plan: ShardPlan):
+    """the process groups of the plan's frame slices, one per CFG half: every rank creates every group, in the same order.
+    Returns this rank's (ranks ``plan.frame_group_ranks()``); None when there is one frame slice and nothing to exchange."""
+    k = plan.frame_shards
+    groups = [dist.new_group(list(range(c * k, (c + 1) * k))) if k > 1 else None for c in range(plan.cfg_groups)]
+    return groups[plan.cfg_index]
+
+
+class NoiseGather:
+    """the one exchange per step over ALL ranks: every rank's noise prediction - ``entries`` batch entries of its ``f_local`` frames,
+    ``per_frame`` elements each - becomes the whole [cfg_groups * entries, num_frames * per_frame] tensor on every rank.  The slices
+    travel padded to ``f_max`` frames (an all-gather wants equal counts) and are compacted on arrival.  The buffers are made here,
+    once per clip; ``full`` is rewritten by every call."""
+
+    def __init__(self, plan: ShardPlan, entries: int, per_frame: int, dtype, device):
+        self.plan, self.entries, self.per_frame = plan, entries, per_frame
+        self.send = torch.zeros(entries, plan.f_max * per_frame, dtype=dtype, device=device)
+        self.buf = torch.empty(plan.world, entries, plan.f_max * per_frame, dtype=dtype, device=device)
+        self.full = torch.empty(plan.cfg_groups * entries, plan.num_frames * per_frame, dtype=dtype, device=device)
+
+    def __call__(self, local: torch.Tensor) -> torch.Tensor:
+        plan, n, per = self.plan, self.entries, self.per_frame
+        self.send[:, :plan.f_local * per].copy_(local.reshape(n, plan.f_local * per))
+        all_gather_into(self.buf.view(-1), self.send.view(-1))
+        for r in range(plan.world):
+            ci, si = divmod(r, plan.frame_shards)
+            k, fs = plan.splits[si], sum(plan.splits[:si])
+            self.full[ci * n:(ci + 1) * n, fs * per:(fs + k) * per].copy_(self.buf[r, :, :k * per])
+        return self.full
+
+
 def _step(f) -> None:
     """run a host-side exchange step now; under lkgd_amd.replay recording also make it part of the plan"""
     from . import replay

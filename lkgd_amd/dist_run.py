@@ -8,6 +8,10 @@ Exchange points per UNet forward on a rank (frame_shards > 1 only)
 and once per step, over ALL ranks, the all-gather of the noise prediction [cfg*F*HW, 4] (1 MB) before the replicated
 CFG-combine + Euler update.  With 2 GPUs (pure CFG-parallel) only the last exchange exists.
 
+The SVD loop itself is not here: ``DistDenoiser.denoise`` runs ``StableVideoDiffusionPipeline.denoise`` (lkgd_amd/pipeline.py) with
+this rank's ``Placement``.  ``DistDiTDenoiser`` keeps the CogVideoX step arithmetic; both share lkgd_amd/dist.py's group builder
+and noise gather.
+
 Correctness notes
   * every rank keeps the full latents (replicated, 1 MB) and the UNet weights; activations are sharded;
   * the temporal cross-attention context of diffusers 0.27 interleaves the CFG halves' embeddings over pixels
@@ -26,10 +30,12 @@ from typing import Optional
 import torch
 import torch.distributed as dist
 
-from . import ops, replay
+from . import replay
 from ._lib import LkgdHipError
-from .dist import (ShardPlan, all_gather_into, allreduce_sums, exchange_halo, exchange_with_mirror_start, frames_to_pixels,
-                   gather_boundary_frames_and_sums, gather_frames, make_plan, pixels_to_frames, pixels_to_frames_start)
+from .dist import (NoiseGather, ShardPlan, allreduce_sums, exchange_halo, exchange_with_mirror_start, frames_to_pixels,
+                   gather_boundary_frames_and_sums, gather_frames, make_plan, new_frame_group, pixels_to_frames,
+                   pixels_to_frames_start)
+from .pipeline import Placement
 
 
 class ShardInfo:
@@ -138,6 +144,31 @@ class ShardInfo:
         return buf
 
 
+class _RankPlacement(Placement):
+    """a rank's answers to ``StableVideoDiffusionPipeline.denoise``; the replay switch and arenas are the runner's"""
+
+    def __init__(self, runner: "DistDenoiser"):
+        super().__init__(runner)
+        self.runner, self.plan, self.shard = runner, runner.plan, runner.shard
+
+    def slice(self, cfg: int, B: int, F: int):
+        # batch entries of the UNet batch are ordered (CFG half, clip): [u_x, u_y, c_x, c_y] for the [start, end] pair of the
+        # trans pipelines (pipeline_stable_video_diffusion_trans.py:549).  A CFG-parallel rank holds the B clips of ITS half -
+        # the pairs the `patch` joint hooks couple (masks [0,1,0,1], utils/util.py:600-606) live on one rank, so the joint
+        # attention needs no exchange of its own - and, under frame sharding, the same frame slice of every one of them.
+        plan = self.plan
+        b_local, e0 = (B, plan.cfg_index * B) if plan.cfg_groups == 2 else (cfg * B, 0)
+        return b_local, e0, plan.f_local, plan.f0
+
+    def noise_gather(self, b_local: int, HW: int, device):
+        gather = NoiseGather(self.plan, b_local, HW * 4, torch.float16, device)
+        return lambda noise_local: gather(noise_local).view(-1, 4)           # [cfg*B*F*HW, 4] on every rank
+
+    def samples_events(self, i: int) -> bool:
+        stride = self.runner.event_stride
+        return i % stride == stride // 2
+
+
 class DistDenoiser:
     def __init__(self, pipe, world: int, rank: int, num_frames: int, cfg: bool = True):
         if not dist.is_initialized():
@@ -152,13 +183,7 @@ class DistDenoiser:
         flip = bool(info and info.get("args", {}).get("flip", False)) and not fsm
         sharded = world > (2 if cfg else 1)
         self.plan = make_plan(world, rank, num_frames, cfg, frame_unit=2 if (fsm and sharded) else 1, symmetric=flip and sharded)
-        # every rank creates every group, in the same order
-        self.frame_group = None
-        for c in range(self.plan.cfg_groups):
-            ranks = list(range(c * self.plan.frame_shards, (c + 1) * self.plan.frame_shards))
-            g = dist.new_group(ranks) if self.plan.frame_shards > 1 else None
-            if c == self.plan.cfg_index:
-                self.frame_group = g
+        self.frame_group = new_frame_group(self.plan)
         self.shard = ShardInfo(self.plan, self.frame_group)
         #: replay the step's UNet forward from a recorded launch list (lkgd_amd/replay.py); a frame-sharded rank has
         #: only ~1/8 of the device work per forward and would otherwise wait on the Python module walk
@@ -175,103 +200,24 @@ class DistDenoiser:
                 max_guidance_scale: float = 3.0, domain_features: Optional[torch.Tensor] = None,
                 flow_features: Optional[torch.Tensor] = None, controlnet_condition: Optional[torch.Tensor] = None,
                 controlnet_cond_scale: float = 1.0) -> torch.Tensor:
-        """``pipeline.denoise`` over the ranks.  ``domain_features`` / ``flow_features`` (the LKGD UNet): the fuse is
-        replicated (2 MFLOP) and every rank holds the fused embedding of BOTH CFG halves.  ``controlnet_condition``
+        """``pipeline.denoise`` over the ranks: the plan checks, then that loop with this rank's placement.  ``domain_features`` /
+        ``flow_features`` (the LKGD UNet): the fuse is replicated (2 MFLOP) and every rank holds the fused embedding of BOTH CFG
+        halves.  ``controlnet_condition``
         [cfg * batch, F, 3, 8h, 8w] (pipeline_stable_video_diffusion_controlnet.py:582-607): every rank embeds the condition frames of
         ITS slice once per clip and runs the ControlNet-SVD encoder on its tokens before the UNet; the residuals are local
         token matrices, so nothing new crosses the links beyond the encoder's own temporal exchanges."""
-        pipe, plan = self.pipe, self.plan
-        unet, sch = pipe.unet, pipe.scheduler
-        dev = unet.device
-        B, F, _, H, W = latents.shape
+        plan = self.plan
+        B, F = latents.shape[:2]
         cfg = 2 if max_guidance_scale > 1 else 1
         if cfg != plan.cfg_groups and not (cfg == 2 and plan.cfg_groups == 1):
             raise LkgdHipError("shard plan was built for classifier-free guidance; got guidance <= 1")
         if F != plan.num_frames:
             raise LkgdHipError(f"the shard plan was built for {plan.num_frames} frames, the latents carry {F}")
-        HW = H * W
-        latents = latents.to(dev).contiguous()
-        image_latents = image_latents.to(device=dev, dtype=torch.float16).contiguous()
-        sch.set_timesteps(num_inference_steps, device=None)
-        guidance = torch.linspace(min_guidance_scale, max_guidance_scale, F, dtype=torch.float32).to(dev)
-        enc = image_embeddings.to(dev)
-        if domain_features is not None:
-            enc = unet.fused_embedding(enc, domain_features.to(dev), flow_features.to(dev))
-        ids = added_time_ids.to(dev)
-        vpred = sch.config.prediction_type == "v_prediction"
-        from . import patch as _patch
-        _patch.set_joint_attention(unet, enable=True)           # reference :555 (no-op unless the model is patched)
-        fl, f0, fmax = plan.f_local, plan.f0, plan.f_max
-        # batch entries of the UNet batch are ordered (CFG half, clip): [u_x, u_y, c_x, c_y] for the [start, end] pair of the
-        # trans pipelines (pipeline_stable_video_diffusion_trans.py:549).  A CFG-parallel rank holds the B clips of ITS half -
-        # the pairs the `patch` joint hooks couple (masks [0,1,0,1], utils/util.py:600-606) live on one rank, so the joint
-        # attention needs no exchange of its own - and, under frame sharding, the same frame slice of every one of them.
-        if plan.cfg_groups == 2:
-            b_local, e0 = B, plan.cfg_index * B
-        else:
-            b_local, e0 = cfg * B, 0
-        ids_local = ids[e0:e0 + b_local]
-        self.shard.set_entries(b_local)
-        send = torch.zeros(b_local, fmax * HW, 4, dtype=torch.float16, device=dev)
-        buf = torch.empty(plan.world, b_local, fmax * HW, 4, dtype=torch.float16, device=dev)
-        noise_full = torch.empty(cfg * B * F * HW, 4, dtype=torch.float16, device=dev)
-        # step-invariant addresses for everything the forward reads, so its launch list can be replayed
-        tok = torch.empty(cfg * B * F * HW, 8, dtype=torch.float16, device=dev)
-        t_dev = torch.zeros(b_local, dtype=torch.float32, device=dev)
-        ids_local = ids_local.to(torch.float32).contiguous()
-        enc = enc.to(torch.float16).contiguous()
-        if plan.frame_shards == 1:
-            tok_local, pick = tok[e0 * F * HW:(e0 + b_local) * F * HW], None
-        elif b_local == 1:
-            r0 = (e0 * F + f0) * HW
-            tok_local, pick = tok[r0:r0 + fl * HW], None
-        else:
-            tok_local = torch.empty(b_local * fl * HW, 8, dtype=torch.float16, device=dev)
-            pick = (tok_local.reshape(b_local, fl, HW, 8), tok.reshape(cfg * B, F, HW, 8)[e0:e0 + b_local, f0:f0 + fl])
-        ctrl_local = None
-        if controlnet_condition is not None:
-            if getattr(pipe, "controlnet", None) is None:
-                raise LkgdHipError("controlnet_condition given but the pipeline has no controlnet")
-            if controlnet_condition.shape[0] != cfg * B or controlnet_condition.shape[1] != F:
-                raise ValueError("controlnet_condition must be [cfg * batch, frames, 3, 8h, 8w] (uncond entries first)")
-            cc = controlnet_condition[e0:e0 + b_local]          # the rank's batch entries (its CFG half's clips)
-            ctrl_local = cc[:, f0:f0 + fl].to(device=dev, dtype=torch.float16).contiguous()
-            pipe.controlnet.prepare()
-            pipe.controlnet._cond_tokens(ctrl_local, b_local, fl, H, W)     # once per clip, outside the recorded forward
-
-        def forward():
-            down = mid = None
-            if ctrl_local is not None:
-                down, mid, _ = pipe.controlnet.forward_tokens(tok_local, b_local, fl, H, W, t_dev, enc, ids_local, ctrl_local,
-                                                              controlnet_cond_scale, shard=self.shard)
-            return unet.forward_tokens(tok_local, b_local, fl, H, W, t_dev, enc, ids_local, down, mid, shard=self.shard)[0]
-        events_all = ops.GEMM_EVENTS
-        try:
-            # the first step runs for real and is recorded, the others replay it; the plan's activations are freed on the way out
-            with replay.Replayed(self._arenas, dev, lambda: (b_local, fl, H, W, ctrl_local is not None, id(unet._pk)), forward,
-                                 enabled=self.use_replay) as step_forward:
-                for i, t in enumerate(sch.timesteps_host):
-                    sigma, sigma_next = sch.sigmas_host[i], sch.sigmas_host[i + 1]
-                    ops.GEMM_EVENTS = events_all if (events_all is not None and i % self.event_stride == self.event_stride // 2) else None
-                    ops.prepare_unet_input(latents, image_latents, cfg, sigma, out=tok)     # [cfg*F*HW, 8], replicated
-                    if pick is not None:
-                        pick[0].copy_(pick[1])
-                    t_dev.fill_(float(t))
-                    noise_local = step_forward(ops.GEMM_EVENTS)
-                    # ---- exchange the noise prediction over all ranks (padded equal counts), compact, replicate the update
-                    send[:, :fl * HW].copy_(noise_local.reshape(b_local, fl * HW, 4))
-                    all_gather_into(buf.reshape(-1, 4), send.reshape(-1, 4))
-                    nf = noise_full.reshape(cfg * B, F * HW, 4)
-                    for r in range(plan.world):
-                        ci, si = divmod(r, plan.frame_shards)
-                        n, fs = plan.splits[si], sum(plan.splits[:si])
-                        er = ci * b_local if plan.cfg_groups == 2 else 0
-                        nf[er:er + b_local, fs * HW:(fs + n) * HW].copy_(buf[r, :, :n * HW])
-                    ops.cfg_euler_step(noise_full, latents, guidance, cfg, sigma, sigma_next, v_prediction=vpred)
-        finally:          # whatever ended the loop, the bench's event list is restored
-            ops.GEMM_EVENTS = events_all
-        sch._step_index = num_inference_steps
-        return latents
+        place = _RankPlacement(self)
+        self.shard.set_entries(place.slice(cfg, B, F)[0])
+        return self.pipe.denoise(latents, image_latents, image_embeddings, added_time_ids, num_inference_steps, min_guidance_scale,
+                                 max_guidance_scale, domain_features, flow_features, controlnet_condition=controlnet_condition,
+                                 controlnet_cond_scale=controlnet_cond_scale, _placement=place)
 
 
 class DistDiTDenoiser:
@@ -299,12 +245,7 @@ class DistDiTDenoiser:
             raise LkgdHipError("torch.distributed is not initialised")
         self.transformer, self.scheduler = transformer, scheduler
         self.plan = make_plan(world, rank, latent_frames, cfg)
-        self.frame_group = None
-        for c in range(self.plan.cfg_groups):
-            ranks = list(range(c * self.plan.frame_shards, (c + 1) * self.plan.frame_shards))
-            g = dist.new_group(ranks) if self.plan.frame_shards > 1 else None
-            if c == self.plan.cfg_index:
-                self.frame_group = g
+        self.frame_group = new_frame_group(self.plan)
         self.shard = ShardInfo(self.plan, self.frame_group)
 
     @torch.no_grad()
@@ -328,12 +269,13 @@ class DistDiTDenoiser:
         text = tr.fused_text(prompt_embeds.to(dev), domain_features.to(dev), flow_features.to(dev))      # replicated, once per clip
         latents = latents.to(device=dev, dtype=torch.float16)
         img = image_latents.to(device=dev, dtype=torch.float16)
-        fl, f0, fmax = plan.f_local, plan.f0, plan.f_max
+        fl, f0 = plan.f_local, plan.f0
         co = tr.config.out_channels
-        per = co * H * W
-        send = torch.zeros(fmax * per, dtype=torch.float16, device=dev)
-        buf = torch.empty(plan.world * fmax * per, dtype=torch.float16, device=dev)
-        noise_full = torch.empty(cfg, F, co, H, W, dtype=torch.float16, device=dev)
+        if plan.cfg_groups == 2:       # a rank holds one batch entry (its CFG half) of its frames
+            gather = NoiseGather(plan, 1, co * H * W, torch.float16, dev)
+            noise_full = gather.full.view(cfg, F, co, H, W)
+        else:
+            noise_full = torch.empty(cfg, F, co, H, W, dtype=torch.float16, device=dev)
         sharded = plan.frame_shards > 1
         tc = tr.config
         rope_all = rope_loc = None
@@ -349,12 +291,7 @@ class DistDiTDenoiser:
                 x = torch.cat([latents[:, f0:f0 + fl], img[:, f0:f0 + fl]], dim=2)
                 out = tr.forward_tokens(x, text[plan.cfg_index:plan.cfg_index + 1], float(t), shard=self.shard if sharded else None,
                                         image_rotary_emb=rope_loc)
-                send[:fl * per].copy_(out.reshape(-1))
-                all_gather_into(buf, send)
-                for r in range(plan.world):
-                    ci, si = divmod(r, plan.frame_shards)
-                    n, fs = plan.splits[si], sum(plan.splits[:si])
-                    noise_full[ci, fs:fs + n].copy_(buf[r * fmax * per:r * fmax * per + n * per].reshape(n, co, H, W))
+                gather(out)            # -> noise_full
             else:                      # one rank: the whole CFG batch, no exchange
                 x = torch.cat([latents] * cfg)
                 x = torch.cat([x, torch.cat([img] * cfg)], dim=2)

@@ -72,6 +72,37 @@ def smooth_chunks(total_frames: int, num_frames: int, rng=np.random):
     return chunks
 
 
+class Placement:
+    """What ``denoise`` asks about the process it runs in.  The default: one process holds every batch entry and frame; a rank of a
+    sharded run (lkgd_amd/dist_run.py) answers for its CFG half and frame slice.  ``owner`` (the pipeline; there the rank's runner)
+    says whether the forward is replayed and holds its arenas."""
+    shard = None             # handed to ``forward_tokens``
+    samples_events = None    # f(i): does Euler step i sample ops.GEMM_EVENTS; None: every step, the global is left alone
+
+    def __init__(self, owner):
+        self.arenas, self.use_replay = owner._arenas, owner.use_replay
+
+    def slice(self, cfg: int, B: int, F: int):
+        """(b_local, e0, fl, f0): batch entries [e0, e0 + b_local) of the cfg * B, frames [f0, f0 + fl) of each of them"""
+        return cfg * B, 0, F, 0
+
+    def token_rows(self, tok: torch.Tensor, F: int, HW: int, b_local: int, e0: int, fl: int, f0: int):
+        """(rows, refresh): this process's rows (entry, frame, pixel) of the static token buffer - a view of ``tok`` where they are
+        contiguous in it (refresh None), else a buffer of their own that ``refresh()`` fills from ``tok``"""
+        if fl == F:
+            return tok[e0 * F * HW:(e0 + b_local) * F * HW], None
+        if b_local == 1:
+            r0 = (e0 * F + f0) * HW
+            return tok[r0:r0 + fl * HW], None
+        rows = torch.empty(b_local * fl * HW, 8, dtype=tok.dtype, device=tok.device)
+        dst, src = rows.reshape(b_local, fl, HW, 8), tok.reshape(-1, F, HW, 8)[e0:e0 + b_local, f0:f0 + fl]
+        return rows, lambda: dst.copy_(src)
+
+    def noise_gather(self, b_local: int, HW: int, device):
+        """f(noise tokens of this process) -> the noise tokens [cfg*B*F*HW, 4] of the whole clip; None: they are the same"""
+        return None
+
+
 class StableVideoDiffusionPipeline:
     model_cpu_offload_seq = "image_encoder->unet->vae"
     _callback_tensor_inputs = ["latents"]
@@ -294,7 +325,8 @@ class StableVideoDiffusionPipeline:
                 flow_features: Optional[torch.Tensor] = None, callback_on_step_end: Optional[Callable] = None,
                 callback_on_step_end_tensor_inputs: List[str] = ["latents"],
                 controlnet_condition: Optional[torch.Tensor] = None, controlnet_cond_scale: float = 1.0,
-                start_step: int = 0, direct_fusion: bool = False, controlnet_scale: float = 1.0) -> torch.Tensor:
+                start_step: int = 0, direct_fusion: bool = False, controlnet_scale: float = 1.0,
+                _placement: Optional[Placement] = None) -> torch.Tensor:
         """Reference loop :503-640.  ``latents`` [B,F,4,h,w] already scaled by init_noise_sigma (fp16 or fp32, updated
         in place and returned); ``image_latents`` [cfg*B,F,4,h,w] fp16; ``image_embeddings`` [cfg*B,1,1024].
         ``controlnet_condition`` [cfg*B,F,3,8h,8w] (already preprocessed and duplicated for CFG) runs ``self.controlnet``
@@ -303,11 +335,17 @@ class StableVideoDiffusionPipeline:
         Euler steps and their callbacks (:571-574); ``controlnet_scale`` multiplies every residual on top of
         ``controlnet_cond_scale`` (:594-598), folded into the zero-convolution epilogue; ``direct_fusion`` switches the joint
         hooks off (:568) and fuses clip b with the frame-reversed clip b + B/2 through their x0 once per step (:637-667,
-        lkgd_cfg_fusion_euler_step)."""
+        lkgd_cfg_fusion_euler_step).
+        ``_placement`` (private; lkgd_amd.dist_run.DistDenoiser passes its rank's): the loop of a sharded run is this one - the
+        rank feeds the forward its batch entries and frames of the replicated token buffer, the noise prediction is gathered
+        over the ranks and the update is replicated.  All tensor arguments are still those of the WHOLE clip."""
         unet, sch = self.unet, self.scheduler
         dev = unet.device
         B, F, _, H, W = latents.shape
+        HW = H * W
         cfg = 2 if max_guidance_scale > 1 else 1
+        place = _placement if _placement is not None else Placement(self)
+        b_local, e0, fl, f0 = place.slice(cfg, B, F)
         if image_latents.shape[0] != cfg * B or image_embeddings.shape[0] != cfg * B:
             raise ValueError("image_latents / image_embeddings must carry cfg*batch entries (uncond first)")
         if direct_fusion and B % 2:
@@ -334,52 +372,70 @@ class StableVideoDiffusionPipeline:
         if controlnet_condition is not None:
             if self.controlnet is None:
                 raise LkgdHipError("controlnet_condition given but the pipeline has no controlnet")
-            if controlnet_condition.shape[0] != cfg * B:
-                raise ValueError("controlnet_condition must carry cfg*batch entries")
-            ctrl = controlnet_condition.to(device=dev, dtype=torch.float16).contiguous()
-        graph = self._graphed_forward(cfg * B, F, H, W, enc, ids) if (self.use_hip_graph and ctrl is None) else None
-        forward_static = None
+            if controlnet_condition.shape[0] != cfg * B or controlnet_condition.shape[1] != F:
+                raise ValueError("controlnet_condition must be [cfg * batch, frames, 3, 8h, 8w] (uncond entries first)")
+            # this process's entries and frames; the whole tensor stays the caller's object, by which the ControlNet's cache knows it
+            ctrl = controlnet_condition if (b_local, fl) == (cfg * B, F) else controlnet_condition[e0:e0 + b_local, f0:f0 + fl]
+            ctrl = ctrl.to(device=dev, dtype=torch.float16).contiguous()
+        one_process = _placement is None           # the HIP graph is a one-process path
+        graph = self._graphed_forward(cfg * B, F, H, W, enc, ids) if (self.use_hip_graph and ctrl is None and one_process) else None
+        forward_static = gather = sampled = None
         if graph is None:
-            tok_buf = torch.empty(cfg * B * F * H * W, 8, dtype=torch.float16, device=dev)
-            t_dev = torch.zeros(cfg * B, dtype=torch.float32, device=dev)
-            enc_r, ids_r = enc.to(torch.float16).contiguous(), ids.to(torch.float32).contiguous()
+            # step-invariant addresses for everything the forward reads, so its launch list can be replayed.  The token buffer
+            # holds the whole clip (every process prepares it from its replicated latents); the forward reads this process's rows
+            tok_buf = torch.empty(cfg * B * F * HW, 8, dtype=torch.float16, device=dev)
+            tok_rows, refresh_rows = place.token_rows(tok_buf, F, HW, b_local, e0, fl, f0)
+            t_dev = torch.zeros(b_local, dtype=torch.float32, device=dev)
+            enc_r, ids_r = enc.to(torch.float16).contiguous(), ids[e0:e0 + b_local].to(torch.float32).contiguous()
+            gather, sampled = place.noise_gather(b_local, HW, dev), place.samples_events
             if ctrl is not None:
                 self.controlnet.prepare()
-                self.controlnet._cond_tokens(ctrl, cfg * B, F, H, W)       # once per clip, outside the recorded forward
+                self.controlnet._cond_tokens(ctrl, b_local, fl, H, W)      # once per clip, outside the recorded forward
 
             def forward_static():      # residuals stay channels-last token matrices between the two models
                 down = mid = None
                 if ctrl is not None:
-                    down, mid, _ = self.controlnet.forward_tokens(tok_buf, cfg * B, F, H, W, t_dev, enc_r, ids_r, ctrl,
-                                                                  ctrl_scale)
-                return unet.forward_tokens(tok_buf, cfg * B, F, H, W, t_dev, enc_r, ids_r, down, mid)[0]
+                    down, mid, _ = self.controlnet.forward_tokens(tok_rows, b_local, fl, H, W, t_dev, enc_r, ids_r, ctrl,
+                                                                  ctrl_scale, shard=place.shard)
+                return unet.forward_tokens(tok_rows, b_local, fl, H, W, t_dev, enc_r, ids_r, down, mid, shard=place.shard)[0]
         # The step's forward is shape-static over the Euler steps: the first step runs for real and is RECORDED as a flat list of
         # C-ABI launches (lkgd_amd/replay.py), the other 24 replay it between in-place updates of its inputs (token buffer,
         # timestep) - bit-identical, and the Python module walk (64 ms of host time per forward against 90 ms of device time)
         # stops leaving the queue dry at the 18x32 / 9x16 levels: +1.1 % frames/s on one GPU (profiles/r05_bench_pair_replay.txt).
         # LKGD_NO_REPLAY=1 walks the modules every step, on the same static inputs.
-        with _replay.Replayed(self._arenas, dev, lambda: (cfg * B, F, H, W, ctrl is not None, id(unet._pk)), forward_static,
-                              enabled=self.use_replay) as forward:
-            def step(latents, t, sigma, sigma_next):
-                if graph is not None:
-                    ops.prepare_unet_input(latents, image_latents, cfg, sigma, out=graph.tok)
-                    noise_tok = graph.run(t)
-                else:
-                    ops.prepare_unet_input(latents, image_latents, cfg, sigma, out=tok_buf)
-                    t_dev.fill_(float(t))
-                    noise_tok = forward(ops.GEMM_EVENTS)
-                if direct_fusion:
-                    ops.cfg_fusion_euler_step(noise_tok, latents, guidance_dev, fusion_w, cfg, sigma, sigma_next,
-                                              v_prediction=vpred)
-                else:
-                    ops.cfg_euler_step(noise_tok, latents, guidance_dev, cfg, sigma, sigma_next, v_prediction=vpred)
-            return self._euler_loop(latents, step, num_inference_steps, start_step, callback_on_step_end,
-                                    callback_on_step_end_tensor_inputs)
+        events_all = ops.GEMM_EVENTS
+        try:
+            with _replay.Replayed(place.arenas, dev, lambda: (b_local, fl, H, W, ctrl is not None, id(unet._pk)), forward_static,
+                                  enabled=place.use_replay) as forward:
+                def step(i, latents, t, sigma, sigma_next):
+                    if graph is not None:
+                        ops.prepare_unet_input(latents, image_latents, cfg, sigma, out=graph.tok)
+                        noise_tok = graph.run(t)
+                    else:
+                        if sampled is not None:    # the module global: the eager walk and the recording step read it in ops
+                            ops.GEMM_EVENTS = events_all if (events_all is not None and sampled(i)) else None
+                        ops.prepare_unet_input(latents, image_latents, cfg, sigma, out=tok_buf)     # replicated
+                        if refresh_rows is not None:
+                            refresh_rows()
+                        t_dev.fill_(float(t))
+                        noise_tok = forward(ops.GEMM_EVENTS)
+                        if gather is not None:     # over all ranks; the update below is replicated
+                            noise_tok = gather(noise_tok)
+                    if direct_fusion:
+                        ops.cfg_fusion_euler_step(noise_tok, latents, guidance_dev, fusion_w, cfg, sigma, sigma_next,
+                                                  v_prediction=vpred)
+                    else:
+                        ops.cfg_euler_step(noise_tok, latents, guidance_dev, cfg, sigma, sigma_next, v_prediction=vpred)
+                return self._euler_loop(latents, step, num_inference_steps, start_step, callback_on_step_end,
+                                        callback_on_step_end_tensor_inputs)
+        finally:          # whatever ended the loop, the caller's event list is back
+            if sampled is not None:
+                ops.GEMM_EVENTS = events_all
 
     def _euler_loop(self, latents: torch.Tensor, step: Callable, num_inference_steps: int, start_step: int,
                     callback_on_step_end: Optional[Callable], callback_on_step_end_tensor_inputs: List[str]) -> torch.Tensor:
-        """the skeleton of every denoising loop here (reference :545-640): ``step(latents, t, sigma, sigma_next)`` takes one Euler
-        step in place; around it the timestep table, the ``start_step`` skip (trans_controlnet :571-574: skipped steps run
+        """the skeleton of every denoising loop here (reference :545-640): ``step(i, latents, t, sigma, sigma_next)`` takes Euler
+        step ``i`` in place; around it the timestep table, the ``start_step`` skip (trans_controlnet :571-574: skipped steps run
         nothing, not even the callback), the roctx range (LKGD_ROCTX=1), the device timers (LKGD_STEP_TIMERS=1: ms per Euler
         step) and the callback, whose returned ``latents`` replace the loop's"""
         sch = self.scheduler
@@ -392,7 +448,7 @@ class StableVideoDiffusionPipeline:
                 continue
             _trace.push(f"euler_step_{i}")
             t_ev = timers.start() if timers is not None else None
-            step(latents, t, sch.sigmas_host[i], sch.sigmas_host[i + 1])
+            step(i, latents, t, sch.sigmas_host[i], sch.sigmas_host[i + 1])
             if timers is not None:
                 timers.stop(t_ev)
             _trace.pop()
@@ -686,7 +742,7 @@ class StableVideoDiffusionPipelineSmooth(StableVideoDiffusionPipeline):
         with _replay.Replayed(self._arenas, dev, lambda: ("smooth", 2 * cfg, nf, H, W, id(unet._pk)),
                               lambda: unet.forward_tokens(tok_buf, 2 * cfg, nf, H, W, t_dev, enc, ids)[0],
                               enabled=self.use_replay) as full_window:
-            def step(latents, t, sigma, sigma_next):
+            def step(_i, latents, t, sigma, sigma_next):
                 for f0, n in smooth_chunks(T, nf):
                     tok = ops.window_prepare_input(latents, image_latents, f0, n, cfg, sigma, out=tok_buf)
                     enc[2].copy_(emb[f0])

@@ -7,7 +7,6 @@ import os
 
 import pytest
 import torch
-import torch.multiprocessing as mp
 import torch.nn.functional as F
 from safetensors.torch import load_file
 
@@ -323,7 +322,7 @@ def _worker_rope_dit(rank, world, port, q):
     rows); world 4: CFG halves x latent frames (2, 1) - a rank rotates its local q and k with the rows of its frames of the
     tables before the K gather, and adds its rows of the learned table"""
     import torch.distributed as dist
-    from test_dist_gpu import _ship
+    from dist_support import ship
     os.environ["MASTER_ADDR"], os.environ["MASTER_PORT"] = "127.0.0.1", str(port)
     torch.set_num_threads(max(1, int(os.environ.get("LKGD_TEST_HOST_CPUS", os.cpu_count() or 8)) // world))
     dist.init_process_group("gloo", rank=rank, world_size=world)
@@ -344,7 +343,7 @@ def _worker_rope_dit(rank, world, port, q):
         if rank == 0:
             res["ref"] = pc.denoise(m, pc.CogVideoXDDIMScheduler(), lat.to(dev), img.to(dev), pe.to(dev), dom.to(dev), flow.to(dev),
                                     3, gs, True).float().cpu()
-        q.put(_ship(res))
+        q.put(ship(res))
     finally:
         dist.destroy_process_group()
 
@@ -354,17 +353,8 @@ def _worker_rope_dit(rank, world, port, q):
 def test_sharded_rotary_dit_loop_equals_single_process(world):
     """against the single-process loop at test_sharded_dit_loop_equals_single_process's bound; world 4 is the one whose ranks hold
     frame slices"""
-    from test_dist_gpu import _collect, _free_port
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    port = _free_port()
-    procs = [ctx.Process(target=_worker_rope_dit, args=(r, world, port, q)) for r in range(world)]
-    for p in procs:
-        p.start()
-    results = _collect(procs, q, world)
-    for p in procs:
-        p.join(60)
-        assert p.exitcode == 0
+    from dist_support import run_world
+    results = run_world(_worker_rope_dit, world)
     ref = [r["ref"] for r in results if "ref" in r][0]
     assert torch.isfinite(ref).all()
     for r in results:

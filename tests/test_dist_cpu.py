@@ -2,13 +2,12 @@
 all-gather of frame slices, the GroupNorm partial-sum all-reduce.  The kernels themselves are covered by -m gpu tests
 (tests/test_dist_gpu.py runs the sharded UNet with two ranks on one GPU)."""
 import os
-import socket
 
 import pytest
 import torch
 import torch.distributed as dist
-import torch.multiprocessing as mp
 
+from dist_support import run_world
 from lkgd_amd.dist import allreduce_sums, gather_frames, make_plan, split_frames
 
 
@@ -52,14 +51,6 @@ def test_split_and_plans():
     sh = ShardInfo(make_plan(2, 1, 6, cfg=True), None, entries=2)
     x = torch.arange(2 * 6 * 4 * 3, dtype=torch.float32).reshape(-1, 3)
     assert sh.gather(x) is x and sh.to_pixels(x, 4) is x and sh.to_frames(x, 4) is x and (sh.b0, sh.B_total) == (2, 4)
-
-
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    port = s.getsockname()[1]
-    s.close()
-    return port
 
 
 def _worker(rank, world, port, frames, q):
@@ -177,31 +168,13 @@ def _worker(rank, world, port, frames, q):
 
 @pytest.mark.parametrize("frames", [4, 5, 14, 3])
 def test_uneven_frame_gather_world2(frames):
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    port = _free_port()
-    procs = [ctx.Process(target=_worker, args=(r, 2, port, frames, q)) for r in range(2)]
-    for p in procs:
-        p.start()
-    for p in procs:
-        p.join(120)
-        assert p.exitcode == 0
-    res = sorted(q.get(timeout=10) for _ in range(2))
+    res = sorted(run_world(_worker, 2, frames))
     assert res == [(0, True), (1, True)]
 
 
 def test_frame_exchanges_world4():
     """14 frames over 4 shards (4, 4, 3, 3): interior ranks have a neighbour on both sides of the Conv3d halo"""
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    port = _free_port()
-    procs = [ctx.Process(target=_worker, args=(r, 4, port, 14, q)) for r in range(4)]
-    for p in procs:
-        p.start()
-    for p in procs:
-        p.join(180)
-        assert p.exitcode == 0
-    res = sorted(q.get(timeout=10) for _ in range(4))
+    res = sorted(run_world(_worker, 4, 14))
     assert res == [(r, True) for r in range(4)]
 
 
@@ -235,6 +208,44 @@ def test_thread_world_collectives_match_their_definitions():
         want = torch.cat([(torch.arange(14, dtype=torch.float32).reshape(7, 2) + 100 * (base + p))[start:start + rows[si]]
                           for p in range(4)])
         assert torch.equal(out, want)
+
+
+@pytest.mark.parametrize("per_frame", [6 * 4, 16 * 2 * 3], ids=["HWx4", "CxHxW"])
+@pytest.mark.parametrize("entries", [1, 2])
+@pytest.mark.parametrize("world,cfg,frames", [(2, True, 3),       # CFG halves only: frame_shards == 1
+                                              (4, True, 5),       # CFG x (3, 2): the shorter slice travels padded
+                                              (4, False, 6),      # cfg_groups == 1 with shards (2, 2, 1, 1)
+                                              (8, True, 14)])     # CFG x (4, 4, 3, 3)
+def test_noise_gather_and_frame_groups(world, cfg, frames, entries, per_frame, monkeypatch):
+    """the once-per-step exchange of both sharded loops (SVD: ``b_local`` entries of HW * 4; DiT: one entry of C * H * W): every
+    rank's slice in, the whole tensor out on every rank.  Values encode (entry, frame, element).  And the group builder hands
+    every rank the group of its CFG half's frame slices."""
+    import lkgd_amd.dist as ld
+    from thread_world import ThreadWorld, run_ranks
+    tw = ThreadWorld(world)
+    monkeypatch.setattr(ld, "dist", tw)
+    total = (2 if cfg else 1) * entries
+    e, f, k = torch.meshgrid(torch.arange(total), torch.arange(frames), torch.arange(per_frame), indexing="ij")
+    full = (10000 * e + 100 * f + k).float()                       # [total, frames, per_frame], exact in fp32
+
+    def fn(r):
+        plan = make_plan(world, r, frames, cfg)
+        group = ld.new_frame_group(plan)
+        gather = ld.NoiseGather(plan, entries, per_frame, torch.float32, "cpu")
+        e0 = plan.cfg_index * entries
+        got = []
+        for scale in (1.0, -2.0):                                  # a second step through the same buffers
+            local = scale * full[e0:e0 + entries, plan.f0:plan.f0 + plan.f_local].clone()
+            got.append(gather(local).clone())
+        return plan, group, got
+
+    for plan, group, got in run_ranks(tw, fn):
+        assert got[0].shape == (total, frames * per_frame)
+        assert torch.equal(got[0], full.reshape(total, -1)) and torch.equal(got[1], -2.0 * full.reshape(total, -1))
+        if plan.frame_shards == 1:
+            assert group is None
+        else:
+            assert group.ranks == plan.frame_group_ranks()
 
 
 def _worker_replay_entries(rank, world, port, frames, q):
@@ -310,29 +321,11 @@ def _worker_mirror(rank, world, port, frames, q):
 
 @pytest.mark.parametrize("world,frames", [(4, 6), (3, 7), (2, 6)])
 def test_mirror_exchange_of_symmetric_slices(world, frames):
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    port = _free_port()
-    procs = [ctx.Process(target=_worker_mirror, args=(r, world, port, frames, q)) for r in range(world)]
-    for p in procs:
-        p.start()
-    for p in procs:
-        p.join(180)
-        assert p.exitcode == 0
-    res = sorted(q.get(timeout=10) for _ in range(world))
+    res = sorted(run_world(_worker_mirror, world, frames))
     assert res == [(r, True) for r in range(world)]
 
 
 @pytest.mark.parametrize("world,frames", [(2, 5), (4, 6)])
 def test_recorded_multi_entry_exchanges_follow_their_inputs(world, frames):
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    port = _free_port()
-    procs = [ctx.Process(target=_worker_replay_entries, args=(r, world, port, frames, q)) for r in range(world)]
-    for p in procs:
-        p.start()
-    for p in procs:
-        p.join(180)
-        assert p.exitcode == 0
-    res = sorted(q.get(timeout=10) for _ in range(world))
+    res = sorted(run_world(_worker_replay_entries, world, frames))
     assert res == [(r, True) for r in range(world)]

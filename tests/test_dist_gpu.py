@@ -6,47 +6,14 @@ the random-init tiny UNet amplifies a ONE-ulp fp16 perturbation of its input to 
 (measured: tools/dist_noise_experiment.py -> sharded 3.2e-3, rerun 0.0, ulp-perturbed 4.0e-3), so the gate there is
 8e-3; the sharded kernel variants themselves are pinned bit-exactly in test_sharded_kernel_variants_are_exact."""
 import os
-import socket
 
 import pytest
-import numpy as np
 import torch
 import torch.distributed as dist
-import torch.multiprocessing as mp
+
+from dist_support import run_world, ship
 
 pytestmark = pytest.mark.gpu
-
-
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
-
-
-def _ship(res):
-    """tensors leave a worker as numpy arrays, pickled BY VALUE: a torch tensor in a multiprocessing queue travels as a file
-    descriptor the parent has to fetch from the worker's resource-sharer socket - gone if the worker has exited by then
-    (seen once on a GPU box: FileNotFoundError in rebuild_storage_fd)"""
-    return {k: (v.numpy() if torch.is_tensor(v) else v) for k, v in res.items()}
-
-
-def _collect(procs, q, world, timeout=600):
-    """one result per rank; a rank that dies (exception in the worker) fails the test at once instead of letting the
-    parent sit in q.get until the timeout"""
-    import queue
-    import time
-    results, t0 = [], time.time()
-    while len(results) < world:
-        try:
-            got = q.get(timeout=2)
-            results.append({k: (torch.from_numpy(v) if isinstance(v, np.ndarray) else v) for k, v in got.items()})
-        except queue.Empty:
-            dead = [p.exitcode for p in procs if p.exitcode not in (None, 0)]
-            assert not dead, f"worker process exited with {dead}"
-            assert time.time() - t0 < timeout, "timed out waiting for the ranks"
-    return results
 
 
 def _inputs(frames, guidance_on):
@@ -100,12 +67,12 @@ def _worker(rank, world, port, frames, guidance_on, q):
             ref = pipe.denoise((lat0 * s0).half().to(dev), img.half().to(dev), emb.half().to(dev), ids.to(dev), 2,
                                1.0, gmax)
             res["ref"] = ref.float().cpu()
-        q.put(_ship(res))
+        q.put(ship(res))
     finally:
         dist.destroy_process_group()
 
 
-def _worker_cn(rank, world, port, frames, q, nclips=1):
+def _worker_cn(rank, world, port, frames, nclips, q):
     """BASELINE.json configs[3]-style combination under sharding: the LKGD UNet (domain / flow features) with the
     ControlNet-SVD encoder in the loop (pipeline_stable_video_diffusion_controlnet.py:582-607)"""
     os.environ["MASTER_ADDR"], os.environ["MASTER_PORT"] = "127.0.0.1", str(port)
@@ -148,12 +115,12 @@ def _worker_cn(rank, world, port, frames, q, nclips=1):
             res["ref"] = pipe.denoise(*args, domain_features=dom.to(dev), flow_features=flow.to(dev),
                                       controlnet_condition=ctrl.to(dev), controlnet_cond_scale=0.8).float().cpu()
             res["plain"] = pipe.denoise(*args, domain_features=dom.to(dev), flow_features=flow.to(dev)).float().cpu()
-        q.put(_ship(res))
+        q.put(ship(res))
     finally:
         dist.destroy_process_group()
 
 
-def _worker_joint(rank, world, port, frames, q, flip=False):
+def _worker_joint(rank, world, port, frames, flip, q):
     """the [start, end] pair of the trans pipelines under sharding (round 5): TWO clips per call, UNet batch [u_x, u_y, c_x, c_y],
     `patch` joint-attention hooks on the spatial AND temporal blocks with masks [0,1,0,1] (utils/util.py:561-606,
     patch/patch.py:438-501,:616-658); a rank holds its frame slice of both clips of its CFG half"""
@@ -194,7 +161,7 @@ def _worker_joint(rank, world, port, frames, q, flip=False):
                 res["noflip"] = pipe.denoise(*args()).float().cpu()
             patch.remove_patch(pipe)                         # the hooks off: the joint branch must matter to the result
             res["plain"] = pipe.denoise(*args()).float().cpu()
-        q.put(_ship(res))
+        q.put(ship(res))
     finally:
         dist.destroy_process_group()
 
@@ -247,7 +214,7 @@ def _worker_lora(rank, world, port, frames, q):
             for a in MASKS:                                  # all-ones masks: the adapters must matter to the loop's result
                 patch.set_patch_lora_mask(unet, a, [1, 1, 1, 1])
             res["plain"] = pipe.denoise(*args()).float().cpu()
-        q.put(_ship(res))
+        q.put(ship(res))
     finally:
         dist.destroy_process_group()
 
@@ -258,16 +225,7 @@ def test_sharded_masked_lora_joint_pair_equals_single_process(world, frames, gat
     clips; ``gather``: the all-gather form of the temporal attention (LKGD_TEMPORAL_GATHER=1) instead of the pixel re-sharding"""
     if gather:
         monkeypatch.setenv("LKGD_TEMPORAL_GATHER", "1")
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    port = _free_port()
-    procs = [ctx.Process(target=_worker_lora, args=(r, world, port, frames, q)) for r in range(world)]
-    for p in procs:
-        p.start()
-    results = _collect(procs, q, world)
-    for p in procs:
-        p.join(60)
-        assert p.exitcode == 0
+    results = run_world(_worker_lora, world, frames)
     r0 = [r for r in results if "ref" in r][0]
     ref = r0["ref"]
     assert ref.shape[0] == 2 and torch.isfinite(ref).all()
@@ -321,23 +279,14 @@ def _worker_fsm(rank, world, port, frames, q):
             res["ref"] = pipe.denoise(*args()).float().cpu()
             patch_FSM.remove_patch(pipe)
             res["plain"] = pipe.denoise(*args()).float().cpu()
-        q.put(_ship(res))
+        q.put(ship(res))
     finally:
         dist.destroy_process_group()
 
 
 @pytest.mark.parametrize("world,frames,splits", [(2, 6, [6]), (4, 8, [4, 4]), (4, 6, [4, 2])])
 def test_sharded_fsm_hook_equals_single_process(world, frames, splits):
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    port = _free_port()
-    procs = [ctx.Process(target=_worker_fsm, args=(r, world, port, frames, q)) for r in range(world)]
-    for p in procs:
-        p.start()
-    results = _collect(procs, q, world)
-    for p in procs:
-        p.join(60)
-        assert p.exitcode == 0
+    results = run_world(_worker_fsm, world, frames)
     r0 = [r for r in results if "ref" in r][0]
     ref = r0["ref"]
     assert torch.isfinite(ref).all()
@@ -355,16 +304,7 @@ def test_sharded_joint_pair_equals_single_process(world, frames, flip):
     runs in the re-sharded layout.  ``flip`` (round 6; patch.apply_patch(flip=True), patch/patch.py:471-475): frame f attends to
     frame F-1-f of the partner clip - symmetric slices (4 ranks: CFG x (3, 3); an odd shard count, whose middle shard is its own mirror, is
     covered on the CPU: the pool allows six GPU processes, pytest included) and one K | V exchange with the mirror shard per spatial joint block"""
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    port = _free_port()
-    procs = [ctx.Process(target=_worker_joint, args=(r, world, port, frames, q, flip)) for r in range(world)]
-    for p in procs:
-        p.start()
-    results = _collect(procs, q, world)
-    for p in procs:
-        p.join(60)
-        assert p.exitcode == 0
+    results = run_world(_worker_joint, world, frames, flip)
     r0 = [r for r in results if "ref" in r][0]
     ref = r0["ref"]
     assert ref.shape[0] == 2 and torch.isfinite(ref).all()
@@ -379,16 +319,7 @@ def test_sharded_joint_pair_equals_single_process(world, frames, flip):
 
 @pytest.mark.parametrize("world,frames,nclips", [(2, 4, 1), (4, 5, 1), (4, 4, 2)])
 def test_sharded_controlnet_lk_loop_equals_single_process(world, frames, nclips):
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    port = _free_port()
-    procs = [ctx.Process(target=_worker_cn, args=(r, world, port, frames, q, nclips)) for r in range(world)]
-    for p in procs:
-        p.start()
-    results = _collect(procs, q, world)
-    for p in procs:
-        p.join(60)
-        assert p.exitcode == 0
+    results = run_world(_worker_cn, world, frames, nclips)
     r0 = [r for r in results if "ref" in r][0]
     ref = r0["ref"]
     assert torch.isfinite(ref).all()
@@ -423,23 +354,14 @@ def _worker_dit(rank, world, port, q):
         if rank == 0:
             res["ref"] = pc.denoise(m, pc.CogVideoXDDIMScheduler(), lat.to(dev), img.to(dev), pe.to(dev), dom.to(dev), flow.to(dev),
                                     3, 6.0, True).float().cpu()
-        q.put(_ship(res))
+        q.put(ship(res))
     finally:
         dist.destroy_process_group()
 
 
 @pytest.mark.parametrize("world", [2, 4])
 def test_sharded_dit_loop_equals_single_process(world):
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    port = _free_port()
-    procs = [ctx.Process(target=_worker_dit, args=(r, world, port, q)) for r in range(world)]
-    for p in procs:
-        p.start()
-    results = _collect(procs, q, world)
-    for p in procs:
-        p.join(60)
-        assert p.exitcode == 0
+    results = run_world(_worker_dit, world)
     ref = [r["ref"] for r in results if "ref" in r][0]
     assert torch.isfinite(ref).all()
     for r in results:
@@ -459,16 +381,7 @@ def test_sharded_loop_equals_single_process(world, frames, guidance_on, gather, 
         monkeypatch.setenv("LKGD_GN_HALO_SPLIT", "1")
     elif gather:
         monkeypatch.setenv("LKGD_TEMPORAL_GATHER", "1")      # read by lkgd_amd.dist at import in the spawned ranks
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    port = _free_port()
-    procs = [ctx.Process(target=_worker, args=(r, world, port, frames, guidance_on, q)) for r in range(world)]
-    for p in procs:
-        p.start()
-    results = _collect(procs, q, world)
-    for p in procs:
-        p.join(60)
-        assert p.exitcode == 0
+    results = run_world(_worker, world, frames, guidance_on)
     ref = [r["ref"] for r in results if "ref" in r][0]
     assert torch.isfinite(ref).all()
     for r in results:

@@ -10,7 +10,6 @@ slices, four ranks sharing the GPU over gloo, each compared with the REFERENCE (
 so a 4-way frame split without CFG-parallel, (4,4,3,3), has no reference run to compare with; it stays pinned against the
 single-process loop in test_dist_gpu.py.)  Gate: relative L2 <= 2e-2 per step (fp16 loop vs fp32 loop)."""
 import os
-import socket
 
 import pytest
 import torch
@@ -47,14 +46,6 @@ def test_hip_loop_14_frames_vs_reference_golden(golden, c1_oracle_model, c1_hip_
     rel = _rel(out.frames, g["final"])
     print(f"\n14-frame loop vs reference: final rel L2 {rel:.3e}")
     assert rel < 2e-2
-
-
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
 
 
 def _worker(rank, world, port, gpath, wpath, q):
@@ -95,23 +86,13 @@ def test_sharded_cfg_x_7_7_loop_vs_reference_golden(golden, golden_dir, c1_hip_m
     REFERENCE's fp32 run.  2 ranks = CFG-parallel only (the 2-GPU layout): every rank runs ONE batch entry with all 14 frames -
     the one-launch temporal attention and the fused feed-forwards with the second entry's context-table offset.  The eight-rank
     CFG x (4,4,3,3) layout runs in tests/test_zz_eight_ranks_gpu.py as threads (this pool admits six GPU processes per card, pytest included)."""
-    import torch.multiprocessing as mp
-    from test_dist_gpu import _collect
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    port = _free_port()
+    from dist_support import run_world
     gpath = os.path.join(golden_dir, "loop_f14_cfg.safetensors")
     # the ranks load the session model's fp16 weights from shared memory (3 GB) instead of re-drawing 1.5 B parameters each
     wpath = "/dev/shm/lkgd_f14_weights_%d.pt" % os.getpid()
     torch.save({k: v.detach().cpu() for k, v in c1_hip_model.state_dict().items()}, wpath)
     try:
-        procs = [ctx.Process(target=_worker, args=(r, world, port, gpath, wpath, q)) for r in range(world)]
-        for p in procs:
-            p.start()
-        results = _collect(procs, q, world, timeout=900)
-        for p in procs:
-            p.join(120)
-            assert p.exitcode == 0
+        results = run_world(_worker, world, gpath, wpath, timeout=900, join=120)
     finally:
         os.remove(wpath)
     for r in results:

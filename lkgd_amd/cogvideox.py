@@ -52,6 +52,12 @@ MI355X design - the UNet's kernels, one joint token buffer:
   ``lkgd_amd.lora.Linear`` wrappers (peft's state-dict names).  An adapter that applies to every row is a different WEIGHT: a wrapped
   linear packs the fp16 (or e4m3) form of ``W + sum_a c_a B_a A_a``, folded in fp32 when the model packs, and the sampling loop
   issues the launch list it issues without adapters.  There is no per-step low-rank path.
+* text-to-video and video-to-video ([EXT] diffusers' two classes, parity unpinned): the stock transformer has no
+  ``quaternion_lora_*`` path, so ``denoise`` without feature tensors takes the prompt embeddings as the text rows, and without image
+  latents ``lkgd_dit_patch_rows`` writes the latents' channels alone; ``denoise(start_step=)`` runs the tail of the schedule on a clip
+  noised by ``add_noise`` (``get_timesteps``, ``prepare_video_latents``; ``prepare_noise_latents`` for text-to-video).  All of it is
+  once-per-clip host glue over existing launches: the step stays ``lkgd_dit_patch_rows[_t]`` -> ``forward_rows`` ->
+  ``lkgd_dit_cfg_ddim_step[_t]`` / ``lkgd_dit_cfg_dpm_step[_t]``.
 """
 from __future__ import annotations
 
@@ -828,6 +834,18 @@ class _CogVideoXSchedule:
     def scale_model_input(self, sample, timestep=None):
         return sample
 
+    def add_noise(self, original_samples: torch.Tensor, noise: torch.Tensor, timesteps) -> torch.Tensor:
+        """[EXT diffusers ``add_noise`` of both schedulers], parity unpinned: ``alphas_cumprod`` cast to the samples' dtype,
+        ``a = alphas_cumprod[timesteps] ** 0.5``, ``s = (1 - alphas_cumprod[timesteps]) ** 0.5`` shaped [B, 1, ...], and
+        ``a * original_samples + s * noise`` with both products and the sum rounded in that dtype.  Plain tensor arithmetic, once per
+        clip (the video-to-video pipeline's start of the loop)"""
+        ac = self.alphas_cumprod.to(device=original_samples.device, dtype=original_samples.dtype)
+        timesteps = torch.as_tensor(timesteps, dtype=torch.int64).reshape(-1).to(original_samples.device)
+        shape = (-1,) + (1,) * (original_samples.dim() - 1)
+        a = (ac[timesteps] ** 0.5).reshape(shape)
+        s = ((1 - ac[timesteps]) ** 0.5).reshape(shape)
+        return a * original_samples + s * noise
+
     def _alpha_pair(self, t: int):
         """(alphas_cumprod[t], alphas_cumprod of the step's target, the target's timestep), fp64 0-dim tensors"""
         prev_t = t - self.config.num_train_timesteps // self.num_inference_steps
@@ -957,7 +975,8 @@ def dynamic_guidance(guidance_scale: float, num_inference_steps: int, t: int) ->
 @torch.no_grad()
 def denoise(transformer: CogVideoXTransformer3DModel, scheduler, latents, image_latents, prompt_embeds,
             domain_features, flow_features, num_inference_steps: int = 50, guidance_scale: float = 6.0,
-            use_dynamic_cfg: bool = True, callback=None, image_rotary_emb=None, ofs=None, generator=None) -> torch.Tensor:
+            use_dynamic_cfg: bool = True, callback=None, image_rotary_emb=None, ofs=None, generator=None,
+            start_step: int = 0) -> torch.Tensor:
     """the loop of pipeline_cogvideox_image2video.py:829-885 (the rotary tables are built once per clip when the config asks for
     them and none are given, :819-823).  latents / image_latents [B, F, C, h, w]; prompt_embeds
     [2B, L, 4096] (negative first) when guidance_scale > 1.  The update runs in fp32 (``noise_pred.float()`` :863) and the
@@ -969,7 +988,15 @@ def denoise(transformer: CogVideoXTransformer3DModel, scheduler, latents, image_
     ``scheduler`` is a ``CogVideoXDDIMScheduler`` (the steps above) or a ``CogVideoXDPMScheduler`` (:874-883): the step is then
     ``lkgd_dit_cfg_dpm_step`` (include/lkgd_hip_dit_dpm.h) on ``coefficients(t, previous t)``, with ``old_pred_original_sample`` kept
     in one fp32 tensor per clip and the step's noise drawn from ``generator`` in the latents' dtype (``dpm_noise``: twice on a
-    second-order step).  Anything else raises: there is no step to fall back to."""
+    second-order step).  Anything else raises: there is no step to fall back to.
+    ``domain_features`` and ``flow_features`` both None (the stock text-to-video / video-to-video transformer, which has no
+    ``quaternion_lora_*`` path): the text rows are ``prompt_embeds`` in fp16, ``fused_text`` is not called; exactly one of them None
+    raises, naming it.
+    ``start_step`` ([EXT] diffusers' video-to-video ``__call__``, parity unpinned): the loop runs ``scheduler.timesteps[start_step:]``.
+    Its first executed step has no previous timestep - a first-order DPM step with one draw; the callback's index counts executed
+    steps; and ``dynamic_guidance`` is given ``num_inference_steps - start_step`` as its step count, because diffusers' class
+    overwrites ``num_inference_steps`` with the truncated count before its loop (a quirk, reproduced: the ramp is not the one of the
+    untruncated schedule)."""
     dpm = isinstance(scheduler, CogVideoXDPMScheduler)
     if not dpm and not isinstance(scheduler, CogVideoXDDIMScheduler):
         raise LkgdHipError(f"denoise: scheduler is a {type(scheduler).__module__}.{type(scheduler).__qualname__}; the loop's step is "
@@ -980,9 +1007,17 @@ def denoise(transformer: CogVideoXTransformer3DModel, scheduler, latents, image_
                            "frames: pad_for_temporal_patches first")
     if ofs is not None and transformer.ofs_embedding is None:
         raise LkgdHipError("denoise: ofs given, but the model has no ofs_embedding (config ofs_embed_dim)")
+    if not 0 <= start_step < num_inference_steps:
+        raise ValueError(f"denoise: start_step={start_step} lies outside [0, num_inference_steps={num_inference_steps})")
     scheduler.set_timesteps(num_inference_steps)
     cfg = guidance_scale > 1.0
-    text = transformer.fused_text(prompt_embeds, domain_features, flow_features)          # step-invariant: once per clip
+    if domain_features is None and flow_features is None:         # no latent-knowledge fuse: the prompt embeddings are the text rows
+        text = prompt_embeds.to(device=dev, dtype=torch.float16).contiguous()
+    elif domain_features is None or flow_features is None:
+        raise LkgdHipError(f"denoise: `{'domain_features' if domain_features is None else 'flow_features'}` is None and the other "
+                           "is given; the latent-knowledge fuse takes both, the stock transformer neither")
+    else:
+        text = transformer.fused_text(prompt_embeds, domain_features, flow_features)      # step-invariant: once per clip
     # the loop's own copy: the step kernel updates it in place
     latents = latents.to(device=dev, dtype=torch.float16).clone(memory_format=torch.contiguous_format)
     # text-to-video (no image latents): the rows hold the latents' channels alone
@@ -1002,11 +1037,12 @@ def denoise(transformer: CogVideoXTransformer3DModel, scheduler, latents, image_
     # DPM: old_pred_original_sample, fp32; step i reads step i - 1's x0 (second order only) and leaves its own
     x0_state = torch.empty(latents.shape, dtype=torch.float32, device=dev) if dpm else None
     t_back = None
-    for i, t in enumerate(scheduler.timesteps.tolist()):
+    guidance_steps = num_inference_steps - start_step
+    for i, t in enumerate(scheduler.timesteps[start_step:].tolist()):
         # torch.cat([latents] * 2), the channel concat and the patch unfold: ONE set of rows, embedded for every CFG entry
         rows = ops.dit_patch_rows(latents, img, p, out=rows, **glue)
         noise_rows = transformer.forward_rows(rows, grid, text, float(t), image_rotary_emb=image_rotary_emb, **extra)
-        g = dynamic_guidance(guidance_scale, num_inference_steps, t) if use_dynamic_cfg else guidance_scale
+        g = dynamic_guidance(guidance_scale, guidance_steps, t) if use_dynamic_cfg else guidance_scale
         # noise_pred.float(), the CFG combine, scheduler.step and the cast back: one launch, in place
         if dpm:
             k = scheduler.coefficients(int(t), t_back)
@@ -1120,9 +1156,7 @@ def prepare_latents(vae, scheduler, transformer_config, image: torch.Tensor, bat
     (``pad_for_temporal_patches``); the noise is drawn with the (padded) latent shape - or ``latents`` taken as given - and
     multiplied by ``scheduler.init_noise_sigma``.  Returns ``(latents, image_latents)``, both [B, F, C, h, w]: what :func:`denoise`
     takes."""
-    if isinstance(generator, list) and len(generator) != batch_size:
-        raise ValueError(f"You have passed a list of generators of length {len(generator)}, but requested an effective batch"
-                         f" size of {batch_size}. Make sure the batch size matches the length of the generators.")
+    _check_generators(generator, batch_size)
     vc = vae.config
     scale_t, scale_s = vc.temporal_compression_ratio, 2 ** (len(vc.block_out_channels) - 1)
     device = device if device is not None else vae.device
@@ -1146,14 +1180,83 @@ def prepare_latents(vae, scheduler, transformer_config, image: torch.Tensor, bat
     image_latents = torch.cat([image_latents, latent_padding], dim=1)
     _, image_latents = pad_for_temporal_patches(shape, image_latents, p_t)              # :416-418 (the shape is padded already)
 
-    if latents is None:
-        if isinstance(generator, list):
-            gdev = generator[0].device
-            latents = torch.cat([torch.randn((1,) + shape[1:], generator=g, device=gdev, dtype=dtype) for g in generator]).to(device)
-        else:
-            gdev = generator.device if generator is not None else device
-            latents = torch.randn(shape, generator=generator, device=gdev, dtype=dtype).to(device)
-    else:
-        latents = latents.to(device)
+    latents = initial_noise(shape, dtype, device, generator) if latents is None else latents.to(device)
     latents = latents * scheduler.init_noise_sigma
     return latents, image_latents
+
+
+def _check_generators(generator, batch_size: int) -> None:
+    if isinstance(generator, list) and len(generator) != batch_size:
+        raise ValueError(f"You have passed a list of generators of length {len(generator)}, but requested an effective batch"
+                         f" size of {batch_size}. Make sure the batch size matches the length of the generators.")
+
+
+def initial_noise(shape, dtype, device, generator) -> torch.Tensor:
+    """the clip's initial noise ([EXT] diffusers ``randn_tensor``): drawn on the generator's device and moved; a list of generators
+    draws every batch entry from its own"""
+    shape = tuple(shape)
+    if isinstance(generator, list):
+        gdev = generator[0].device
+        return torch.cat([torch.randn((1,) + shape[1:], generator=g, device=gdev, dtype=dtype) for g in generator]).to(device)
+    gdev = generator.device if generator is not None else device
+    return torch.randn(shape, generator=generator, device=gdev, dtype=dtype).to(device)
+
+
+# ---- text-to-video and video-to-video in front of the loop ([EXT] diffusers pipeline_cogvideox.py / pipeline_cogvideox_video2video.py,
+# ---- parity unpinned: the reference imports the two classes and does not vendor them) ------------------------------------------------
+def get_timesteps(scheduler, num_inference_steps: int, strength: float):
+    """[EXT] the video-to-video class's ``get_timesteps``, called after ``set_timesteps`` -> (the timesteps the loop runs, their count,
+    ``t_start``: ``denoise``'s ``start_step``).  ``strength`` 1.0 runs the whole schedule, 0.8 of 50 steps its last 40.  A strength that
+    leaves no step raises here (diffusers fails later, on the empty ``timesteps[:1]``)"""
+    init_timestep = min(int(num_inference_steps * strength), num_inference_steps)
+    t_start = max(num_inference_steps - init_timestep, 0)
+    if init_timestep <= 0:
+        raise ValueError(f"`strength`={strength} with `num_inference_steps`={num_inference_steps} leaves no denoising step "
+                         f"(int(num_inference_steps * strength) = {init_timestep})")
+    return scheduler.timesteps[t_start:], num_inference_steps - t_start, t_start
+
+
+def prepare_noise_latents(scheduler, transformer_config, vae_config, batch_size: int = 1, num_channels_latents: int = 16,
+                          num_frames: int = 13, height: int = 60, width: int = 90, dtype=None, device=None, generator=None,
+                          latents=None) -> torch.Tensor:
+    """[EXT] the text-to-video class's ``prepare_latents``: noise [B, (num_frames - 1) // temporal ratio + 1, C, height // 8,
+    width // 8] drawn as ``prepare_latents`` draws it (``initial_noise``) - or ``latents`` as given - times
+    ``scheduler.init_noise_sigma``.  For a ``patch_size_t`` model the caller passes the padded pixel frame count
+    (``pipeline_cogvideox.additional_latent_frames``); ``transformer_config`` takes no part in the shape"""
+    _check_generators(generator, batch_size)
+    scale_t, scale_s = vae_config.temporal_compression_ratio, 2 ** (len(vae_config.block_out_channels) - 1)
+    shape = (batch_size, (num_frames - 1) // scale_t + 1, num_channels_latents, height // scale_s, width // scale_s)
+    latents = initial_noise(shape, dtype, device, generator) if latents is None else latents.to(device)
+    return latents * scheduler.init_noise_sigma
+
+
+@torch.no_grad()
+def prepare_video_latents(vae, scheduler, video: Optional[torch.Tensor] = None, batch_size: int = 1, num_channels_latents: int = 16,
+                          height: int = 60, width: int = 90, dtype=None, device=None, generator=None, latents=None,
+                          timestep=None) -> torch.Tensor:
+    """[EXT] the video-to-video class's ``prepare_latents``: every clip [3, T, H, W] of ``video`` [B, 3, T, H, W] is encoded on its own
+    and sampled with its generator (or the shared one), ``scaling_factor`` folded into the sampling launch (``_scaled_sample``); the
+    samples, concatenated and permuted to [B, F, C, h, w], are noised to ``timestep`` [B] - ``scheduler.add_noise(init, noise,
+    timestep)`` with noise of their shape - and multiplied by ``init_noise_sigma``.  The generator is consumed in that order: all
+    posterior samples, then the noise.  Given ``latents`` are taken as they are (times ``init_noise_sigma``); the video is not encoded"""
+    _check_generators(generator, batch_size)
+    vc = vae.config
+    scale_t, scale_s = vc.temporal_compression_ratio, 2 ** (len(vc.block_out_channels) - 1)
+    device = device if device is not None else vae.device
+    dtype = dtype if dtype is not None else vae.dtype
+    if latents is not None:
+        return latents.to(device) * scheduler.init_noise_sigma
+    if video is None or video.dim() != 5 or video.shape[0] != batch_size:
+        raise ValueError(f"prepare_video_latents: `video` must be [{batch_size}, C, T, H, W], got "
+                         f"{None if video is None else tuple(video.shape)}")
+    T = video.shape[2]
+    frames = (T - 1) // scale_t + 1
+    shape = (batch_size, frames, num_channels_latents, height // scale_s, width // scale_s)
+    gens = generator if isinstance(generator, list) else [generator] * batch_size
+    init = [_scaled_sample(vae.encode(video[i].unsqueeze(0)), gens[i], vc.scaling_factor) for i in range(batch_size)]
+    init = torch.cat(init, dim=0).to(device=device, dtype=dtype).permute(0, 2, 1, 3, 4)      # [B, F, C, h, w]
+    if tuple(init.shape) != shape:
+        raise LkgdHipError(f"prepare_video_latents: the encoder returned latents {tuple(init.shape)} for T = {T} pixel frames at "
+                           f"{height} x {width}; the loop takes {shape} ((T - 1) // {scale_t} + 1 latent frames)")
+    noise = initial_noise(shape, dtype, device, generator)
+    return scheduler.add_noise(init, noise, timestep) * scheduler.init_noise_sigma

@@ -58,6 +58,11 @@ MI355X design - the UNet's kernels, one joint token buffer:
   noised by ``add_noise`` (``get_timesteps``, ``prepare_video_latents``; ``prepare_noise_latents`` for text-to-video).  All of it is
   once-per-clip host glue over existing launches: the step stays ``lkgd_dit_patch_rows[_t]`` -> ``forward_rows`` ->
   ``lkgd_dit_cfg_ddim_step[_t]`` / ``lkgd_dit_cfg_dpm_step[_t]``.
+* reference attention (inference/ddim_inversion.py, lkgd_amd/ddim_inversion.py): ``Attention`` holds a marker
+  processor (``get_processor`` / ``set_processor``).  While a block's marker has ``reference_attention``, ``forward_rows`` takes the
+  batch as [sample, reference] pairs: a pair's keys / values are 2L adjacent rows, so a sample entry's attention is
+  ``lkgd_attn_spatial_qk`` with ``nbatch`` 1 (Sq = L, S = 2L) on row windows and its reference's ``lkgd_attn_spatial`` on its own L
+  rows - K and V are never copied -, and the head runs for the sample entries only.  With the default marker nothing changes.
 """
 from __future__ import annotations
 
@@ -254,9 +259,16 @@ class AdaLayerNorm(nn.Module):
         self.norm = nn.LayerNorm(output_dim // 2, eps)
 
 
+class CogVideoXAttnProcessor2_0:
+    """[EXT diffusers attention_processor.py] as a MARKER: the attention itself is ``CogVideoXBlock.run``'s launches, and the processor
+    an ``Attention`` holds only selects among them.  ``reference_attention`` False: every batch entry attends itself"""
+    reference_attention = False
+
+
 class Attention(nn.Module):
     def __init__(self, dim, heads, head_dim, bias):
         super().__init__()
+        self.processor = CogVideoXAttnProcessor2_0()
         if head_dim != 64:
             raise LkgdHipError("the attention kernel is built for head_dim 64")
         self.heads = heads
@@ -266,6 +278,18 @@ class Attention(nn.Module):
         self.norm_q = nn.LayerNorm(head_dim, eps=1e-6)
         self.norm_k = nn.LayerNorm(head_dim, eps=1e-6)
         self.to_out = nn.ModuleList([nn.Linear(dim, dim), nn.Dropout(0.0)])
+
+    def get_processor(self):
+        """[EXT diffusers Attention.get_processor]"""
+        return self.processor
+
+    def set_processor(self, processor) -> None:
+        """[EXT diffusers Attention.set_processor]; a processor is a marker (``CogVideoXAttnProcessor2_0``) - anything else has no
+        launches to select and raises"""
+        if not isinstance(processor, CogVideoXAttnProcessor2_0):
+            raise LkgdHipError(f"set_processor: {type(processor).__qualname__} is no CogVideoXAttnProcessor2_0 marker; the attention "
+                               "runs as HIP launches, a processor's own __call__ is never executed")
+        self.processor = processor
 
 
 class GELU(nn.Module):
@@ -336,7 +360,14 @@ class CogVideoXBlock(nn.Module):
             ops.layernorm(q.view(T * heads, 64), bp.nq[0], bp.nq[1], 1e-6, out=q.view(T * heads, 64))     # per-head qk norm
             ops.layernorm(k.view(T * heads, 64), bp.nk[0], bp.nk[1], 1e-6, out=k.view(T * heads, 64))
         a = empty()
-        if st.shard is None:
+        if st.pairs and self.attn1.processor.reference_attention:
+            # the batch is [sample, its reference] pairs (``forward_rows``): a pair's keys / values are 2L adjacent rows, so a sample
+            # entry's L queries read them in place (Sq = L, S = 2L) and its reference entry attends its own L rows
+            for b in range(0, B, 2):
+                s0, r0, r1 = b * L, (b + 1) * L, (b + 2) * L
+                ops.attn_spatial(q[s0:r0], k[s0:r1], v[s0:r1], a[s0:r0], 1, 2 * L, heads, Sq=L)
+                ops.attn_spatial(q[r0:r1], k[r0:r1], v[r0:r1], a[r0:r1], 1, L, heads)
+        elif st.shard is None:
             ops.attn_spatial(q, k, v, a, B, L, heads)
         else:                   # keys / values of every frame of this CFG half: text rows (replicated) + gathered video rows
             for full, loc in zip(st.KV, (k, v)):
@@ -646,6 +677,17 @@ class CogVideoXTransformer3DModel(PackedModule):
             raise LkgdHipError(f"patch_size_t {pt} does not divide the {Fr} latent frames: pad_for_temporal_patches first")
         extra = dict(ofs_emb=self.embed_ofs(ofs, B)) if ofs is not None else {}
         xh = hidden_states.to(device=self.device, dtype=torch.float16)
+        pair = None
+        if any(b.attn1.processor.reference_attention for b in self.transformer_blocks):
+            # the script's batch [samples | references] (ddim_inversion.py:212-215) -> ``forward_rows``' pairs, and back: host indexing
+            if B % 2:
+                raise LkgdHipError(f"reference attention (CogVideoXAttnProcessor2_0ForDDIMInversion): the batch is [sample | reference] "
+                                   f"entries and has to be even, got {B}")
+            pair = torch.arange(B, device=self.device).reshape(2, B // 2).t().reshape(-1)
+            xh, fused_text = xh[pair], fused_text.to(self.device)[pair]
+            if torch.is_tensor(timestep) and timestep.numel() == B:
+                timestep = timestep.to(self.device).reshape(-1)[pair]
+            extra["reference_rows"] = True
         # [EXT diffusers CogVideoXPatchEmbed, 1.5] (column (c, pt, py, px)), and cogvideox_transformer_3d.py:626-630; with pt = 1
         # bit for bit the 2-D unfold (column (c, py, px)) and un-patchify of :624-625
         patches = xh.permute(0, 1, 3, 4, 2).reshape(B, Fr // pt, pt, h, p, w, p, C_).permute(0, 1, 3, 5, 7, 2, 4, 6) \
@@ -653,6 +695,8 @@ class CogVideoXTransformer3DModel(PackedModule):
         out_tok = self.forward_rows(patches, (Fr // pt, h, w), fused_text, timestep, shard=shard, image_rotary_emb=image_rotary_emb,
                                     **extra)
         out = out_tok.reshape(B, Fr // pt, h, w, -1, pt, p, p).permute(0, 1, 5, 4, 2, 6, 3, 7).flatten(6, 7).flatten(4, 5).flatten(1, 2)
+        if pair is not None:
+            out = out[torch.argsort(pair)]
         return out.contiguous()
 
     @torch.no_grad()
@@ -671,7 +715,7 @@ class CogVideoXTransformer3DModel(PackedModule):
 
     @torch.no_grad()
     def forward_rows(self, patch_rows: torch.Tensor, grid, fused_text: torch.Tensor, timestep, shard=None,
-                     image_rotary_emb=None, ofs_emb=None) -> torch.Tensor:
+                     image_rotary_emb=None, ofs_emb=None, reference_rows: bool = False) -> torch.Tensor:
         """the row-level core.  ``patch_rows`` fp16 [Bv * Tv, in_channels * p * p] (``ops.dit_patch_rows``; column (c, py, px)),
         ``grid`` = (F, h, w) tokens, Tv = F h w; fused_text [B, L, 4096] fp16.  Bv divides B: batch entry b embeds the rows of
         entry b % Bv, so ONE copy of the rows (Bv = 1) serves both CFG entries, as ``torch.cat([latents] * 2)`` did.  Returns
@@ -683,13 +727,21 @@ class CogVideoXTransformer3DModel(PackedModule):
         A ``patch_size_t`` model: ``patch_rows`` [Bv * Tv, in_channels * p_t * p * p] (``ops.dit_patch_rows(p_t=)``; column
         (c, pt, py, px)), ``grid`` = (F / p_t, h, w), the result [B * Tv, out_channels * p_t * p * p]; ``ofs_emb`` fp16
         [B, time_embed_dim] (``embed_ofs``) exactly when the model has an ``ofs_embedding``: added to the time embedding in fp16
-        (:517) before the modulation GEMM."""
+        (:517) before the modulation GEMM.
+        Reference attention (``lkgd_amd.ddim_inversion.OverrideAttnProcessors``): while a block's ``attn1`` holds
+        a processor with ``reference_attention``, the batch is PAIRS - entry 2i a sample, entry 2i + 1 its reference
+        (``[u, ref_u, c, ref_c]`` under guidance; ``patch_rows`` with Bv = 2: ``[sample rows | reference rows]``, text
+        ``[neg, neg, pos, pos]``).  In such a block a sample entry's queries attend its own L rows followed by its reference's L rows -
+        adjacent rows of k and v, read in place - and a reference entry attends itself; everything else is row-local.  The result holds
+        the SAMPLE entries' rows only, [(B / 2) * Tv, ...] contiguous (what the step kernel takes), or with ``reference_rows`` every
+        entry's, in the pair order.  An odd batch, a non-rotary model, a ``patch_size_t`` model, a frame shard and the FP8 mode raise."""
         st = self._check_rows(patch_rows, grid, fused_text, shard, image_rotary_emb, ofs_emb)
         eff_g, eff_b, gates, fin = self._modulation(timestep, st.B, ofs_emb)
         X = self._embed_rows(st, patch_rows, fused_text)
         for i, block in enumerate(self.transformer_blocks):
             X = block.run(st, X, eff_g[:, i], eff_b[:, i], gates[i])
-        return self._head(st, X, fin)
+        # under reference attention the loop reads the sample entries' prediction only (ddim_inversion.py:416-417)
+        return self._head(st, X, fin, range(0, st.B, 2) if st.pairs and not reference_rows else range(st.B))
 
     def _check_rows(self, patch_rows, grid, fused_text, shard, image_rotary_emb, ofs_emb):
         """``forward_rows``' argument checks -> the call's sizes, shard window, rotary tables and row format"""
@@ -707,6 +759,19 @@ class CogVideoXTransformer3DModel(PackedModule):
             raise LkgdHipError("frame sharding of the DiT supports one batch entry per rank")
         Tt, Tv = fused_text.shape[1], Fr * h * w
         Kp = pk.w_pe.shape[1]
+        pairs = any(b.attn1.processor.reference_attention for b in self.transformer_blocks)
+        if pairs:
+            what = "reference attention (CogVideoXAttnProcessor2_0ForDDIMInversion)"
+            if not cfg.use_rotary_positional_embeddings:
+                raise NotImplementedError("This script supports CogVideoX 5B model only.")               # ddim_inversion.py:477-478
+            if cfg.patch_size_t is not None:
+                raise LkgdHipError(f"{what} of a patch_size_t (CogVideoX 1.5) model is not built")
+            if shard is not None:
+                raise LkgdHipError(f"{what} together with frame sharding is not built")
+            if pk.fp8:
+                raise LkgdHipError(f"{what} together with the FP8 mode (quantize_to_float8 / LKGD_DIT_FP8) is not built")
+            if B % 2:
+                raise LkgdHipError(f"{what}: the batch is [sample | reference] entries and has to be even, got {B}")
         if patch_rows.dim() != 2 or patch_rows.dtype != torch.float16 or patch_rows.device != dev or patch_rows.shape[1] != Kp \
                 or patch_rows.shape[0] % Tv or patch_rows.shape[0] == 0 or B % (patch_rows.shape[0] // Tv) \
                 or patch_rows.stride(1) != 1:
@@ -729,7 +794,7 @@ class CogVideoXTransformer3DModel(PackedModule):
             rope = tuple(t[v0:v0 + Tv].contiguous() for t in rope)
         KV = [] if shard is None else [torch.empty(Tt + F_all * h * w, self.inner_dim, dtype=torch.float16, device=dev) for _ in range(2)]
         return SimpleNamespace(B=B, Bv=patch_rows.shape[0] // Tv, Tt=Tt, Tv=Tv, L=Tt + Tv, grid=(F_all, h, w), v0=v0, rope=rope, KV=KV,
-                               shard=shard, heads=cfg.num_attention_heads, eps=cfg.norm_eps, rows=_FP8_ROWS if pk.fp8 else _FP16_ROWS)
+                               shard=shard, pairs=pairs, heads=cfg.num_attention_heads, eps=cfg.norm_eps, rows=_FP8_ROWS if pk.fp8 else _FP16_ROWS)
 
     def _modulation(self, timestep, B: int, ofs_emb):
         """time embedding (+ ``ofs_emb``) -> the step's modulation (one GEMM), fp32: the effective affine of norm(x) * (1 + scale) +
@@ -774,18 +839,19 @@ class CogVideoXTransformer3DModel(PackedModule):
                      bias=pk.b_pe, **rb_v)
         return X
 
-    def _head(self, st, X, fin):
-        """norm_final on the video stream, norm_out (adaLN), proj_out -> [B * Tv, out_channels * p * p]"""
-        pk, B, L, Tt, Tv = self._pk, st.B, st.L, st.Tt, st.Tv
+    def _head(self, st, X, fin, entries):
+        """norm_final on the video stream, norm_out (adaLN), proj_out of the batch ``entries`` -> [len(entries) * Tv, out_channels * p * p]"""
+        pk, L, Tt, Tv = self._pk, st.L, st.Tt, st.Tv
         po = pk.w_po.shape[0]
+        B = len(entries)
         out_tok = torch.empty(B, Tv, po, dtype=torch.float16, device=X.device)
-        for b in range(B):
+        for o, b in enumerate(entries):
             vid = X[b * L + Tt:(b + 1) * L]
             y = ops.layernorm(vid, pk.fin[0], pk.fin[1], st.eps)
             gg = (pk.out_g * (1 + fin[b, 1])).contiguous()
             bb = (pk.out_b * (1 + fin[b, 1]) + fin[b, 0]).contiguous()
             y = ops.layernorm(y, gg, bb, st.eps)
-            ops.gemm(y, pk.w_po, out_tok[b], M=Tv, N=po, K=self.inner_dim, bias=pk.b_po)
+            ops.gemm(y, pk.w_po, out_tok[o], M=Tv, N=po, K=self.inner_dim, bias=pk.b_po)
         return out_tok.view(B * Tv, po)
 
     @torch.no_grad()
@@ -807,6 +873,16 @@ class CogVideoXTransformer3DModel(PackedModule):
 
 
 # ------------------------------------------------------------------------------------------------ scheduler + loop
+class SchedulerConfig(dict):
+    """[EXT diffusers FrozenDict]: a scheduler's config, its keys readable as attributes as well"""
+
+    def __getattr__(self, name):
+        try:
+            return self[name]
+        except KeyError:
+            raise AttributeError(name) from None
+
+
 class _CogVideoXSchedule:
     """what the two CogVideoX schedulers share, [EXT diffusers scheduling_ddim_cogvideox.py / scheduling_dpm_cogvideox.py] with
     CogVideoX's scheduler_config.json (scaled-linear betas 0.00085..0.012, snr_shift_scale 3.0 for the 2B and 1.0 for the 5B models,
@@ -822,8 +898,12 @@ class _CogVideoXSchedule:
         s0, sT = s[0].clone(), s[-1].clone()
         self.alphas_cumprod = ((s - sT) * (s0 / (s0 - sT))) ** 2
         self.final_alpha_cumprod = torch.tensor(1.0, dtype=torch.float64)
-        self.config = SimpleNamespace(num_train_timesteps=num_train_timesteps, prediction_type="v_prediction",
-                                      timestep_spacing="trailing", snr_shift_scale=snr_shift_scale, _class_name=type(self).__name__)
+        # the keys of scheduler_config.json with the values built here: a mapping, so that ``Scheduler(**other.config)`` works as it
+        # does with diffusers' FrozenDict (ddim_inversion.py:489)
+        self.config = SchedulerConfig(num_train_timesteps=num_train_timesteps, beta_start=beta_start, beta_end=beta_end,
+                                      beta_schedule="scaled_linear", clip_sample=False, set_alpha_to_one=True,
+                                      rescale_betas_zero_snr=True, prediction_type="v_prediction", timestep_spacing="trailing",
+                                      snr_shift_scale=snr_shift_scale, _class_name=type(self).__name__)
         self.timesteps = None
 
     def set_timesteps(self, num_inference_steps: int, device=None):

@@ -1,0 +1,271 @@
+"""DDIM inversion (lkgd_amd/ddim_inversion.py), host side: the inverse scheduler's tables, timesteps and step against independent
+numpy / fp64 statements, the frame selection of ``get_video_frames``, ``OverrideAttnProcessors``, every refusal by name, and - on the
+CPU oracle alone - that each wrong processor of ddim_inversion_oracle.py is far from the true one at the seed the GPU test uses."""
+from types import SimpleNamespace
+
+import numpy as np
+import pytest
+import torch
+
+import ddim_inversion_oracle as dio
+from cogvideox_support import hip_twin, tiny_cpu_model
+from lkgd_amd import cogvideox as pc
+from lkgd_amd import ddim_inversion as di
+from lkgd_amd._lib import LkgdHipError
+
+GATE = dio.GATE
+
+
+def _inverse(shift=1.0, **over):
+    return di.DDIMInverseScheduler(**{**pc.CogVideoXDDIMScheduler(snr_shift_scale=shift).config, **over})
+
+
+# ------------------------------------------------------------------------------------------------ 1. the scheduler
+@pytest.mark.parametrize("n", [50, 7, 3])
+def test_inverse_timesteps(n):
+    s = _inverse()
+    s.set_timesteps(n)
+    want = np.round(np.arange(1000, 0, -1000 / n)[::-1]).astype(np.int64) - 1
+    assert s.timesteps.tolist() == want.tolist() == dio.inverse_timesteps(n)
+    assert s.timesteps.tolist() == sorted(s.timesteps.tolist()) and s.timesteps[-1] == 999
+    if n == 50:
+        assert s.timesteps[:2].tolist() == [19, 39]
+    fwd = pc.CogVideoXDDIMScheduler()
+    fwd.set_timesteps(n)
+    assert s.timesteps.tolist() == fwd.timesteps.flip(0).tolist()
+
+
+@pytest.mark.parametrize("shift", [1.0, 3.0])
+def test_inverse_table_ignores_snr_shift_scale(shift):
+    s = _inverse(shift)
+    base = pc._CogVideoXSchedule(snr_shift_scale=1.0).alphas_cumprod
+    assert s.alphas_cumprod.dtype == torch.float64 and torch.equal(s.alphas_cumprod, base)
+    np.testing.assert_allclose(s.alphas_cumprod.numpy(), dio.alphas_cumprod(snr_shift_scale=1.0), rtol=1e-12, atol=1e-300)
+    fwd = pc.CogVideoXDDIMScheduler(snr_shift_scale=shift).alphas_cumprod
+    assert torch.equal(s.alphas_cumprod, fwd) == (shift == 1.0)
+    assert s.config._class_name == "DDIMInverseScheduler" and s.order == 1 and s.init_noise_sigma == 1.0
+
+
+@pytest.mark.parametrize("n", [50, 7, 3])
+def test_first_and_last_step_coefficients(n):
+    s = _inverse()
+    s.set_timesteps(n)
+    ts = s.timesteps.tolist()
+    at, ap, cur = s._alpha_pair(ts[0])
+    # the integer N // n beside the fractional spacing N / n: 50 -> 19 - 20, 3 -> round(333.3) - 1 - 333, both -1 (at = 1, the clean
+    # sample); 7 -> round(142.86) - 1 - 142 = 0: the first sample is taken to sit at t = 0
+    assert cur == ts[0] - 1000 // n == {50: -1, 7: 0, 3: -1}[n] and (cur >= 0 or float(at) == 1.0)
+    for t in ts:
+        assert all(np.isfinite(c) for c in s.coefficients(t))
+    A, M = s.linear_coefficients(ts[0])
+    if cur == -1:           # at = 1: A = sqrt(ap), M = sqrt(1 - ap); the (a, b) form of the forward scheduler divides by 1 - at = 0
+        assert A == pytest.approx(float(ap) ** 0.5, rel=1e-15) and M == pytest.approx((1 - float(ap)) ** 0.5, rel=1e-15)
+    at, ap, cur = s._alpha_pair(ts[-1])
+    assert ts[-1] == 999 and float(ap) == 0.0 and cur == 999 - 1000 // n
+    A, M = s.linear_coefficients(999)
+    assert A == pytest.approx((1 - float(at)) ** 0.5, rel=1e-15) and M == pytest.approx(float(at) ** 0.5, rel=1e-15)
+    assert s.coefficients(999) == (A, -M, 0.0, 1.0)
+
+
+@pytest.mark.parametrize("n", [50, 7, 3])
+def test_step_fp32_vs_fp64_statements(n):
+    """``step`` computes fl(fl(A32 x) + fl(M32 n)) with u = 2^-24: A32, M32 and each product carry one rounding each, the sum one more,
+    so |step - exact| <= 3u (|A x| + |M n|) + O(u^2); the literal fp64 statements differ from the collected A x + M n by fp64 rounding
+    only.  Bound used: 4u (|A x| + |M n|)"""
+    s = _inverse()
+    s.set_timesteps(n)
+    ac = dio.alphas_cumprod()
+    g = torch.Generator().manual_seed(n)
+    x, v = torch.randn(2, 3, 16, 8, 12, generator=g), 2 * torch.randn(2, 3, 16, 8, 12, generator=g)
+    for t in s.timesteps.tolist():
+        got = s.step(v, t, x)[0]
+        assert got.dtype == torch.float32
+        want = dio.inverse_step_fp64(ac, t, n, x, v)
+        A, M = s.linear_coefficients(t)
+        bound = 4 * 2.0 ** -24 * (abs(A) * x.double().abs() + abs(M) * v.double().abs())
+        err = (got.double() - want).abs()
+        assert (err <= bound).all(), (t, (err / bound.clamp_min(1e-300)).max().item())
+        # and within one fp16 ulp of the fp64 value (the statement test_ddim_inversion_gpu.py makes of the kernel's fp16 result)
+        ulp = torch.pow(torch.tensor(2.0, dtype=torch.float64), torch.floor(torch.log2(want.abs().clamp_min(2.0 ** -14))) - 10)
+        assert (err < ulp).all(), (t, (err / ulp).max().item())
+
+
+def test_inverse_then_forward_is_the_identity_in_fp64():
+    """the oracle's two fp64 restatements agree: an inverse step onto t fixes (x0, e); the forward DDIM step from t, given the
+    v-prediction of that same (x0, e) at t, returns to the sample the inverse step started from"""
+    ac = dio.alphas_cumprod()
+    g = torch.Generator().manual_seed(0)
+    x, v = torch.randn(4, 5, generator=g).double(), torch.randn(4, 5, generator=g).double()
+    t, n = 499, 50
+    up = dio.inverse_step_fp64(ac, t, n, x, v)
+    at, ap = float(ac[t - 20]), float(ac[t])
+    x0, e = at ** 0.5 * x - (1 - at) ** 0.5 * v, at ** 0.5 * v + (1 - at) ** 0.5 * x
+    v_up = ap ** 0.5 * e - (1 - ap) ** 0.5 * x0            # the v-prediction of the same (x0, e) at the target
+    back = dio.ddim_step_fp64(ac, t, n, up, v_up)
+    assert (back - x).abs().max() < 1e-12
+
+
+@pytest.mark.parametrize("key,value", [("clip_sample", True), ("prediction_type", "epsilon"), ("timestep_spacing", "leading"),
+                                       ("set_alpha_to_one", False)])
+def test_refused_config_keys(key, value):
+    with pytest.raises(LkgdHipError, match=key):
+        _inverse(**{key: value})
+    with pytest.raises(LkgdHipError, match="clip_sample"):       # diffusers' own defaults are not the built values
+        di.DDIMInverseScheduler()
+
+
+def test_scheduler_config_is_a_mapping_and_has_attributes():
+    c = pc.CogVideoXDDIMScheduler(snr_shift_scale=1.0).config
+    assert dict(**c)["snr_shift_scale"] == 1.0 and c.snr_shift_scale == 1.0 and c.prediction_type == "v_prediction"
+    with pytest.raises(AttributeError):
+        c.no_such_key
+
+
+# ------------------------------------------------------------------------------------------------ 2. the frame selection
+def _clip(n, h=4, w=6):
+    return (torch.arange(n, dtype=torch.uint8)[:, None, None, None] + torch.zeros(1, h, w, 3, dtype=torch.uint8)).contiguous()
+
+
+def _literal(n, start, end, maxf, step):
+    """:274-294 on a list of frame numbers"""
+    s, e = min(start, n), max(0, n - end)
+    if e <= s:
+        idx = [s]
+    elif e - s <= maxf:
+        idx = list(range(s, e))
+    else:
+        idx = list(range(s, e, step or (e - s) // maxf))
+    idx = idx[:maxf]
+    r = (3 + len(idx)) % 4
+    return idx[:-r] if r else idx
+
+
+@pytest.mark.parametrize("n,start,end,maxf,step,want", [
+    (20, 3, 4, 81, None, list(range(3, 16))),          # shorter than max: 13 = 4*3 + 1 frames kept
+    (21, 0, 0, 81, None, list(range(21))),             # 4k + 1
+    (22, 0, 0, 81, None, list(range(21))),             # 4k + 2
+    (23, 0, 0, 81, None, list(range(21))),             # 4k + 3
+    (24, 0, 0, 81, None, list(range(21))),             # 4k + 4
+    (100, 0, 0, 9, None, list(range(0, 99, 11))),      # subsampled by (end - start) // max = 11: 10 indices, cut to 9
+    (100, 10, 10, 9, 3, list(range(10, 37, 3))),       # subsampled by frame_sample_step: 27 indices, cut to 9
+    (100, 0, 0, 8, 2, [0, 2, 4, 6, 8]),                # cut to max 8, then to 4k + 1 = 5
+    (40, 5, 0, 13, 1, list(range(5, 18))),             # a step that subsamples nothing: the cut to max decides
+])
+def test_get_video_frames_selection(n, start, end, maxf, step, want):
+    assert di.select_frame_indices(n, start, end, maxf, step) == want == _literal(n, start, end, maxf, step)
+    frames = di.get_video_frames(_clip(n), 6, 4, start, end, maxf, step)
+    assert frames.shape == (len(want), 3, 4, 6) and frames.dtype == torch.float32 and len(want) % 4 == 1
+    px = torch.tensor(want, dtype=torch.float32)
+    assert torch.equal(frames[:, 0, 0, 0], px / 255.0 * 2.0 - 1.0)
+    as_numpy = di.get_video_frames(_clip(n).numpy(), 6, 4, start, end, maxf, step)
+    assert torch.equal(as_numpy, frames)
+
+
+@pytest.mark.parametrize("n,start,end", [(10, 10, 0), (10, 12, 0), (10, 4, 6), (10, 0, 12)])
+def test_get_video_frames_empty_window(n, start, end):
+    """``end <= start``: the script asks for the single frame ``start`` - past the clip's end, which decord (and the index here) refuses;
+    inside it, one frame"""
+    idx = di.select_frame_indices(n, start, end, 81, None)
+    assert idx == [min(start, n)]
+    if idx[0] < n:
+        assert di.get_video_frames(_clip(n), 6, 4, start, end, 81, None).shape[0] == 1
+    else:
+        with pytest.raises(IndexError):
+            di.get_video_frames(_clip(n), 6, 4, start, end, 81, None)
+
+
+def test_get_video_frames_inputs():
+    import PIL.Image
+    clip = _clip(9)
+    pil = [PIL.Image.fromarray(f.numpy()) for f in clip]
+    assert torch.equal(di.get_video_frames(pil, 6, 4, 0, 0, 81, None), di.get_video_frames(clip, 6, 4, 0, 0, 81, None))
+    with pytest.raises(LkgdHipError, match="decord"):
+        di.get_video_frames("clip.mp4", 6, 4, 0, 0, 81, None)
+    with pytest.raises(LkgdHipError, match="uint8"):
+        di.get_video_frames(clip.float(), 6, 4, 0, 0, 81, None)
+    with pytest.raises(LkgdHipError, match="resize"):
+        di.get_video_frames(clip, 8, 4, 0, 0, 81, None)
+
+
+# ------------------------------------------------------------------------------------------------ 3. the context manager
+def test_override_installs_and_restores():
+    m = tiny_cpu_model()
+    blocks = list(m.transformer_blocks)
+    before = [b.attn1.get_processor() for b in blocks]
+    assert all(type(p) is pc.CogVideoXAttnProcessor2_0 and not p.reference_attention for p in before)
+    assert not di.reference_attention_installed(m)
+    with di.OverrideAttnProcessors(m):
+        assert all(type(b.attn1.get_processor()) is di.CogVideoXAttnProcessor2_0ForDDIMInversion for b in blocks)
+        assert di.reference_attention_installed(m)
+    assert [b.attn1.get_processor() for b in blocks] == before
+    with pytest.raises(RuntimeError, match="boom"):
+        with di.OverrideAttnProcessors(m):
+            raise RuntimeError("boom")
+    assert all(b.attn1.get_processor() is p for b, p in zip(blocks, before))
+    with pytest.raises(LkgdHipError, match="set_processor"):
+        blocks[0].attn1.set_processor(object())
+    assert "processor" not in "".join(m.state_dict().keys())
+
+
+# ------------------------------------------------------------------------------------------------ 4. the refusals
+def _cpu_pipeline(rotary=True):
+    dit = hip_twin(dio.seeded_model(), dio.TINY) if rotary else tiny_cpu_model(in_channels=16)
+    return SimpleNamespace(transformer=dit, scheduler=pc.CogVideoXDDIMScheduler(snr_shift_scale=1.0), _execution_device="cpu")
+
+
+def test_sample_refusals():
+    pipe = _cpu_pipeline()
+    lat = torch.zeros(1, 3, 16, 8, 12, dtype=torch.float16)
+    inv = _inverse()
+    with pytest.raises(LkgdHipError, match="CogVideoXDPMScheduler"):
+        di.sample(pipe, lat, pc.CogVideoXDPMScheduler(), prompt="")
+    with pytest.raises(LkgdHipError, match="scheduler is a"):
+        di.sample(pipe, lat, object(), prompt="")
+    with pytest.raises(LkgdHipError, match="eta"):
+        di.sample(pipe, lat, inv, prompt="", eta=0.5)
+    with pytest.raises(LkgdHipError, match="attention_kwargs"):
+        di.sample(pipe, lat, inv, prompt="", attention_kwargs={"scale": 1.0})
+    with pytest.raises(LkgdHipError, match="bf16"):
+        di.sample(pipe, lat.to(torch.bfloat16), inv, prompt="")
+    with di.OverrideAttnProcessors(pipe.transformer):
+        with pytest.raises(LkgdHipError, match="odd batch"):            # no reference entries under the override
+            di.sample(pipe, lat, pipe.scheduler, prompt="")
+    flat = _cpu_pipeline(rotary=False)
+    with di.OverrideAttnProcessors(flat.transformer):
+        with pytest.raises(NotImplementedError, match="This script supports CogVideoX 5B model only."):
+            di.sample(flat, lat, flat.scheduler, prompt="", reference_latents=[lat] * 50)
+    with pytest.raises(NotImplementedError, match="This script supports CogVideoX 5B model only."):
+        di.ddim_inversion(flat, "a prompt", torch.zeros(9, 64, 96, 3, dtype=torch.uint8), width=96, height=64)
+
+
+def test_entry_refusals():
+    pipe = _cpu_pipeline()
+    clip = torch.zeros(9, 64, 96, 3, dtype=torch.uint8)
+    for dtype in ("bf16", torch.bfloat16):
+        with pytest.raises(LkgdHipError, match="bf16"):
+            di.ddim_inversion(pipe, "a prompt", clip, dtype=dtype)
+    with pytest.raises(LkgdHipError, match="export_to_video"):
+        di.ddim_inversion(pipe, "a prompt", clip, output_path="out")
+    with pytest.raises(LkgdHipError, match="export_to_video"):
+        di.export_latents_to_video(pipe, torch.zeros(1, 3, 16, 8, 12), "out.mp4", 8)
+
+
+# ------------------------------------------------------------------------------------------------ 7 (CPU half). the decoys
+def _rel(a, b):
+    return ((a.float() - b.float()).norm() / b.float().norm()).item()
+
+
+def test_decoys_are_far_from_the_true_processor():
+    m = dio.seeded_model()
+    hidden, text = dio.guided_inputs()
+    rope = dio.rope_for(m.config, hidden)
+    with dio.override(m, "true"):
+        true = dio.dit_forward(m, hidden, text, 721, rope)
+    plain = dio.dit_forward(m, hidden, text, 721, rope)
+    assert torch.allclose(true[2:], plain[2:], atol=1e-5)           # a reference entry attends itself only
+    for mode in dio.DECOYS:
+        with dio.override(m, mode):
+            out = dio.dit_forward(m, hidden, text, 721, rope)
+        d = _rel(out, true)
+        print(f"decoy {mode}: rel L2 {d:.3e} from the true oracle ({d / GATE:.1f} gates)")
+        assert d >= 11 * GATE, (mode, d)

@@ -935,6 +935,7 @@ class _CogVideoXSchedule:
 class CogVideoXDDIMScheduler(_CogVideoXSchedule):
     """[EXT diffusers scheduling_ddim_cogvideox.py] (the reference's cli_demo.py recommends it for CogVideoX-2B); host tables in
     fp64, the update itself runs on the device"""
+    step_kind = "ddim"
 
     def coefficients(self, t: int):
         at, ap, _ = self._alpha_pair(t)
@@ -958,6 +959,7 @@ class CogVideoXDPMScheduler(_CogVideoXSchedule):
     the DDIM class - the scheduler the reference's pipeline keeps ``old_pred_original_sample`` for
     (pipeline_cogvideox_image2video.py:832-883) and its cli_demo.py installs for CogVideoX-5B / 5B-I2V.  ``coefficients`` in fp64 on
     the host; ``step`` is the out-of-place ATen form, ``denoise`` runs the same statements as one launch (``ops.dit_cfg_dpm_step``)"""
+    step_kind = "dpm"
 
     def coefficients(self, t: int, t_back: Optional[int] = None) -> DPMCoefficients:
         """``t_back``: the previous timestep of the loop, None on its first step.  At t = 999 alphas_cumprod is 0 (zero terminal SNR):
@@ -1052,11 +1054,31 @@ def dynamic_guidance(guidance_scale: float, num_inference_steps: int, t: int) ->
     return 1 + guidance_scale * ((1 - math.cos(math.pi * ((num_inference_steps - t) / num_inference_steps) ** 5.0)) / 2)
 
 
+class LoopPlacement:
+    """What ``denoise`` asks about the batch it embeds and the process it runs in.  The default: this process holds every entry and
+    frame, and there are no reference entries.  A rank of a sharded run (lkgd_amd/dist_run.py) answers for its CFG half and frame
+    slice, reference-guided sampling (lkgd_amd/ddim_inversion.py) for its [sample | reference] pairs."""
+    shard = None          # handed to ``forward_rows``: the rows are then those of the shard's ``plan.f_local`` frames
+    after_step = None     # f(i, t, latents) after step i: the loop's own latents, updated in place - no clone
+
+    def rows(self, i: int, latents, img, out, p: int, **glue) -> torch.Tensor:
+        """the patch rows step i's forward embeds; ``out``: what the previous step's call returned (None on the first)"""
+        return ops.dit_patch_rows(latents, img, p, out=out, **glue)
+
+    def text(self, text: torch.Tensor) -> torch.Tensor:
+        """the text rows of the entries ``forward_rows`` runs, of the [cfg * B, L, 4096] of the whole batch"""
+        return text
+
+    def noise(self, noise_rows: torch.Tensor) -> torch.Tensor:
+        """``forward_rows``' result -> the [cfg * B * Tv, C p p] rows of the whole batch, which the step kernel takes"""
+        return noise_rows
+
+
 @torch.no_grad()
 def denoise(transformer: CogVideoXTransformer3DModel, scheduler, latents, image_latents, prompt_embeds,
             domain_features, flow_features, num_inference_steps: int = 50, guidance_scale: float = 6.0,
             use_dynamic_cfg: bool = True, callback=None, image_rotary_emb=None, ofs=None, generator=None,
-            start_step: int = 0) -> torch.Tensor:
+            start_step: int = 0, _placement: Optional[LoopPlacement] = None) -> torch.Tensor:
     """the loop of pipeline_cogvideox_image2video.py:829-885 (the rotary tables are built once per clip when the config asks for
     them and none are given, :819-823).  latents / image_latents [B, F, C, h, w]; prompt_embeds
     [2B, L, 4096] (negative first) when guidance_scale > 1.  The update runs in fp32 (``noise_pred.float()`` :863) and the
@@ -1065,7 +1087,9 @@ def denoise(transformer: CogVideoXTransformer3DModel, scheduler, latents, image_
     A ``patch_size_t`` model takes tensors prepared by ``pad_for_temporal_patches`` (F % p_t == 0, or it raises), runs the ``_t``
     glue pair (include/lkgd_hip_dit_tpatch.h) on the (F / p_t, h, w) grid, and embeds ``ofs`` (default 2.0 when the config has
     ``ofs_embed_dim``, :826) once per clip.
-    ``scheduler`` is a ``CogVideoXDDIMScheduler`` (the steps above) or a ``CogVideoXDPMScheduler`` (:874-883): the step is then
+    ``scheduler`` declares its step in a class attribute ``step_kind``.  ``"ddim"`` (``CogVideoXDDIMScheduler``, the steps above;
+    ``lkgd_amd.ddim_inversion.DDIMInverseScheduler``, whose ``coefficients`` have the same four-tuple form), or ``"dpm"``
+    (``CogVideoXDPMScheduler``, :874-883): the step is then
     ``lkgd_dit_cfg_dpm_step`` (include/lkgd_hip_dit_dpm.h) on ``coefficients(t, previous t)``, with ``old_pred_original_sample`` kept
     in one fp32 tensor per clip and the step's noise drawn from ``generator`` in the latents' dtype (``dpm_noise``: twice on a
     second-order step).  Anything else raises: there is no step to fall back to.
@@ -1076,9 +1100,12 @@ def denoise(transformer: CogVideoXTransformer3DModel, scheduler, latents, image_
     Its first executed step has no previous timestep - a first-order DPM step with one draw; the callback's index counts executed
     steps; and ``dynamic_guidance`` is given ``num_inference_steps - start_step`` as its step count, because diffusers' class
     overwrites ``num_inference_steps`` with the truncated count before its loop (a quirk, reproduced: the ramp is not the one of the
-    untruncated schedule)."""
-    dpm = isinstance(scheduler, CogVideoXDPMScheduler)
-    if not dpm and not isinstance(scheduler, CogVideoXDDIMScheduler):
+    untruncated schedule).
+    ``_placement`` (private, ``LoopPlacement``): the one loop also serves the ranks of ``DistDiTDenoiser`` and the pairs of
+    ``ddim_inversion.sample``; without it the launches are the ones listed above."""
+    kind = getattr(type(scheduler), "step_kind", None)
+    dpm = kind == "dpm"
+    if kind not in ("ddim", "dpm"):
         raise LkgdHipError(f"denoise: scheduler is a {type(scheduler).__module__}.{type(scheduler).__qualname__}; the loop's step is "
                            "built for CogVideoXDDIMScheduler and CogVideoXDPMScheduler")
     dev = transformer.device
@@ -1098,14 +1125,17 @@ def denoise(transformer: CogVideoXTransformer3DModel, scheduler, latents, image_
                            "is given; the latent-knowledge fuse takes both, the stock transformer neither")
     else:
         text = transformer.fused_text(prompt_embeds, domain_features, flow_features)      # step-invariant: once per clip
+    place = _placement if _placement is not None else LoopPlacement()
+    text = place.text(text)
     # the loop's own copy: the step kernel updates it in place
     latents = latents.to(device=dev, dtype=torch.float16).clone(memory_format=torch.contiguous_format)
     # text-to-video (no image latents): the rows hold the latents' channels alone
     img = image_latents.to(device=dev, dtype=torch.float16).contiguous() if image_latents is not None else None
     tc = transformer.config
     p, pt = tc.patch_size, tc.patch_size_t
-    grid = (latents.shape[1] // (pt or 1), latents.shape[3] // p, latents.shape[4] // p)
-    extra = {}
+    grid = (latents.shape[1] // (pt or 1), latents.shape[3] // p, latents.shape[4] // p)       # of the whole clip
+    local_grid = grid if place.shard is None else (place.shard.plan.f_local,) + grid[1:]
+    extra = {} if place.shard is None else {"shard": place.shard}
     if transformer.ofs_embedding is not None:         # step-invariant: once per clip
         extra["ofs_emb"] = transformer.embed_ofs(2.0 if ofs is None else ofs, text.shape[0])
     glue = {} if pt is None else {"p_t": pt}
@@ -1120,8 +1150,8 @@ def denoise(transformer: CogVideoXTransformer3DModel, scheduler, latents, image_
     guidance_steps = num_inference_steps - start_step
     for i, t in enumerate(scheduler.timesteps[start_step:].tolist()):
         # torch.cat([latents] * 2), the channel concat and the patch unfold: ONE set of rows, embedded for every CFG entry
-        rows = ops.dit_patch_rows(latents, img, p, out=rows, **glue)
-        noise_rows = transformer.forward_rows(rows, grid, text, float(t), image_rotary_emb=image_rotary_emb, **extra)
+        rows = place.rows(i, latents, img, rows, p, **glue)
+        noise_rows = place.noise(transformer.forward_rows(rows, local_grid, text, float(t), image_rotary_emb=image_rotary_emb, **extra))
         g = dynamic_guidance(guidance_scale, guidance_steps, t) if use_dynamic_cfg else guidance_scale
         # noise_pred.float(), the CFG combine, scheduler.step and the cast back: one launch, in place
         if dpm:
@@ -1131,6 +1161,8 @@ def denoise(transformer: CogVideoXTransformer3DModel, scheduler, latents, image_
             t_back = int(t)
         else:
             ops.dit_cfg_ddim_step(noise_rows, latents, p, 2 if cfg else 1, g, *scheduler.coefficients(int(t)), **glue)
+        if place.after_step is not None:
+            place.after_step(i, t, latents)
         if callback is not None:
             callback(i, t, latents.clone())         # a tensor of the callback's own, as the out-of-place loop handed out
     return latents

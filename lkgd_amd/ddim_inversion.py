@@ -50,6 +50,7 @@ class DDIMInverseScheduler:
     ``trailing`` and ``set_alpha_to_one=False`` raise, naming the key."""
     order = 1
     init_noise_sigma = 1.0
+    step_kind = "ddim"        # ``cogvideox.denoise`` runs ``lkgd_dit_cfg_ddim_step`` on ``coefficients(t)``
 
     def __init__(self, num_train_timesteps: int = 1000, beta_start: float = 0.0001, beta_end: float = 0.02,
                  beta_schedule: str = "linear", clip_sample: bool = True, set_alpha_to_one: bool = True,
@@ -231,13 +232,46 @@ def _check_dtype(dtype, where: str) -> None:
         raise LkgdHipError(f"{where}: dtype={dtype!r}; fp16 is the only dtype of the HIP path")
 
 
+class _ReferencePlacement(cx.LoopPlacement):
+    """``sample`` with ``reference_latents``: the batch doubles into pairs, entry 2j a sample and 2j + 1 its reference, and the text
+    of a pair is the sample's (:355-356, :396-399).  ``keep_samples``: no reference attention is installed, so ``forward_rows``
+    returns every entry's rows - plain attention over the doubled batch - and the reference entries' are discarded, as the script
+    does"""
+
+    def __init__(self, reference_latents, keep_samples: bool):
+        self.reference_latents, self.keep_samples = reference_latents, keep_samples
+
+    def rows(self, i, latents, img, out, p, **glue):
+        reference = self.reference_latents[i].to(device=latents.device, dtype=torch.float16).contiguous()
+        if tuple(reference.shape) != tuple(latents.shape):
+            raise ValueError(f"sample: reference_latents[{i}] is {tuple(reference.shape)}, the latents {tuple(latents.shape)}")
+        Bl, Fr, C, H, W = latents.shape
+        self.Tv = Fr * (H // p) * (W // p)
+        if out is None:
+            out = torch.empty(2 * Bl * self.Tv, C * p * p, dtype=torch.float16, device=latents.device)
+        for j in range(Bl):                 # [sample j | reference j]: the rows ``forward_rows`` embeds for both CFG entries
+            ops.dit_patch_rows(latents[j:j + 1], None, p, out=out[2 * j * self.Tv:(2 * j + 1) * self.Tv])
+            ops.dit_patch_rows(reference[j:j + 1], None, p, out=out[(2 * j + 1) * self.Tv:(2 * j + 2) * self.Tv])
+        return out
+
+    def text(self, text):
+        return text.repeat_interleave(2, dim=0)
+
+    def noise(self, noise_rows):
+        if not self.keep_samples:
+            return noise_rows
+        entries = noise_rows.shape[0] // self.Tv            # [u, ref_u, c, ref_c]: keep the even ones
+        return noise_rows.view(entries, self.Tv, -1)[0::2].reshape(entries // 2 * self.Tv, -1)
+
+
 @torch.no_grad()
 def sample(pipeline, latents: torch.Tensor, scheduler, prompt: Optional[Union[str, List[str]]] = None,
            negative_prompt: Optional[Union[str, List[str]]] = None, num_inference_steps: int = 50, guidance_scale: float = 6,
            use_dynamic_cfg: bool = False, eta: float = 0.0, generator=None, attention_kwargs: Optional[Dict[str, Any]] = None,
            reference_latents=None) -> torch.Tensor:
     """:321-452, "modified from CogVideoXPipeline.__call__" -> the trajectory [steps, B, F, C, h, w] fp16, whose last entry is the
-    final latents.  Per step: ``ops.dit_patch_rows`` for the latents (and for ``reference_latents[i]`` when given), ``forward_rows``,
+    final latents.  The loop is ``cogvideox.denoise`` on the stock transformer (no image latents, no latent-knowledge fuse); per step:
+    ``ops.dit_patch_rows`` for the latents (and for ``reference_latents[i]`` when given: ``_ReferencePlacement``), ``forward_rows``,
     ``ops.dit_cfg_ddim_step`` with ``scheduler.coefficients(t)``, one device copy into ``trajectory[i]``.  The prompt is encoded and
     the rotary tables are built once per clip; dynamic guidance is the script's ``num_inference_steps - t`` (:420-430); the update runs
     in fp32 and is cast back to fp16 every step (:414, :441).
@@ -278,58 +312,35 @@ def sample(pipeline, latents: torch.Tensor, scheduler, prompt: Optional[Union[st
     prompt_embeds, negative_prompt_embeds = pipeline.encode_prompt(prompt, negative_prompt, do_classifier_free_guidance, device=device)
     if do_classifier_free_guidance:
         prompt_embeds = torch.cat([negative_prompt_embeds, prompt_embeds], dim=0)
-    text = prompt_embeds.to(device=device, dtype=torch.float16)
     # 4. timesteps (:359-360)
     scheduler.set_timesteps(num_inference_steps)
     timesteps = scheduler.timesteps.tolist()
     pipeline._num_timesteps = len(timesteps)
-    # 5. the loop's own copy of the latents: the step kernel updates it in place (:363)
-    latents = (latents.to(device=device) * scheduler.init_noise_sigma).to(torch.float16).clone(memory_format=torch.contiguous_format)
-    Bl, Fr = latents.shape[0], latents.shape[1]
-    p = tc.patch_size
-    grid = (Fr, latents.shape[3] // p, latents.shape[4] // p)
-    Tv = grid[0] * grid[1] * grid[2]
+    # 5. latents (:363)
+    latents = latents.to(device=device) * scheduler.init_noise_sigma
     ncfg = 2 if do_classifier_free_guidance else 1
-    if text.shape[0] != ncfg * Bl:
-        raise ValueError(f"sample: {text.shape[0]} prompt embeddings for {Bl} latents under cfg x{ncfg}")
+    if prompt_embeds.shape[0] != ncfg * latents.shape[0]:
+        raise ValueError(f"sample: {prompt_embeds.shape[0]} prompt embeddings for {latents.shape[0]} latents under cfg x{ncfg}")
+    place = cx.LoopPlacement()
     if reference_latents is not None:
         if isinstance(reference_latents, reversed):            # the script hands ``reversed(inverse_latents)`` (:508)
             reference_latents = list(reference_latents)
         if len(reference_latents) != len(timesteps):
             raise ValueError(f"sample: {len(reference_latents)} reference latents for {len(timesteps)} steps")
-        # pairs: entry 2i a sample, 2i + 1 its reference; the text of a pair is the sample's (:356 doubles the embeddings)
-        text = text.repeat_interleave(2, dim=0)
-    text = text.contiguous()
+        place = _ReferencePlacement(reference_latents, keep_samples=not guided)
     # 7. rotary tables, once per clip (:373-382)
     rope = None
     if tc.use_rotary_positional_embeddings:
         rope = pipeline._prepare_rotary_positional_embeddings(height=latents.size(3) * pipeline.vae_scale_factor_spatial,
                                                               width=latents.size(4) * pipeline.vae_scale_factor_spatial,
                                                               num_frames=latents.size(1), device=device)
-        rope = tuple(t.to(device=device, dtype=torch.float32).contiguous() for t in rope)
-    # 8. the loop (:387-447)
-    trajectory = torch.zeros((len(timesteps),) + tuple(latents.shape), dtype=latents.dtype, device=device)
-    rows = None
-    for i, t in enumerate(timesteps):
-        if reference_latents is None:
-            rows = ops.dit_patch_rows(latents, None, p, out=rows)
-        else:
-            reference = reference_latents[i].to(device=device, dtype=torch.float16).contiguous()
-            if tuple(reference.shape) != tuple(latents.shape):
-                raise ValueError(f"sample: reference_latents[{i}] is {tuple(reference.shape)}, the latents {tuple(latents.shape)}")
-            if rows is None:
-                rows = torch.empty(2 * Bl * Tv, latents.shape[2] * p * p, dtype=torch.float16, device=device)
-            for j in range(Bl):                 # [sample j | reference j]: the rows ``forward_rows`` embeds for both CFG entries
-                ops.dit_patch_rows(latents[j:j + 1], None, p, out=rows[2 * j * Tv:(2 * j + 1) * Tv])
-                ops.dit_patch_rows(reference[j:j + 1], None, p, out=rows[(2 * j + 1) * Tv:(2 * j + 2) * Tv])
-        noise_rows = dit.forward_rows(rows, grid, text, float(t), image_rotary_emb=rope)
-        if reference_latents is not None and not guided:       # plain attention over the doubled batch: keep the sample entries
-            noise_rows = noise_rows.view(2 * ncfg * Bl, Tv, -1)[0::2].reshape(ncfg * Bl * Tv, -1)
-        if use_dynamic_cfg:
-            pipeline._guidance_scale = cx.dynamic_guidance(guidance_scale, num_inference_steps, t)
-        # noise_pred.float(), the CFG combine, scheduler.step and the cast back: one launch, in place
-        ops.dit_cfg_ddim_step(noise_rows, latents, p, ncfg, pipeline._guidance_scale, *scheduler.coefficients(int(t)))
-        trajectory[i].copy_(latents)
+    # 8. the loop (:387-447): ``cogvideox.denoise`` on the stock transformer, one device copy per step into the trajectory
+    trajectory = torch.zeros((len(timesteps),) + tuple(latents.shape), dtype=torch.float16, device=device)
+    place.after_step = lambda i, t, x: trajectory[i].copy_(x)
+    cx.denoise(dit, scheduler, latents, None, prompt_embeds, None, None, num_inference_steps, guidance_scale, use_dynamic_cfg,
+               image_rotary_emb=rope, _placement=place)
+    if use_dynamic_cfg:                         # what the script's loop leaves in ``pipeline.guidance_scale``: the last step's
+        pipeline._guidance_scale = cx.dynamic_guidance(guidance_scale, num_inference_steps, timesteps[-1])
     pipeline.maybe_free_model_hooks()
     return trajectory
 

@@ -9,8 +9,8 @@ and once per step, over ALL ranks, the all-gather of the noise prediction [cfg*F
 CFG-combine + Euler update.  With 2 GPUs (pure CFG-parallel) only the last exchange exists.
 
 The SVD loop itself is not here: ``DistDenoiser.denoise`` runs ``StableVideoDiffusionPipeline.denoise`` (lkgd_amd/pipeline.py) with
-this rank's ``Placement``.  ``DistDiTDenoiser`` keeps the CogVideoX step arithmetic; both share lkgd_amd/dist.py's group builder
-and noise gather.
+this rank's ``Placement``, and ``DistDiTDenoiser.denoise`` runs ``lkgd_amd.cogvideox.denoise`` with this rank's ``LoopPlacement``;
+both share lkgd_amd/dist.py's group builder and noise gather.
 
 Correctness notes
   * every rank keeps the full latents (replicated, 1 MB) and the UNet weights; activations are sharded;
@@ -30,6 +30,7 @@ from typing import Optional
 import torch
 import torch.distributed as dist
 
+from . import cogvideox as cx
 from . import replay
 from ._lib import LkgdHipError
 from .dist import (NoiseGather, ShardPlan, allreduce_sums, exchange_halo, exchange_with_mirror_start, frames_to_pixels,
@@ -220,6 +221,30 @@ class DistDenoiser:
                                  controlnet_cond_scale=controlnet_cond_scale, _placement=place)
 
 
+class _DiTRankPlacement(cx.LoopPlacement):
+    """a CFG-parallel rank's answers to ``lkgd_amd.cogvideox.denoise``: one batch entry (its CFG half) of its frames [f0, f0 + fl).
+    A frame's token rows [h w, C p p] hold exactly ``per_frame`` = C H W contiguous elements, so the noise gather serves rows as it
+    serves frames; it runs once per step and the update is replicated"""
+
+    def __init__(self, plan: ShardPlan, shard: ShardInfo, per_frame: int, device):
+        self.plan = plan
+        self.shard = shard if plan.frame_shards > 1 else None
+        self.gather = NoiseGather(plan, 1, per_frame, torch.float16, device)
+
+    def frames(self, x):
+        """[1, F, ...] -> the rank's frames of it, contiguous (one clip)"""
+        return None if x is None else x[:, self.plan.f0:self.plan.f0 + self.plan.f_local]
+
+    def rows(self, i, latents, img, out, p, **glue):
+        return super().rows(i, self.frames(latents), self.frames(img), out, p, **glue)
+
+    def text(self, text):
+        return text[self.plan.cfg_index:self.plan.cfg_index + 1]
+
+    def noise(self, noise_rows):
+        return self.gather(noise_rows).view(-1, noise_rows.shape[1])          # [cfg * Tv, C p p] on every rank
+
+
 class DistDiTDenoiser:
     """BASELINE.json configs[4] over N GPUs: the CogVideoX DiT loop (lkgd_amd/cogvideox.py) with the SAME decomposition as the
     SVD loop - CFG-parallel x slices of the clip's latent frames (13 latent frames: 2 GPUs = CFG halves, 4 = CFG x (7, 6),
@@ -236,8 +261,7 @@ class DistDiTDenoiser:
         if getattr(transformer.config, "patch_size_t", None) is not None:
             raise LkgdHipError("DistDiTDenoiser: a patch_size_t (CogVideoX 1.5) model is not sharded - a token spans two latent "
                                "frames, the frame split is not built; run lkgd_amd.cogvideox.denoise on one GPU")
-        from .cogvideox import CogVideoXDPMScheduler
-        if isinstance(scheduler, CogVideoXDPMScheduler):
+        if isinstance(scheduler, cx.CogVideoXDPMScheduler):
             raise LkgdHipError("DistDiTDenoiser: the replicated stochastic step of CogVideoXDPMScheduler needs identical noise on "
                                "every rank; sharded DPM sampling is not built - sharded sampling needs CogVideoXDDIMScheduler "
                                "(lkgd_amd.cogvideox.denoise runs the DPM scheduler on one GPU)")
@@ -250,14 +274,19 @@ class DistDiTDenoiser:
 
     @torch.no_grad()
     def denoise(self, latents, image_latents, prompt_embeds, domain_features, flow_features, num_inference_steps: int = 50,
-                guidance_scale: float = 6.0, use_dynamic_cfg: bool = True, image_rotary_emb=None) -> torch.Tensor:
-        """``lkgd_amd.cogvideox.denoise`` over the ranks; latents / image_latents [1, F, C, h, w], prompt_embeds [2, L, 4096];
-        ``image_rotary_emb``: the tables of the WHOLE clip (built here when the config asks for rotary embeddings and none are
-        given), of which a frame-sharded rank uses the rows of its frames"""
-        from .cogvideox import dynamic_guidance, rotary_tables
-        tr, sch, plan = self.transformer, self.scheduler, self.plan
-        dev = tr.device
-        B, F, C_, H, W = latents.shape
+                guidance_scale: float = 6.0, use_dynamic_cfg: bool = True, image_rotary_emb=None, callback=None,
+                start_step: int = 0) -> torch.Tensor:
+        """``lkgd_amd.cogvideox.denoise`` over the ranks: the plan checks, then that loop with this rank's placement.  latents /
+        image_latents [1, F, C, h, w], prompt_embeds [2, L, 4096]; ``image_rotary_emb``: the tables of the WHOLE clip (built by the
+        loop when the config asks for rotary embeddings and none are given), of which a frame-sharded rank uses the rows of its frames.
+        A plan without CFG groups (``cfg_groups == 1``: one rank, or a larger world built with ``cfg=False``, which is only reached
+        with guidance off) runs the whole clip unsharded on every rank with no exchange, whatever ``frame_shards`` says: a
+        guidance-off frame split is not built.
+        Observable difference to the loop this class used to carry, sharded runs only: ``callback`` and ``start_step``, text-to-video
+        (``image_latents`` None) and the stock transformer (``domain_features`` and ``flow_features`` None) are ``denoise``'s
+        keywords and are passed through; no branch here knows of them."""
+        plan = self.plan
+        B, F = latents.shape[:2]
         if B != 1 or F != plan.num_frames:
             raise LkgdHipError("sharded DiT denoising handles one clip whose latent frame count matches the plan")
         cfg = 2 if guidance_scale > 1.0 else 1
@@ -265,39 +294,10 @@ class DistDiTDenoiser:
             raise LkgdHipError("shard plan was built for classifier-free guidance; got guidance_scale <= 1")
         if plan.cfg_groups == 1 and cfg == 2 and plan.frame_shards > 1:
             raise LkgdHipError("frame sharding without CFG-parallel needs guidance off (one batch entry per rank)")
-        sch.set_timesteps(num_inference_steps)
-        text = tr.fused_text(prompt_embeds.to(dev), domain_features.to(dev), flow_features.to(dev))      # replicated, once per clip
-        latents = latents.to(device=dev, dtype=torch.float16)
-        img = image_latents.to(device=dev, dtype=torch.float16)
-        fl, f0 = plan.f_local, plan.f0
-        co = tr.config.out_channels
-        if plan.cfg_groups == 2:       # a rank holds one batch entry (its CFG half) of its frames
-            gather = NoiseGather(plan, 1, co * H * W, torch.float16, dev)
-            noise_full = gather.full.view(cfg, F, co, H, W)
-        else:
-            noise_full = torch.empty(cfg, F, co, H, W, dtype=torch.float16, device=dev)
-        sharded = plan.frame_shards > 1
-        tc = tr.config
-        rope_all = rope_loc = None
-        if tc.use_rotary_positional_embeddings:
-            if image_rotary_emb is None:
-                image_rotary_emb = rotary_tables(tc, F, H // tc.patch_size, W // tc.patch_size)
-            rope_all = tuple(t.to(device=dev, dtype=torch.float32).contiguous() for t in image_rotary_emb)
-            hw = (H // tc.patch_size) * (W // tc.patch_size)
-            # a CFG-parallel rank without frame shards runs its own frames [f0, f0 + fl) = the whole clip
-            rope_loc = rope_all if sharded else tuple(t[f0 * hw:(f0 + fl) * hw] for t in rope_all)
-        for t in sch.timesteps.tolist():
-            if plan.cfg_groups == 2:
-                x = torch.cat([latents[:, f0:f0 + fl], img[:, f0:f0 + fl]], dim=2)
-                out = tr.forward_tokens(x, text[plan.cfg_index:plan.cfg_index + 1], float(t), shard=self.shard if sharded else None,
-                                        image_rotary_emb=rope_loc)
-                gather(out)            # -> noise_full
-            else:                      # one rank: the whole CFG batch, no exchange
-                x = torch.cat([latents] * cfg)
-                x = torch.cat([x, torch.cat([img] * cfg)], dim=2)
-                noise_full.copy_(tr.forward_tokens(x, text, float(t), image_rotary_emb=rope_all))
-            noise = noise_full.float()
-            g = dynamic_guidance(guidance_scale, num_inference_steps, t) if use_dynamic_cfg else guidance_scale
-            n = noise[0:1] + g * (noise[1:2] - noise[0:1]) if cfg == 2 else noise
-            latents = sch.step(n, t, latents.float())[0].to(torch.float16)
-        return latents
+        place = None
+        if plan.cfg_groups == 2:
+            place = _DiTRankPlacement(plan, self.shard, self.transformer.config.out_channels * latents.shape[3] * latents.shape[4],
+                                      self.transformer.device)
+        return cx.denoise(self.transformer, self.scheduler, latents, image_latents, prompt_embeds, domain_features, flow_features,
+                          num_inference_steps, guidance_scale, use_dynamic_cfg, callback=callback, image_rotary_emb=image_rotary_emb,
+                          start_step=start_step, _placement=place)

@@ -2,6 +2,7 @@
 
 A worker is ``worker(rank, world, port, *args, q)``: it joins the gloo world at 127.0.0.1:``port`` and puts ONE result into ``q`` -
 a dict through ``ship`` when it carries tensors."""
+import os
 import queue
 import socket
 import time
@@ -57,3 +58,40 @@ def run_world(worker, world, *args, timeout=600, join=60):
         p.join(join)
         assert p.exitcode == 0
     return results
+
+
+def sharded_dit_loop(rank, world, port, make_model, q, stock=False, start_step=0):
+    """the body of a worker that runs the tiny sharded DiT loop: 3 DDIM steps with dynamic CFG on 3 latent frames of 8 x 12 through
+    ``DistDiTDenoiser`` (world 2: the CFG halves; world 4: CFG halves x latent frames (2, 1)), on ``make_model(device)``.  Puts
+    {"rank", "out", "frame_shards", "steps"} and, on rank 0, "ref" and "ref_steps": ``cogvideox.denoise`` of the same inputs in
+    that process.  ``stock``: no image latents and no domain / flow features (the text-to-video transformer); ``start_step`` > 0
+    also hands both loops a callback, whose (index, timestep) pairs are the "steps" """
+    import torch.distributed as dist
+    os.environ["MASTER_ADDR"], os.environ["MASTER_PORT"] = "127.0.0.1", str(port)
+    torch.set_num_threads(max(1, int(os.environ.get("LKGD_TEST_HOST_CPUS", os.cpu_count() or 8)) // world))   # the ranks share the box's host cores
+    dist.init_process_group("gloo", rank=rank, world_size=world)
+    try:
+        from lkgd_amd import cogvideox as pc
+        from lkgd_amd.dist_run import DistDiTDenoiser
+        dev = torch.device("cuda", 0)
+        m = make_model(dev)
+        g = torch.Generator().manual_seed(79)
+        lat = torch.randn(1, 3, 16, 8, 12, generator=g).half().to(dev)
+        img = (0.5 * torch.randn(1, 3, 16, 8, 12, generator=g)).half().to(dev)
+        pe = torch.randn(2, 16, 4096, generator=g).half().to(dev)
+        dom, flow = torch.randn(1, 1, 1000, generator=g).to(dev), torch.randn(1, 1, 1000, generator=g).to(dev)
+        if stock:
+            img = dom = flow = None
+        steps, ref_steps = [], []
+
+        def loop_kw(seen):
+            return dict(start_step=start_step, callback=lambda i, t, x: seen.append((i, t))) if start_step else {}
+        runner = DistDiTDenoiser(m, pc.CogVideoXDDIMScheduler(), world, rank, 3, cfg=True)
+        out = runner.denoise(lat, img, pe, dom, flow, 3, 6.0, True, **loop_kw(steps))
+        res = {"rank": rank, "out": out.float().cpu(), "frame_shards": runner.plan.frame_shards, "steps": steps}
+        if rank == 0:
+            res["ref"] = pc.denoise(m, pc.CogVideoXDDIMScheduler(), lat, img, pe, dom, flow, 3, 6.0, True, **loop_kw(ref_steps)).float().cpu()
+            res["ref_steps"] = ref_steps
+        q.put(ship(res))
+    finally:
+        dist.destroy_process_group()

@@ -272,6 +272,41 @@ def test_denoise_refuses_what_is_no_scheduler():
     assert inspect.signature(pc.denoise).parameters["generator"].default is None
 
 
+def test_denoise_picks_its_step_by_the_declared_kind():
+    """``step_kind`` of the class is what ``denoise`` reads: the three schedulers declare theirs, and a class that declares none, or
+    one that is not built, is refused with the message of a class that is no scheduler at all"""
+    from lkgd_amd import cogvideox as pc
+    from lkgd_amd import ddim_inversion as di
+    from lkgd_amd._lib import LkgdHipError
+    assert (pc.CogVideoXDDIMScheduler.step_kind, pc.CogVideoXDPMScheduler.step_kind, di.DDIMInverseScheduler.step_kind) \
+        == ("ddim", "dpm", "ddim")
+    assert not hasattr(pc._CogVideoXSchedule, "step_kind")
+
+    class Euler(pc.CogVideoXDDIMScheduler):
+        step_kind = "euler"
+    m = tiny_cpu_model()
+    z = torch.zeros(1, 3, 16, 8, 12)
+    for bad in (Euler(), pc._CogVideoXSchedule()):
+        with pytest.raises(LkgdHipError) as e:
+            pc.denoise(m, bad, z, z, torch.zeros(2, 16, 4096), torch.zeros(1, 1, 1000), torch.zeros(1, 1, 1000), 2)
+        assert str(e.value) == (f"denoise: scheduler is a {type(bad).__module__}.{type(bad).__qualname__}; the loop's step is built "
+                                "for CogVideoXDDIMScheduler and CogVideoXDPMScheduler")
+
+
+def test_default_loop_placement_is_the_identity(monkeypatch):
+    """``denoise`` without ``_placement``: every rows / text / noise answer is its argument, no shard, no hook"""
+    from lkgd_amd import cogvideox as pc
+    calls = []
+    monkeypatch.setattr(pc.ops, "dit_patch_rows", lambda *a, **kw: calls.append((a, kw)) or "rows")
+    place = pc.LoopPlacement()
+    assert place.shard is None and place.after_step is None
+    t = torch.zeros(2, 16, 4096)
+    assert place.text(t) is t and place.noise(t) is t
+    lat, img, out = object(), object(), object()
+    assert place.rows(0, lat, img, out, 2) == "rows" and place.rows(1, lat, None, None, 2, p_t=2) == "rows"
+    assert calls == [((lat, img, 2), dict(out=out)), ((lat, None, 2), dict(out=None, p_t=2))]
+
+
 def test_dist_dit_denoiser_refuses_the_dpm_scheduler():
     """no process group is needed: the refusal comes before ``torch.distributed`` is asked anything"""
     import torch.distributed as dist

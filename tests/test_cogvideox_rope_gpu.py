@@ -317,35 +317,16 @@ def test_hip_rotary_dit_loop_vs_twin(tiny):
 
 
 # ------------------------------------------------------------------------------------------------------------------- two ranks
+def _tiny_rope_dit(dev):
+    return hip_twin(ro.seeded_model(ro.TINY_ROPE_DIT, 4), ro.TINY_ROPE_DIT, dev)
+
+
 def _worker_rope_dit(rank, world, port, q):
-    """test_dist_gpu._worker_dit for the tiny rotary model.  World 2: the ranks are the CFG halves (each rotates the whole clip's
+    """test_dist_gpu._worker_dit (dist_support.sharded_dit_loop) for the tiny rotary model.  World 2: the ranks are the CFG halves (each rotates the whole clip's
     rows); world 4: CFG halves x latent frames (2, 1) - a rank rotates its local q and k with the rows of its frames of the
     tables before the K gather, and adds its rows of the learned table"""
-    import torch.distributed as dist
-    from dist_support import ship
-    os.environ["MASTER_ADDR"], os.environ["MASTER_PORT"] = "127.0.0.1", str(port)
-    torch.set_num_threads(max(1, int(os.environ.get("LKGD_TEST_HOST_CPUS", os.cpu_count() or 8)) // world))
-    dist.init_process_group("gloo", rank=rank, world_size=world)
-    try:
-        from lkgd_amd import cogvideox as pc
-        from lkgd_amd.dist_run import DistDiTDenoiser
-        dev = torch.device("cuda", 0)
-        m = hip_twin(ro.seeded_model(ro.TINY_ROPE_DIT, 4), ro.TINY_ROPE_DIT, DEV)
-        g = torch.Generator().manual_seed(79)
-        lat = torch.randn(1, 3, 16, 8, 12, generator=g).half()
-        img = (0.5 * torch.randn(1, 3, 16, 8, 12, generator=g)).half()
-        pe = torch.randn(2, 16, 4096, generator=g).half()
-        dom, flow = torch.randn(1, 1, 1000, generator=g), torch.randn(1, 1, 1000, generator=g)
-        gs = 6.0
-        runner = DistDiTDenoiser(m, pc.CogVideoXDDIMScheduler(), world, rank, 3, cfg=True)
-        out = runner.denoise(lat.to(dev), img.to(dev), pe.to(dev), dom.to(dev), flow.to(dev), 3, gs, True)
-        res = {"rank": rank, "out": out.float().cpu(), "frame_shards": runner.plan.frame_shards}
-        if rank == 0:
-            res["ref"] = pc.denoise(m, pc.CogVideoXDDIMScheduler(), lat.to(dev), img.to(dev), pe.to(dev), dom.to(dev), flow.to(dev),
-                                    3, gs, True).float().cpu()
-        q.put(ship(res))
-    finally:
-        dist.destroy_process_group()
+    from dist_support import sharded_dit_loop
+    sharded_dit_loop(rank, world, port, _tiny_rope_dit, q)
 
 
 @gpu

@@ -238,6 +238,41 @@ def test_sample_refusals():
         di.ddim_inversion(flat, "a prompt", torch.zeros(9, 64, 96, 3, dtype=torch.uint8), width=96, height=64)
 
 
+def test_reference_placement_pairs(monkeypatch):
+    """what ``sample`` answers ``cogvideox.denoise`` with reference latents, against the index arithmetic written out: the rows of
+    entry j's sample at [2j Tv, (2j + 1) Tv) and of its reference at [(2j + 1) Tv, (2j + 2) Tv) of ONE buffer that the next step
+    refills; the text of a pair twice; and without reference attention the even entries of ``forward_rows``' result"""
+    from cogvideox_support import patchify
+
+    def patch_rows(latents, image_latents, p, out=None):
+        assert image_latents is None and p == 2
+        return out.copy_(patchify(latents))
+    monkeypatch.setattr(di.ops, "dit_patch_rows", patch_rows)
+    g = torch.Generator().manual_seed(3)
+    Bl, Tv = 2, 3 * 4 * 6
+    lat = torch.randn(Bl, 3, 16, 8, 12, generator=g).half()
+    refs = torch.randn(2, Bl, 3, 16, 8, 12, generator=g).half()
+    place = di._ReferencePlacement(refs, keep_samples=True)
+    rows = None
+    for i in range(2):
+        got = place.rows(i, lat, None, rows, 2)
+        assert rows is None or got is rows
+        rows = got
+        assert rows.shape == (2 * Bl * Tv, 64) and rows.dtype == torch.float16
+        for j in range(Bl):
+            assert torch.equal(rows[2 * j * Tv:(2 * j + 1) * Tv], patchify(lat[j:j + 1]))
+            assert torch.equal(rows[(2 * j + 1) * Tv:(2 * j + 2) * Tv], patchify(refs[i, j:j + 1]))
+    text = torch.arange(4 * 5, dtype=torch.float32).reshape(4, 5, 1)                 # [u0, u1, c0, c1]
+    assert torch.equal(place.text(text), text[[0, 0, 1, 1, 2, 2, 3, 3]])
+    noise = torch.arange(8 * Tv * 64, dtype=torch.float32).reshape(8 * Tv, 64)      # 2 * cfg * Bl entries
+    kept = place.noise(noise)
+    assert kept.is_contiguous() and torch.equal(kept, torch.cat([noise[e * Tv:(e + 1) * Tv] for e in (0, 2, 4, 6)]))
+    guided = di._ReferencePlacement(refs, keep_samples=False)                        # ``forward_rows`` returned the sample entries
+    assert guided.noise(noise) is noise
+    with pytest.raises(ValueError, match=r"sample: reference_latents\[1\] is \(1, 3, 16, 8, 12\), the latents \(2, 3, 16, 8, 12\)"):
+        di._ReferencePlacement([refs[0], refs[1, :1]], True).rows(1, lat, None, rows, 2)
+
+
 def test_entry_refusals():
     pipe = _cpu_pipeline()
     clip = torch.zeros(9, 64, 96, 3, dtype=torch.uint8)

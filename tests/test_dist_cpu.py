@@ -248,6 +248,42 @@ def test_noise_gather_and_frame_groups(world, cfg, frames, entries, per_frame, m
             assert group.ranks == plan.frame_group_ranks()
 
 
+@pytest.mark.parametrize("world,windows", [(2, [(0, 0, 3), (1, 0, 3)]),                               # the CFG halves, whole clip
+                                           (4, [(0, 0, 2), (0, 2, 1), (1, 0, 2), (1, 2, 1)])])        # CFG halves x frames (2, 1)
+def test_dit_rank_placement_windows_and_row_gather(world, windows, monkeypatch):
+    """what a rank of ``DistDiTDenoiser`` answers ``cogvideox.denoise`` for 3 latent frames: (CFG half, first frame, frames) per rank
+    written out, against ``make_plan``; the text rows of its half; the shard only where frames are split.  And the noise gather in
+    row format: each rank hands in its [f_local h w, C p p] token rows, every rank gets the [cfg F h w, C p p] rows of the whole
+    clip (values encode (entry, token, column))"""
+    import lkgd_amd.dist as ld
+    import lkgd_amd.dist_run as dr
+    from thread_world import ThreadWorld, run_ranks
+    tw = ThreadWorld(world)
+    monkeypatch.setattr(ld, "dist", tw)
+    F, C, H, W, p = 3, 16, 8, 12, 2
+    hw, width = (H // p) * (W // p), C * p * p
+    e, t, k = torch.meshgrid(torch.arange(2), torch.arange(F * hw), torch.arange(width), indexing="ij")
+    full = (100000 * e + 100 * t + k).float().reshape(2 * F * hw, width)          # exact in fp32
+    lat = torch.arange(F * 5, dtype=torch.float32).reshape(1, F, 5)
+    text = torch.arange(2 * 4, dtype=torch.float32).reshape(2, 4)
+    shard = object()
+
+    def fn(r):
+        plan = make_plan(world, r, F, True)
+        place = dr._DiTRankPlacement(plan, shard, C * H * W, "cpu")
+        place.gather = ld.NoiseGather(plan, 1, C * H * W, torch.float32, "cpu")       # the values above need fp32
+        ci, f0, fl = windows[r]
+        assert (plan.cfg_index, plan.f0, plan.f_local) == (ci, f0, fl)
+        assert torch.equal(place.frames(lat), lat[:, f0:f0 + fl]) and place.frames(lat).is_contiguous() and place.frames(None) is None
+        assert torch.equal(place.text(text), text[ci:ci + 1])
+        assert place.shard is (shard if world == 4 else None)
+        local = full[(ci * F + f0) * hw:(ci * F + f0 + fl) * hw]
+        return [place.noise(scale * local).clone() for scale in (1.0, -2.0)]         # a second step through the same buffers
+
+    for got in run_ranks(tw, fn):
+        assert got[0].shape == full.shape and torch.equal(got[0], full) and torch.equal(got[1], -2.0 * full)
+
+
 def _worker_replay_entries(rank, world, port, frames, q):
     """with several batch entries per rank the joined result of the per-entry exchanges must be refreshed by
     the recorded steps themselves - record, change the inputs in place, replay, compare"""

@@ -11,7 +11,7 @@ import pytest
 import torch
 import torch.distributed as dist
 
-from dist_support import run_world, ship
+from dist_support import run_world, sharded_dit_loop, ship
 
 pytestmark = pytest.mark.gpu
 
@@ -329,44 +329,48 @@ def test_sharded_controlnet_lk_loop_equals_single_process(world, frames, nclips)
         assert rel <= 8e-3, f"rank {r['rank']}: sharded ControlNet + LK loop vs single process: relative L2 {rel:.3e}"
 
 
-def _worker_dit(rank, world, port, q):
+def _tiny_dit(dev, in_channels=32):
+    from lkgd_amd import cogvideox as pc
+    from lkgd_amd import unet as pu
+    cfg = pc.DiTConfig(num_attention_heads=2, in_channels=in_channels, time_embed_dim=64, num_layers=2, sample_width=12, sample_height=8,
+                       sample_frames=9, max_text_seq_length=16)
+    m = pc.CogVideoXTransformer3DModel(cfg).half().to(dev)
+    pu.init_synthetic_weights_(m, seed=4)
+    return m
+
+
+def _tiny_stock_dit(dev):
+    return _tiny_dit(dev, in_channels=16)
+
+
+def _worker_dit(rank, world, port, stock, start_step, q):
     """configs[4] under sharding: the CogVideoX DiT loop, CFG-parallel x latent-frame slices (3 latent frames over (2, 1))"""
-    os.environ["MASTER_ADDR"], os.environ["MASTER_PORT"] = "127.0.0.1", str(port)
-    torch.set_num_threads(max(1, int(os.environ.get("LKGD_TEST_HOST_CPUS", os.cpu_count() or 8)) // world))   # the ranks share the box's host cores
-    dist.init_process_group("gloo", rank=rank, world_size=world)
-    try:
-        from lkgd_amd import cogvideox as pc
-        from lkgd_amd import unet as pu
-        from lkgd_amd.dist_run import DistDiTDenoiser
-        dev = torch.device("cuda", 0)
-        cfg = pc.DiTConfig(num_attention_heads=2, in_channels=32, time_embed_dim=64, num_layers=2, sample_width=12, sample_height=8,
-                           sample_frames=9, max_text_seq_length=16)
-        m = pc.CogVideoXTransformer3DModel(cfg).half().to(dev)
-        pu.init_synthetic_weights_(m, seed=4)
-        g = torch.Generator().manual_seed(79)
-        lat = torch.randn(1, 3, 16, 8, 12, generator=g).half()
-        img = (0.5 * torch.randn(1, 3, 16, 8, 12, generator=g)).half()
-        pe = torch.randn(2, 16, 4096, generator=g).half()
-        dom, flow = torch.randn(1, 1, 1000, generator=g), torch.randn(1, 1, 1000, generator=g)
-        runner = DistDiTDenoiser(m, pc.CogVideoXDDIMScheduler(), world, rank, 3, cfg=True)
-        out = runner.denoise(lat.to(dev), img.to(dev), pe.to(dev), dom.to(dev), flow.to(dev), 3, 6.0, True)
-        res = {"rank": rank, "out": out.float().cpu()}
-        if rank == 0:
-            res["ref"] = pc.denoise(m, pc.CogVideoXDDIMScheduler(), lat.to(dev), img.to(dev), pe.to(dev), dom.to(dev), flow.to(dev),
-                                    3, 6.0, True).float().cpu()
-        q.put(ship(res))
-    finally:
-        dist.destroy_process_group()
+    sharded_dit_loop(rank, world, port, _tiny_stock_dit if stock else _tiny_dit, q, stock=stock, start_step=start_step)
 
 
 @pytest.mark.parametrize("world", [2, 4])
 def test_sharded_dit_loop_equals_single_process(world):
-    results = run_world(_worker_dit, world)
+    results = run_world(_worker_dit, world, False, 0)
     ref = [r["ref"] for r in results if "ref" in r][0]
     assert torch.isfinite(ref).all()
     for r in results:
         rel = ((r["out"] - ref).norm() / ref.norm()).item()
         assert rel <= 8e-3, f"rank {r['rank']}: sharded DiT loop vs single process: relative L2 {rel:.3e}"
+
+
+def test_sharded_dit_loop_passes_the_loop_keywords_through():
+    """what the sharded loop has because it IS ``cogvideox.denoise``: the stock text-to-video transformer (no image latents, no
+    latent-knowledge fuse) from ``start_step`` 1 with a callback, on 4 ranks (CFG halves x frames (2, 1)) - every rank's latents at
+    test_sharded_dit_loop_equals_single_process's bound from the single-process loop with the same keywords, and its callback
+    called for the same (executed step, timestep) pairs"""
+    results = run_world(_worker_dit, 4, True, 1)
+    r0 = [r for r in results if "ref" in r][0]
+    ref = r0["ref"]
+    assert torch.isfinite(ref).all() and [i for i, _ in r0["ref_steps"]] == [0, 1] and len(r0["ref_steps"]) == 2
+    for r in results:
+        assert r["frame_shards"] == 2 and r["steps"] == r0["ref_steps"]
+        rel = ((r["out"] - ref).norm() / ref.norm()).item()
+        assert rel <= 8e-3, f"rank {r['rank']}: sharded stock DiT loop from start_step 1 vs single process: relative L2 {rel:.3e}"
 
 
 @pytest.mark.parametrize("world,frames,guidance_on,gather", [(2, 4, True, False), (4, 5, True, False), (2, 5, False, False),

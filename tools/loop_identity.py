@@ -7,8 +7,12 @@ The gate of a refactor that must not change what a loop enqueues.  Only signatur
 UNet and inputs of tests/test_dist_gpu.py (8x8 latents, block_out_channels (64, 128, 128, 128)) run on cuda:0 through
 ``pipe.denoise`` (one process: CFG on / off, ``start_step`` + callback, ``direct_fusion``, a ControlNet condition, the eager module
 walk, the HIP graph), through ``DistDenoiser`` (worlds 2 and 4 over gloo, replay on and off, one and two clips, with and without a
-ControlNet) and through ``DistDiTDenoiser`` (worlds 2 and 4, 3 latent frames).  One line per case and rank: the sha256 of the final
-latents' bytes.  Two 7-step cases also run with ``ops.GEMM_EVENTS = []`` and print how many entries were appended and whether
+ControlNet) and through ``DistDiTDenoiser`` (worlds 2 and 4, 3 latent frames).  The one-process CogVideoX cases (``dit_one``: 3 to
+4 steps on 3 latent frames of 8 x 12, tiny two-layer models with synthetic weights) run ``cogvideox.denoise`` (DDIM, DPM with a
+seeded generator, guidance off, ``start_step`` + callback, text-to-video, a ``patch_size_t`` model with ``ofs``) and
+``ddim_inversion.sample`` (inverse, guided under ``OverrideAttnProcessors``, references without the override; the whole
+trajectory is hashed).  ``sample`` is handed a minimal pipeline object - ``encode_prompt`` returns seeded embeddings, no tokenizer
+or T5 is involved.  One line per case and rank: the sha256 of the final latents' bytes.  Two 7-step cases also run with ``ops.GEMM_EVENTS = []`` and print how many entries were appended and whether
 ``ops.GEMM_EVENTS`` is the same list afterwards.  Two outputs are compared with diff(1).
 
 Every rank is a fresh child process under its own ``timeout -k 10``; the first non-zero exit status ends the run.
@@ -190,6 +194,75 @@ def child_dit(case, rank, world, port):
         dist.destroy_process_group()
 
 
+def tiny_dit(dev, **over):
+    from lkgd_amd import cogvideox as pc
+    from lkgd_amd import unet as pu
+    cfg = pc.DiTConfig(**{**dict(num_attention_heads=2, in_channels=32, time_embed_dim=64, num_layers=2, sample_width=12,
+                                 sample_height=8, sample_frames=9, max_text_seq_length=16), **over})
+    m = pc.CogVideoXTransformer3DModel(cfg).half().to(dev)
+    pu.init_synthetic_weights_(m, seed=4)
+    return m
+
+
+class SamplePipeline:
+    """what ``ddim_inversion.sample`` reads of a pipeline; the prompt embeddings are seeded noise ([1, 16, 4096] per prompt)"""
+    vae_scale_factor_spatial = 8
+    guidance_scale = property(lambda self: self._guidance_scale)
+
+    def __init__(self, transformer, dev):
+        self.transformer, self._execution_device = transformer, dev
+
+    def encode_prompt(self, prompt, negative_prompt, do_classifier_free_guidance, device=None):
+        import torch
+        g = torch.Generator().manual_seed(81 + len(prompt or ""))
+        pe, ne = (torch.randn(1, 16, 4096, generator=g).half().to(device) for _ in range(2))
+        return pe, (ne if do_classifier_free_guidance else None)
+
+    def _prepare_rotary_positional_embeddings(self, height, width, num_frames, device):
+        from lkgd_amd import cogvideox as pc
+        return pc.rotary_tables(self.transformer.config, num_frames, height // 16, width // 16)
+
+    def maybe_free_model_hooks(self):
+        pass
+
+
+def child_dit_one():
+    import torch
+    from lkgd_amd import cogvideox as pc
+    from lkgd_amd import ddim_inversion as di
+    dev = torch.device("cuda", 0)
+    g = torch.Generator().manual_seed(79)
+    lat = torch.randn(1, 3, 16, 8, 12, generator=g).half().to(dev)
+    img = (0.5 * torch.randn(1, 3, 16, 8, 12, generator=g)).half().to(dev)
+    pe = torch.randn(2, 16, 4096, generator=g).half().to(dev)
+    dom, flow = torch.randn(1, 1, 1000, generator=g).to(dev), torch.randn(1, 1, 1000, generator=g).to(dev)
+    ddim = pc.CogVideoXDDIMScheduler
+
+    m = tiny_dit(dev)
+    say("dit_one_ddim", 0, sha(pc.denoise(m, ddim(), lat, img, pe, dom, flow, 3, 6.0, True)))
+    say("dit_one_dpm_seeded", 0, sha(pc.denoise(m, pc.CogVideoXDPMScheduler(), lat, img, pe, dom, flow, 4, 6.0, True,
+                                                generator=torch.Generator().manual_seed(5))))
+    say("dit_one_nocfg", 0, sha(pc.denoise(m, ddim(), lat, img, pe[1:], dom, flow, 3, 1.0, False)))
+    seen = []
+    out = pc.denoise(m, ddim(), lat, img, pe, dom, flow, 4, 6.0, True, start_step=1, callback=lambda i, t, x: seen.append((i, t, x)))
+    say("dit_one_start_step_callback", 0, sha(out))
+    say("dit_one_start_step_callback", 0, f"callback {[(i, t) for i, t, _ in seen]} {sha(torch.stack([x for _, _, x in seen]))}")
+    say("dit_one_t2v", 0, sha(pc.denoise(tiny_dit(dev, in_channels=16), ddim(), lat, None, pe, None, None, 3, 6.0, True)))
+    m15 = tiny_dit(dev, patch_size_t=2, use_rotary_positional_embeddings=True, ofs_embed_dim=64, patch_bias=False, sample_frames=13)
+    lat15, img15 = pc.pad_for_temporal_patches(lat, img, 2)
+    say("dit_one_v15_ofs", 0, sha(pc.denoise(m15, ddim(), lat15, img15, pe, dom, flow, 3, 6.0, True, ofs=2.0)))
+
+    pipe = SamplePipeline(tiny_dit(dev, in_channels=16, use_rotary_positional_embeddings=True), dev)
+    forward = ddim(snr_shift_scale=1.0)
+    inverse = di.sample(pipe, lat, di.DDIMInverseScheduler(**forward.config), prompt="", num_inference_steps=3, guidance_scale=6.0)
+    say("dit_sample_inverse", 0, sha(inverse))
+    kw = dict(prompt="a cat", num_inference_steps=3, guidance_scale=6.0, use_dynamic_cfg=True)
+    with di.OverrideAttnProcessors(pipe.transformer):
+        guided = di.sample(pipe, img, forward, reference_latents=reversed(inverse), **kw)
+    say("dit_sample_guided", 0, f"{sha(guided)} guidance_scale {pipe.guidance_scale!r}")
+    say("dit_sample_references_no_override", 0, sha(di.sample(pipe, img, forward, reference_latents=reversed(inverse), **kw)))
+
+
 # ---- parent: no GPU work of its own ---------------------------------------------------------------------------------------------
 def free_port():
     s = socket.socket()
@@ -218,6 +291,7 @@ def main():
         launch(c[0], c[1], 300)
     for name, world in DIT_WORLDS:
         launch(name, world, 300)
+    launch("dit_one", 1, 300)
 
 
 if __name__ == "__main__":
@@ -227,6 +301,8 @@ if __name__ == "__main__":
         case, rank, world, port = sys.argv[1], int(sys.argv[2]), int(sys.argv[3]), int(sys.argv[4])
         if case == "single":
             child_single()
+        elif case == "dit_one":
+            child_dit_one()
         elif case.startswith("dit"):
             child_dit(case, rank, world, port)
         else:
